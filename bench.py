@@ -18,7 +18,12 @@ batches are in flight on three side streams (--prefetch-depth; 2 until the f16x2
 6290 img/s with the third; --no-overlap disables it).  Weak scaling: every rank
 processes --batch images per step (default 64 = BASELINE.json configs[1]); value = N*batch*K / max-rank time.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step = milliseconds per timed step,
+loss, config).  --dump-outputs DIR then writes what the last timed step computed as DIR/<name>.npy (float32, < 64 MB; the
+inputs are seeded, so two builds can be compared output for output).  Everything below takes runs of its own and comes
+only with --full (--no-cpu-baseline, --no-alt-mode, --no-decoder-batch256 trim that run).
+
+With --full the JSON line also carries
   roofline     - the contraction kernel instantiation with the largest total time (per-launch HIP events on the
                  launch stream).  Its bound is chosen by arithmetic intensity: algorithmic FLOPs / algorithmic HBM bytes of its
                  launches (operands read once, output written once) against the machine balance peak / 8 TB/s, where peak =
@@ -202,6 +207,44 @@ def pmc_for(rocprof_name: str, batch: int = 64):
 
 pmc_for.source = "profiles/ (no PMC summary found)"
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: an output of more elements is written as this many, at fixed seeded positions
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, whole=()) -> None:
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy in float32.  An output larger than DUMP_SAMPLE elements whose name is
+    not in `whole` is written as out_dir/<name>_sample.npy: its flattened elements at DUMP_SAMPLE positions drawn from a fixed seed
+    (the same positions in every run of the same shape)."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if name not in whole and flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            flat, name = flat[idx.to(flat.device)], name + "_sample"
+        out[name] = flat.float().cpu().numpy().reshape(t.shape if flat.numel() == t.numel() else (-1,))
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def train_step_outputs(trainer, loss) -> dict:
+    """What a caller of CaptionTrainer.train_step holds after the step: the loss, the updated parameters and their gradients, the
+    BatchNorm running statistics of both encoders, and trainer.last (the loss gradient w.r.t. the logits is written in place of
+    the logits)."""
+    last = trainer.last
+    out = {"loss": loss.reshape(1), "parameters": trainer.flat.data, "parameter_grads": trainer.flat.grad,
+           "resnet_bn_running_stats": trainer.rn_stats}
+    if trainer.enc_state:
+        out["depth_bn_running_stats"] = torch.cat([v.reshape(-1).float() for v in trainer.enc_state.values()])
+    for k, name in (("features", "features"), ("depth_features", "depth_features"), ("alphas", "alphas"), ("logits", "dlogits")):
+        if last.get(k) is not None:
+            out[name] = last[k]
+    return out
+
 
 def cpu_baseline(sample_b: int, iters: int, hard: bool = False):
     """Time the CPU oracle (port of the reference path) on the host cores: same step, same shapes.
@@ -300,8 +343,9 @@ def parity_gate(first, dev: str, conv_mode: str, compact: bool, hard: bool = Fal
 def bench_dpt(args, dev: str, world: int, rank: int):
     """`--dpt`: images/s of the frozen DPT-Hybrid depth front-end (config 5's extra stage, epoch 0 only): forward at 384x384 +
     per-image standardisation + resize to 224x224, inputs resident in HBM; every rank runs its own batch (no collective:
-    the estimator is frozen).  Reported beside: achieved fp32-equivalent rate (algorithmic FLOPs / time) against the peak of the arithmetic in use, the CPU oracle on
-    the host cores (2 images) and the max deviation of one predicted map from it (parity unpinned, see oracle/dpt_oracle.py)."""
+    the estimator is frozen).  Reported beside: achieved fp32-equivalent rate (algorithmic FLOPs / time) against the peak of the arithmetic in use; with
+    --full also the CPU oracle on the host cores (2 images) and the max deviation of one predicted map from it (parity unpinned, see
+    oracle/dpt_oracle.py)."""
     from depth_image_captioning_pub_amd import synthetic as syn
     from depth_image_captioning_pub_amd.Captioning_models.Depth_caption_model.DPT_model import DPT_Depthestimator
     from depth_image_captioning_pub_amd.hostinfo import host_cores
@@ -325,6 +369,8 @@ def bench_dpt(args, dev: str, world: int, rank: int):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"depth_maps": d})
     if rank == 0:
         flops = dpt._runner.flops_per_image(384) * B * args.steps
         ach = flops / elapsed / 1e12
@@ -343,7 +389,7 @@ def bench_dpt(args, dev: str, world: int, rank: int):
                                      "f16x2": "TFLOP/s (fp32-equivalent; peak = 2.5 PF fp16 / 3 products)"}.get(arith, "TFLOP/s"),
                             "frac": round(ach / peak, 4), "traffic": None,
                             "gflop_per_image": round(dpt._runner.flops_per_image(384) / 1e9, 1)}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import dpt_oracle
             torch.set_num_threads(host_cores())
             w = {k[len("model."):]: v.cpu() for k, v in dpt.state_dict().items()}
@@ -394,6 +440,11 @@ def build_parser():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="images per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: stage and per-kernel times, roofline, the other "
+                         "ResNet convolution mode, the decoder stage at batch 256, the CPU baseline and the same-run parity gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--conv-mode", choices=["fp32", "bf16x3", "f16x2"], default=DEFAULT_CONV_MODE,
                     help="ResNet convolutions: exact-fp32 MFMA; bf16x3 = exact three-way bf16 split, 6 matrix-core products; f16x2 "
@@ -553,10 +604,61 @@ def main():
     loss_val = float(loss.item())
     trainer.check_status()                  # f16x2 overflow guard: a tripped step would have skipped its update (DicError here)
     dropped_timed = trainer.prefetch_dropped     # must be 0: a dropped prefetch means the timed steps ran un-overlapped forwards
-
-    # ---- per-stage and per-kernel measurements: two extra steps after the timed region (every rank runs
-    #      them so the collectives stay matched) ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_step_outputs(trainer, loss), whole=("parameters",))
     cells = int(trainer.last["features"].shape[1]) if trainer.last.get("features") is not None else 196
+    ms_step = elapsed / args.steps * 1e3
+    value = world * B * args.steps / elapsed
+
+    def headline():
+        result = {
+            "metric": f"images/sec (train, depth-{'hard' if args.hard else 'soft'}, 224x224, seq-len 20)", "value": round(value, 2),
+            "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"depth-{'hard (Gumbel-softmax attention, temp 1.0, CE only)' if args.hard else 'soft'} train step, synthetic RGB-D 224x224, batch {B}/GPU, seq-len {SEQ_LEN}, "
+                                   f"V={VOCAB}, ResNet-152 (random init, batch-stat BN) + depth CNN + soft-attention LSTM",
+                       "global_batch": world * B, "batch_per_gpu": B, "seq_len": SEQ_LEN, "vocab": VOCAB,
+                       "parallelism": f"dp{world}", "resnet_conv_mode": args.conv_mode,
+                       "resnet_arithmetic": {"fp32": "exact-fp32 MFMA", "bf16x3": "fp32 operands split exactly into three bf16 planes, six bf16 MFMA products, fp32 accumulation",
+                                             "f16x2": "fp32 operands as two fp16 planes of a power-of-two multiple (2^-22 representation error), three fp16 MFMA "
+                                                      "products, fp32 accumulation; error against fp64 = that of an fp32 evaluation (parity.max_abs_dlogit_*_vs_fp64)"}[args.conv_mode],
+                       "cross_step_resnet_overlap": not args.no_overlap,
+                       "resnet_forwards_in_flight": 0 if args.no_overlap else args.prefetch_depth, "annotation_cells": cells},
+            "loss": round(loss_val, 5),
+            "prefetch_dropped": dropped_timed,
+        }
+        result["config"]["ranks"] = world
+        result["config"]["collective"] = (f"{backend} all-reduce of 2 gradient buckets over {world} ranks" if world > 1
+                                          else "none (single rank)")
+        if world > 1:
+            result["config"]["collective_ranks"] = torch.distributed.get_world_size(pg)
+            result["config"]["collective_self_check"] = "1-element all-reduce before the warm-up: ok"
+            result["config"]["gradient_bytes_per_step"] = int(4 * trainer_numel)
+        return result
+
+    def finish(result):
+        parity_failed = False
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+            parity_failed = bool(result.get("parity")) and not result["parity"]["ok"]
+            if dropped_timed:
+                print(f"bench.py: {dropped_timed} prefetched ResNet forward(s) were DISCARDED inside the warm-up / timed region - the steps "
+                      "did not run the pipelined schedule the number claims", file=sys.stderr)
+                parity_failed = True
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        if parity_failed:       # a fast step whose results differ from the reference's is not a result
+            print("bench.py: the same-run parity gate FAILED (see \"parity\" in the line above)", file=sys.stderr)
+            raise SystemExit(3)
+
+    if not args.full:
+        finish(headline() if rank == 0 else None)
+        return
+
+    # ---- --full: per-stage and per-kernel measurements: two extra steps after the timed region (every rank runs
+    #      them so the collectives stay matched) ----
     torch.cuda.synchronize()
     # ---- stage times of the main stream UNDER LOAD: five more pipelined steps with stage-boundary events (one host sync per
     #      step, so these steps are not part of `value`); the same stages alone on the chip are `stages_ms` below
@@ -582,8 +684,6 @@ def main():
         prof = profile_step(trainer, step_args)
     else:
         trainer.train_step(*step_args)
-    ms_step = elapsed / args.steps * 1e3
-    value = world * B * args.steps / elapsed
     # ---- same workload with the other convolution arithmetic (short run: 2 warm-up + 5 timed steps) ----
     alt = None
     if not args.no_alt_mode:
@@ -609,7 +709,6 @@ def main():
                "ms_per_step": round(e2 / 5 * 1e3, 3), "steps": 5, "warmup": 2}
         del tr2
     result = None
-    parity_failed = False
     if rank == 0:
         top = prof[0]
         kr = kernel_roofline(top)
@@ -674,21 +773,9 @@ def main():
                                                                                 (dec_ms * 1e-3) / 1e12, 3) if dec_ms > 0 else 0.0,
                                       "note": "work-equivalent rate only (the reference layout would need this much "
                                               "bandwidth for the same stage time); not a bandwidth claim"}}
-        result = {
-            "metric": f"images/sec (train, depth-{'hard' if args.hard else 'soft'}, 224x224, seq-len 20)", "value": round(value, 2),
-            "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"depth-{'hard (Gumbel-softmax attention, temp 1.0, CE only)' if args.hard else 'soft'} train step, synthetic RGB-D 224x224, batch {B}/GPU, seq-len {SEQ_LEN}, "
-                                   f"V={VOCAB}, ResNet-152 (random init, batch-stat BN) + depth CNN + soft-attention LSTM",
-                       "global_batch": world * B, "batch_per_gpu": B, "seq_len": SEQ_LEN, "vocab": VOCAB,
-                       "parallelism": f"dp{world}", "resnet_conv_mode": args.conv_mode,
-                       "resnet_arithmetic": {"fp32": "exact-fp32 MFMA", "bf16x3": "fp32 operands split exactly into three bf16 planes, six bf16 MFMA products, fp32 accumulation",
-                                             "f16x2": "fp32 operands as two fp16 planes of a power-of-two multiple (2^-22 representation error), three fp16 MFMA "
-                                                      "products, fp32 accumulation; error against fp64 = that of an fp32 evaluation (parity.max_abs_dlogit_*_vs_fp64)"}[args.conv_mode],
-                       "cross_step_resnet_overlap": not args.no_overlap,
-                       "resnet_forwards_in_flight": 0 if args.no_overlap else args.prefetch_depth, "annotation_cells": cells},
-            "loss": round(loss_val, 5), "stages_ms": stages,
+        result = headline()
+        result.update({
+            "stages_ms": stages,
             "stages_note": "one extra un-overlapped step after the timed region: every stage on the main stream, incl. "
                            "the ResNet-152 forward that the timed steps run on the side stream",
             "overlap_hidden_ms": round(sum(stages.values()) - ms_step, 3) if not args.no_overlap else 0.0,
@@ -698,33 +785,14 @@ def main():
                                       "'resnet152_fwd' there is only the wait for the prefetched features",
             "roofline": roofline, "resnet_forward": resnet_forward, "decoder_roofline": decoder_roofline,
             "other_conv_mode": alt,
-            "prefetch_dropped": dropped_timed,
-        }
+        })
         if world == 1 and not args.no_decoder_batch256 and B != 256:
             torch.cuda.empty_cache()
             result["decoder_roofline_batch256"] = decoder_stage_roofline(dev, 256, args.hard, args.reference_cells)
-        result["config"]["ranks"] = world
-        result["config"]["collective"] = (f"{backend} all-reduce of 2 gradient buckets over {world} ranks" if world > 1
-                                          else "none (single rank)")
-        if world > 1:
-            result["config"]["collective_ranks"] = torch.distributed.get_world_size(pg)
-            result["config"]["collective_self_check"] = "1-element all-reduce before the warm-up: ok"
-            result["config"]["gradient_bytes_per_step"] = int(4 * trainer_numel)
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"], first = cpu_baseline(args.cpu_batch, args.cpu_iters, hard=args.hard)
             result["parity"] = parity_gate(first, dev, args.conv_mode, not args.reference_cells, hard=args.hard)
-        print(json.dumps(result), flush=True)
-        parity_failed = bool(result.get("parity")) and not result["parity"]["ok"]
-        if dropped_timed:
-            print(f"bench.py: {dropped_timed} prefetched ResNet forward(s) were DISCARDED inside the warm-up / timed region - the steps "
-                  "did not run the pipelined schedule the number claims", file=sys.stderr)
-            parity_failed = True
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
-    if parity_failed:       # a fast step whose results differ from the reference's is not a result
-        print("bench.py: the same-run parity gate FAILED (see \"parity\" in the line above)", file=sys.stderr)
-        raise SystemExit(3)
+    finish(result)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ for round in 1 2; do
   for cfg in "$@"; do
     name=${cfg%%=*}; codes=${cfg#*=}
     if [ "$codes" = "-" ]; then unset DIC_DEBUG_SWITCHES; else export DIC_DEBUG_SWITCHES=$codes; fi
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-alt-mode --no-decoder-batch256 ${AB_ARGS} 2>>$out.err | python -c "
+    python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-alt-mode --no-decoder-batch256 ${AB_ARGS} 2>>$out.err | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,8 +1,9 @@
 #!/bin/bash
 # rocprofv3 kernel trace of the un-overlapped bench; prints per-step time of every (kernel, grid) that is not part of the ResNet forward
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/ms_stats
-rocprofv3 --kernel-trace --output-format csv -d /tmp/ms_stats -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt-mode --no-decoder-batch256 --no-overlap > /tmp/ms_stats.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/ms_stats" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt-mode --no-decoder-batch256 --no-overlap > "$TMPDIR/ms_stats.log" 2>&1
 f=$(find /tmp/ms_stats -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY' | tee $GRAFT_REPO_ROOT/gpurun_out/main_stream_stats.txt
 import collections,csv,sys

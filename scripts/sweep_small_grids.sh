@@ -4,10 +4,10 @@
 mkdir -p gpurun_out
 out=gpurun_out/sweep_small_grids.txt; : > $out
 run() {
-  python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decoder-batch256 --no-alt-mode "$@" > gpurun_out/_sg.log 2>gpurun_out/_sg.err
-  python3 - "$*" <<'PY' >> gpurun_out/sweep_small_grids.txt
+  python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-decoder-batch256 --no-alt-mode "$@" > "$out.log" 2>"$out.err"
+  python3 - "$*" "$out.log" <<'PY' >> "$out"
 import json, sys
-d = json.loads([l for l in open("gpurun_out/_sg.log") if l.startswith("{")][-1])
+d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 print(f"{sys.argv[1]:40s} {d['value']:8.1f} img/s {d['ms_per_step']:.3f} ms; resnet alone {d['stages_ms'].get('resnet152_fwd')} ms")
 PY
 }

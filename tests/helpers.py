@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (golden loader + comparisons)."""
+import contextlib
 import os
 
 import numpy as np
@@ -6,6 +7,20 @@ import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SUB = 61
+GOLDEN_THREADS = 8      # intra-op threads the golden vectors were computed with (golden/make_golden.py)
+
+
+@contextlib.contextmanager
+def torch_threads(n):
+    """Run a CPU evaluation on exactly `n` intra-op threads.  How an fp32 reduction is split over threads changes its rounding,
+    so a comparison with another fp32 evaluation at a tight tolerance only holds when both split it alike - whatever number of
+    cores the host grants (tests/conftest.py uses all of them)."""
+    old = torch.get_num_threads()
+    torch.set_num_threads(n)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(old)
 
 
 def load_golden(name):

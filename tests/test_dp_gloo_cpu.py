@@ -10,6 +10,7 @@ import torch.multiprocessing as mp
 
 from depth_image_captioning_pub_amd import synthetic as syn
 from depth_image_captioning_pub_amd.engine import FlatParams, exchange_gradients, gradient_scales, shard_rows
+from tests.helpers import torch_threads
 
 
 def _free_port():
@@ -112,8 +113,11 @@ def test_token_weighted_exchange_world4_ragged(tmp_path):
     mp.spawn(_worker_ragged, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     summed = torch.load(tmp_path / "summed.pt")
     dw = {k: v.clone().requires_grad_(True) for k, v in dec.items()}
-    packed, _, alphas = orc.decoder_forward(dw, f_rgb, f_dep, caps, lens, drop)
-    orc.caption_loss(packed, orc.pack_targets(caps, lens), alphas).backward()
+    # on the ranks' thread count: the true gradient of attention.full_att.bias is exactly zero (softmax shift invariance), so both
+    # sides hold rounding noise of ~1e-9 whose value depends on how the reductions are split over threads
+    with torch_threads(2):
+        packed, _, alphas = orc.decoder_forward(dw, f_rgb, f_dep, caps, lens, drop)
+        orc.caption_loss(packed, orc.pack_targets(caps, lens), alphas).backward()
     shares = [sum(l - 1 for l in lens[2 * r:2 * r + 2]) for r in range(world)]
     assert shares == [27, 19, 11, 5]
     for k, v in dw.items():

@@ -25,7 +25,7 @@ def test_bench_gpus2_self_launch_over_gloo_on_one_gpu(lib):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(SHARE)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--no-alt-mode"]
+           "--full", "--no-cpu-baseline", "--no-alt-mode"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -91,8 +91,8 @@ def test_bench_hard_workload_line(lib):
     """`bench.py --hard` (the depth-hard step of BASELINE config 4 as a separate workload line, never the headline): runs, names
     itself, streams all 196 cells, and its same-run parity gate (CPU oracle's depth-hard step on the same Gumbel draws) is green."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--hard", "--steps", "3", "--warmup", "2", "--batch", "16", "--no-alt-mode",
-           "--cpu-batch", "8", "--cpu-iters", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--hard", "--full", "--steps", "3", "--warmup", "2", "--batch", "16",
+           "--no-alt-mode", "--cpu-batch", "8", "--cpu-iters", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
