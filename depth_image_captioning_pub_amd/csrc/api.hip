@@ -2,6 +2,8 @@
 #include "dic.h"
 #include "conv.h"
 
+#include <cstdio>
+
 using namespace dic;
 
 namespace dic { void resnet_fuse_bn_operand(int mask); void resnet_fuse_bn_halo(int on); void resnet_fuse_res_bn(int on); void depth_encoder_l1_sparse(int on); void bn_finalize_two_level_rows(int rows); void resnet_debug_fused_tail_bn(int on); void conv1_depth_debug_blocks(int n);
@@ -66,7 +68,7 @@ int dic_debug_force_staged_gemm(int on) {
   if (on == 140 || on == 141) { dic::decoder_debug_persistent(on - 140); return 0; }          // decoder forward: per-step launches / persistent loop
   if (on == 142 || on == 143) { dic::decoder_persist_debug_placement(on - 142); return 0; }   // persistent loop: workgroup placement
   if (on >= 130 && on <= 134) { dic::conv1_depth_debug_blocks(256 * (on - 130)); return 0; }   // generic path / 256 / 512 / 768 / 1024 workgroups
-  if (on >= 120 && on <= 123) { dic::resnet_debug_fused_tail_bn(on - 120); return 0; }
+  if (on >= 150 && on <= 153) { dic::resnet_debug_fused_tail_bn(on - 150); return 0; }   // (measurement only) fused tail fix-up + BatchNorm finalize: no / yes (default); stem: gather kernel / strips (default)
   if (on >= 124 && on <= 127) { dic::resnet_debug_skip_bn_apply(on == 125 ? 3 : on == 126 ? 2 : on == 127 ? 1 : 0); return 0; }   // (measurement only) bn_apply_planes: run / skip all / skip block outputs / skip c1, c2 outputs
   if (on >= 0 && on <= 13) { gemm_force_v1(on); return 0; }
 #endif
@@ -95,6 +97,19 @@ int dic_debug_conv_bf3(const uint16_t* const x_planes[3], int B, int H, int W, i
                        int k, int stride, int pad, float* y, float* bn_partial, int* mtiles_out, float* tail_ws, void* stream) {
   ConvDesc d{B, H, W, C, CO, k, k, stride, pad, 0};
   return conv_fwd_bf3(x_planes, d, w_planes, y, bn_partial, mtiles_out, tail_ws, (hipStream_t)stream, nullptr, nullptr, nullptr);
+}
+/* development aid (not in dic.h): the launch plan of one split-operand convolution, without operands and without a GPU (plan_bf3,
+ * gemm_bf3.hip; routes and flags at bf3_plan_route).  name receives the kernel as the profiler names it (without "void dic::" and the
+ * parameter list), out the grid, the workgroup size, the fix-up (0 none, 1 remainder of the 128x128 kernels over out[3] quadrants,
+ * 2 / 3 64x64 tail over out[3] tiles, 3: fused with the BatchNorm finalize when asked), the BatchNorm partial-sum rows and the profile
+ * key.  Returns 1 when the route does not take the shape. */
+int dic_debug_bf3_plan(int route, int fmt, int B, int H, int W, int C, int CO, int k, int stride, int pad, int flags, int splitk,
+                       int tail_ws_slabs, char* name, int name_bytes, int* out) {
+  DIC_REQUIRE(name && name_bytes > 0 && out, "debug_bf3_plan: bad arguments");
+  const char* kernel = nullptr;
+  DIC_TRY(bf3_plan_route(route, fmt, ConvDesc{B, H, W, C, CO, k, k, stride, pad, 0}, flags, splitk, tail_ws_slabs, &kernel, out));
+  snprintf(name, name_bytes, "%s", kernel);
+  return DIC_OK;
 }
 /* the same two with the operand format explicit (0 = bf16x3, 1 = f16x2: two planes per operand from dic_split_f16x2_paired,
  * out_scale = 1 / (scale of the x planes * scale of the w planes); the on-the-fly operand is scaled by 4 inside the kernel;

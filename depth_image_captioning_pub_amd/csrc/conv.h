@@ -40,7 +40,9 @@ int conv1x1_fwd_bf3_bn(const float* raw, const float* scale, const float* shift,
                        int* bn_fused = nullptr, int fmt = 0, float out_scale = 1.0f,
                        unsigned* status = nullptr /* f16x2: overflow guard word (common.h) */,
                        const float* res_scale = nullptr, const float* res_shift = nullptr /* f16x2: BatchNorm of the residual itself */);
-bool conv1x1_bf3_bn_eligible(int M, int C, int CO, int tail_ws_slabs, int fmt = 0);
+bool conv1x1_bf3_bn_eligible(const float* raw, int M, int C, int CO, float* tail_ws, int tail_ws_slabs, int fmt = 0);   // (nothing launched)
+// the launch plan of one of these routes, without operands (dic_debug_bf3_plan, api.hip)
+int bf3_plan_route(int route, int fmt, const ConvDesc& d, int flags, int splitk, int tail_ws_slabs, const char** kernel, int out[6]);
 // 3x3 / stride 1 / pad 1 convolution of 14x14 maps with the same fusion, in the LDS-halo kernel's producer waves (f16x2 format only);
 // returns 1 (nothing launched) for every other shape / format
 int conv3x3_fwd_bf3_bn(const float* raw, const float* scale, const float* shift, int relu, const ConvDesc& d,

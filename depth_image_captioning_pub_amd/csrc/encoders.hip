@@ -237,8 +237,8 @@ void resnet_debug_skip_bn_apply(int on) { g_skip_bn_apply = on; }
 #define DIC_BN_APPLY_PLANES(...) DIC_TRY(bn_apply_planes(__VA_ARGS__))
 #define DIC_BN_APPLY_PLANES_OUT(...) DIC_TRY(bn_apply_planes(__VA_ARGS__))
 #endif
-static int g_strip_stem = 1;        // benchmarking (codes 122/123): 0 = stem on the exact-fp32 gather kernel
-static int g_fused_tail_bn = 1;     // benchmarking (codes 120/121): 0 = separate tail fix-up and BN finalize launches
+static int g_strip_stem = 1;        // benchmarking (codes 152/153): 0 = stem on the exact-fp32 gather kernel
+static int g_fused_tail_bn = 1;     // benchmarking (codes 150/151): 0 = separate tail fix-up and BN finalize launches
 void resnet_debug_fused_tail_bn(int on) { if (on >= 2) g_strip_stem = on - 2; else g_fused_tail_bn = on; }
 
 // conv (bf16x3 planes in, raw fp32 out) -> BN scale/shift
@@ -429,7 +429,7 @@ static int resnet_fwd_bf3(const dic_conv_bn_layer* layers, const int* blocks, co
       // (decided here, by the next conv1's shape: a shape the persistent kernel does not take would pay for the fp32 copy on top of
       //  the planes)
       const bool next_fused = (g_fuse_bn_operand & 1) && b + 1 < blocks[s] && (b == 0 || in32) &&
-                              conv1x1_bf3_bn_eligible(c3.d.M(), c3.d.CO, c1.d.CO, kResnetTailSlabs, fmt);
+                              conv1x1_bf3_bn_eligible(R3, c3.d.M(), c3.d.CO, c1.d.CO, ws.tail, kResnetTailSlabs, fmt);
       if (next_fused) {
         // left to the next block's conv1.  The downsample output is normalised in place first (the kernel adds a plain residual)
         // (f16x2: the kernel applies the branch's BatchNorm to the residual itself - switch 99; else an in-place pass over it first)

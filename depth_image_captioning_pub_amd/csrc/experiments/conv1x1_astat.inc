@@ -211,3 +211,35 @@ __global__ void __launch_bounds__(512) conv1x1_astat_bn_kernel(const Bf3Params p
 #undef DIC_AS_MFMA_ALL
 }
 
+// the host side (experiments build only, like the kernel)
+// conv3-style 1x1 convolution on the A-stationary kernel (conv1x1_astat_bn_kernel): y_raw[M][CO] = relu(raw[M][C] * scale + shift) . W^T,
+// f16x2 weights planes (scale in out_scale = 1 / (kF16ActScale * w_scale)); BatchNorm partials per 32-row wave tile: *mtiles_out rows
+static int g_astat = 0;                  // codes 110 / 111 (experiments build): off (default) / on
+void conv1x1_astat_switch(int on) { g_astat = on; }
+bool conv1x1_astat_eligible(int M, int C, int CO) {
+  return g_astat != 0 && (C == 128 || C == 256) && CO % 128 == 0 && CO >= 128 && M >= 64 && (long long)(CO + 1) * C * 2 < (1ll << 31);
+}
+int conv1x1_astat_bn(const float* raw, const float* scale, const float* shift, int relu, int M, int C, const unsigned short* const w_planes[3],
+                     int CO, float* y, float* bn_partial, int* mtiles_out, hipStream_t st, float out_scale, unsigned* status) {
+  DIC_REQUIRE(raw && scale && shift && y && w_planes && w_planes[0] && w_planes[1], "conv1x1_astat_bn: null pointer");
+  if (!conv1x1_astat_eligible(M, C, CO)) return 1;
+  Bf3Params p{};
+  p.M = M; p.N = CO; p.K = C;
+  p.B.p[0] = w_planes[0]; p.B.p[1] = w_planes[1]; p.B.p[2] = nullptr;
+  p.B.kind = OPK_ROWK; p.B.ld = C; p.B.paired = 1;
+  p.a_raw = raw; p.a_scale = scale; p.a_shift = shift; p.a_ld = C; p.a_relu = relu; p.status = status;
+  p.ep = ep_store(y, CO, nullptr, ACT_NONE);
+  p.ep.stats = bn_partial;
+  p.ep.alpha = out_scale;
+  p.fmt = 1;
+  const int mt = ceil_div(M, 64);
+  p.mtiles = mt; p.ntiles = CO / 128;
+  gemm_profile_mark_begin(st, 2.0 * M * CO * (double)C, 3000 + OPK_ROWK_BN * 10 + 9,
+                          4.0 * ((double)M * C + (double)CO * C + (double)M * CO));
+  if (C == 256) hipLaunchKernelGGL(conv1x1_astat_bn_kernel<8>, dim3(mt), dim3(512), 0, st, p);
+  else hipLaunchKernelGGL(conv1x1_astat_bn_kernel<4>, dim3(mt), dim3(512), 0, st, p);
+  DIC_LAUNCH_CHECK();
+  gemm_profile_mark_end(st);
+  if (mtiles_out) *mtiles_out = 2 * mt;
+  return DIC_OK;
+}

@@ -1870,17 +1870,13 @@ __global__ void __launch_bounds__(512) conv3x3_bf3_halo_kernel(const Bf3Params p
 
 
 #ifdef DIC_EXPERIMENTS
-#include "experiments/conv1x1_astat.inc"      // parked: A-stationary conv3 kernel with the BatchNorm-apply fused in (see the note in the file)
+#include "experiments/conv1x1_astat.inc"      // parked: A-stationary conv3 kernel with the BatchNorm-apply fused in, and its launch (see the note in the file)
 #endif
 
 }  // namespace dic
 
 namespace dic {
 
-static int g_last_mtiles = 0;   // M tiles of the most recent launch (row count of the BN partial-sum table)
-#ifdef DIC_EXPERIMENTS
-void conv1x1_astat_switch(int on);
-#endif
 // Kernel-selection switches (dic_debug_force_staged_gemm, include/dic.h).  The product library keeps the ones its tests use to
 // compare kernels that the policy below really selects (tile forcing 11 / 21 / 24 / 20, persistent policy 70 / 73 / 79, halo
 // 74 / 75 / 78); the ablations and the parked kernels exist only in the experiments build (-DDIC_EXPERIMENTS).
@@ -1913,18 +1909,8 @@ static int g_bf3_bn_ablate = 0;        // on-the-fly-operand kernel, timing only
 static int g_bf3_ws256_ablate = 0;     // 256x128 kernel (f16x2, planes), timing only: 1 = no DMA in the loop, 2 = no tile stores, 3 = neither, 4 = no fragment reads (44..47)
 static int g_bf3_halo_bna_ablate = 0;  // LDS-halo kernel, on-the-fly form, timing only (wrong results): bit 0 = no weight DMA in the loop, bit 1 = no input loads / transform in the loop (64..66)
 #else
-constexpr int g_bf3_stages = 2, g_bf3_ws = 1, g_bf3_ablate = 0, g_bf3_halo56 = 0;
+constexpr int g_bf3_ws = 1, g_bf3_ablate = 0, g_bf3_halo56 = 0, g_bf3_ws256_bn = 0;
 #endif
-template <int AK, int TM, int TN>
-static void launch_bf3_variant(const Bf3Params& p, int blocks, hipStream_t st) {
-#ifdef DIC_EXPERIMENTS
-  if constexpr (TM == 2) {
-    if (g_bf3_stages == 3) { hipLaunchKernelGGL((gemm_bf3_kernel<AK, TM, TN, 3>), dim3(blocks), dim3(256), 0, st, p); return; }
-  }
-#endif
-  if (p.fmt == 1) { hipLaunchKernelGGL((gemm_bf3_kernel<AK, TM, TN, 2, 0, 1>), dim3(blocks), dim3(256), 0, st, p); return; }
-  hipLaunchKernelGGL((gemm_bf3_kernel<AK, TM, TN, 2>), dim3(blocks), dim3(256), 0, st, p);
-}
 
 // Workgroups per persistent launch (dic_conv_persistent_grid, include/dic.h): a launch never asks for more than this many CUs,
 // so that the convolutions of SEVERAL ResNet forwards in flight (engine.py) run side by side instead of taking turns.
@@ -1971,8 +1957,71 @@ int gemm_bf3_force_tile(int code) {      // 0 = accepted, -1 = unknown in this b
   return -1;
 }
 
-static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 1, float* splitk_ws = nullptr,
-                      const BnFuseArgs* bn_fuse = nullptr, int* bn_fused = nullptr, int tail_ws_slabs = 256, bool probe = false) {
+// Launch table: one row per instantiation of the contraction kernels, all launched by launch_bf3.  A row's kernel is spelled with every
+// template argument (operand kinds: 0 row-major, 2 im2col, 6 on the fly), so that its name is the one the profiler prints.
+struct Bf3Kernel { const char* name; int block; void (*fn)(Bf3Params); };
+#define DIC_BF3_KERNELS(X) \
+  X(HALO_BN28_ILV, 512, conv3x3_bf3_halo_kernel<0, 1, true, 32, 9, 1>) X(HALO_BN28, 512, conv3x3_bf3_halo_kernel<0, 1, true, 32, 9, 0>) \
+  X(HALO_BN_ILV, 512, conv3x3_bf3_halo_kernel<0, 1, true, 16, 13, 1>) X(HALO_BN, 512, conv3x3_bf3_halo_kernel<0, 1, true, 16, 13, 0>) \
+  X(HALO_F16, 512, conv3x3_bf3_halo_kernel<0, 1, false, 16, 13, 0>) X(HALO_BF3, 512, conv3x3_bf3_halo_kernel<0, 0, false, 16, 13, 0>) \
+  X(WS_BN8_S6, 768, gemm_bf3_persist_ws_kernel<6, 0, 3, 1, 8, 6, 1>) X(WS_BN8_BLOCK, 768, gemm_bf3_persist_ws_kernel<6, 0, 3, 1, 8, 4, 0>) \
+  X(WS_BN8, 768, gemm_bf3_persist_ws_kernel<6, 0, 3, 1, 8, 4, 1>) X(WS_BN4, 512, gemm_bf3_persist_ws_kernel<6, 0, 3, 1, 4, 4, 1>) \
+  X(WS_IM_F16_BLOCK, 512, gemm_bf3_persist_ws_kernel<2, 0, 3, 1, 4, 4, 0>) X(WS_IM_F16, 512, gemm_bf3_persist_ws_kernel<2, 0, 3, 1, 4, 4, 1>) \
+  X(WS_ROWK_F16_BLOCK, 512, gemm_bf3_persist_ws_kernel<0, 0, 3, 1, 4, 4, 0>) X(WS_ROWK_F16, 512, gemm_bf3_persist_ws_kernel<0, 0, 3, 1, 4, 4, 1>) \
+  X(WS_BN_BF3, 512, gemm_bf3_persist_ws_kernel<6, 0, 3, 0, 4, 4, 1>) X(WS_IM_BF3, 512, gemm_bf3_persist_ws_kernel<2, 0, 3, 0, 4, 4, 1>) \
+  X(WS_ROWK_BF3, 512, gemm_bf3_persist_ws_kernel<0, 0, 3, 0, 4, 4, 1>) \
+  X(WS256_ILV, 768, gemm_bf3_persist_ws256_kernel<0, 1, false, 0, 1>) X(WS256_BLOCK, 768, gemm_bf3_persist_ws256_kernel<0, 1, false, 0, 0>) \
+  X(T11_ROWK_BF3, 256, gemm_bf3_kernel<0, 1, 1, 2, 0, 0>) X(T11_ROWK_F16, 256, gemm_bf3_kernel<0, 1, 1, 2, 0, 1>) \
+  X(T11_IM_BF3, 256, gemm_bf3_kernel<2, 1, 1, 2, 0, 0>) X(T11_IM_F16, 256, gemm_bf3_kernel<2, 1, 1, 2, 0, 1>) \
+  X(T21_ROWK_BF3, 256, gemm_bf3_kernel<0, 2, 1, 2, 0, 0>) X(T21_ROWK_F16, 256, gemm_bf3_kernel<0, 2, 1, 2, 0, 1>) \
+  X(T21_IM_BF3, 256, gemm_bf3_kernel<2, 2, 1, 2, 0, 0>) X(T21_IM_F16, 256, gemm_bf3_kernel<2, 2, 1, 2, 0, 1>)
+#ifdef DIC_EXPERIMENTS      // the parked forms, the ablations (timing only), ring depth 3 and the forced 128x128 tile
+#define DIC_BF3_EXPERIMENT_KERNELS(X) \
+  X(HALO_BN56, 512, conv3x3_bf3_halo_kernel<0, 1, true, 58, 7, 1>) X(HALO_BN_ABL1, 512, conv3x3_bf3_halo_kernel<1, 1, true, 16, 13, 1>) \
+  X(HALO_BN_ABL2, 512, conv3x3_bf3_halo_kernel<2, 1, true, 16, 13, 1>) X(HALO_BN_ABL3, 512, conv3x3_bf3_halo_kernel<3, 1, true, 16, 13, 1>) \
+  X(HALO_BN_ABL4, 512, conv3x3_bf3_halo_kernel<4, 1, true, 16, 13, 1>) X(HALO_BN_ABL8, 512, conv3x3_bf3_halo_kernel<8, 1, true, 16, 13, 1>) \
+  X(HALO_BN_ABL12, 512, conv3x3_bf3_halo_kernel<12, 1, true, 16, 13, 1>) X(HALO_ABL1, 512, conv3x3_bf3_halo_kernel<1, 0, false, 16, 13, 0>) \
+  X(HALO_ABL2, 512, conv3x3_bf3_halo_kernel<2, 0, false, 16, 13, 0>) X(HALO_ABL3, 512, conv3x3_bf3_halo_kernel<3, 0, false, 16, 13, 0>) \
+  X(WS256_BN, 768, gemm_bf3_persist_ws256_kernel<0, 1, true, 0, 0>) X(WS256_ABL1, 768, gemm_bf3_persist_ws256_kernel<0, 1, false, 1, 0>) \
+  X(WS256_ABL2, 768, gemm_bf3_persist_ws256_kernel<0, 1, false, 2, 0>) X(WS256_ABL3, 768, gemm_bf3_persist_ws256_kernel<0, 1, false, 3, 0>) \
+  X(WS256_ABL4, 768, gemm_bf3_persist_ws256_kernel<0, 1, false, 4, 0>) X(WS256_IM_BF3, 768, gemm_bf3_persist_ws256_kernel<2, 0, false, 0, 0>) \
+  X(WS256_ROWK_BF3, 768, gemm_bf3_persist_ws256_kernel<0, 0, false, 0, 0>) X(WS_ABL1, 512, gemm_bf3_persist_ws_kernel<0, 1, 3, 0, 4, 4, 1>) \
+  X(WS_ABL2, 512, gemm_bf3_persist_ws_kernel<0, 0, 2, 0, 4, 4, 1>) X(WS_ABL4, 512, gemm_bf3_persist_ws_kernel<0, 3, 3, 0, 4, 4, 1>) \
+  X(WS_ABL5, 512, gemm_bf3_persist_ws_kernel<0, 4, 3, 0, 4, 4, 1>) X(WS_ABL6, 512, gemm_bf3_persist_ws_kernel<0, 6, 3, 1, 4, 4, 1>) \
+  X(PERSIST_IM, 256, gemm_bf3_persist_kernel<2>) X(PERSIST_ROWK, 256, gemm_bf3_persist_kernel<0>) \
+  X(PIPE_ABL1, 256, gemm_bf3_pipe_kernel<0, 2, 1>) X(PIPE_ABL2, 256, gemm_bf3_pipe_kernel<0, 2, 2>) X(PIPE_ABL3, 256, gemm_bf3_pipe_kernel<0, 2, 3>) \
+  X(PIPE_IM, 256, gemm_bf3_pipe_kernel<2, 2, 0>) X(PIPE_ROWK, 256, gemm_bf3_pipe_kernel<0, 2, 0>) \
+  X(PIPE3_IM, 256, gemm_bf3_pipe_kernel<2, 3, 0>) X(PIPE3_ROWK, 256, gemm_bf3_pipe_kernel<0, 3, 0>) \
+  X(T11_ROWK_ABL1, 256, gemm_bf3_kernel<0, 1, 1, 2, 1, 0>) X(T11_ROWK_ABL2, 256, gemm_bf3_kernel<0, 1, 1, 2, 2, 0>) \
+  X(T21_ROWK_S3, 256, gemm_bf3_kernel<0, 2, 1, 3, 0, 0>) X(T21_IM_S3, 256, gemm_bf3_kernel<2, 2, 1, 3, 0, 0>) \
+  X(T22_ROWK_S3, 256, gemm_bf3_kernel<0, 2, 2, 3, 0, 0>) X(T22_IM_S3, 256, gemm_bf3_kernel<2, 2, 2, 3, 0, 0>) \
+  X(T22_ROWK_BF3, 256, gemm_bf3_kernel<0, 2, 2, 2, 0, 0>) X(T22_ROWK_F16, 256, gemm_bf3_kernel<0, 2, 2, 2, 0, 1>) \
+  X(T22_IM_BF3, 256, gemm_bf3_kernel<2, 2, 2, 2, 0, 0>) X(T22_IM_F16, 256, gemm_bf3_kernel<2, 2, 2, 2, 0, 1>)
+#else
+#define DIC_BF3_EXPERIMENT_KERNELS(X)
+#endif
+#define DIC_BF3_ID(id, block, ...) K_##id,
+#define DIC_BF3_ROW(id, block, ...) {#__VA_ARGS__, block, &__VA_ARGS__},
+enum : int { DIC_BF3_KERNELS(DIC_BF3_ID) DIC_BF3_EXPERIMENT_KERNELS(DIC_BF3_ID) };
+static const Bf3Kernel kBf3Kernels[] = { DIC_BF3_KERNELS(DIC_BF3_ROW) DIC_BF3_EXPERIMENT_KERNELS(DIC_BF3_ROW) };
+
+// what a launch may use besides its operands: the remainder-round / few-tiles K split tail_ws_slabs slabs of [64][64] floats in
+// tail_ws (null: no such split); a split-K over every tile (weight gradients) its slices in splitk_ws
+struct Bf3Work { float* tail_ws = nullptr; int tail_ws_slabs = 256, splitk = 1; float* splitk_ws = nullptr; };
+enum : int { BF3_FIX_NONE = 0, BF3_FIX_REM128 = 1, BF3_FIX_TAIL64 = 2 };
+struct Bf3Plan {
+  int kernel = -1, grid = 0;    // row of kBf3Kernels (-1: not eligible) and workgroups
+  Bf3Params p{};                // the kernel's parameters
+  int fixup = BF3_FIX_NONE, fixup_n = 0;    // then nothing / the 128x128 remainder fix-up over fixup_n quadrants / the 64x64 tail fix-up
+  GemmParams fix{};             // over fixup_n tiles (fused with the BatchNorm finalize when the caller asks and the shape allows)
+  int rows = 0, key = 0; double flops = 0, bytes = 0;    // BatchNorm partial-sum rows written; profile key (bench.py decodes it), work
+};
+
+// The launch policy, apart from its launches: no HIP call, and no global written but the error text of a split-K launch without its
+// workspace.  DIC_OK, or 1 for an on-the-fly operand (p.a_raw) that no kernel takes at this shape (launch_bf3 reports why).
+int plan_bf3(const Bf3Params& p_in, const Bf3Work& w, Bf3Plan* pl) {
+  Bf3Params p = p_in;
+  int splitk = w.splitk;
   // tile choice (measured, scripts/bench_bf3.py): bigger per-wave tiles halve the LDS fragment traffic per MFMA and
   // amortise the per-K-tile barrier, but need >= ~2 workgroups per CU to keep 256 CUs busy
   int tmv = 1, tnv = 1;
@@ -2015,8 +2064,8 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
   double fill22 = (double)t22 / ((double)rounds22 * g_bf3_persist_grid);      // how evenly the tiles divide among the CUs
   {   // ... or, with the remainder-round K split (below), among all of them
     const int gmax = g_bf3_remainder_grid, r = (int)(t22 % gmax), fullr = (int)(t22 / gmax), units = ceil_div(p.K, BK3);
-    if (g_bf3_remainder_split && tail_ws && splitk <= 1 && fullr >= 1 && r > 0 && units >= 4) {
-      int sp = std::min(std::min(std::min(gmax / r, units / 2), 16), tail_ws_slabs / 4 / r);
+    if (g_bf3_remainder_split && w.tail_ws && splitk <= 1 && fullr >= 1 && r > 0 && units >= 4) {
+      int sp = std::min(std::min(std::min(gmax / r, units / 2), 16), w.tail_ws_slabs / 4 / r);
       while (sp > 1 && (sp - 1) * ceil_div(units, sp) >= units) --sp;
       if (sp >= 2) fill22 = std::max(fill22, (double)t22 / ((fullr + (double)ceil_div(units, sp) / units + 0.15) * gmax));
     }
@@ -2027,8 +2076,8 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
   int few_sp = 0;
   {
     const int gmax = g_bf3_remainder_grid, units = ceil_div(p.K, BK3);
-    if (g_bf3_remainder_split && tail_ws && splitk <= 1 && t22 >= 32 && t22 < gmax && units >= 32 && !narrow_bn) {
-      int sp = std::min(std::min(std::min(gmax / (int)t22, units / 8), 16), tail_ws_slabs / 4 / (int)t22);
+    if (g_bf3_remainder_split && w.tail_ws && splitk <= 1 && t22 >= 32 && t22 < gmax && units >= 32 && !narrow_bn) {
+      int sp = std::min(std::min(std::min(gmax / (int)t22, units / 8), 16), w.tail_ws_slabs / 4 / (int)t22);
       while (sp > 1 && (sp - 1) * ceil_div(units, sp) >= units) --sp;
       if (sp >= 2 && t22 * sp >= 160) few_sp = sp;
     }
@@ -2049,18 +2098,13 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
     const long long t42 = (long long)ceil_div(p.M, 256) * ceil_div(p.N, 128);
     const int rounds42 = (int)((t42 + g_bf3_persist_grid - 1) / g_bf3_persist_grid);
     const double fill42 = (double)t42 / ((double)rounds42 * g_bf3_persist_grid);
-    // (with the on-the-fly operand - round 4, switch 107: conv3 reading conv2's raw output - only without residual / fp32 copy)
-#ifdef DIC_EXPERIMENTS      // parked (see the kernel's header): correct, bit-identical to the plane route, neutral in the step
+    // (with the on-the-fly operand - round 4, switch 107: conv3 reading conv2's raw output - only without residual / fp32 copy; parked
+    //  in the experiments build: correct, bit-identical to the plane route, neutral in the step)
     const bool bna_ok = !p.a_raw || (g_bf3_ws256_bn != 0 && !p.a_res && !p.a_out && p.K >= 128 && p.K <= kWs256BnTab);
-#else
-    const bool bna_ok = !p.a_raw;
-#endif
     if (g_bf3_force == 0 && g_bf3_ws256 != 0 && p.fmt == 1 && bna_ok && p.A.kind == OPK_ROWK && persist && few_sp == 0 && g_bf3_ws && plain_ep &&
         t42 >= 192 && fill42 >= 0.75 && p.K >= 64)
       ws256 = true;
-#ifdef DIC_EXPERIMENTS
     if (g_bf3_force == 26) ws256 = persist_ok && plain_ep;
-#endif
   }
   // 3x3 convolutions of 14x14 maps: the LDS-halo kernel
   const ConvGeom& cg = p.A.g;
@@ -2074,7 +2118,7 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
   const bool pipe = tmv == 2 && tnv == 2 && g_bf3_force != 22;       // 128x128 (experiments build: the deep-pipelined kernel when not persistent; 22: the plain loop)
   persist = persist && pipe;
   p.mtiles = ceil_div(p.M, 64 * tmv); p.ntiles = ceil_div(p.N, 64 * tnv);
-  g_last_mtiles = p.mtiles;
+  pl->rows = p.mtiles;
   p.splitk = 1; p.ws = nullptr;
   if (p.fmt != 1) p.ep.alpha = 1.0f;
   const int T = p.mtiles * p.ntiles, nk = ceil_div(p.K, BK3);
@@ -2083,21 +2127,21 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
   int tail_tiles = 0;
   if (splitk > 1) {   // split-K over every tile (weight gradients: few tiles, very long K): all tiles go through the
                       // slice + tail_fixup machinery, slices summed in fixed order
-    DIC_REQUIRE(splitk_ws != nullptr && splitk <= 16, "gemm_bf3: split-K needs a workspace and <= 16 slices");
+    DIC_REQUIRE(w.splitk_ws != nullptr && splitk <= 16, "gemm_bf3: split-K needs a workspace and <= 16 slices");
     tmv = 1; tnv = 1;
     p.mtiles = ceil_div(p.M, 64); p.ntiles = ceil_div(p.N, 64);
-    g_last_mtiles = p.mtiles;
+    pl->rows = p.mtiles;
     const int T2 = p.mtiles * p.ntiles;
     splitk = std::min(splitk, std::max(1, nk / 2));
-    tail_tiles = T2; p.tail_first_tile = 0; p.tail_first_block = 0; p.tail_split = splitk; p.tail_ws = splitk_ws;
+    tail_tiles = T2; p.tail_first_tile = 0; p.tail_first_block = 0; p.tail_split = splitk; p.tail_ws = w.splitk_ws;
     total = T2 * splitk;
   } else
-  if (tail_ws && tmv == 1 && tnv == 1 && g_bf3_tail_mode != 1) {
+  if (w.tail_ws && tmv == 1 && tnv == 1 && g_bf3_tail_mode != 1) {
     const int r = T % 256;
     int sp = r > 0 ? 256 / r : 0;
     sp = std::min(sp, std::min(nk / 2, g_bf3_tail_mode == 3 ? 4 : 16));
     if (r > 0 && r <= 128 && sp >= 2 && (T < 7 * 256 || g_bf3_tail_mode == 2)) {
-      tail_tiles = r; p.tail_first_tile = T - r; p.tail_first_block = T - r; p.tail_split = sp; p.tail_ws = tail_ws;
+      tail_tiles = r; p.tail_first_tile = T - r; p.tail_first_block = T - r; p.tail_split = sp; p.tail_ws = w.tail_ws;
       total = (T - r) + r * sp;
     }
   }
@@ -2112,35 +2156,29 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
     const int units = halo ? cg.C / BK3 : nk;                 // what a slice is made of
     const int gmax = g_bf3_remainder_grid;                     // CUs a split launch may use
     const int r = T % gmax, fullr = T / gmax;
-    if (fullr == 0 && few_sp > 0 && !halo && g_bf3_remainder_split && tail_ws) {      // few tiles, long K: every tile in slices
+    if (fullr == 0 && few_sp > 0 && !halo && g_bf3_remainder_split && w.tail_ws) {      // few tiles, long K: every tile in slices
       persist_grid = r * few_sp; rem128 = r;
-      p.tail_first_tile = 0; p.tail_split = few_sp; p.tail_ws = tail_ws;
+      p.tail_first_tile = 0; p.tail_split = few_sp; p.tail_ws = w.tail_ws;
       p.few_remap = g_bf3_few_remap;
     } else
-    if (g_bf3_remainder_split && tail_ws && (plain_ep || !halo) && fullr >= 1 && r > 0 && units >= 4 && !narrow) {      // (the fix-up works on whole 64x64 quadrants of N % 128 == 0)
+    if (g_bf3_remainder_split && w.tail_ws && (plain_ep || !halo) && fullr >= 1 && r > 0 && units >= 4 && !narrow) {      // (the fix-up works on whole 64x64 quadrants of N % 128 == 0)
       // tail_ws holds tail_ws_slabs slabs of [64][64] floats (kGemmTailWsBytes = 256 for callers of the C ABI, 1024 inside the
       // ResNet workspace); a piece writes four (one per consumer wave): r * sp <= slabs / 4
-      const int kSlabs = tail_ws_slabs;
+      const int kSlabs = w.tail_ws_slabs;
       int sp = std::min(std::min(std::min(gmax / r, units / 2), 16), kSlabs / 4 / r);
       while (sp > 1 && (sp - 1) * ceil_div(units, sp) >= units) --sp;      // no empty slice
       const double longest_now = (double)ceil_div(T, persist_grid);
       const double longest_split = fullr + (sp > 1 ? (double)ceil_div(units, sp) / units : 1.0) + 0.15;     // + the fix-up launch
       if (sp >= 2 && r * sp <= gmax && r * 4 * sp <= kSlabs && longest_split + 0.2 <= longest_now) {
         persist_grid = gmax; rem128 = r;
-        p.tail_first_tile = T - r; p.tail_split = sp; p.tail_ws = tail_ws;
+        p.tail_first_tile = T - r; p.tail_split = sp; p.tail_ws = w.tail_ws;
       }
     }
   }
   const bool halo_bna = halo && p.a_raw && p.fmt == 1 && !p.a_res && !p.a_out && cg.C <= kHaloBnTab && g_bf3_ablate == 0;      // 3x3 halo kernel with the on-the-fly operand
   const bool ws256_bna = ws256 && persist && !halo && p.a_raw != nullptr;
-  if (p.a_raw && !halo_bna && !ws256_bna && !(persist && !halo && !ws256 && g_bf3_ws && g_bf3_ablate == 0 && !im)) {      // on-the-fly operand: persistent 1x1 kernel, the halo kernel, or nothing
-    if (!probe && !im)      // (a caller that gets 1 takes the plane route; one that cannot - dic_debug_conv1x1_bn* - reports this text)
-      set_last_error("conv1x1 with on-the-fly BatchNorm operand: shape M=%d C=%d -> CO=%d is not eligible (the launch policy keeps it off "
-                     "the persistent 128x128 kernel: needs CO %% 128 == 0, C %% 32 == 0, C > 32 and enough output tiles to fill the CUs); "
-                     "nothing was launched", p.M, p.K, p.N);
+  if (p.a_raw && !halo_bna && !ws256_bna && !(persist && !halo && !ws256 && g_bf3_ws && g_bf3_ablate == 0 && !im))      // on-the-fly operand: persistent 1x1 kernel, the halo kernel, or nothing
     return 1;
-  }
-  if (probe) return DIC_OK;                 // conv1x1_bf3_bn_eligible: the decision only
   // algorithmic HBM bytes of the launch (bench.py roofline): every operand element read once, the output written once.  Plane operands
   // cost 2 B per plane and element; an im2col A operand is its input image (each pixel read once, not once per tap); the on-the-fly
   // operand reads the raw fp32 tensor (+ the residual) and may write the fp32 copy of its input
@@ -2149,168 +2187,101 @@ static int launch_bf3(Bf3Params p, hipStream_t st, float* tail_ws, int splitk = 
   else if (p.a_raw) abytes += (double)p.M * p.K * 4.0 * (1 + (p.a_res ? 1 : 0) + (p.a_out ? 1 : 0));
   else if (im) abytes += (double)(p.M / std::max(1, cg.OH * cg.OW)) * cg.H * cg.W * cg.C * 2.0 * (p.fmt == 1 ? 2 : 3);
   else abytes += (double)p.M * p.K * 2.0 * (p.fmt == 1 ? 2 : 3);
-  gemm_profile_mark_begin(st, 2.0 * p.M * p.N * (double)p.K, (p.fmt == 1 ? 3000 : 2000) + (p.a_raw ? OPK_ROWK_BN : p.A.kind) * 10 + (halo ? 6 : (persist && ws256) ? 7 : (persist && !g_bf3_ws) ? 8 : persist ? 5 : pipe ? 4 : (tmv - 1) * 2 + (tnv - 1)), abytes);
-  if (persist && (halo || !ws256) && (halo || g_bf3_ws) && g_bf3_ablate == 0) {      // the product's 128x128 kernels
-    g_last_mtiles = 2 * p.mtiles;          // statistics rows per 64-row wave tile
+  pl->flops = 2.0 * p.M * p.N * (double)p.K; pl->bytes = abytes;
+  pl->key = (p.fmt == 1 ? 3000 : 2000) + (p.a_raw ? OPK_ROWK_BN : p.A.kind) * 10 + (halo ? 6 : (persist && ws256) ? 7 : (persist && !g_bf3_ws) ? 8 : persist ? 5 : pipe ? 4 : (tmv - 1) * 2 + (tnv - 1));
+  const bool ilv = g_bf3_halo_ilv != 0, f16 = p.fmt == 1;
+  const bool ws_main = persist && (halo || !ws256) && (halo || g_bf3_ws) && g_bf3_ablate == 0;      // the product's 128x128 kernels
+  int k, grid = total;
+  if (ws_main) {
+    pl->rows = 2 * p.mtiles;          // statistics rows per 64-row wave tile
     // as few workgroups as give the same number of tiles per workgroup: the CUs left over serve the other stream's kernels
-    const int grid = persist_grid;
-#ifdef DIC_EXPERIMENTS
-    if (p.a_raw && (g_bf3_bn_ablate & 1)) p.a_res = nullptr;
-    if (p.a_raw && (g_bf3_bn_ablate & 2)) p.a_out = nullptr;
-#endif
-    if (p.fmt == 1) {
-#ifdef DIC_EXPERIMENTS
-      if (halo_bna && cg.W == 56) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<0, 1, true, 58, 7, 1>), dim3(grid), dim3(512), 0, st, p);
-      else
-#endif
-      if (halo_bna && cg.W == 28 && g_bf3_halo_ilv) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<0, 1, true, 32, 9, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna && cg.W == 28) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<0, 1, true, 32, 9>), dim3(grid), dim3(512), 0, st, p);
-#ifdef DIC_EXPERIMENTS
-      else if (halo_bna && g_bf3_halo_bna_ablate == 1) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<1, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna && g_bf3_halo_bna_ablate == 2) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<2, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna && g_bf3_halo_bna_ablate == 3) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<3, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna && g_bf3_halo_bna_ablate == 4) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<4, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna && g_bf3_halo_bna_ablate == 8) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<8, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna && g_bf3_halo_bna_ablate == 12) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<12, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-#endif
-      else if (halo_bna && g_bf3_halo_ilv) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<0, 1, true, 16, 13, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo_bna) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<0, 1, true>), dim3(grid), dim3(512), 0, st, p);
-      else if (p.a_raw && g_bf3_producers == 8 && g_bf3_slots == 6) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK_BN, 0, 3, 1, 8, 6>), dim3(grid), dim3(768), 0, st, p);
-      else if (p.a_raw && g_bf3_producers == 8 && !g_bf3_halo_ilv) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK_BN, 0, 3, 1, 8, 4, 0>), dim3(grid), dim3(768), 0, st, p);
-      else if (p.a_raw && g_bf3_producers == 8) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK_BN, 0, 3, 1, 8>), dim3(grid), dim3(768), 0, st, p);
-      else if (p.a_raw) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK_BN, 0, 3, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (halo) hipLaunchKernelGGL((conv3x3_bf3_halo_kernel<0, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (im && !g_bf3_halo_ilv) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_IM2COL, 0, 3, 1, 4, 4, 0>), dim3(grid), dim3(512), 0, st, p);
-      else if (im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_IM2COL, 0, 3, 1>), dim3(grid), dim3(512), 0, st, p);
-      else if (!g_bf3_halo_ilv) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 0, 3, 1, 4, 4, 0>), dim3(grid), dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 0, 3, 1>), dim3(grid), dim3(512), 0, st, p);
-    } else
-    if (p.a_raw) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK_BN>), dim3(grid), dim3(512), 0, st, p);
-    else
-    if (halo) hipLaunchKernelGGL(conv3x3_bf3_halo_kernel<0>, dim3(grid), dim3(512), 0, st, p);
-    else if (im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_IM2COL>), dim3(grid), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK>), dim3(grid), dim3(512), 0, st, p);
-  }
-  else if (persist && ws256 && !halo) {
+    grid = persist_grid;
+    if (!f16) k = p.a_raw ? K_WS_BN_BF3 : halo ? K_HALO_BF3 : im ? K_WS_IM_BF3 : K_WS_ROWK_BF3;
+    else if (halo_bna && cg.W == 28) k = ilv ? K_HALO_BN28_ILV : K_HALO_BN28;
+    else if (halo_bna) k = ilv ? K_HALO_BN_ILV : K_HALO_BN;
+    else if (p.a_raw && g_bf3_producers == 8) k = g_bf3_slots == 6 ? K_WS_BN8_S6 : ilv ? K_WS_BN8 : K_WS_BN8_BLOCK;
+    else if (p.a_raw) k = K_WS_BN4;
+    else if (halo) k = K_HALO_F16;
+    else if (im) k = ilv ? K_WS_IM_F16 : K_WS_IM_F16_BLOCK;
+    else k = ilv ? K_WS_ROWK_F16 : K_WS_ROWK_F16_BLOCK;
+  } else if (persist && ws256 && !halo) {      // (ws256: f16x2, row-major A)
     p.mtiles = ceil_div(p.M, 256); p.ntiles = ceil_div(p.N, 128);
-    g_last_mtiles = ceil_div(p.M, 64);     // statistics rows per 64-row wave tile
-    const int T4 = p.mtiles * p.ntiles, grid = ceil_div(T4, ceil_div(T4, g_bf3_persist_grid));
-#ifdef DIC_EXPERIMENTS
-    if (ws256_bna) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1, true>), dim3(grid), dim3(768), 0, st, p);
-    else
-#endif
-#ifdef DIC_EXPERIMENTS
-    if (p.fmt == 1 && !im && g_bf3_ws256_ablate == 1) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1, false, 1>), dim3(grid), dim3(768), 0, st, p);
-    else if (p.fmt == 1 && !im && g_bf3_ws256_ablate == 2) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1, false, 2>), dim3(grid), dim3(768), 0, st, p);
-    else if (p.fmt == 1 && !im && g_bf3_ws256_ablate == 3) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1, false, 3>), dim3(grid), dim3(768), 0, st, p);
-    else if (p.fmt == 1 && !im && g_bf3_ws256_ablate == 4) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1, false, 4>), dim3(grid), dim3(768), 0, st, p);
-    else
-#endif
-    if (p.fmt == 1 && !im && g_bf3_halo_ilv) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1, false, 0, 1>), dim3(grid), dim3(768), 0, st, p);
-    else if (p.fmt == 1 && !im) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK, 1>), dim3(grid), dim3(768), 0, st, p);
-#ifdef DIC_EXPERIMENTS
-    else if (im) hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_IM2COL>), dim3(grid), dim3(768), 0, st, p);
-    else hipLaunchKernelGGL((gemm_bf3_persist_ws256_kernel<OPK_ROWK>), dim3(grid), dim3(768), 0, st, p);
-#else
-    else DIC_REQUIRE(false, "gemm_bf3: no 256x128 kernel for this operand kind / format in the product library");
-#endif
+    pl->rows = ceil_div(p.M, 64);     // statistics rows per 64-row wave tile
+    const int T4 = p.mtiles * p.ntiles; grid = ceil_div(T4, ceil_div(T4, g_bf3_persist_grid));
+    k = ilv ? K_WS256_ILV : K_WS256_BLOCK;
+  } else {
+    static const int tiles[2][2][2] = {{{K_T11_ROWK_BF3, K_T11_ROWK_F16}, {K_T11_IM_BF3, K_T11_IM_F16}},      // [128x64][im2col][f16x2]
+                                       {{K_T21_ROWK_BF3, K_T21_ROWK_F16}, {K_T21_IM_BF3, K_T21_IM_F16}}};
+    k = tiles[tmv == 2][im][f16];
   }
 #ifdef DIC_EXPERIMENTS
-  else if (persist) {                    // ablations of the product kernels, and the persistent kernel without producer waves
-    g_last_mtiles = 2 * p.mtiles;
-    const int grid = ceil_div(T, ceil_div(T, g_bf3_persist_grid));
-    if (!halo && g_bf3_ws && g_bf3_ablate == 2 && !im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 0, 2>), dim3(grid), dim3(512), 0, st, p);
-    else if (!halo && g_bf3_ws && g_bf3_ablate == 1 && !im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 1>), dim3(grid), dim3(512), 0, st, p);
-    else if (!halo && g_bf3_ws && g_bf3_ablate == 4 && !im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 3>), dim3(grid), dim3(512), 0, st, p);
-    else if (!halo && g_bf3_ws && g_bf3_ablate == 5 && !im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 4>), dim3(grid), dim3(512), 0, st, p);
-    else if (!halo && g_bf3_ws && g_bf3_ablate == 6 && !im && p.fmt == 1) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 6, 3, 1>), dim3(grid), dim3(512), 0, st, p);      // (56: f16x2, every other barrier skipped - timing only)
-    else if (!halo && g_bf3_ws && g_bf3_ablate == 0 && !im && p.fmt == 1) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK, 0, 3, 1>), dim3(grid), dim3(512), 0, st, p);
-    else if (!halo && g_bf3_ws) { if (im) hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_IM2COL>), dim3(grid), dim3(512), 0, st, p);
-                                  else hipLaunchKernelGGL((gemm_bf3_persist_ws_kernel<OPK_ROWK>), dim3(grid), dim3(512), 0, st, p); }
-    else if (halo && g_bf3_ablate == 1) hipLaunchKernelGGL(conv3x3_bf3_halo_kernel<1>, dim3(grid), dim3(512), 0, st, p);
-    else if (halo && g_bf3_ablate == 2) hipLaunchKernelGGL(conv3x3_bf3_halo_kernel<2>, dim3(grid), dim3(512), 0, st, p);
-    else if (halo) hipLaunchKernelGGL(conv3x3_bf3_halo_kernel<3>, dim3(grid), dim3(512), 0, st, p);
-    else if (im) hipLaunchKernelGGL((gemm_bf3_persist_kernel<OPK_IM2COL>), dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_bf3_persist_kernel<OPK_ROWK>), dim3(grid), dim3(256), 0, st, p);
-  } else if (pipe && g_bf3_ablate > 0 && !im) {
-    if (g_bf3_ablate == 1) hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_ROWK, 2, 1>), dim3(total), dim3(256), 0, st, p);
-    else if (g_bf3_ablate == 2) hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_ROWK, 2, 2>), dim3(total), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_ROWK, 2, 3>), dim3(total), dim3(256), 0, st, p);
-  } else if (pipe && g_bf3_stages == 3) {
-    if (im) hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_IM2COL, 3>), dim3(total), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_ROWK, 3>), dim3(total), dim3(256), 0, st, p);
-  } else if (pipe) {
-    if (im) hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_IM2COL, 2>), dim3(total), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gemm_bf3_pipe_kernel<OPK_ROWK, 2>), dim3(total), dim3(256), 0, st, p);
-  } else if (tmv == 2 && tnv == 2) { if (im) launch_bf3_variant<OPK_IM2COL, 2, 2>(p, total, st); else launch_bf3_variant<OPK_ROWK, 2, 2>(p, total, st); }
-  else if (!im && g_bf3_ablate == 1 && tmv == 1) hipLaunchKernelGGL((gemm_bf3_kernel<OPK_ROWK, 1, 1, 2, 1>), dim3(total), dim3(256), 0, st, p);
-  else if (!im && g_bf3_ablate == 2 && tmv == 1) hipLaunchKernelGGL((gemm_bf3_kernel<OPK_ROWK, 1, 1, 2, 2>), dim3(total), dim3(256), 0, st, p);
+  // Experiments build: the parked forms, the ablations (timing only), the persistent kernel without producer waves and the ring depth 3
+  // replace the product's kernel where their switches say so
+  if (ws_main) {
+    if (p.a_raw && (g_bf3_bn_ablate & 1)) p.a_res = nullptr; if (p.a_raw && (g_bf3_bn_ablate & 2)) p.a_out = nullptr;
+    const int hab = g_bf3_halo_bna_ablate;
+    if (f16 && halo_bna && cg.W == 56) k = K_HALO_BN56;
+    else if (f16 && halo_bna && cg.W != 28 && (hab == 1 || hab == 2 || hab == 3 || hab == 4 || hab == 8 || hab == 12))
+      k = hab == 1 ? K_HALO_BN_ABL1 : hab == 2 ? K_HALO_BN_ABL2 : hab == 3 ? K_HALO_BN_ABL3 : hab == 4 ? K_HALO_BN_ABL4 : hab == 8 ? K_HALO_BN_ABL8 : K_HALO_BN_ABL12;
+  } else if (persist && ws256 && !halo) {
+    if (ws256_bna) k = K_WS256_BN;
+    else if (f16 && !im && g_bf3_ws256_ablate >= 1 && g_bf3_ws256_ablate <= 4) k = g_bf3_ws256_ablate == 1 ? K_WS256_ABL1 : g_bf3_ws256_ablate == 2 ? K_WS256_ABL2 : g_bf3_ws256_ablate == 3 ? K_WS256_ABL3 : K_WS256_ABL4;
+    else if (!f16 || im) k = im ? K_WS256_IM_BF3 : K_WS256_ROWK_BF3;
+  } else if (persist) {                    // ablations of the product kernels, and the persistent kernel without producer waves
+    pl->rows = 2 * p.mtiles;
+    grid = ceil_div(T, ceil_div(T, g_bf3_persist_grid));
+    const int ab = g_bf3_ablate;
+    if (!halo && g_bf3_ws && !im && (ab == 1 || ab == 2 || ab == 4 || ab == 5 || (ab == 6 && f16)))
+      k = ab == 1 ? K_WS_ABL1 : ab == 2 ? K_WS_ABL2 : ab == 4 ? K_WS_ABL4 : ab == 5 ? K_WS_ABL5 : K_WS_ABL6;
+    else if (!halo && g_bf3_ws && ab == 0 && !im && f16) k = K_WS_ROWK_F16;
+    else if (!halo && g_bf3_ws) k = im ? K_WS_IM_BF3 : K_WS_ROWK_BF3;
+    else if (halo) k = ab == 1 ? K_HALO_ABL1 : ab == 2 ? K_HALO_ABL2 : K_HALO_ABL3;
+    else k = im ? K_PERSIST_IM : K_PERSIST_ROWK;
+  } else if (pipe && g_bf3_ablate > 0 && !im) k = g_bf3_ablate == 1 ? K_PIPE_ABL1 : g_bf3_ablate == 2 ? K_PIPE_ABL2 : K_PIPE_ABL3;
+  else if (pipe) k = g_bf3_stages == 3 ? (im ? K_PIPE3_IM : K_PIPE3_ROWK) : (im ? K_PIPE_IM : K_PIPE_ROWK);
+  else if (tmv == 2 && tnv == 2 && g_bf3_stages == 3) k = im ? K_T22_IM_S3 : K_T22_ROWK_S3;
+  else if (tmv == 2 && tnv == 2) k = im ? (f16 ? K_T22_IM_F16 : K_T22_IM_BF3) : (f16 ? K_T22_ROWK_F16 : K_T22_ROWK_BF3);
+  else if (!im && tmv == 1 && (g_bf3_ablate == 1 || g_bf3_ablate == 2)) k = g_bf3_ablate == 1 ? K_T11_ROWK_ABL1 : K_T11_ROWK_ABL2;
+  else if (tmv == 2 && g_bf3_stages == 3) k = im ? K_T21_IM_S3 : K_T21_ROWK_S3;
 #endif
-  else if (tmv == 2) { if (im) launch_bf3_variant<OPK_IM2COL, 2, 1>(p, total, st); else launch_bf3_variant<OPK_ROWK, 2, 1>(p, total, st); }
-  else { if (im) launch_bf3_variant<OPK_IM2COL, 1, 1>(p, total, st); else launch_bf3_variant<OPK_ROWK, 1, 1>(p, total, st); }
-  DIC_LAUNCH_CHECK();
-  gemm_profile_mark_end(st);
-  if (rem128 > 0) {        // finish the remainder tiles of a persistent launch (quadrant-wise: the fix-up works on 64x64 tiles)
-    GemmParams g{};
-    g.M = p.M; g.N = p.N; g.K = p.K; g.ep = p.ep; g.mtiles = ceil_div(p.M, 64); g.ntiles = ceil_div(p.N, 64);      // (ep.alpha: 1, or the f16x2 unscale of the raw sums)
-    g.tail_split = p.tail_split; g.tail_ws = p.tail_ws;
-    g.tail128_first = p.tail_first_tile; g.tail128_ntiles = p.ntiles;
-    DIC_TRY(gemm_launch_tail_fixup(g, rem128 * 4, st));
-  }
-  if (tail_tiles > 0) {
-    GemmParams g{};
-    g.M = p.M; g.N = p.N; g.K = p.K; g.ep = p.ep; g.mtiles = p.mtiles; g.ntiles = p.ntiles;
-    g.tail_first_tile = p.tail_first_tile; g.tail_split = p.tail_split; g.tail_ws = p.tail_ws;
-    if (bn_fuse && gemm_tail_fixup_bn_eligible(g, tail_tiles)) {      // fix-up + BatchNorm finalize in one launch
-      DIC_TRY(gemm_launch_tail_fixup_bn(g, tail_tiles, *bn_fuse, st));
-      if (bn_fused) *bn_fused = 1;
-    } else {
-      DIC_TRY(gemm_launch_tail_fixup(g, tail_tiles, st));
-    }
-  }
+  pl->kernel = k; pl->grid = grid; pl->p = p;
+  pl->fixup = rem128 > 0 ? BF3_FIX_REM128 : tail_tiles > 0 ? BF3_FIX_TAIL64 : BF3_FIX_NONE;
+  pl->fixup_n = rem128 > 0 ? rem128 * 4 : tail_tiles;     // (the remainder fix-up works quadrant-wise, on 64x64 tiles)
+  GemmParams& g = pl->fix;      // (ep.alpha: 1, or the f16x2 unscale of the raw sums)
+  g.M = p.M; g.N = p.N; g.K = p.K; g.ep = p.ep; g.tail_split = p.tail_split; g.tail_ws = p.tail_ws;
+  g.mtiles = rem128 > 0 ? ceil_div(p.M, 64) : p.mtiles; g.ntiles = rem128 > 0 ? ceil_div(p.N, 64) : p.ntiles;
+  if (rem128 > 0) { g.tail128_first = p.tail_first_tile; g.tail128_ntiles = p.ntiles; } else g.tail_first_tile = p.tail_first_tile;
   return DIC_OK;
 }
 
-#ifdef DIC_EXPERIMENTS
-// conv3-style 1x1 convolution on the A-stationary kernel (conv1x1_astat_bn_kernel): y_raw[M][CO] = relu(raw[M][C] * scale + shift) . W^T,
-// f16x2 weights planes (scale in out_scale = 1 / (kF16ActScale * w_scale)); BatchNorm partials per 32-row wave tile: *mtiles_out rows
-static int g_astat = 0;                  // codes 110 / 111 (experiments build): off (default) / on
-void conv1x1_astat_switch(int on) { g_astat = on; }
-bool conv1x1_astat_eligible(int M, int C, int CO) {
-  return g_astat != 0 && (C == 128 || C == 256) && CO % 128 == 0 && CO >= 128 && M >= 64 && (long long)(CO + 1) * C * 2 < (1ll << 31);
-}
-int conv1x1_astat_bn(const float* raw, const float* scale, const float* shift, int relu, int M, int C, const unsigned short* const w_planes[3],
-                     int CO, float* y, float* bn_partial, int* mtiles_out, hipStream_t st, float out_scale, unsigned* status) {
-  DIC_REQUIRE(raw && scale && shift && y && w_planes && w_planes[0] && w_planes[1], "conv1x1_astat_bn: null pointer");
-  if (!conv1x1_astat_eligible(M, C, CO)) return 1;
-  Bf3Params p{};
-  p.M = M; p.N = CO; p.K = C;
-  p.B.p[0] = w_planes[0]; p.B.p[1] = w_planes[1]; p.B.p[2] = nullptr;
-  p.B.kind = OPK_ROWK; p.B.ld = C; p.B.paired = 1;
-  p.a_raw = raw; p.a_scale = scale; p.a_shift = shift; p.a_ld = C; p.a_relu = relu; p.status = status;
-  p.ep = ep_store(y, CO, nullptr, ACT_NONE);
-  p.ep.stats = bn_partial;
-  p.ep.alpha = out_scale;
-  p.fmt = 1;
-  const int mt = ceil_div(M, 64);
-  p.mtiles = mt; p.ntiles = CO / 128;
-  gemm_profile_mark_begin(st, 2.0 * M * CO * (double)C, 3000 + OPK_ROWK_BN * 10 + 9,
-                          4.0 * ((double)M * C + (double)CO * C + (double)M * CO));
-  if (C == 256) hipLaunchKernelGGL(conv1x1_astat_bn_kernel<8>, dim3(mt), dim3(512), 0, st, p);
-  else hipLaunchKernelGGL(conv1x1_astat_bn_kernel<4>, dim3(mt), dim3(512), 0, st, p);
+static int launch_bf3(const Bf3Params& p, const Bf3Work& w, hipStream_t st, const BnFuseArgs* bn_fuse = nullptr, int* bn_fused = nullptr,
+                      int* rows = nullptr) {
+  Bf3Plan pl;
+  if (bn_fused) *bn_fused = 0;
+  const int rc = plan_bf3(p, w, &pl);
+  if (rc == 1 && p.A.kind != OPK_IM2COL)      // (a caller that gets 1 takes the plane route; one that cannot - dic_debug_conv1x1_bn* - reports this text)
+    set_last_error("conv1x1 with on-the-fly BatchNorm operand: shape M=%d C=%d -> CO=%d is not eligible (the launch policy keeps it off "
+                   "the persistent 128x128 kernel: needs CO %% 128 == 0, C %% 32 == 0, C > 32 and enough output tiles to fill the CUs); "
+                   "nothing was launched", p.M, p.K, p.N);
+  if (rc != DIC_OK) return rc;
+  const Bf3Kernel& kern = kBf3Kernels[pl.kernel];
+  void* args[] = {&pl.p};      // (the kernels' one parameter: what hipLaunchKernelGGL would pass)
+  gemm_profile_mark_begin(st, pl.flops, pl.key, pl.bytes);
+  DIC_CHECK_HIP(hipLaunchKernel(reinterpret_cast<const void*>(kern.fn), dim3(pl.grid), dim3(kern.block), args, 0, st));
   DIC_LAUNCH_CHECK();
   gemm_profile_mark_end(st);
-  if (mtiles_out) *mtiles_out = 2 * mt;
+  const bool fuse = pl.fixup == BF3_FIX_TAIL64 && bn_fuse && gemm_tail_fixup_bn_eligible(pl.fix, pl.fixup_n);      // + BatchNorm finalize
+  if (fuse) DIC_TRY(gemm_launch_tail_fixup_bn(pl.fix, pl.fixup_n, *bn_fuse, st));
+  else if (pl.fixup != BF3_FIX_NONE) DIC_TRY(gemm_launch_tail_fixup(pl.fix, pl.fixup_n, st));
+  if (bn_fused && fuse) *bn_fused = 1;
+  if (rows) *rows = pl.rows;
   return DIC_OK;
 }
-#endif
 
 // y_raw[B,OH,OW,CO] (fp32) = conv(x planes NHWC, w planes OHWI); BN partial sums like conv_fwd
-int conv_fwd_bf3(const unsigned short* const x_planes[3], const ConvDesc& d, const unsigned short* const w_planes[3],
-                 float* y, float* bn_partial, int* mtiles_out, float* tail_ws, hipStream_t st, const float* bias,
-                 const BnFuseArgs* bn_fuse, int* bn_fused, int act, int tail_ws_slabs, int fmt, float out_scale,
-                 const float* alpha_dev0, const float* alpha_dev1) {
-  DIC_REQUIRE(!d.in_nchw && d.C % 32 == 0 && d.KH * d.KW <= 32, "conv_fwd_bf3: needs NHWC input with C %% 32 == 0");
+static Bf3Params conv_fwd_bf3_params(const unsigned short* const x_planes[3], const ConvDesc& d, const unsigned short* const w_planes[3],
+                                     float* y, float* bn_partial, const float* bias, int act, int fmt, float out_scale,
+                                     const float* alpha_dev0 = nullptr, const float* alpha_dev1 = nullptr) {
   Bf3Params p{};
   p.M = d.M(); p.N = d.CO; p.K = d.K();
   for (int i = 0; i < 3; ++i) { p.A.p[i] = x_planes[i]; p.B.p[i] = w_planes[i]; }
@@ -2318,15 +2289,18 @@ int conv_fwd_bf3(const unsigned short* const x_planes[3], const ConvDesc& d, con
   p.A.ld = d.C; p.A.g = d.geom(); p.A.paired = 1;
   p.B.kind = OPK_ROWK; p.B.ld = d.K(); p.B.paired = 1;
   p.ep = ep_store(y, d.CO, bias, act);
-  p.ep.stats = bn_partial;
-  p.fmt = fmt;
-  if (fmt == 1) {      // 1 / (activation scale * weight scale): the f16x2 planes hold scaled values; factors chosen on the device come by pointer
-    p.ep.alpha = out_scale; p.ep.alpha_dev[0] = alpha_dev0; p.ep.alpha_dev[1] = alpha_dev1;
-  }
-  if (bn_fused) *bn_fused = 0;
-  DIC_TRY(launch_bf3(p, st, tail_ws, 1, nullptr, bn_fuse, bn_fused, tail_ws_slabs));
-  if (mtiles_out) *mtiles_out = g_last_mtiles;
-  return DIC_OK;
+  p.ep.stats = bn_partial; p.fmt = fmt;
+  // 1 / (activation scale * weight scale): the f16x2 planes hold scaled values; factors chosen on the device come by pointer
+  if (fmt == 1) { p.ep.alpha = out_scale; p.ep.alpha_dev[0] = alpha_dev0; p.ep.alpha_dev[1] = alpha_dev1; }
+  return p;
+}
+int conv_fwd_bf3(const unsigned short* const x_planes[3], const ConvDesc& d, const unsigned short* const w_planes[3],
+                 float* y, float* bn_partial, int* mtiles_out, float* tail_ws, hipStream_t st, const float* bias,
+                 const BnFuseArgs* bn_fuse, int* bn_fused, int act, int tail_ws_slabs, int fmt, float out_scale,
+                 const float* alpha_dev0, const float* alpha_dev1) {
+  DIC_REQUIRE(!d.in_nchw && d.C % 32 == 0 && d.KH * d.KW <= 32, "conv_fwd_bf3: needs NHWC input with C %% 32 == 0");
+  return launch_bf3(conv_fwd_bf3_params(x_planes, d, w_planes, y, bn_partial, bias, act, fmt, out_scale, alpha_dev0, alpha_dev1),
+                    Bf3Work{tail_ws, tail_ws_slabs}, st, bn_fuse, bn_fused, mtiles_out);
 }
 
 // 1x1 convolution whose input is formed on the fly: y_raw[M][CO] = act(raw[M][C] * scale[C] + shift[C] (+ res[M][C])) . W^T,
@@ -2334,18 +2308,29 @@ int conv_fwd_bf3(const unsigned short* const x_planes[3], const ConvDesc& d, con
 // persistent warp-specialised kernel instead of in a bn_apply_planes pass (20 B per element of HBM traffic and a launch less).
 // act_out (nullable) receives the fp32 input values once.  Returns DIC_OK, 1 when the launch policy would not run this shape on
 // that kernel (nothing launched: the caller takes the bn_apply_planes route), or a negative error.
-// would conv1x1_fwd_bf3_bn run this shape (the launch policy's answer, nothing launched)?
-bool conv1x1_bf3_bn_eligible(int M, int C, int CO, int tail_ws_slabs, int fmt) {
-  if (C % 32 != 0 || C > kBnTabMax || (long long)M * C * 4 >= (1ll << 32)) return false;
-  static float dummy;                         // stands for "a tail workspace is there"; never dereferenced
+static Bf3Params conv1x1_bn_bf3_params(const float* raw, const float* scale, const float* shift, const float* res, int relu, float* act_out,
+                                       int M, int C, const unsigned short* const w_planes[3], int CO, float* y, float* bn_partial, int fmt,
+                                       float out_scale, unsigned* status, const float* res_scale, const float* res_shift) {
   Bf3Params p{};
   p.M = M; p.N = CO; p.K = C;
+  for (int i = 0; i < 3; ++i) { p.A.p[i] = nullptr; p.B.p[i] = w_planes[i]; }
   p.A.kind = OPK_ROWK; p.A.ld = C; p.A.paired = 1;
   p.B.kind = OPK_ROWK; p.B.ld = C; p.B.paired = 1;
-  p.a_raw = &dummy;
-  p.fmt = fmt;
-  p.ep = ep_store(&dummy, CO, nullptr, ACT_NONE);
-  return launch_bf3(p, nullptr, &dummy, 1, nullptr, nullptr, nullptr, tail_ws_slabs, true) == DIC_OK;
+  p.a_raw = raw; p.a_scale = scale; p.a_shift = shift; p.a_res = res; p.a_out = act_out; p.a_ld = C; p.a_relu = relu;
+  p.a_res_scale = res_scale; p.a_res_shift = res_shift; p.status = status;
+  p.ep = ep_store(y, CO, nullptr, ACT_NONE);
+  p.ep.stats = bn_partial; p.fmt = fmt;
+  if (fmt == 1) p.ep.alpha = out_scale;      // 1 / (kF16ActScale * weight scale): the producer waves scale the activations by kF16ActScale
+  return p;
+}
+static bool conv1x1_bn_bf3_shape_ok(int M, int C) { return C % 32 == 0 && C <= kBnTabMax && (long long)M * C * 4 < (1ll << 32); }
+
+// would conv1x1_fwd_bf3_bn run this shape on the input raw with this tail workspace (the launch policy's answer, nothing launched)?
+bool conv1x1_bf3_bn_eligible(const float* raw, int M, int C, int CO, float* tail_ws, int tail_ws_slabs, int fmt) {
+  const unsigned short* const none[3] = {};
+  Bf3Plan pl;
+  return conv1x1_bn_bf3_shape_ok(M, C) && plan_bf3(conv1x1_bn_bf3_params(raw, nullptr, nullptr, nullptr, 1, nullptr, M, C, none, CO, nullptr,
+                                                                        nullptr, fmt, 1.0f, nullptr, nullptr, nullptr), Bf3Work{tail_ws, tail_ws_slabs}, &pl) == DIC_OK;
 }
 
 int conv1x1_fwd_bf3_bn(const float* raw, const float* scale, const float* shift, const float* res, int relu, float* act_out,
@@ -2354,55 +2339,42 @@ int conv1x1_fwd_bf3_bn(const float* raw, const float* scale, const float* shift,
                        float out_scale, unsigned* status, const float* res_scale, const float* res_shift) {
   DIC_REQUIRE(!res_scale || (fmt == 1 && res && res_shift), "conv1x1_fwd_bf3_bn: a BatchNorm on the residual needs the f16x2 format, the residual and both tables");
   DIC_REQUIRE(raw && scale && shift && y && C % 32 == 0 && C <= kBnTabMax, "conv1x1_fwd_bf3_bn: C %% 32 == 0, C <= 2048");
-  if ((long long)M * C * 4 >= (1ll << 32)) {                // the kernel addresses the input with 32-bit byte offsets
+  if (!conv1x1_bn_bf3_shape_ok(M, C)) {                // the kernel addresses the input with 32-bit byte offsets
     set_last_error("conv1x1 with on-the-fly BatchNorm operand: input of %d x %d floats exceeds 4 GiB (32-bit offsets); nothing was launched", M, C);
     return 1;
   }
-  Bf3Params p{};
-  p.M = M; p.N = CO; p.K = C;
-  for (int i = 0; i < 3; ++i) { p.A.p[i] = nullptr; p.B.p[i] = w_planes[i]; }
-  p.A.kind = OPK_ROWK; p.A.ld = C; p.A.paired = 1;
-  p.B.kind = OPK_ROWK; p.B.ld = C; p.B.paired = 1;
-  p.a_raw = raw; p.a_scale = scale; p.a_shift = shift; p.a_res = res; p.a_out = act_out; p.a_ld = C; p.a_relu = relu;
-  p.a_res_scale = res_scale; p.a_res_shift = res_shift;
-  p.status = status;
-  p.ep = ep_store(y, CO, nullptr, ACT_NONE);
-  p.ep.stats = bn_partial;
-  p.fmt = fmt;
-  if (fmt == 1) p.ep.alpha = out_scale;      // 1 / (kF16ActScale * weight scale): the producer waves scale the activations by kF16ActScale
-  if (bn_fused) *bn_fused = 0;
-  const int rc = launch_bf3(p, st, tail_ws, 1, nullptr, bn_fuse, bn_fused, tail_ws_slabs);
-  if (rc != DIC_OK) return rc;
-  if (mtiles_out) *mtiles_out = g_last_mtiles;
-  return DIC_OK;
+  return launch_bf3(conv1x1_bn_bf3_params(raw, scale, shift, res, relu, act_out, M, C, w_planes, CO, y, bn_partial, fmt, out_scale, status,
+                                          res_scale, res_shift),
+                    Bf3Work{tail_ws, tail_ws_slabs}, st, bn_fuse, bn_fused, mtiles_out);
 }
 
 // 3x3 / stride 1 / pad 1 convolution of 14x14 maps whose input is formed on the fly (f16x2 format): y_raw = conv(act(raw * scale[c] +
 // shift[c])), the BatchNorm-apply + ReLU + split of the input done by the producer waves of the LDS-halo kernel (BNA form) instead of
 // a bn_apply_planes pass.  Returns DIC_OK, 1 when the launch policy would not run this shape on that kernel (nothing launched: the
 // caller takes the plane route), or a negative error.
-int conv3x3_fwd_bf3_bn(const float* raw, const float* scale, const float* shift, int relu, const ConvDesc& d,
-                       const unsigned short* const w_planes[3], float* y, float* bn_partial, int* mtiles_out, float* tail_ws,
-                       int tail_ws_slabs, hipStream_t st, const BnFuseArgs* bn_fuse, int* bn_fused, int fmt, float out_scale, unsigned* status) {
-  if (fmt != 1 || d.in_nchw || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad != 1 || d.C % 32 != 0 || d.C > kHaloBnTab ||
-      (long long)d.B * d.H * d.W * d.C * 4 >= (1ll << 32))
-    return 1;
-  DIC_REQUIRE(raw && scale && shift && y, "conv3x3_fwd_bf3_bn: null pointer");
+static bool conv3x3_bn_bf3_shape_ok(const ConvDesc& d, int fmt) {
+  return fmt == 1 && !d.in_nchw && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.C % 32 == 0 && d.C <= kHaloBnTab &&
+         (long long)d.B * d.H * d.W * d.C * 4 < (1ll << 32);
+}
+static Bf3Params conv3x3_bn_bf3_params(const float* raw, const float* scale, const float* shift, int relu, const ConvDesc& d,
+                                       const unsigned short* const w_planes[3], float* y, float* bn_partial, float out_scale, unsigned* status) {
   Bf3Params p{};
   p.M = d.M(); p.N = d.CO; p.K = d.K();
   for (int i = 0; i < 3; ++i) { p.A.p[i] = nullptr; p.B.p[i] = w_planes[i]; }
   p.A.kind = OPK_IM2COL; p.A.ld = d.C; p.A.g = d.geom(); p.A.paired = 1;
   p.B.kind = OPK_ROWK; p.B.ld = d.K(); p.B.paired = 1;
-  p.a_raw = raw; p.a_scale = scale; p.a_shift = shift; p.a_ld = d.C; p.a_relu = relu;
-  p.status = status;
+  p.a_raw = raw; p.a_scale = scale; p.a_shift = shift; p.a_ld = d.C; p.a_relu = relu; p.status = status;
   p.ep = ep_store(y, d.CO, nullptr, ACT_NONE);
-  p.ep.stats = bn_partial;
-  p.fmt = 1; p.ep.alpha = out_scale;
-  if (bn_fused) *bn_fused = 0;
-  const int rc = launch_bf3(p, st, tail_ws, 1, nullptr, bn_fuse, bn_fused, tail_ws_slabs);
-  if (rc != DIC_OK) return rc;
-  if (mtiles_out) *mtiles_out = g_last_mtiles;
-  return DIC_OK;
+  p.ep.stats = bn_partial; p.fmt = 1; p.ep.alpha = out_scale;
+  return p;
+}
+int conv3x3_fwd_bf3_bn(const float* raw, const float* scale, const float* shift, int relu, const ConvDesc& d,
+                       const unsigned short* const w_planes[3], float* y, float* bn_partial, int* mtiles_out, float* tail_ws,
+                       int tail_ws_slabs, hipStream_t st, const BnFuseArgs* bn_fuse, int* bn_fused, int fmt, float out_scale, unsigned* status) {
+  if (!conv3x3_bn_bf3_shape_ok(d, fmt)) return 1;
+  DIC_REQUIRE(raw && scale && shift && y, "conv3x3_fwd_bf3_bn: null pointer");
+  return launch_bf3(conv3x3_bn_bf3_params(raw, scale, shift, relu, d, w_planes, y, bn_partial, out_scale, status),
+                    Bf3Work{tail_ws, tail_ws_slabs}, st, bn_fuse, bn_fused, mtiles_out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2488,6 +2460,21 @@ size_t conv_wgrad_bf3_ws_floats(const ConvDesc& d, int splitk) {
   return n;
 }
 
+// the contraction of the weight gradient and what it may use: the persistent kernel's few-tiles form, or the caller's K split
+static Bf3Params conv_wgrad_bf3_params(const ConvDesc& d, unsigned short* const dyT[3], unsigned short* const pT[3], float* dw_ohwi, int fmt,
+                                       const float* dy_slot, int splitk, float* ws, Bf3Work* w) {
+  const int Kpad = (d.M() + 31) / 32 * 32;
+  Bf3Params p{};
+  p.M = d.CO; p.N = d.K(); p.K = Kpad;
+  for (int i = 0; i < 3; ++i) { p.A.p[i] = dyT[i]; p.B.p[i] = pT[i]; }
+  if (fmt) p.A.p[2] = p.B.p[2] = nullptr;
+  p.A.kind = p.B.kind = OPK_ROWK; p.A.ld = p.B.ld = Kpad; p.A.paired = p.B.paired = 1;
+  p.ep = ep_store(dw_ohwi, d.K(), nullptr, ACT_NONE);
+  if (fmt) { p.fmt = 1; p.ep.alpha = 1.0f / kF16ActScale; p.ep.alpha_dev[0] = dy_slot + 1; }      // 1 / (s_dy * 4): the first factor lives on the device
+  *w = g_bf3_wgrad_persist && wgrad_persist_shape(d) ? Bf3Work{ws, 4 * g_bf3_remainder_grid} : Bf3Work{nullptr, 256, splitk, ws};
+  return p;
+}
+
 int conv_wgrad_bf3(const float* x, const ConvDesc& d, const float* dy, float* dw_ohwi, int splitk,
                    unsigned short* const dyT[3], unsigned short* const pT[3], float* ws, hipStream_t st, int fmt, const float* dy_slot) {
   DIC_REQUIRE(!d.in_nchw && d.C % 32 == 0 && d.CO % 32 == 0, "conv_wgrad_bf3: NHWC input, C and CO %% 32");
@@ -2500,17 +2487,8 @@ int conv_wgrad_bf3(const float* x, const ConvDesc& d, const float* dy, float* dw
   hipLaunchKernelGGL((transpose_split_kernel<true>), dim3(Kpad / 32, d.KH * d.KW * (d.C / 32)), dim3(256), 0, st, x,
                      (long long)d.C, M, Kpad, d.C, g, pT[0], pT[1], fmt ? nullptr : pT[2], kF16ActScale, (const float*)nullptr);
   DIC_LAUNCH_CHECK();
-  Bf3Params p{};
-  p.M = d.CO; p.N = d.K(); p.K = Kpad;
-  for (int i = 0; i < 3; ++i) { p.A.p[i] = dyT[i]; p.B.p[i] = pT[i]; }
-  if (fmt) p.A.p[2] = p.B.p[2] = nullptr;
-  p.A.kind = OPK_ROWK; p.A.ld = Kpad; p.A.paired = 1;
-  p.B.kind = OPK_ROWK; p.B.ld = Kpad; p.B.paired = 1;
-  p.ep = ep_store(dw_ohwi, d.K(), nullptr, ACT_NONE);
-  if (fmt) { p.fmt = 1; p.ep.alpha = 1.0f / kF16ActScale; p.ep.alpha_dev[0] = dy_slot + 1; }      // 1 / (s_dy * 4): the first factor lives on the device
-  if (g_bf3_wgrad_persist && wgrad_persist_shape(d))
-    return launch_bf3(p, st, ws, 1, nullptr, nullptr, nullptr, 4 * g_bf3_remainder_grid);
-  return launch_bf3(p, st, nullptr, splitk, ws);
+  Bf3Work w; const Bf3Params p = conv_wgrad_bf3_params(d, dyT, pT, dw_ohwi, fmt, dy_slot, splitk, ws, &w);
+  return launch_bf3(p, w, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2567,31 +2545,33 @@ int conv_stem_pack_weights(const float* w_oihw, int CO, float* scratch_f32, unsi
   return split_bf16x3_paired(scratch_f32, CO, 224, w_planes[0], w_planes[1], w_planes[2], st);
 }
 
+static Bf3Params conv_stem_bf3_params(int B, int H, int W, int CO, unsigned short* const x_planes[3], const unsigned short* const w_planes[3],
+                                      float* y, float* bn_partial, int fmt, float out_scale) {
+  const int Hp = H + 6, Wp = W + 8, OH = H / 2, OW = W / 2;
+  Bf3Params p{};
+  p.M = B * OH * OW; p.N = CO; p.K = 224;
+  for (int i = 0; i < 3; ++i) { p.A.p[i] = x_planes[i]; p.B.p[i] = w_planes[i]; }
+  p.A.kind = OPK_IM2COL; p.A.ld = 4; p.A.paired = 0;
+  p.A.g = ConvGeom{Hp, Wp, 4, OH, OW, 7, 1, 2, 0, 2};        // nchw = 2: strip mode of the loader
+  p.B.kind = OPK_ROWK; p.B.ld = 224; p.B.paired = 1;
+  p.ep = ep_store(y, CO, nullptr, ACT_NONE); p.ep.stats = bn_partial;
+  if (fmt) { p.A.p[2] = p.B.p[2] = nullptr; p.fmt = 1; p.ep.alpha = out_scale; }      // (alpha: 1 / (kF16ActScale * weight scale))
+  return p;
+}
+
 // y_raw[B,OH,OW,CO] = conv7x7s2p3(imgs NCHW) with BN partial sums; x_planes: conv_stem_bf3_plane_elems(B,H,W) each
 int conv_stem_bf3(const float* imgs_nchw, int B, int H, int W, int CO, unsigned short* const x_planes[3],
                   const unsigned short* const w_planes[3], float* y, float* bn_partial, int* mtiles_out, hipStream_t st, int fmt,
                   float out_scale, unsigned* status) {
   DIC_REQUIRE(H % 2 == 0 && W % 2 == 0, "conv_stem_bf3: even image sizes");
-  const int Hp = H + 6, Wp = W + 8, OH = H / 2, OW = W / 2;
+  const int Hp = H + 6, Wp = W + 8;
   const long long px = (long long)B * Hp * Wp;
   hipLaunchKernelGGL(stem_pack_image_kernel, dim3((unsigned)std::min<long long>((px + 255) / 256, 16384)), dim3(256), 0, st,
                      imgs_nchw, B, H, W, Hp, Wp, x_planes[0], x_planes[1], fmt ? nullptr : x_planes[2], status);
   DIC_LAUNCH_CHECK();
-  Bf3Params p{};
-  p.M = B * OH * OW; p.N = CO; p.K = 224;
-  for (int i = 0; i < 3; ++i) { p.A.p[i] = x_planes[i]; p.B.p[i] = w_planes[i]; }
-  if (fmt) { p.A.p[2] = p.B.p[2] = nullptr; p.fmt = 1; }
-  p.A.kind = OPK_IM2COL; p.A.ld = 4; p.A.paired = 0;
-  p.A.g = ConvGeom{Hp, Wp, 4, OH, OW, 7, 1, 2, 0, 2};        // nchw = 2: strip mode of the loader
-  p.B.kind = OPK_ROWK; p.B.ld = 224; p.B.paired = 1;
-  p.ep = ep_store(y, CO, nullptr, ACT_NONE);
-  p.ep.stats = bn_partial;
-  if (fmt) p.ep.alpha = out_scale;      // 1 / (kF16ActScale * weight scale)
-  DIC_TRY(launch_bf3(p, st, nullptr));
-  if (mtiles_out) *mtiles_out = g_last_mtiles;
-  return DIC_OK;
+  return launch_bf3(conv_stem_bf3_params(B, H, W, CO, x_planes, w_planes, y, bn_partial, fmt, out_scale), Bf3Work{}, st, nullptr, nullptr,
+                    mtiles_out);
 }
-
 int conv_dgrad_s1_bf3(const unsigned short* const dy_planes[3], const ConvDesc& d,
                       const unsigned short* const wflip_planes[3], float* dx, hipStream_t st, float* tail_ws, int tail_ws_slabs,
                       int fmt, const float* alpha_dev0, const float* alpha_dev1) {
@@ -2600,6 +2580,31 @@ int conv_dgrad_s1_bf3(const unsigned short* const dy_planes[3], const ConvDesc& 
   const ConvDesc dd{d.B, d.OH(), d.OW(), d.CO, d.C, d.KH, d.KW, 1, d.KH - 1 - d.pad, 0};
   return conv_fwd_bf3(dy_planes, dd, wflip_planes, dx, nullptr, nullptr, tail_ws, st, nullptr, nullptr, nullptr, ACT_NONE,
                       tail_ws_slabs, fmt, 1.0f, alpha_dev0, alpha_dev1);
+}
+
+// The plan of one route's contraction without its operands (dic_debug_bf3_plan, api.hip): DIC_OK, or 1 when the route does not take the
+// shape.  route: 0 = planes (conv_fwd_bf3), 1 = on-the-fly 1x1 (conv1x1_fwd_bf3_bn, M = B * H * W), 2 = on-the-fly 3x3 (conv3x3_fwd_bf3_bn),
+// 3 = weight gradient (conv_wgrad_bf3), 4 = stem (conv_stem_bf3; B, H, W, CO); flags: 1 = residual, 2 = fp32 copy, 4 = BatchNorm of the
+// residual, 8 = bias, 16 = no BatchNorm statistics.  The plan reads only whether a pointer is there, so `t` stands for every one.
+int bf3_plan_route(int route, int fmt, const ConvDesc& d, int flags, int splitk, int tail_ws_slabs, const char** kernel, int out[6]) {
+  static float t[1];
+  unsigned short* const u = reinterpret_cast<unsigned short*>(t), * const pl3[3] = {u, u, fmt ? nullptr : u};
+  float* const stats = (flags & 16) ? nullptr : t, * const rbn = (flags & 4) ? t : nullptr;
+  Bf3Params p{};
+  Bf3Work w{route == 4 ? nullptr : t, tail_ws_slabs};
+  if (route == 0) p = conv_fwd_bf3_params(pl3, d, pl3, t, stats, (flags & 8) ? t : nullptr, ACT_NONE, fmt, 1.0f);
+  else if (route == 1 && conv1x1_bn_bf3_shape_ok(d.M(), d.C))
+    p = conv1x1_bn_bf3_params(t, t, t, (flags & 1) ? t : nullptr, 1, (flags & 2) ? t : nullptr, d.M(), d.C, pl3, d.CO, t, stats, fmt, 1.0f, nullptr, rbn, rbn);
+  else if (route == 2 && conv3x3_bn_bf3_shape_ok(d, fmt)) p = conv3x3_bn_bf3_params(t, t, t, 1, d, pl3, t, stats, 1.0f, nullptr);
+  else if (route == 3) p = conv_wgrad_bf3_params(d, pl3, pl3, t, fmt, t, splitk, t, &w);
+  else if (route == 4) p = conv_stem_bf3_params(d.B, d.H, d.W, d.CO, pl3, pl3, t, stats, fmt, 1.0f);
+  else { DIC_REQUIRE(route == 1 || route == 2, "bf3_plan_route: unknown route %d", route); return 1; }
+  Bf3Plan pl;
+  DIC_TRY(plan_bf3(p, w, &pl));
+  const int fused = pl.fixup == BF3_FIX_TAIL64 && gemm_tail_fixup_bn_eligible(pl.fix, pl.fixup_n);
+  *kernel = kBf3Kernels[pl.kernel].name;
+  out[0] = pl.grid; out[1] = kBf3Kernels[pl.kernel].block; out[2] = pl.fixup + fused; out[3] = pl.fixup_n; out[4] = pl.rows; out[5] = pl.key;
+  return DIC_OK;
 }
 
 int split_bf16x3_paired(const float* x, long long rows, int K, unsigned short* hi, unsigned short* mid,
@@ -2637,8 +2642,6 @@ extern "C" {
 
 int dic_split_bf16x3(const float* x, long long n, uint16_t* hi, uint16_t* mid, uint16_t* lo, void* stream) {
   DIC_REQUIRE(x && hi && mid && lo && n > 0, "split_bf16x3: bad arguments");
-  const int blocks = (int)std::min<long long>((n + 255) / 256, 8192);
-  (void)blocks;
   return split_bf16x3(x, n, hi, mid, lo, (hipStream_t)stream);
 }
 
@@ -2670,22 +2673,27 @@ static int gemm_bf16x3_any(int M, int N, int K, const uint16_t* a_hi, const uint
   p.A.paired = p.B.paired = paired;
   if (paired) DIC_REQUIRE(K % 32 == 0, "gemm_bf16x3_paired: K %% 32");
   p.ep = ep_store(C, ldc, bias, ACT_NONE);
-  return launch_bf3(p, (hipStream_t)stream, nullptr);
+  return launch_bf3(p, Bf3Work{}, (hipStream_t)stream);
 }
 
 /* y = act(x W^T + b) (+= with accumulate) and NHWC convolution with bias / activation on the split-bf16 kernels, operands as
  * paired planes (include/dic.h).  Used by the DPT front-end (dpt.py). */
-int dic_linear_bf16x3(int M, int N, int K, const uint16_t* const x_planes[3], const uint16_t* const w_planes[3], const float* bias,
-                      int act, int accumulate, float* C, long long ldc, void* stream) {
-  DIC_REQUIRE(x_planes && w_planes && C && M > 0 && N > 0 && K > 0 && K % 32 == 0, "linear_bf16x3: bad arguments (K %% 32)");
+static int linear_bf3(int M, int N, int K, const uint16_t* const x_planes[], const uint16_t* const w_planes[], const float* bias, int act,
+                      int accumulate, float* C, long long ldc, int fmt, float out_scale, void* stream) {
   Bf3Params p{};
   p.M = M; p.N = N; p.K = K;
-  for (int i = 0; i < 3; ++i) { p.A.p[i] = x_planes[i]; p.B.p[i] = w_planes[i]; }
+  for (int i = 0; i < (fmt ? 2 : 3); ++i) { p.A.p[i] = x_planes[i]; p.B.p[i] = w_planes[i]; }
   p.A.ld = K; p.A.kind = OPK_ROWK; p.B.ld = K; p.B.kind = OPK_ROWK;
   p.A.paired = p.B.paired = 1;
   p.ep = ep_store(C, ldc, bias, act);
   p.ep.accumulate = accumulate;
-  return launch_bf3(p, (hipStream_t)stream, nullptr);
+  if (fmt) { p.fmt = 1; p.ep.alpha = out_scale; }
+  return launch_bf3(p, Bf3Work{}, (hipStream_t)stream);
+}
+int dic_linear_bf16x3(int M, int N, int K, const uint16_t* const x_planes[3], const uint16_t* const w_planes[3], const float* bias,
+                      int act, int accumulate, float* C, long long ldc, void* stream) {
+  DIC_REQUIRE(x_planes && w_planes && C && M > 0 && N > 0 && K > 0 && K % 32 == 0, "linear_bf16x3: bad arguments (K %% 32)");
+  return linear_bf3(M, N, K, x_planes, w_planes, bias, act, accumulate, C, ldc, 0, 1.0f, stream);
 }
 int dic_conv2d_bf16x3(const uint16_t* const x_planes[3], int B, int H, int W, int Cin, const uint16_t* const w_planes[3],
                       const float* bias, int CO, int KH, int KW, int stride, int pad, int act, float* y_nhwc, float* tail_ws,
@@ -2699,15 +2707,7 @@ int dic_conv2d_bf16x3(const uint16_t* const x_planes[3], int B, int H, int W, in
 int dic_linear_f16x2(int M, int N, int K, const uint16_t* const x_planes[2], const uint16_t* const w_planes[2], const float* bias,
                      int act, int accumulate, float* C, long long ldc, float out_scale, void* stream) {
   DIC_REQUIRE(x_planes && w_planes && C && M > 0 && N > 0 && K > 0 && K % 32 == 0 && out_scale > 0.f, "linear_f16x2: bad arguments (K %% 32)");
-  Bf3Params p{};
-  p.M = M; p.N = N; p.K = K;
-  for (int i = 0; i < 2; ++i) { p.A.p[i] = x_planes[i]; p.B.p[i] = w_planes[i]; }
-  p.A.ld = K; p.A.kind = OPK_ROWK; p.B.ld = K; p.B.kind = OPK_ROWK;
-  p.A.paired = p.B.paired = 1;
-  p.ep = ep_store(C, ldc, bias, act);
-  p.ep.accumulate = accumulate;
-  p.fmt = 1; p.ep.alpha = out_scale;
-  return launch_bf3(p, (hipStream_t)stream, nullptr);
+  return linear_bf3(M, N, K, x_planes, w_planes, bias, act, accumulate, C, ldc, 1, out_scale, stream);
 }
 int dic_conv2d_f16x2(const uint16_t* const x_planes[2], int B, int H, int W, int Cin, const uint16_t* const w_planes[2],
                      const float* bias, int CO, int KH, int KW, int stride, int pad, int act, float* y_nhwc, float* tail_ws,
