@@ -116,6 +116,9 @@ class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def batch_sample(self, features, word_to_id, max_length=30):
         return super().batch_sample(features, None, word_to_id, max_length)
 
+    def beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, return_all=False):
+        return super().beam_sample(features, None, word_to_id, beam_size, max_length, length_penalty, return_all)
+
 
 class RNNDecoderWithHardAttention(_CaptionDecoderBase):
     """base-hard decoder (base_caption_models.py:257-508)."""
@@ -141,3 +144,6 @@ class RNNDecoderWithHardAttention(_CaptionDecoderBase):
 
     def batch_sample(self, features, word_to_id, max_length=30):
         return super().batch_sample(features, None, word_to_id, max_length)
+
+    def beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, return_all=False):
+        return super().beam_sample(features, None, word_to_id, beam_size, max_length, length_penalty, return_all)

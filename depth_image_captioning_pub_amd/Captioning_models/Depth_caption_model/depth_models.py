@@ -206,6 +206,24 @@ class _CaptionDecoderBase(nn.Module):
         ids, _ = self._greedy(features, depth_features, word_to_id, max_length)
         return ids.cpu().numpy().astype(np.int64)
 
+    # ---- beam-search decoding (no counterpart in the reference, whose evaluation is greedy; semantics: include/dic.h) -------
+    @torch.no_grad()
+    def beam_sample(self, features, depth_features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0,
+                    return_all=False):
+        """Beam-search captions of a batch: np.int64 [B,max_length], the best of `beam_size` hypotheses per image ranked by
+        score / length^length_penalty; positions behind the first '<end>' hold '<end>'.  return_all=True: (ids np.int64
+        [B,K,max_length], scores np.float32 [B,K] (sums of log-probabilities), lengths np.int32 [B,K]), best first."""
+        if self.hard:
+            raise DicError("beam_sample: beam search is built for the soft-attention decoders only (a Gumbel-max beam would need "
+                           "one noise draw per hypothesis and step); use batch_sample for hard attention")
+        ids, scores, lengths = native.decoder_beam(self._weights(), _contig(features), _contig(depth_features),
+                                                   word_to_id["<start>"], word_to_id["<end>"], beam_size, max_length,
+                                                   float(length_penalty))
+        if return_all:
+            return (ids.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return ids[:, 0].cpu().numpy().astype(np.int64)
+
 
 class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,

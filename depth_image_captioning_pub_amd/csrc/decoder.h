@@ -1,4 +1,4 @@
-// Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy decode.
+// Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy and beam-search decode.
 // Host orchestration + kernels live in decoder.hip; the C ABI wrappers are at the bottom of that file.
 #pragma once
 #include "dic.h"

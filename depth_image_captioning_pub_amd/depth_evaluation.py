@@ -50,14 +50,21 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
 
 @torch.no_grad()
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
-                      n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None):
+                      n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
+                      length_penalty: float = 0.0):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
-    in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0."""
+    in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
+    beam_size > 1 (soft attention only) decodes with decoder.beam_sample - the best of `beam_size` hypotheses per image, ranked
+    by score / length^length_penalty - instead of the reference's greedy batch_sample; 1 is the greedy loop itself."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
         raise DicError("atten must be 'soft' or 'hard'")
+    if int(beam_size) < 1:
+        raise DicError(f"beam_size={beam_size!r} must be at least 1")
+    if int(beam_size) > 1 and atten != "soft":
+        raise DicError("beam_size > 1 needs atten='soft': beam search is built for the soft-attention decoder only")
     config = config or ConfigTrain()
     dev = config.device
     tag = f"depth_{atten}"
@@ -90,7 +97,11 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             depth_maps = dpt.depth_maps_for_training(imgs_for_dep)                          # :155-159
             depth_features = depth_encoder(depth_maps)                                      # :161
             feature = encoder(imgs)                                                         # :164
-            hypos_id.append(decoder.batch_sample(feature, depth_features, word_to_id))     # :165
+            if int(beam_size) > 1:
+                hypos_id.append(decoder.beam_sample(feature, depth_features, word_to_id, beam_size=int(beam_size),
+                                                    length_penalty=length_penalty))
+            else:
+                hypos_id.append(decoder.batch_sample(feature, depth_features, word_to_id))     # :165
         hypos_id = np.concatenate(hypos_id)
         hypos_word = ids_to_captions(hypos_id, id_to_word)
         results[key] = {"hypotheses": hypos_word, "ids": hypos_id}

@@ -545,6 +545,32 @@ def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
     return ids, alphas
 
 
+def decoder_beam(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                 id_end: int, beam_size: int, max_length: int = 30, length_penalty: float = 0.0,
+                 return_alphas: bool = False):
+    """dic_decoder_beam: fixed-width beam search of the soft-attention decoder, on the device (semantics: include/dic.h).
+    Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K][, alphas [B,K,max_length,196]]), best first."""
+    lib = _lib.load()
+    f_rgb = _dev_f32(feat_rgb, "features")
+    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
+    B, K = f_rgb.shape[0], int(beam_size)
+    vocab = weights["linear.weight"].shape[0]
+    wp, keep = decoder_ptrs(weights)
+    lib.dic_decoder_beam_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_decoder_beam_workspace_bytes(B, K, max_length, vocab)      # (0 for sizes the call below refuses with its text)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f_rgb.device)
+    kk = max(K, 1)
+    ids = torch.empty((B, kk, max_length), dtype=torch.int64, device=f_rgb.device)
+    scores = torch.empty((B, kk), dtype=torch.float32, device=f_rgb.device)
+    lengths = torch.empty((B, kk), dtype=torch.int32, device=f_rgb.device)
+    alphas = torch.empty((B, kk, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device) if return_alphas else None
+    rc = lib.dic_decoder_beam(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, C.c_longlong(int(id_start)),
+                              C.c_longlong(int(id_end)), max_length, C.c_float(length_penalty), ptr(ids), ptr(scores),
+                              ptr(lengths), ptr(alphas), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    check(rc, "dic_decoder_beam")
+    return (ids, scores, lengths, alphas) if return_alphas else (ids, scores, lengths)
+
+
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""

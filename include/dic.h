@@ -129,6 +129,33 @@ int dic_decoder_greedy(const dic_decoder_weights* w, int V, const float* feat_rg
                        long long id_start, int max_length, int mode, const float* gumbel_u, int64_t* out_ids,
                        float* alphas_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* fixed-width beam search for the soft-attention decoder (depth-soft, or base-soft with feat_depth = NULL), entirely on the
+ *   device: every launch is enqueued on `stream`, nothing is copied to the host, nothing synchronises.  There is no reference
+ *   implementation (the reference decodes greedily); this comment is the specification.
+ *   Per image K hypotheses ("beams") are kept at every step, for exactly max_length steps.
+ *   State per beam: h, c (init_linear(mean_L F), the same for the K beams), previous token (id_start), score (fp32 sum of
+ *     log-probabilities; beam 0 starts at 0, beams 1..K-1 at -inf, so step 0 picks K different first tokens), finished, length.
+ *   One step, every beam: the decode-step body of dic_decoder_greedy (embedding, soft attention over F = F_rgb (+ F_depth),
+ *     gate = sigmoid(f_beta h), LSTMCell([e ; gate*ctx]), logits = linear(h), no dropout), then
+ *     lsm = logits - max - log sum exp(logits - max) in fp32.
+ *   Candidates of an image: a live beam k offers score[k] + lsm[k,v] for every v; a finished beam offers exactly one, token
+ *     id_end at unchanged score.  The K best of them survive, ordered by value descending, ties broken by the lower flat index
+ *     k*V + v.  A survivor inherits its parent's h', c' and token history, sets finished |= (token == id_end), and gets
+ *     length = t + 1 from a live parent (a finished parent hands its length on: length counts the tokens up to and including
+ *     the first id_end, or max_length).
+ *   Result: hypotheses ranked by score / length^length_penalty (0: the raw score), descending, stable in the beam index.
+ *   out_ids int64 [B,K,max_length] (positions behind the first id_end hold id_end), out_scores float [B,K] (the raw sums),
+ *   out_lengths int [B,K], alphas_out (nullable) [B,K,max_length,196]: the attention weights along each returned hypothesis
+ *   (steps at or after `length`: those of the beam the frozen hypothesis was copied from; cut at length).
+ *   1 <= K <= 8, K <= V, 0 <= id_start, id_end < V, length_penalty >= 0, max_length >= 1: a violation or a short workspace
+ *   returns a negative code with a dic_last_error() text before anything is launched.  The K beams of an image share one read
+ *   of its F and P = W_z F + b_z per step; K = 1 decodes what dic_decoder_greedy decodes up to the first id_end. */
+size_t dic_decoder_beam_workspace_bytes(int B, int K, int max_length, int V);
+int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                     long long id_start, long long id_end, int max_length, float length_penalty, int64_t* out_ids,
+                     float* out_scores, int* out_lengths, float* alphas_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* stand-alone attention module: Soft_Attention.forward (attention.py:81-95), Hard_Attention.forward (:132-148,
  *   mode 1, gumbel_u [B,196], temp) and Hard_Attention.Hard_sample (:150-167, mode 2): feats [B,196,2048],
  *   h [B,128] -> ctx [B,2048], alpha [B,196] (float; one-hot in mode 2). */
