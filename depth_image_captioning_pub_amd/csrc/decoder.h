@@ -1,8 +1,14 @@
 // Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy and beam-search decode.
-// Host orchestration + kernels live in decoder.hip; the C ABI wrappers are at the bottom of that file.
+// One translation unit per route, each with its kernels, host orchestration and C ABI entry points; this header declares only
+// what more than one of them uses:
+//   decoder.hip         what the routes share: workspace carving, set-up, the attention step and LSTM cell kernels + launchers
+//   decoder_fwd.hip     teacher-forced forward, stand-alone attention forward
+//   decoder_bwd.hip     BPTT backward, stand-alone attention backward
+//   decoder_decode.hip  greedy and beam-search decode
 #pragma once
 #include "dic.h"
 #include "gemm.h"
+#include <vector>
 
 namespace dic {
 
@@ -15,11 +21,17 @@ constexpr int kLc = 49;                 // distinct cells when the 14x14 grid is
 constexpr int kS_LSTM = 18;             // split-K of the per-step LSTM gate GEMM (72 K tiles -> 4 per workgroup)
 constexpr int kS_DX = 4;                // split-K of the per-step dX GEMM (16 K tiles)
 
+// what decoder_setup() fills: the leading part of every decoder workspace
+struct SetupBufs {
+  float *F, *P, *mean, *Wcat, *WcatT, *bcat, *WhT, *WbT, *gemm_ws;
+  size_t gemm_ws_floats;
+};
+
 // workspace ("tape") shared by forward and backward of one decoder call
-struct DecoderWs {
+struct DecoderWs : SetupBufs {
   // forward / saved for backward
-  float *F, *P, *mean, *Wcat, *WcatT, *bcat, *WhT, *WbT, *WzT, *Xall, *Hall, *Call, *Gact, *Qall, *ctx, *gate, *Hdrop;
-  float *slab_g, *gemm_ws;
+  float *WzT, *Xall, *Hall, *Call, *Gact, *Qall, *ctx, *gate, *Hdrop;
+  float* slab_g;
   // backward
   float *dHd, *dG, *slab_dx, *dctx, *dgpre, *dq, *dalp, *pbeta, *dqp, *dwf_acc, *dbf_acc, *dPacc, *carry_dc;
   float *dinit, *dmean, *colsum_ws;
@@ -33,11 +45,75 @@ struct DecoderWs {
   int* poff;                     // [T+1] packed row offsets (device copy of the host plan)
   float* logits_step;
   long long* ids;
-  size_t gemm_ws_floats;
   size_t bytes;
 };
 
 DecoderWs decoder_carve(void* ws, size_t ws_bytes, int B, int T, int V, int N, bool* overflow);
+
+// runs STMT with a compile-time cell count L_ (196 = reference layout, 49 = compact)
+#define DIC_CELLS_SWITCH(CELLS, STMT)   \
+  if ((CELLS) == kL) {                  \
+    constexpr int L_ = kL;              \
+    STMT                                \
+  } else {                              \
+    constexpr int L_ = kLc;             \
+    STMT                                \
+  }
+
+// rows active per step and their packed offsets, from the (descending) caption lengths
+struct StepPlan { int T = 0, N = 0; std::vector<int> bs, off; };
+int make_plan(const int* dec_len, int B, StepPlan* pl);
+
+int launch_transpose(const float* in, float* out, int R, int Cc, hipStream_t st);      // out[c*R + r] = in[r*C + c]
+int gemm(int M, int N, int K, GemmOperand A, GemmOperand B, GemmEpilogue ep, hipStream_t st, int splitk = 1, float* ws = nullptr,
+         int tile = 0, int raw_partials = 0);
+// raw split-K partial slabs [splitk][M][N] (no reduce launch; the consumer kernel sums the slabs)
+int gemm_slabs(int M, int N, int K, GemmOperand A, GemmOperand B, float* slabs, int splitk, hipStream_t st);
+
+// Time-invariant work ahead of the step loop: Wcat = [W_ih | W_hh] and bcat (and Wcat^T when `WcatT`), W_h^T, W_beta^T,
+// F = F_rgb + F_depth and its mean over the cells, P = W_z F + b_z (hoisted, quirk Q4), [h0 | c0] = init_linear(mean) into
+// h0 / c0 with row stride ld.
+struct InitState { float *h0, *c0; long long ld; bool WcatT; };
+int decoder_setup(const dic_decoder_weights* w, const float* feat_rgb, const float* feat_depth, int B, int cells,
+                  const SetupBufs& s, const InitState& o, hipStream_t st);
+
+// LSTM cell of step t from the gate-GEMM slabs [nslab][nb][4H]: writes slot t+1 of Hall / Call, the gate activations of
+// (b, t) and the dropped hidden state (drop: multiplier [B][T][H] or null) at packed row packed_off + b
+struct LstmCell {
+  const float *slab, *bcat, *drop; float *Hall, *Call, *Gact, *Hdrop;
+  int nslab, nb, packed_off;
+};
+int launch_lstm_fwd(const LstmCell& c, int t, int T, hipStream_t st);      // lstm_fwd_kernel, one workgroup per row
+
+// LSTM cell of the PREVIOUS step, fused into the prologue of attn_fwd_kernel (saves one dependent launch per decode
+// step): every chunk-workgroup of row b recomputes h_t from the gate-GEMM slabs of step t-1 (72 loads per thread, one
+// round trip); the chunk-0 workgroup also stores what lstm_fwd_kernel(t-1) stores.  Rows that were active at t-1
+// (nb rows) but not at t (nb_cur rows) get only that part.  slab null: not fused.
+struct FusedLstm : LstmCell { int nb_cur; };
+
+// One attention step (attn_fwd_kernel<cells>) over rows [0, nrows): scores -> softmax / Gumbel -> context -> beta gate.
+// Nullable: Qall, and with do_gate = 0 (the stand-alone attention module stops at the context) WbT, b_beta, gate_all, Xall.
+struct AttnStepArgs {
+  const float *F, *P, *Hall, *WhT, *b_h, *w_full, *b_full, *WbT, *b_beta;
+  int t, T, mode; const float* gumbel_u; int B; float temp;
+  float *alphas, *Qall, *ctx_all, *gate_all, *Xall;
+  int do_gate; FusedLstm fl; int nrows;
+};
+int launch_attn_step(const AttnStepArgs& a, int cells, hipStream_t st);
+
+// Grid of the attention step kernels and its decoding.  Workgroup (chunk, b) owns channels [chunk*256, +256) of row b.  The
+// eight chunk workgroups of a row share its P rows and LSTM slabs (each recomputes scores and cell): they are mapped to
+// dispatch ids with equal id % 8, i.e. to ONE XCD under round-robin placement (speed only), so those bytes leave HBM / the
+// Infinity Cache once per row, not eight times.  Rows beyond the caller's count exist in the grid: the kernel returns on them.
+inline dim3 attn_step_grid(int rows) { return dim3(kNCH, (rows + 7) / 8 * 8); }
+#ifdef __HIPCC__
+struct RowChunk { int b, chunk; };
+__device__ __forceinline__ RowChunk attn_step_row() {
+  const int lin = blockIdx.y * kNCH + blockIdx.x;
+  return {(lin & 7) + 8 * (lin >> 6), (lin >> 3) & 7};
+}
+__device__ __forceinline__ long long clamp_token(long long id, int V) { return id < 0 ? 0 : (id >= V ? V - 1 : id); }
+#endif
 
 // Experiments build only (-DDIC_EXPERIMENTS): one launch for all T forward steps (soft attention, B <= 64); see experiments/decoder_persist.hip.  Expects F, P, h0/c0 (slot 0 of
 // Hall/Call), the embedding columns of Xall, WhT / WbT / WcatT, Gemb and the device copy of the lengths in the workspace.

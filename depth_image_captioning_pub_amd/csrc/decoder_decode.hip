@@ -1,0 +1,662 @@
+// Decoding on the device: greedy (dic_decoder_greedy) and beam search (dic_decoder_beam).
+#include "decoder.h"
+#include <algorithm>
+
+namespace dic {
+
+// ------------------------------------------------------------------------------------------
+// greedy decoding helpers (batch_sample / sample, depth_models.py:216-305): everything stays on the device
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) fill_ids_kernel(long long* ids, int n, long long v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) ids[i] = v;
+}
+
+__global__ void __launch_bounds__(kE) embed_step_kernel(const float* __restrict__ embed, const long long* __restrict__ ids,
+                                                         int t, int T, int V, float* __restrict__ Xall) {
+  const int b = blockIdx.x;
+  const long long id = clamp_token(ids[b], V);
+  Xall[((long long)b * T + t) * kXK + threadIdx.x] = embed[id * kE + threadIdx.x];
+}
+
+// ids[b] = argmax_v logits[b,v] (first maximum on ties, like torch.argmax); also out[b*T + t]
+__global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ logits, int V, int t, int T,
+                                                      long long* __restrict__ ids, long long* __restrict__ out) {
+  __shared__ float bv[4];
+  __shared__ int bi[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* x = logits + (long long)b * V;
+  float best = -INFINITY;
+  int idx = 0x7fffffff;
+  for (int v = tid; v < V; v += 256) {
+    const float f = x[v];
+    if (f > best) { best = f; idx = v; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+  }
+  if (lane == 0) { bv[w] = best; bi[w] = idx; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < 4; ++i)
+      if (bv[i] > best || (bv[i] == best && bi[i] < idx)) { best = bv[i]; idx = bi[i]; }
+    ids[b] = idx;
+    out[(long long)b * T + t] = idx;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// beam search (dic_decoder_beam; semantics in include/dic.h, layout in DESIGN.md 5.6): KB hypotheses per image, rows b*KB + k.
+// Per step: beam_attn_kernel -> gate GEMM slabs -> lstm_fwd_kernel -> vocabulary GEMM -> beam_topk_kernel -> beam_select_kernel.
+// State: Hst / Cst [B*KB][2][kH] (slot 0 = state entering the step, slot 1 = state the LSTM cell wrote: lstm_fwd_kernel's
+// Hall / Call layout at T = 1), score / fin / length / prev [B*KB], token and back-pointer history [T][B*KB].
+// ------------------------------------------------------------------------------------------
+constexpr int kBeamMax = 8;
+// context pass of beam_attn_kernel: NFB batches of FB cells per wave (8 waves x NFB x FB >= 196 cells; the weights of the padding
+// cells are 0), each with 64 / NFB of the gate's K range.  Wide beams take smaller batches: the per-beam operands of a batch
+// (attention weights, hidden state) live in scalar registers, and there are about a hundred of those.
+constexpr int beam_fb(int KB) { return KB <= 4 ? 7 : 4; }
+constexpr int beam_nfb(int KB) { return KB <= 4 ? 4 : 8; }
+
+// Attention step of all KB beams of an image.  grid attn_step_grid(B), 512 threads: workgroup (chunk, b) owns channels
+// [chunk*256, +256) of image b for EVERY beam: the W_h / W_beta slices, the image's P rows and its F rows are loaded once and
+// used KB times (attn_fwd_kernel at B*KB replicated rows reads them KB times).  Thread roles, per-element arithmetic and
+// summation orders per beam are those of attn_fwd_kernel<196> (mode 0), so KB = 1 computes what the greedy step computes; only
+// the batching of the F / W_beta loads differs (4 x 7 or 8 x 4 cells instead of 2 x 13: the KB accumulators need the registers).
+// Writes the LSTM input rows X[b*KB+k] = [embed[prev] | gate * ctx | h] and, when asked, the attention weights of the step.
+typedef unsigned int beam_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 beam_load4(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
+  const beam_u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
+  return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
+}
+__device__ __forceinline__ float beam_load1(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+}
+// a value every lane of the wave read from the same LDS address, moved to a scalar register: the attention weights and hidden
+// states of the KB beams would otherwise take 23 vector registers per beam in the context pass
+__device__ __forceinline__ float beam_uniform(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+// no memory access and no instruction moves across this point, in the compiler's passes or in its scheduler
+#define DIC_BEAM_FENCE()                   \
+  do {                                     \
+    asm volatile("" ::: "memory");         \
+    __builtin_amdgcn_sched_barrier(0);     \
+  } while (0)
+template <int KB>
+__global__ void __launch_bounds__(512, 4) beam_attn_kernel(
+    const float* __restrict__ F, const float* __restrict__ P, const float* __restrict__ Hst,
+    const long long* __restrict__ prev, const float* __restrict__ embed, int V, const float* __restrict__ WhT,
+    const float* __restrict__ b_h, const float* __restrict__ w_full, const float* __restrict__ b_full,
+    const float* __restrict__ WbT, const float* __restrict__ b_beta, float* __restrict__ alphas, float* __restrict__ X,
+    const int nrows) {
+  constexpr int L = kL;
+  constexpr int NPS = (L + 15) / 16;                 // score passes: 16 cells (half-waves) per pass
+  constexpr int NPAIR = (KB + 1) / 2;                // softmax / final reduction: two beams at a time (256 threads each)
+  constexpr int kBeamFB = beam_fb(KB), kBeamNFB = beam_nfb(KB);
+  constexpr int kBeamEP = 8 * kBeamFB * kBeamNFB;    // padded cell count
+  constexpr int kBeamGK = 64 / kBeamNFB;             // gate K slice per batch (each half of the workgroup owns 64 of K)
+  __shared__ float h_s[KB][kH];
+  __shared__ __align__(16) float q_s[KB][4][kA];
+  __shared__ float e_s[KB][kBeamEP];
+  __shared__ float red_s[KB][8];
+  __shared__ __align__(16) float cred[2][8][256];
+  __shared__ float gp_s[2][2][256];
+  const auto [b, chunk] = attn_step_row();
+  if (b >= nrows) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l32 = lane & 31, hw = w * 2 + (lane >> 5);
+  const int quarter = w >> 1;
+  const long long row0 = (long long)b * KB;
+  const float* Pu = P + (long long)b * L * kA;                       // uniform
+  const float* Wq = WhT + quarter * 32 * kA + (w & 1) * 64;
+  float wv[32];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) wv[k] = Wq[k * kA + lane];
+  for (int i = tid; i < KB * kH; i += 512) h_s[i / kH][i % kH] = Hst[(row0 + i / kH) * 2 * kH + i % kH];
+  for (int i = tid; i < KB * (kBeamEP - L); i += 512) e_s[i / (kBeamEP - L)][L + i % (kBeamEP - L)] = 0.f;
+  __syncthreads();
+  {  // q = Wh h + bh   (four quarters of K per output), the weights of the quarter held once for all beams
+    const int a = tid & (kA - 1);
+#pragma unroll 1
+    for (int kb = 0; kb < KB; ++kb) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < 32; ++k) s += wv[k] * h_s[kb][quarter * 32 + k];
+      q_s[kb][quarter][a] = s;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < KB * kA; i += 512) {
+    const int kb = i / kA, a = i % kA;
+    q_s[kb][0][a] = b_h[a] + ((q_s[kb][0][a] + q_s[kb][1][a]) + (q_s[kb][2][a] + q_s[kb][3][a]));
+  }
+  if (chunk == 0) {          // h_prev slot of the LSTM input
+    for (int i = tid; i < KB * kH; i += 512) X[(row0 + i / kH) * kXK + kE + kD + i % kH] = h_s[i / kH][i % kH];
+  } else if (chunk == 1) {   // embedding of the previous token (kept on the device by beam_select_kernel)
+    for (int i = tid; i < KB * kE; i += 512) {
+      const long long id = clamp_token(prev[row0 + i / kE], V);
+      X[(row0 + i / kE) * kXK + i % kE] = embed[id * kE + i % kE];
+    }
+  }
+  __syncthreads();
+  {  // e[k][l] = w . relu(P[l,:] + q_k) + b : the P rows are read once, every beam scores them
+    float4 p4[NPS];
+#pragma unroll
+    for (int i = 0; i < NPS; ++i) {     // branch-free guard: cells past the end re-read the last cell (never stored)
+      const unsigned poff = (unsigned)min(hw + 16 * i, L - 1) * kA + l32 * 4;
+      p4[i] = *reinterpret_cast<const float4*>(Pu + poff);
+    }
+    const float4 w4 = *reinterpret_cast<const float4*>(w_full + l32 * 4);
+    const float bf = b_full[0];
+#pragma unroll 1
+    for (int kb = 0; kb < KB; ++kb) {      // (rolled: 13 half-wave sums in flight per beam are enough)
+      const float4 q4 = *reinterpret_cast<const float4*>(&q_s[kb][0][l32 * 4]);
+#pragma unroll
+      for (int i = 0; i < NPS; ++i) {
+        const int l = hw + 16 * i;
+        float sc = w4.x * fmaxf(p4[i].x + q4.x, 0.f) + w4.y * fmaxf(p4[i].y + q4.y, 0.f) +
+                   w4.z * fmaxf(p4[i].z + q4.z, 0.f) + w4.w * fmaxf(p4[i].w + q4.w, 0.f);
+        sc = half_wave_sum(sc);
+        if (l < L && l32 == 0) e_s[kb][l] = sc + bf;
+      }
+    }
+  }
+  const int dl = tid & 255, half = w >> 2;
+  const float* Wg = WbT + (long long)(half * 64) * kD + chunk * 256 + (w & 3) * 64;           // uniform
+  const float* Fu = F + (long long)b * L * kD + chunk * 256;                              // uniform
+  const unsigned foff = lane * 4;
+  float4 v0[kBeamFB];
+  float wg[kBeamGK];
+  // first batch of the F pass and of the gate weights: their addresses do not depend on the softmax, in flight under it
+  // Buffer loads: (descriptor of a wave-uniform base) + scalar row offset + 32-bit lane offset.  As plain pointer loads
+  // the compiler keeps a 64-bit address per row in vector registers and, the memory being kernel-constant, moves all four
+  // batches to the top: hundreds of spilled registers from KB = 3 on.  In bounds: row <= L-1 of image b, K row <= kH-1.
+  const __amdgpu_buffer_rsrc_t Frs = __builtin_amdgcn_make_buffer_rsrc((void*)Fu, 0, (L * kD - chunk * 256) * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t Wrs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)Wg, 0, (64 * kD - (w & 3) * 64 - chunk * 256) * 4, 0x00020000);
+#pragma unroll
+  for (int i = 0; i < kBeamFB; ++i) v0[i] = beam_load4(Frs, foff * 4, (unsigned)min(w + 8 * i, L - 1) * (kD * 4));
+#pragma unroll
+  for (int k = 0; k < kBeamGK; ++k) wg[k] = beam_load1(Wrs, lane * 4, (unsigned)k * (kD * 4));
+  __syncthreads();
+  {  // softmax over the L cells, beams 2p and 2p+1 side by side: cells live in the four waves of each half
+    const int c = dl, wq = w & 3;
+    float ex[NPAIR];
+#pragma unroll
+    for (int p = 0; p < NPAIR; ++p) {
+      const int kb = 2 * p + half;
+      float z = -INFINITY;
+      if (kb < KB && c < L) z = e_s[kb][c];
+      ex[p] = z;
+      const float m = wave_max(z);
+      if (lane == 0 && kb < KB) red_s[kb][wq] = m;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < NPAIR; ++p) {
+      const int kb = 2 * p + half;
+      if (kb < KB) {             // (wave-uniform)
+        const float m = fmaxf(fmaxf(red_s[kb][0], red_s[kb][1]), fmaxf(red_s[kb][2], red_s[kb][3]));
+        ex[p] = (c < L) ? expf(ex[p] - m) : 0.f;
+        const float sm = wave_sum(ex[p]);
+        if (lane == 0) red_s[kb][4 + wq] = sm;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < NPAIR; ++p) {
+      const int kb = 2 * p + half;
+      if (kb < KB && c < L) {
+        const float al = ex[p] / (red_s[kb][4] + red_s[kb][5] + red_s[kb][6] + red_s[kb][7]);
+        e_s[kb][c] = al;
+        if (chunk == 0 && alphas) alphas[(row0 + kb) * L + c] = al;
+      }
+    }
+  }
+  __syncthreads();
+  // ctx_k[d] = sum_l alpha_k[l] F[b,l,d] over this chunk: ONE pass over the image's F rows feeds the KB accumulators; fused with
+  // the pre-activation of gate_k = sigmoid(W_beta h_k + b) for the same 256 channels (two halves of K per channel)
+  float4 acc[KB];
+  float gs[KB];
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) { acc[kb] = make_float4(0.f, 0.f, 0.f, 0.f); gs[kb] = 0.f; }
+#pragma unroll 1
+  for (int bt2 = 0; bt2 < kBeamNFB; ++bt2) {       // (rolled: one basic block per batch bounds what the scheduler may interleave)
+#pragma unroll
+    for (int i = 0; i < kBeamFB; ++i) {
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        const float a = beam_uniform(e_s[kb][w + 8 * (bt2 * kBeamFB + i)]);      // padded with zeros up to kBeamEP
+        acc[kb].x += a * v0[i].x; acc[kb].y += a * v0[i].y; acc[kb].z += a * v0[i].z; acc[kb].w += a * v0[i].w;
+      }
+      DIC_BEAM_FENCE();         // (keeps the LDS reads of later cells from being hoisted: register budget)
+    }
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+      for (int k = 0; k < kBeamGK; ++k) gs[kb] += wg[k] * beam_uniform(h_s[kb][half * 64 + bt2 * kBeamGK + k]);
+      DIC_BEAM_FENCE();
+    }
+    if (bt2 + 1 < kBeamNFB) {
+      DIC_BEAM_FENCE();         // (the next batch re-uses the registers of this one: keep the order)
+#pragma unroll
+      for (int i = 0; i < kBeamFB; ++i)
+        v0[i] = beam_load4(Frs, foff * 4, (unsigned)min(w + 8 * ((bt2 + 1) * kBeamFB + i), L - 1) * (kD * 4));
+#pragma unroll
+      for (int k = 0; k < kBeamGK; ++k) wg[k] = beam_load1(Wrs, lane * 4, (unsigned)((bt2 + 1) * kBeamGK + k) * (kD * 4));
+    }
+  }
+  // cross-wave reduction and x = gate * ctx, two beams per round through one staging buffer
+#pragma unroll
+  for (int p = 0; p < NPAIR; ++p) {
+    if (p > 0) __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (2 * p + s < KB) {        // (odd KB: the last round holds one beam; min() keeps the dead branch's index in the array)
+        *reinterpret_cast<float4*>(&cred[s][w][lane * 4]) = acc[min(2 * p + s, KB - 1)];
+        gp_s[s][half][dl] = gs[min(2 * p + s, KB - 1)];
+      }
+    }
+    __syncthreads();
+    const int kb = 2 * p + half;
+    if (kb < KB) {
+      const int d = chunk * 256 + dl;
+      const float c = ((cred[half][0][dl] + cred[half][1][dl]) + (cred[half][2][dl] + cred[half][3][dl])) +
+                      ((cred[half][4][dl] + cred[half][5][dl]) + (cred[half][6][dl] + cred[half][7][dl]));
+      const float g = sigmoidf_(b_beta[d] + (gp_s[half][0][dl] + gp_s[half][1][dl]));
+      X[(row0 + kb) * kXK + kE + d] = g * c;
+    }
+  }
+}
+
+// (value descending, flat index ascending): the order of the candidate list
+__device__ __forceinline__ bool beam_better(float av, long long ai, float bv, long long bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+// Row b*KB+k: lsm = logits - max - log sum exp(logits - max) (fp32), then the KB best of score + lsm[v] (ties: lower v), best
+// first, into cand_val / cand_tok [row][KB].  A finished beam has the single candidate (score, id_end); unused slots get
+// token -1.  grid (B*KB), 256 threads; the first 256*kTopkNPT logits of the row stay in registers over the three passes
+// (max, sum, selection), any beyond that are read again (V > 10240).
+constexpr int kTopkNPT = 40;
+template <int KB>
+__global__ void __launch_bounds__(256) beam_topk_kernel(const float* __restrict__ logits, int V,
+                                                         const float* __restrict__ score, const int* __restrict__ fin,
+                                                         long long id_end, float* __restrict__ cand_val,
+                                                         int* __restrict__ cand_tok) {
+  __shared__ float sv[2][4];
+  __shared__ int si[2][4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float sc = score[row];
+  if (fin[row]) {            // (uniform) frozen hypothesis: carried at unchanged score
+    if (tid < KB) {
+      cand_val[(long long)row * KB + tid] = tid == 0 ? sc : -INFINITY;
+      cand_tok[(long long)row * KB + tid] = tid == 0 ? (int)id_end : -1;
+    }
+    return;
+  }
+  const float* x = logits + (long long)row * V;
+  float xr[kTopkNPT];
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < kTopkNPT; ++i) {
+    const int v = tid + 256 * i;
+    xr[i] = v < V ? x[v] : -INFINITY;
+    m = fmaxf(m, xr[i]);
+  }
+  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) m = fmaxf(m, x[v]);
+  m = wave_max(m);
+  if (lane == 0) sv[0][w] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(sv[0][0], sv[0][1]), fmaxf(sv[0][2], sv[0][3]));
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < kTopkNPT; ++i) s += expf(xr[i] - m);          // (exp(-inf) = 0 for the slots past V)
+  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) s += expf(x[v] - m);
+  s = wave_sum(s);
+  if (lane == 0) sv[1][w] = s;
+  __syncthreads();
+  const float ls = logf((sv[1][0] + sv[1][1]) + (sv[1][2] + sv[1][3]));
+  // this thread's KB best, sorted; its elements arrive in ascending v
+  float lv[KB];
+  int li[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) { lv[j] = -INFINITY; li[j] = 0x7fffffff; }
+  auto offer = [&](float c, int v) {
+    if (beam_better(c, v, lv[KB - 1], li[KB - 1])) {
+      lv[KB - 1] = c; li[KB - 1] = v;
+#pragma unroll
+      for (int j = KB - 1; j > 0; --j) {
+        if (beam_better(lv[j], li[j], lv[j - 1], li[j - 1])) {
+          const float tv = lv[j]; lv[j] = lv[j - 1]; lv[j - 1] = tv;
+          const int ti = li[j]; li[j] = li[j - 1]; li[j - 1] = ti;
+        }
+      }
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < kTopkNPT; ++i) {
+    const int v = tid + 256 * i;
+    if (v < V) offer(sc + ((xr[i] - m) - ls), v);
+  }
+  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) offer(sc + ((x[v] - m) - ls), v);
+  // KB rounds: the best head of the 256 lists wins and its thread moves on to its next element
+#pragma unroll
+  for (int r = 0; r < KB; ++r) {
+    float bv = lv[0];
+    int bi = li[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (beam_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    __syncthreads();                        // (the previous round's readers are done with sv / si)
+    if (lane == 0) { sv[r & 1][w] = bv; si[r & 1][w] = bi; }
+    __syncthreads();
+    bv = sv[r & 1][0]; bi = si[r & 1][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+      if (beam_better(sv[r & 1][i], si[r & 1][i], bv, bi)) { bv = sv[r & 1][i]; bi = si[r & 1][i]; }
+    if (li[0] == bi) {                      // (token ids are unique: one thread)
+#pragma unroll
+      for (int j = 0; j + 1 < KB; ++j) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
+      lv[KB - 1] = -INFINITY; li[KB - 1] = 0x7fffffff;
+    }
+    if (tid == 0) {
+      cand_val[(long long)row * KB + r] = bv;
+      cand_tok[(long long)row * KB + r] = bi == 0x7fffffff ? -1 : bi;
+    }
+  }
+}
+
+// Image b: the KB best of its KB x KB candidates by (value descending, flat index k*V + v ascending) become the new beams,
+// in that order; each takes over score, token, finished flag, length and - the state hand-over - h', c' of its parent (slot 1
+// of the parent -> slot 0 of the survivor).  grid (B), kH threads.
+template <int KB>
+__global__ void __launch_bounds__(kH) beam_select_kernel(const float* __restrict__ cand_val,
+                                                          const int* __restrict__ cand_tok, int V, long long id_end, int t,
+                                                          int BK, float* __restrict__ score, int* __restrict__ fin,
+                                                          int* __restrict__ length, long long* __restrict__ prev,
+                                                          int* __restrict__ tok_hist, int* __restrict__ bp_hist,
+                                                          float* __restrict__ Hst, float* __restrict__ Cst) {
+  constexpr int NC = KB * KB;
+  __shared__ float cv_s[NC];
+  __shared__ long long cf_s[NC];
+  __shared__ float s_val[KB];
+  __shared__ int s_src[KB], s_tok[KB], fin_s[KB], len_s[KB];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row0 = (long long)b * KB;
+  int tok = -1;
+  float val = -INFINITY;
+  if (tid < NC) {
+    tok = cand_tok[row0 * KB + tid];
+    val = cand_val[row0 * KB + tid];
+    cv_s[tid] = val;
+    cf_s[tid] = tok < 0 ? 0x7fffffffffffffffLL : (long long)(tid / KB) * V + tok;
+  }
+  if (tid < KB) {
+    fin_s[tid] = fin[row0 + tid];
+    len_s[tid] = length[row0 + tid];
+    s_src[tid] = 0; s_tok[tid] = (int)id_end; s_val[tid] = -INFINITY;
+  }
+  __syncthreads();
+  if (tid < NC && tok >= 0) {
+    const long long mine = cf_s[tid];
+    int rank = 0;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) rank += (cf_s[c] != 0x7fffffffffffffffLL && beam_better(cv_s[c], cf_s[c], val, mine)) ? 1 : 0;
+    if (rank < KB) { s_src[rank] = tid / KB; s_tok[rank] = tok; s_val[rank] = val; }
+  }
+  __syncthreads();
+  if (tid < KB) {
+    const int src = s_src[tid], tk = s_tok[tid];
+    const int was = fin_s[src];
+    score[row0 + tid] = s_val[tid];
+    fin[row0 + tid] = (was || tk == (int)id_end) ? 1 : 0;
+    length[row0 + tid] = was ? len_s[src] : t + 1;
+    prev[row0 + tid] = tk;
+    tok_hist[(long long)t * BK + row0 + tid] = tk;
+    bp_hist[(long long)t * BK + row0 + tid] = src;
+  }
+#pragma unroll
+  for (int r = 0; r < KB; ++r) {
+    const long long from = ((row0 + s_src[r]) * 2 + 1) * kH + tid, to = (row0 + r) * 2 * kH + tid;
+    Hst[to] = Hst[from];
+    Cst[to] = Cst[from];
+  }
+}
+
+// start of the search: h0 / c0 of the image (written by the init_linear GEMM into slot 1 of beam 0) for all KB beams, beam 0
+// at score 0 and the others at -inf, previous token <start>
+__global__ void __launch_bounds__(kH) beam_init_kernel(int KB, long long id_start, float* __restrict__ score,
+                                                        int* __restrict__ fin, int* __restrict__ length,
+                                                        long long* __restrict__ prev, float* __restrict__ Hst,
+                                                        float* __restrict__ Cst) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row0 = (long long)b * KB;
+  const float h = Hst[(row0 * 2 + 1) * kH + tid], c = Cst[(row0 * 2 + 1) * kH + tid];
+  for (int k = 0; k < KB; ++k) {
+    Hst[(row0 + k) * 2 * kH + tid] = h;
+    Cst[(row0 + k) * 2 * kH + tid] = c;
+  }
+  if (tid < KB) {
+    score[row0 + tid] = tid == 0 ? 0.f : -INFINITY;
+    fin[row0 + tid] = 0;
+    length[row0 + tid] = 0;
+    prev[row0 + tid] = id_start;
+  }
+}
+
+// end of the search: rank the KB hypotheses of image b by score / length^length_penalty (descending, stable in the beam index)
+// and follow the back-pointers from each, last step first, to emit its tokens (and the attention weights its steps used).
+__global__ void __launch_bounds__(256) beam_backtrack_kernel(int KB, int T, int BK, float length_penalty,
+                                                              const float* __restrict__ score, const int* __restrict__ length,
+                                                              const int* __restrict__ tok_hist, const int* __restrict__ bp_hist,
+                                                              const float* __restrict__ alpha_hist, int* __restrict__ path,
+                                                              long long* __restrict__ out_ids, float* __restrict__ out_scores,
+                                                              int* __restrict__ out_lengths, float* __restrict__ alphas_out) {
+  __shared__ float rk[kBeamMax];
+  __shared__ int ord[kBeamMax];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row0 = (long long)b * KB;
+  if (tid < KB) {
+    const float s = score[row0 + tid];
+    // length^penalty as exp(penalty * log(length)): the inlined powf compiles to packed fp32 forms the build audit refuses
+    rk[tid] = length_penalty > 0.f ? s / expf(length_penalty * logf((float)length[row0 + tid])) : s;
+  }
+  __syncthreads();
+  if (tid < KB) {
+    int rank = 0;
+    for (int k = 0; k < KB; ++k) rank += (rk[k] > rk[tid] || (rk[k] == rk[tid] && k < tid)) ? 1 : 0;
+    ord[rank] = tid;
+  }
+  __syncthreads();
+  if (tid < KB) {
+    int cur = ord[tid];
+    out_scores[row0 + tid] = score[row0 + cur];
+    out_lengths[row0 + tid] = length[row0 + cur];
+    for (int t = T - 1; t >= 0; --t) {
+      const long long at = (long long)t * BK + row0 + cur;
+      out_ids[(row0 + tid) * T + t] = tok_hist[at];
+      cur = bp_hist[at];                       // the beam that was extended at step t: its attention weights belong to the token
+      path[(row0 + tid) * T + t] = cur;
+    }
+  }
+  if (alphas_out == nullptr) return;
+  __syncthreads();
+  const int n = KB * T * kL;
+  for (int i = tid; i < n; i += 256) {
+    const int rt = i / kL, l = i - rt * kL;
+    const int t = rt % T;
+    alphas_out[(row0 * T + rt) * kL + l] = alpha_hist[((long long)t * BK + row0 + path[row0 * T + rt]) * kL + l];
+  }
+}
+
+}  // namespace dic
+
+using namespace dic;
+
+extern "C" {
+
+size_t dic_decoder_greedy_workspace_bytes(int B, int max_length, int V) {
+  bool ov;
+  return decoder_carve(nullptr, 0, B, max_length, V, B * max_length, &ov).bytes;
+}
+
+int dic_decoder_greedy(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B,
+                       long long id_start, int max_length, int mode, const float* gumbel_u, int64_t* out_ids,
+                       float* alphas_out, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  DIC_REQUIRE(w != nullptr && workspace != nullptr, "decoder: null weights/workspace");
+  DIC_REQUIRE(V > 0 && B > 0, "decoder: bad sizes");
+  DIC_REQUIRE(feat_rgb && out_ids && max_length >= 1, "decoder_greedy: bad arguments");
+  DIC_REQUIRE(mode == 0 || mode == 2, "decoder_greedy: mode must be 0 (soft) or 2 (Gumbel-max hard attention)");
+  DIC_REQUIRE(mode == 0 || gumbel_u != nullptr, "decoder_greedy: hard attention needs the uniform draws");
+  const int T = max_length, N = B * T;
+  bool ov = false;
+  DecoderWs ws = decoder_carve(workspace, workspace_bytes, B, T, V, N, &ov);
+  DIC_REQUIRE(!ov, "decoder_greedy: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+  float* alphas = alphas_out ? alphas_out : ws.dalp;     // [B,T,196] needed by the step kernel; dalp is [8,B,196]
+  if (!alphas_out) DIC_REQUIRE(T <= kNCH, "decoder_greedy: alphas_out required when max_length > %d", kNCH);
+  DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hall, ws.Call, (long long)(T + 1) * kH, false}, st));
+  hipLaunchKernelGGL(fill_ids_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, ws.ids, B, id_start);
+  DIC_LAUNCH_CHECK();
+  for (int t = 0; t < T; ++t) {
+    hipLaunchKernelGGL(embed_step_kernel, dim3(B), dim3(kE), 0, st, w->embed, ws.ids, t, T, V, ws.Xall);
+    DIC_TRY(launch_attn_step(AttnStepArgs{ws.F, ws.P, ws.Hall, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b, ws.WbT, w->fbeta_b, t, T,
+                                          mode, gumbel_u, B, 1.0f, alphas, ws.Qall, ws.ctx, ws.gate, ws.Xall, 1, FusedLstm{}, B}, kL, st));
+    DIC_TRY(gemm_slabs(B, kG, kXK, op_rowk(ws.Xall + (long long)t * kXK, (long long)T * kXK), op_rowk(ws.Wcat, kXK),
+                       ws.slab_g, kS_LSTM, st));
+    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab_g, ws.bcat, nullptr, ws.Hall, ws.Call, ws.Gact, ws.Hdrop, kS_LSTM, B, t * B}, t, T, st));
+    // pred = linear(h) (no dropout, depth_models.py:295); softmax is monotone -> argmax of the logits
+    DIC_TRY(gemm(B, V, kH, op_rowk(ws.Hdrop + (long long)t * B * kH, kH), op_rowk(w->out_w, kH),
+                 ep_store(ws.logits_step, V, w->out_b), st, 1, nullptr, 64));
+    hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, ws.logits_step, V, t, T, ws.ids, (long long*)out_ids);
+    DIC_LAUNCH_CHECK();
+  }
+  return DIC_OK;
+}
+
+// ---- beam search ------------------------------------------------------------------------------------------------------------
+namespace {
+struct BeamWs : SetupBufs {      // (no WcatT)
+  float *Hst, *Cst, *X, *slab, *Gact, *Hdrop, *logits, *cand_val, *score;
+  float* alpha_hist;
+  int *cand_tok, *fin, *length, *tok_hist, *bp_hist, *path;
+  long long* prev;
+  size_t bytes;
+};
+
+BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overflow) {
+  Carver c(p, bytes);
+  BeamWs w{};
+  const size_t BK = (size_t)B * K;
+  w.F = c.take<float>((size_t)B * kL * kD);
+  w.P = c.take<float>((size_t)B * kL * kA);
+  w.mean = c.take<float>((size_t)B * kD);
+  w.Wcat = c.take<float>((size_t)kG * kXK);
+  w.bcat = c.take<float>(kG);
+  w.WhT = c.take<float>((size_t)kH * kA);
+  w.WbT = c.take<float>((size_t)kH * kD);
+  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
+  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
+  w.Hst = c.take<float>(BK * 2 * kH);
+  w.Cst = c.take<float>(BK * 2 * kH);
+  w.X = c.take<float>(BK * kXK);
+  w.slab = c.take<float>((size_t)kS_LSTM * BK * kG);
+  w.Gact = c.take<float>(BK * kG);
+  w.Hdrop = c.take<float>(BK * kH);
+  w.logits = c.take<float>(BK * V);
+  w.cand_val = c.take<float>(BK * K);
+  w.cand_tok = c.take<int>(BK * K);
+  w.score = c.take<float>(BK);
+  w.fin = c.take<int>(BK);
+  w.length = c.take<int>(BK);
+  w.prev = c.take<long long>(BK);
+  w.tok_hist = c.take<int>(BK * T);
+  w.bp_hist = c.take<int>(BK * T);
+  w.path = c.take<int>(BK * T);
+  w.alpha_hist = c.take<float>(BK * T * kL);
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+
+// runs STMT with the beam width as the compile-time constant KB_
+#define DIC_BEAM_SWITCH(K, STMT)                       \
+  switch (K) {                                         \
+    case 1: { constexpr int KB_ = 1; STMT } break;     \
+    case 2: { constexpr int KB_ = 2; STMT } break;     \
+    case 3: { constexpr int KB_ = 3; STMT } break;     \
+    case 4: { constexpr int KB_ = 4; STMT } break;     \
+    case 5: { constexpr int KB_ = 5; STMT } break;     \
+    case 6: { constexpr int KB_ = 6; STMT } break;     \
+    case 7: { constexpr int KB_ = 7; STMT } break;     \
+    default: { constexpr int KB_ = 8; STMT } break;    \
+  }
+
+bool beam_sizes_ok(int B, int K, int max_length, int V) {
+  return B > 0 && K >= 1 && K <= kBeamMax && max_length >= 1 && V >= K;
+}
+}  // namespace
+
+size_t dic_decoder_beam_workspace_bytes(int B, int K, int max_length, int V) {
+  if (!beam_sizes_ok(B, K, max_length, V)) return 0;
+  bool ov;
+  return beam_carve(nullptr, 0, B, K, max_length, V, &ov).bytes;
+}
+
+int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                     long long id_start, long long id_end, int max_length, float length_penalty, int64_t* out_ids,
+                     float* out_scores, int* out_lengths, float* alphas_out, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call
+  DIC_REQUIRE(K >= 1 && K <= kBeamMax, "decoder_beam: beam width K=%d is outside 1..%d", K, kBeamMax);
+  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "decoder_beam: bad sizes (B=%d, V=%d, max_length=%d)", B, V, max_length);
+  DIC_REQUIRE(V >= K, "decoder_beam: vocabulary V=%d is smaller than the beam width K=%d", V, K);
+  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_beam: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_beam: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(length_penalty >= 0.f, "decoder_beam: length_penalty=%g must be >= 0 (NaN is refused too)", (double)length_penalty);
+  DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace, "decoder_beam: null pointer");
+  const int T = max_length, BK = B * K;
+  bool ov = false;
+  BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov);
+  if (ov) {
+    set_last_error("decoder_beam: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  // per image, never per beam.  [h0 | c0] -> slot 1 of beam 0, then copied to the KB beams
+  DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)K * 2 * kH, false}, st));
+  hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
+                     ws.Cst);
+  DIC_LAUNCH_CHECK();
+  for (int t = 0; t < T; ++t) {
+    float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * BK * kL : nullptr;
+    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P,
+                                          ws.Hst, ws.prev, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b,
+                                          ws.WbT, w->fbeta_b, alpha_t, ws.X, B);)
+    DIC_LAUNCH_CHECK();
+    DIC_TRY(gemm_slabs(BK, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
+    // the state arrays are lstm_fwd_kernel's Hall / Call at T = 1, t = 0: c from slot 0, h' / c' into slot 1
+    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.Hdrop, kS_LSTM, BK, 0}, 0, 1, st));
+    DIC_TRY(gemm(BK, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
+    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_topk_kernel<KB_>, dim3(BK), dim3(256), 0, st, ws.logits, V, ws.score, ws.fin,
+                                          id_end, ws.cand_val, ws.cand_tok);
+                    hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
+                                       BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
+    DIC_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(beam_backtrack_kernel, dim3(B), dim3(256), 0, st, K, T, BK, length_penalty, ws.score, ws.length,
+                     ws.tok_hist, ws.bp_hist, ws.alpha_hist, ws.path, (long long*)out_ids, out_scores, out_lengths, alphas_out);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
+
+}  // extern "C"
