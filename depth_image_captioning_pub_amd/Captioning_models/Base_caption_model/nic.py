@@ -1,0 +1,296 @@
+"""NIC / Show-and-Tell baseline (Captioning_models/Base_caption_model/nic.py): drop-in NIC_CNNEncoder / NIC_RNNDecoder and
+train_nic.
+
+Model (nic.py:23-118): frozen ResNet-152 -> global average pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) ->
+nn.Linear(128, V).  The image embedding is step 0 of the input sequence, states start at zero, dropout acts on the top layer's
+output only, the targets are ALL tokens of a caption.  Every number comes from libdic_hip.so (dic_nic_*, include/dic.h): the two
+modules keep the reference's parameter trees and state_dict keys (a checkpoint written by the reference loads with strict=True)
+and route forward / backward through torch.autograd.Function objects like the other shims.
+
+train_nic is the loop of nic.py:178-356 on synthetic batches (the COCO loaders and the vocabulary pickle are out of scope, as in
+depth_train.py).  Single GPU: data-parallel NIC is out of scope.  evaluation_nic (datasets, pycocoevalcap) is out of scope like
+the other caption metrics."""
+from __future__ import annotations
+
+import os
+from typing import Dict, Optional, Sequence
+
+import torch
+from torch import nn
+
+from ... import native, synthetic as syn
+from ..._lib import DicError
+from ...engine import CaptionTrainer, FlatParams
+from ..config import ConfigTrain
+from .base_caption_models import _LAYERS, CNNEncoder_Atten
+
+tqdm_disable = True   # nic.py:20
+_DEC_KEYS = [k for k, _ in native.NIC_FIELDS]
+
+
+def _contig(t):
+    return t if t is None or t.is_contiguous() else t.contiguous()
+
+
+class _NicHeadFn(torch.autograd.Function):
+    """pooled = mean over the cells of the backbone's final map, features = linear(pooled); no gradient into the frozen backbone."""
+
+    @staticmethod
+    def forward(ctx, fmap, weight, bias):
+        pooled, feats = native.nic_head_forward(weight.detach(), bias.detach(), _contig(fmap.detach()))
+        ctx.pooled = pooled
+        return feats
+
+    @staticmethod
+    def backward(ctx, d_features):
+        gw, gb = native.nic_head_backward(ctx.pooled, _contig(d_features))
+        return None, gw, gb
+
+
+class _NicDecoderFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cfg, features, captions, *params):
+        weights = {k: p.detach() for k, p in zip(_DEC_KEYS, params)}
+        logits, tape = native.nic_forward(weights, _contig(features.detach()), captions, cfg["lengths"], cfg.get("drop_mult"))
+        ctx.tape = tape
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        grads, dfeat = native.nic_backward(ctx.tape, _contig(d_logits))
+        return (None, dfeat, None) + tuple(grads[k] for k in _DEC_KEYS)
+
+
+class NIC_CNNEncoder(CNNEncoder_Atten):
+    """nic.py:23-57.  `backbone` = the ResNet-152 children()[:-1] of the reference (its own global average pool last: the state_dict
+    keys are those of CNNEncoder_Atten's backbone), `linear` = nn.Linear(2048, dim_embedding), the only trained part.
+    `layers` / `conv_mode` are the knobs of CNNEncoder_Atten (not part of the reference's signature)."""
+
+    def __init__(self, dim_embedding: int, layers=_LAYERS, conv_mode: str = None):
+        super().__init__(14, layers=layers, conv_mode=conv_mode)
+        if dim_embedding != native.NIC_EMB:
+            raise DicError(f"NIC_CNNEncoder: the native NIC path is built for dim_embedding = {native.NIC_EMB} "
+                           f"(config.py:28; DIC_NIC_E of include/dic.h), got {dim_embedding}")
+        self.backbone[-1] = nn.AdaptiveAvgPool2d((1, 1))      # (no parameters: the average is taken by dic_nic_head_fwd)
+        self.linear = nn.Linear(native.D_ENC, dim_embedding)
+
+    def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+        """[B,3,224,224] -> [B,300].  The backbone runs without gradient, in train() mode with batch statistics and running-stat
+        updates (quirk Q1, nic.py:265), exactly as CNNEncoder_Atten.forward does; `linear` is differentiable."""
+        if tuple(imgs.shape[-2:]) != (224, 224):
+            raise DicError("NIC_CNNEncoder: the native path takes the reference's 224x224 inputs (nic.py:193: T.Resize((224, 224)))")
+        with torch.no_grad():
+            runner = self._native()
+            fmap = runner.forward(imgs, train_bn=self.training, compact=True)        # the 7x7 map itself, [B,49,2048]
+            if self.check_overflow:
+                runner.check_overflow()
+            if self.training:
+                for m in self.modules():
+                    if isinstance(m, nn.BatchNorm2d):
+                        m.num_batches_tracked += 1
+        return _NicHeadFn.apply(fmap, self.linear.weight, self.linear.bias)
+
+
+class NIC_RNNDecoder(nn.Module):
+    """nic.py:61-175.  Parameters live in the reference's sub-modules (embed, lstm, linear), so state_dict() has its keys."""
+
+    def __init__(self, dim_embedding: int, dim_hidden: int, vocab_size: int, num_layers: int, dropout: float = 0.1):
+        super().__init__()
+        if dim_embedding != native.NIC_EMB or dim_hidden != native.D_HID or num_layers != 2:
+            raise DicError(f"NIC_RNNDecoder: the native kernels are built for dim_embedding = {native.NIC_EMB}, dim_hidden = "
+                           f"{native.D_HID} and num_layers = 2 (config.py:28-29,15), got ({dim_embedding}, {dim_hidden}, {num_layers})")
+        self.vocab_size = vocab_size
+        self.embed = nn.Embedding(vocab_size, dim_embedding)
+        self.lstm = nn.LSTM(dim_embedding, dim_hidden, num_layers, batch_first=True)      # parameter holder: never called
+        self.linear = nn.Linear(dim_hidden, vocab_size)
+        self.dropout = nn.Dropout(dropout)
+        self._rng_seed = int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
+        self._rng_offset = 0
+
+    def _params(self):
+        sd = dict(self.named_parameters())
+        return [sd[k] for k in _DEC_KEYS]
+
+    def _weights(self) -> Dict[str, torch.Tensor]:
+        return {k: p.detach() for k, p in zip(_DEC_KEYS, self._params())}
+
+    def forward(self, features: torch.Tensor, captions: torch.Tensor, lengths: list) -> torch.Tensor:
+        """-> logits [sum(lengths), V], the rows of PackedSequence.data (nic.py:93-118)."""
+        cfg = {"lengths": [int(l) for l in lengths]}
+        p = float(self.dropout.p)
+        if self.training and p > 0.0:
+            B, tmax = features.shape[0], max(cfg["lengths"])
+            cfg["drop_mult"] = native.dropout_mask((B, tmax, native.D_HID), p, self._rng_seed, self._rng_offset, features.device)
+            self._rng_offset += B * tmax * native.D_HID // 4 + 1
+        return _NicDecoderFn.apply(cfg, features, captions, *self._params())
+
+    def _greedy(self, features, states, max_length):
+        if states is not None:
+            raise DicError("NIC_RNNDecoder: the native greedy decode starts from zero states (the reference never passes any)")
+        return native.nic_greedy(self._weights(), _contig(features), max_length)
+
+    @torch.no_grad()
+    def sample(self, features: torch.Tensor, states=None, max_length: int = 30):
+        """Greedy caption of the FIRST image: list of token ids (nic.py:126-148)."""
+        return [int(v) for v in self._greedy(features[:1], states, max_length)[0].cpu().tolist()]
+
+    @torch.no_grad()
+    def batch_sample(self, features: torch.Tensor, states=None, max_length: int = 30):
+        """Greedy captions of a batch: list of B lists of token ids (nic.py:150-175)."""
+        return [[int(v) for v in row] for row in self._greedy(features, states, max_length).cpu().tolist()]
+
+
+class NicTrainer(CaptionTrainer):
+    """Weights, optimiser state and workspaces of one NIC training run: the 11 decoder tensors and encoder.linear in one flat fp32
+    buffer (one AdamW launch per step, nic.py:243-245).  The frozen ResNet-152 side is CaptionTrainer's as it stands - forwards of
+    the next batches running ahead on side streams (captured graphs), BatchNorm running statistics applied in batch order, the
+    f16x2 overflow guard as AdamW's skip word - with the depth branch and the attention decoder switched off.  Single GPU."""
+
+    def __init__(self, vocab: int, device: str = "cuda:0", seed: int = 123, lr: float = 1e-3, dropout: float = 0.5,
+                 resnet_layers: Sequence[int] = _LAYERS, conv_mode: Optional[str] = None,
+                 decoder_init: Optional[Dict[str, torch.Tensor]] = None, head_init: Optional[Dict[str, torch.Tensor]] = None,
+                 resnet_init: Optional[Dict[str, torch.Tensor]] = None):
+        placeholder = {k: torch.zeros(1) for k, _ in native.DECODER_FIELDS}       # (the attention decoder's slots stay empty)
+        super().__init__(vocab, device=device, seed=seed, lr=lr, hard=False, resnet_layers=resnet_layers, dropout=dropout,
+                         decoder_init=placeholder, resnet_init=resnet_init, conv_mode=conv_mode, use_depth=False)
+        dec, head = syn.nic_weights(vocab, seed=seed)
+        dec = decoder_init if decoder_init is not None else dec
+        head = head_init if head_init is not None else head
+        merged = {"decoder." + k: dec[k] for k in _DEC_KEYS}
+        merged.update({"encoder.linear.weight": head["linear.weight"], "encoder.linear.bias": head["linear.bias"]})
+        self.flat = FlatParams(merged, self.device)
+        self.dec_names = list(_DEC_KEYS)
+        self.dec_w = {k: self.flat.view(self.flat.data, "decoder." + k) for k in _DEC_KEYS}
+        self.dec_g = {k: self.flat.view(self.flat.grad, "decoder." + k) for k in _DEC_KEYS}
+        self.head_w, self.head_b = (self.flat.view(self.flat.data, "encoder.linear." + k) for k in ("weight", "bias"))
+        self.head_gw, self.head_gb = (self.flat.view(self.flat.grad, "encoder.linear." + k) for k in ("weight", "bias"))
+        self.dec_span = (0, self.flat.total)
+
+    def step_on_map(self, fmap: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int],
+                    drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False) -> torch.Tensor:
+        """Head + decoder forward, loss, backward and AdamW on a final feature map [B,cells,2048] (nic.py:278-290).  Unless
+        keep_guard, the map is taken as given (no ResNet forward behind it: the overflow guard word is cleared)."""
+        if not keep_guard:
+            self._guard_take(None)
+        B, tmax = fmap.shape[0], max(lengths)
+        pooled, feats = native.nic_head_forward(self.head_w, self.head_b, fmap)
+        if drop_mult is None and dropout and self.p_drop > 0:
+            drop_mult = native.dropout_mask((B, tmax, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset, self.device)
+            self.rng_offset += B * tmax * native.D_HID // 4 + 1
+        logits, tape = native.nic_forward(self.dec_w, feats, captions, lengths, drop_mult, workspace=self.dec_ws)
+        self.dec_ws = tape.workspace
+        self._mark("nic_fwd")
+        loss, dlogits, _ = native.caption_loss(logits, native.nic_pack_targets(captions, lengths), None,
+                                               in_place=not self.keep_outputs)
+        self._mark("loss")
+        _, dfeat = native.nic_backward(tape, dlogits, grads=self.dec_g)
+        gw, gb = native.nic_head_backward(pooled, dfeat)
+        self.head_gw.copy_(gw)
+        self.head_gb.copy_(gb)
+        self._mark("nic_bwd")
+        self.apply_update()                    # AdamW on the flat buffer, skipped on the device when the guard word is raised
+        self._mark("adamw")
+        self.last = {"logits": logits, "features": feats, "map": fmap}
+        return loss
+
+    def train_step(self, imgs: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int], next_imgs=None) -> torch.Tensor:
+        """One iteration of nic.py:270-290; returns the loss as a 1-element device tensor (no host sync).  next_imgs: the images
+        of the following batches in order (CaptionTrainer.train_step's convention): their ResNet forwards run ahead."""
+        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
+        self.marks = []
+        self._mark("start")
+        fmap = self._take_prefetched(imgs)
+        if fmap is None:
+            fmap = self._resnet_eager(imgs, True, True)                       # train-mode BatchNorm in the frozen net (Q1)
+            self._guard_take(self.resnet)
+        if next_imgs is not None:
+            upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
+            for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
+                if k >= len(self.queue):
+                    self.prefetch_features(nxt, compact=True)
+        self._mark("resnet152_fwd")
+        return self.step_on_map(fmap, captions, lengths, keep_guard=True)
+
+    @torch.no_grad()
+    def eval_loss(self, imgs: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
+        """Validation forward (nic.py:312-331): eval-mode BatchNorm, dropout off."""
+        fmap = self._resnet_eager(imgs, False, True)
+        _, feats = native.nic_head_forward(self.head_w, self.head_b, fmap)
+        logits, tape = native.nic_forward(self.dec_w, feats, captions, lengths, None, workspace=self.dec_ws)
+        self.dec_ws = tape.workspace
+        loss, _, _ = native.caption_loss(logits, native.nic_pack_targets(captions, lengths), None)
+        return loss
+
+    def state_dicts(self):
+        """state_dict contents of NIC_CNNEncoder / NIC_RNNDecoder, loadable with strict=True."""
+        enc = super().state_dicts()["encoder"]                       # backbone.* incl. num_batches_tracked (Q1)
+        enc["linear.weight"], enc["linear.bias"] = self.head_w.detach().clone(), self.head_b.detach().clone()
+        return {"encoder": enc, "decoder": {k: v.detach().clone() for k, v in self.dec_w.items()}}
+
+
+def _synthetic_batches(config, n: int, seed0: int):
+    for i in range(n):
+        s = seed0 + 7919 * i
+        caps, lens = syn.captions_fixed(config.batch_size, config.vocab_size, config.seq_len, seed=s)
+        yield syn.rgb_images(config.batch_size, seed=s), caps, lens
+
+
+def train_nic(ext, useData: str = "synthetic", config=None, stats=None):
+    """The loop of nic.py:178-356 on synthetic batches: ResNet forward in train mode (config.conv_mode arithmetic), NIC forward,
+    mean cross-entropy over all packed tokens, backward, AdamW (lr config.lr; the reference builds a MultiStepLR scheduler and never
+    steps it, quirk Q2) over the decoder and encoder.linear; per epoch a validation loss in eval mode, loss CSVs and the
+    best-validation checkpoints nic_encoder_best{ext}.pth / nic_decoder_best{ext}.pth under config.save_directory_nic.
+    Returns [(train loss, validation loss)] per epoch.  Single GPU; data-parallel NIC is out of scope.
+    config.resnet_layers (optional, not in the reference) shrinks the backbone's block counts for smoke runs."""
+    config = config or ConfigTrain()
+    resnet_layers = tuple(getattr(config, "resnet_layers", None) or _LAYERS)
+    if useData != "synthetic":
+        raise DicError(f"useData={useData!r}: the MSCOCO / original-dataset loaders and the vocabulary pickle are outside "
+                       "this build's scope (SURVEY.md 8f) and not available offline; use useData='synthetic'")
+    save_directory = config.save_directory_nic
+    os.makedirs(save_directory, exist_ok=True)
+    train_loss_file = f"{save_directory}/nic_train_loss{ext}.csv"
+    val_loss_file = f"{save_directory}/nic_val_loss{ext}.csv"
+    trainer = NicTrainer(config.vocab_size, device=config.device, seed=123 + int(ext), lr=config.lr, dropout=config.dropout,
+                         resnet_layers=resnet_layers, conv_mode=getattr(config, "conv_mode", None))
+    print(f"[nic] frozen ResNet-152 convolutions in {trainer.conv_mode} arithmetic (config.conv_mode)", flush=True)
+    if stats is not None:
+        stats.update(conv_mode=trainer.conv_mode)
+    dev = config.device
+    n_val = max(1, config.iters_per_epoch // 4)
+    val_loss_best = float("inf")
+    history = []
+    for epoch in range(config.num_epochs):
+        losses = []
+        # two batches of look-ahead: the frozen ResNet runs ahead of the step on side streams (as depth_train._train)
+        stream_it = ((imgs.to(dev), caps.to(dev), lens) for imgs, caps, lens in
+                     _synthetic_batches(config, config.iters_per_epoch, 1000 * epoch))
+        ahead = []
+        for nxt in stream_it:
+            ahead.append(nxt)
+            if len(ahead) > 2:
+                break
+        while ahead:
+            imgs, caps, lens = ahead.pop(0)
+            nxt = next(stream_it, None)
+            if nxt is not None:
+                ahead.append(nxt)
+            losses.append(trainer.train_step(imgs, caps, lens, next_imgs=[a[0] for a in ahead[:2]]))      # no per-iteration host sync
+        trainer.check_status()          # f16x2 overflow guard: raises DicError if a step of this epoch tripped it
+        train_loss = float(torch.stack(losses).mean().item())
+        with open(train_loss_file, "a") as f:
+            print(f"{epoch}, {train_loss}", file=f)
+        val_losses = [trainer.eval_loss(imgs.to(dev), caps.to(dev), lens) for imgs, caps, lens in _synthetic_batches(config, n_val, 777)]
+        trainer.check_status()
+        val_loss = float(torch.stack(val_losses).mean().item())
+        with open(val_loss_file, "a") as f:
+            print(f"{epoch}, {val_loss}", file=f)
+        history.append((train_loss, val_loss))
+        if val_loss < val_loss_best:                                               # nic.py:343-356
+            val_loss_best = val_loss
+            sd = trainer.state_dicts()
+            torch.save(sd["encoder"], f"{save_directory}/nic_encoder_best{ext}.pth")
+            torch.save(sd["decoder"], f"{save_directory}/nic_decoder_best{ext}.pth")
+    if stats is not None:
+        stats.update(steps=trainer.step_count, best_val_loss=val_loss_best)
+    return history

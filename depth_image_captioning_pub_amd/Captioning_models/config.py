@@ -13,6 +13,8 @@ class ConfigTrain(object):
         self.dim_embedding = 128        # :13
         self.dim_encoder = 2048         # :14
         self.dim_hidden = 128           # :15
+        self.nic_dim_embedding = 300    # :28 (NIC / Show-and-Tell)
+        self.num_layers = 2             # :29 (NIC: stacked LSTM layers)
         self.lr = 0.001                 # :20
         self.dropout = 0.5              # :21
         self.batch_size = 30            # :22
@@ -25,6 +27,7 @@ class ConfigTrain(object):
         self.moving_avg = 100           # :71
         self.save_directory_soft = self.cwd + "/exp_result/base_soft"           # config.py:45 (base-soft; base_train.py:253 also puts base-hard here)
         self.save_directory_hard = self.cwd + "/exp_result/base_hard"           # :51
+        self.save_directory_nic = self.cwd + "/exp_result/NIC"                        # :57
         self.save_directory_Cdep_soft = self.cwd + "/exp_result/CNN_depth_soft"
         self.save_directory_Cdep_hard = self.cwd + "/exp_result/CNN_depth_hard"
         # synthetic-run knobs (no dataset / vocabulary ships with the reference)

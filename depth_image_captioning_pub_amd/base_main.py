@@ -1,13 +1,16 @@
 """CLI with the reference's argument convention (base_main.py:14-43):
     python -m depth_image_captioning_pub_amd.base_main {soft,hard} {coco,original,synthetic}
-= 3 repetitions of train_base_{soft,hard}(i, useData) (base_main.py:23-27, 31-35).  `nic` (Show-and-Tell, base_main.py:41-43)
-is outside this build's scope.  The reference's hard branch compares instead of assigning
+    python -m depth_image_captioning_pub_amd.base_main nic [synthetic]
+= 3 repetitions of train_base_{soft,hard}(i, useData) (base_main.py:23-27, 31-35) resp. of train_nic(i) (Show-and-Tell,
+base_main.py:40-42; the reference's nic branch takes no data argument, here it defaults to `synthetic`, and any other value
+raises the DicError the other trainers raise for `coco` / `original`).  The reference's hard branch compares instead of assigning
 (`useData == args[2]`, base_main.py:31) and therefore raises NameError as shipped; the intent is kept."""
 from __future__ import annotations
 
 import sys
 
 from .Captioning_models.Base_caption_model.base_train import train_base_hard, train_base_soft
+from .Captioning_models.Base_caption_model.nic import train_nic
 from .depth_main import EXP_TIME, torch_seed
 
 
@@ -19,8 +22,9 @@ def main(argv=None):
         print("input {soft/hard} {coco/original} or only nic")
         return 1
     if args[1] == "nic":
-        print("nic (Show-and-Tell) is outside this build's scope")
-        return 1
+        for i in range(EXP_TIME):
+            train_nic(i, args[2] if len(args) > 2 else "synthetic")
+        return 0
     fn = {"soft": train_base_soft, "hard": train_base_hard}.get(args[1])
     if fn is None or len(args) < 3 or args[2] not in datas:
         print("input coco or original")

@@ -24,6 +24,8 @@ size_t dic_struct_bytes(int which) {
     case 3: return sizeof(dic_depth_encoder_weights);
     case 4: return sizeof(dic_depth_encoder_grads);
     case 5: return sizeof(dic_depth_bn_state);
+    case 6: return sizeof(dic_nic_weights);
+    case 7: return sizeof(dic_nic_grads);
     default: return 0;
   }
 }

@@ -613,3 +613,173 @@ def attention_backward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: tor
                                ptr(g["full_att.bias"]), ptr(d_feats), ptr(d_h), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
     check(rc, "dic_attention_bwd")
     return g, d_feats, d_h
+
+
+# ---------------------------------------------------------------------------------------------
+# NIC / Show-and-Tell baseline (dic_nic_*; semantics: include/dic.h)
+# ---------------------------------------------------------------------------------------------
+NIC_EMB = 300
+# state_dict key of NIC_RNNDecoder  ->  field of dic_nic_weights / dic_nic_grads
+NIC_FIELDS = (
+    ("embed.weight", "embed"),
+    ("lstm.weight_ih_l0", "w_ih_l0"), ("lstm.weight_hh_l0", "w_hh_l0"), ("lstm.bias_ih_l0", "b_ih_l0"), ("lstm.bias_hh_l0", "b_hh_l0"),
+    ("lstm.weight_ih_l1", "w_ih_l1"), ("lstm.weight_hh_l1", "w_hh_l1"), ("lstm.bias_ih_l1", "b_ih_l1"), ("lstm.bias_hh_l1", "b_hh_l1"),
+    ("linear.weight", "out_w"), ("linear.bias", "out_b"),
+)
+
+
+class NicPtrs(C.Structure):
+    """Mirrors dic_nic_weights AND dic_nic_grads (identical field order)."""
+    _fields_ = [(field, C.c_void_p) for _, field in NIC_FIELDS]
+
+
+def nic_shapes(vocab: int) -> Dict[str, Tuple[int, ...]]:
+    G = 4 * D_HID
+    return {"embed.weight": (vocab, NIC_EMB), "lstm.weight_ih_l0": (G, NIC_EMB), "lstm.weight_hh_l0": (G, D_HID),
+            "lstm.bias_ih_l0": (G,), "lstm.bias_hh_l0": (G,), "lstm.weight_ih_l1": (G, D_HID), "lstm.weight_hh_l1": (G, D_HID),
+            "lstm.bias_ih_l1": (G,), "lstm.bias_hh_l1": (G,), "linear.weight": (vocab, D_HID), "linear.bias": (vocab,)}
+
+
+def nic_ptrs(tensors: Dict[str, torch.Tensor]) -> Tuple[NicPtrs, list]:
+    lib = _lib.load()
+    _lib.check_struct(lib, 6, NicPtrs)
+    _lib.check_struct(lib, 7, NicPtrs)
+    shapes = nic_shapes(tensors["linear.weight"].shape[0])
+    keep, s = [], NicPtrs()
+    for key, field in NIC_FIELDS:
+        t = _dev_f32(tensors[key], key)
+        if tuple(t.shape) != shapes[key]:
+            raise _lib.DicError(f"{key}: expected {shapes[key]}, got {tuple(t.shape)} (the native NIC path is built for "
+                                f"dim_embedding {NIC_EMB}, dim_hidden {D_HID}, 2 layers)")
+        keep.append(t)
+        setattr(s, field, t.data_ptr())
+    return s, keep
+
+
+def _nic_captions(captions: torch.Tensor) -> torch.Tensor:
+    caps = captions if captions.is_contiguous() else captions.contiguous()
+    if caps.dtype != torch.int64 or not caps.is_cuda or caps.dim() != 2:
+        raise _lib.DicError("captions must be an int64 GPU tensor [B, length]")
+    return caps
+
+
+@dataclass
+class NicTape:
+    """Everything dic_nic_bwd needs from the matching forward call."""
+    workspace: torch.Tensor
+    lengths: List[int]
+    batch_sizes: List[int]
+    n_packed: int
+    tmax: int
+    vocab: int
+    captions: torch.Tensor
+    drop_mult: Optional[torch.Tensor]
+    weights: Dict[str, torch.Tensor]
+
+
+def nic_head_forward(enc_w: torch.Tensor, enc_b: torch.Tensor, fmap: torch.Tensor):
+    """dic_nic_head_fwd: map [B,cells,2048] (or an already pooled [B,2048]) -> (pooled [B,2048], features [B,300])."""
+    lib = _lib.load()
+    m = _dev_f32(fmap, "map")
+    if m.dim() == 2:
+        m = m.unsqueeze(1)
+    if m.dim() != 3 or m.shape[2] != D_ENC:
+        raise _lib.DicError(f"map must be [B,cells,{D_ENC}], got {tuple(fmap.shape)}")
+    w, b = _dev_f32(enc_w, "encoder.linear.weight"), _dev_f32(enc_b, "encoder.linear.bias")
+    if tuple(w.shape) != (NIC_EMB, D_ENC) or tuple(b.shape) != (NIC_EMB,):
+        raise _lib.DicError(f"encoder.linear must be [{NIC_EMB},{D_ENC}] / [{NIC_EMB}]")
+    B, cells = int(m.shape[0]), int(m.shape[1])
+    pooled = torch.empty((B, D_ENC), dtype=torch.float32, device=m.device)
+    feats = torch.empty((B, NIC_EMB), dtype=torch.float32, device=m.device)
+    check(lib.dic_nic_head_fwd(ptr(w), ptr(b), ptr(m), cells, B, ptr(pooled), ptr(feats), stream_ptr()), "dic_nic_head_fwd")
+    return pooled, feats
+
+
+def nic_head_backward(pooled: torch.Tensor, d_features: torch.Tensor):
+    """dic_nic_head_bwd: (gradient of encoder.linear.weight [300,2048], of encoder.linear.bias [300])."""
+    lib = _lib.load()
+    p, d = _dev_f32(pooled, "pooled"), _dev_f32(d_features, "d_features")
+    B = int(p.shape[0])
+    if tuple(p.shape) != (B, D_ENC) or tuple(d.shape) != (B, NIC_EMB):
+        raise _lib.DicError("nic_head_backward: expected pooled [B,2048] and d_features [B,300]")
+    gw = torch.empty((NIC_EMB, D_ENC), dtype=torch.float32, device=p.device)
+    gb = torch.empty((NIC_EMB,), dtype=torch.float32, device=p.device)
+    check(lib.dic_nic_head_bwd(ptr(p), ptr(d), B, ptr(gw), ptr(gb), stream_ptr()), "dic_nic_head_bwd")
+    return gw, gb
+
+
+def nic_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int],
+                drop_mult: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """dic_nic_fwd.  Returns (logits_packed [n_packed,V], tape); `lengths` are the full caption lengths (descending)."""
+    lib = _lib.load()
+    f = _dev_f32(features, "features")
+    B = int(f.shape[0])
+    if tuple(f.shape) != (B, NIC_EMB):
+        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    lens = [int(l) for l in lengths]
+    if len(lens) != B:
+        raise _lib.DicError("one length per batch row")
+    wp, keep = nic_ptrs(weights)
+    caps = _nic_captions(captions)
+    vocab = int(weights["linear.weight"].shape[0])
+    tmax = max(lens) if lens else 0
+    bsz = batch_sizes_of(lens) if tmax > 0 else []
+    n_packed = sum(bsz)
+    lib.dic_nic_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_nic_workspace_bytes(B, tmax, vocab, n_packed)       # (0 for sizes the call below refuses with its text)
+    if workspace is None or workspace.numel() < max(need, 256):
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=f.device)
+    dm = _dev_f32(drop_mult, "drop_mult") if drop_mult is not None else None
+    if dm is not None and tuple(dm.shape) != (B, tmax, D_HID):
+        raise _lib.DicError(f"drop_mult must be [B,Tmax,{D_HID}] = {(B, tmax, D_HID)}, got {tuple(dm.shape)}")
+    logits = torch.empty((max(n_packed, 1), vocab), dtype=torch.float32, device=f.device)[:n_packed]
+    rc = lib.dic_nic_fwd(C.byref(wp), vocab, ptr(f), ptr(caps), caps.stride(0), _i32_host(lens), B, ptr(dm), ptr(logits),
+                         ptr(workspace), C.c_size_t(workspace.numel()), stream_ptr())
+    check(rc, "dic_nic_fwd")
+    return logits, NicTape(workspace, lens, bsz, n_packed, tmax, vocab, caps, dm, {k: t for (k, _), t in zip(NIC_FIELDS, keep)})
+
+
+def nic_backward(tape: NicTape, dlogits: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]] = None):
+    """dic_nic_bwd.  Returns (grads dict keyed like state_dict, d_features [B,300])."""
+    lib = _lib.load()
+    if grads is None:
+        grads = {k: torch.empty_like(t) for k, t in tape.weights.items()}
+    gp, keep_g = nic_ptrs(grads)
+    wp, keep_w = nic_ptrs(tape.weights)
+    dl = _dev_f32(dlogits, "dlogits")
+    B = len(tape.lengths)
+    dfeat = torch.empty((B, NIC_EMB), dtype=torch.float32, device=dl.device)
+    rc = lib.dic_nic_bwd(C.byref(wp), tape.vocab, ptr(tape.captions), tape.captions.stride(0), _i32_host(tape.lengths), B,
+                         ptr(tape.drop_mult), ptr(dl), C.byref(gp), ptr(dfeat), ptr(tape.workspace),
+                         C.c_size_t(tape.workspace.numel()), stream_ptr())
+    check(rc, "dic_nic_bwd")
+    return grads, dfeat
+
+
+def nic_pack_targets(captions: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
+    """dic_nic_pack_targets: pack_padded_sequence(captions, lengths).data - all len_b tokens of a row."""
+    lib = _lib.load()
+    lens = [int(l) for l in lengths]
+    caps = _nic_captions(captions)
+    out = torch.empty(max(sum(max(l, 0) for l in lens), 1), dtype=torch.int64, device=caps.device)
+    check(lib.dic_nic_pack_targets(ptr(caps), caps.stride(0), _i32_host(lens), len(lens), ptr(out), stream_ptr()),
+          "dic_nic_pack_targets")
+    return out[:sum(lens)]
+
+
+def nic_greedy(weights: Dict[str, torch.Tensor], features: torch.Tensor, max_length: int = 30) -> torch.Tensor:
+    """dic_nic_greedy.  Returns ids int64 [B,max_length] on the device."""
+    lib = _lib.load()
+    f = _dev_f32(features, "features")
+    B = int(f.shape[0])
+    if tuple(f.shape) != (B, NIC_EMB):
+        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    wp, keep = nic_ptrs(weights)
+    vocab = int(weights["linear.weight"].shape[0])
+    lib.dic_nic_greedy_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_nic_greedy_workspace_bytes(B, int(max_length), vocab)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f.device)
+    ids = torch.empty((B, max(int(max_length), 1)), dtype=torch.int64, device=f.device)
+    rc = lib.dic_nic_greedy(C.byref(wp), vocab, ptr(f), B, int(max_length), ptr(ids), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    check(rc, "dic_nic_greedy")
+    return ids

@@ -281,3 +281,41 @@ def dpt_images(batch: int, seed: int = 123, size: int = 384) -> torch.Tensor:
     """What util.dep_trans hands the estimator: RGB in [0,1) -> Normalize(0.5, 0.5) = [-1,1)   (util.py:14-17)."""
     x = _rng(seed + 6000).random((batch, 3, size, size), dtype=np.float32)
     return torch.from_numpy((x - 0.5) / 0.5)
+
+
+# ---------------------------------------------------------------------------------------------
+# NIC / Show-and-Tell baseline (Base_caption_model/nic.py)
+# ---------------------------------------------------------------------------------------------
+NIC_EMB = 300                                                     # Captioning_models/config.py:28 (nic_dim_embedding)
+
+
+def nic_weights(vocab: int, seed: int = 123, sharp: bool = False) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+    """(decoder, encoder head): the 11 tensors of NIC_RNNDecoder(300, 128, vocab, 2) under the reference's state_dict names and
+    `linear.weight` [300,2048] / `linear.bias` of NIC_CNNEncoder.  embed / linear.weight U(-0.1, 0.1) like decoder_weights, the
+    rest PyTorch's defaults.  sharp=True draws embed.weight and linear.weight from U(-1, 1) instead: with the plain bounds every
+    logit is of magnitude <= 0.1 and a greedy decode emits a handful of distinct tokens for a whole batch, which tests nothing."""
+    r = _rng(seed)
+    E, H, V = NIC_EMB, D_HID, vocab
+    wide = 1.0 if sharp else 0.1
+    k = 1.0 / math.sqrt(H)
+    w: Dict[str, torch.Tensor] = {"embed.weight": _uniform(r, (V, E), wide)}
+    for layer, in_f in ((0, E), (1, H)):
+        w[f"lstm.weight_ih_l{layer}"] = _uniform(r, (4 * H, in_f), k)
+        w[f"lstm.weight_hh_l{layer}"] = _uniform(r, (4 * H, H), k)
+        w[f"lstm.bias_ih_l{layer}"] = _uniform(r, (4 * H,), k)
+        w[f"lstm.bias_hh_l{layer}"] = _uniform(r, (4 * H,), k)
+    w["linear.weight"] = _uniform(r, (V, H), wide)
+    w["linear.bias"] = torch.zeros(V, dtype=torch.float32)
+    b = 1.0 / math.sqrt(D_ENC)
+    head = {"linear.weight": _uniform(r, (E, D_ENC), b), "linear.bias": _uniform(r, (E,), b)}
+    return w, head
+
+
+def nic_map(batch: int, cells: int, seed: int) -> torch.Tensor:
+    """Non-negative final feature map [B, cells, 2048] for the NIC encoder head whose rows keep their identity under the mean
+    over the cells: relu(row vector + half-size per-cell noise).  (A map of independent cells pools to nearly the same vector for
+    every image, and a batch of identical captions tests nothing.)"""
+    r = _rng(seed)
+    base = r.standard_normal((batch, 1, D_ENC))
+    noise = r.standard_normal((batch, cells, D_ENC))
+    return torch.from_numpy(np.maximum(base + 0.5 * noise, 0).astype(np.float32))

@@ -38,7 +38,7 @@ int dic_version(void);
 const char* dic_last_error(void);
 /* sizeof() of the structs of this header as the library sees them, for bindings that mirror them by hand (ctypes.Structure, cgo, JNI):
  * which 0 dic_conv_bn_layer, 1 dic_decoder_weights, 2 dic_decoder_grads, 3 dic_depth_encoder_weights, 4 dic_depth_encoder_grads,
- * 5 dic_depth_bn_state; 0 for an unknown index. */
+ * 5 dic_depth_bn_state, 6 dic_nic_weights, 7 dic_nic_grads; 0 for an unknown index. */
 size_t dic_struct_bytes(int which);
 
 /* ---- generic exact-fp32 MFMA contraction (building block; replaces the aten::addmm / aten::mm
@@ -155,6 +155,59 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
                      long long id_start, long long id_end, int max_length, float length_penalty, int64_t* out_ids,
                      float* out_scores, int* out_lengths, float* alphas_out, void* workspace, size_t workspace_bytes,
                      void* stream);
+
+/* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
+ *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
+ *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both
+ *     biases b_ih + b_hh per layer; no dropout between the layers (nn.LSTM is built without it, nic.py:78-79); h and c of both
+ *     layers start at ZERO (nic.py:110: there is no init_linear).
+ *   Encoder head (nic.py:47-57): pooled[b,:] = mean over the `cells` rows of map[b,:,:] (map [B,cells,2048], cells >= 1: the 7x7
+ *     map of dic_resnet_fwd_map, a 196-cell map or an already pooled vector), features = pooled enc_w^T + enc_b (enc_w [300,2048]).
+ *     The backbone runs frozen, in train mode while training (quirk Q1: dic_resnet_fwd_map(train_bn=1) as it stands); the head's
+ *     backward turns d_features into the gradients of enc_w / enc_b (written) and stops there.
+ *   Teacher-forced forward (nic.py:93-118): the input sequence of row b is [features[b], embed(c[b,0]), ..., embed(c[b,len_b-2])] -
+ *     the image is step 0, the last token is never an input - packed with the FULL caption lengths (HOST int[B], descending,
+ *     1 <= len_b <= cap_stride), so row b runs len_b steps, Tmax = lengths[0], n_packed = sum(lengths).
+ *     logits_packed [n_packed,V], time-major rows like PackedSequence.data (row of (t, b) = sum_b' min(len_b', t) + b),
+ *     = linear(drop * h_top); drop_mult [B,Tmax,H] is an explicit multiplier (0 or 1/(1-p)) on the top layer's output, NULL = eval
+ *     (quirk Q6, as dic_decoder_fwd).
+ *   Targets (nic.py:282-285): pack(captions, lengths).data - ALL len_b tokens of a row, not captions[:,1:]: dic_nic_pack_targets
+ *     (`targets`: n_packed int64, nothing else).  The loss is dic_caption_loss with alphas = NULL.  The reference passes
+ *     ignore_index = <null>; a <null> inside a caption's length does not occur in collated data (padding starts at len_b), and
+ *     like the attention decoders this path does not treat it specially.
+ *   Backward: consumes the workspace left by dic_nic_fwd (same arguments); writes (not accumulates) the 11 gradients and
+ *     d_features [B,300].  The embedding gradient is reduced in a fixed order without float atomics: two runs on the same inputs
+ *     give bit-identical gradients.
+ *   Greedy decode (batch_sample / sample, nic.py:126-175): step 0 input is features[b], states zero, exactly max_length steps,
+ *     token = argmax(linear(h_top)) (softmax is monotone; first maximum on ties), next input embed(token); there is NO start token
+ *     and no early stop.  Tokens stay on the device.  out_ids int64 [B,max_length].
+ *   Every argument violation - a null pointer, B <= 0, V <= 0, cells < 1, lengths not descending, a length < 1 or > cap_stride, a
+ *     short workspace, max_length < 1 - returns a negative code with a dic_last_error() text that starts with the entry point's
+ *     name, before anything is launched.  The workspace queries return 0 for sizes the calls refuse. */
+#define DIC_NIC_E 300
+typedef struct dic_nic_weights {           /* NIC_RNNDecoder state_dict names, native [out][in] layouts */
+  const float *embed;                                   /* embed.weight  [V,300] */
+  const float *w_ih_l0, *w_hh_l0, *b_ih_l0, *b_hh_l0;   /* lstm.*_l0     [512,300],[512,128],[512],[512] */
+  const float *w_ih_l1, *w_hh_l1, *b_ih_l1, *b_hh_l1;   /* lstm.*_l1     [512,128],[512,128],[512],[512] */
+  const float *out_w, *out_b;                           /* linear        [V,128],[V] */
+} dic_nic_weights;
+typedef struct dic_nic_grads {             /* same order, written (not accumulated) by dic_nic_bwd */
+  float *embed, *w_ih_l0, *w_hh_l0, *b_ih_l0, *b_hh_l0, *w_ih_l1, *w_hh_l1, *b_ih_l1, *b_hh_l1, *out_w, *out_b;
+} dic_nic_grads;
+int dic_nic_head_fwd(const float* enc_w, const float* enc_b, const float* map, int cells, int B, float* pooled, float* features,
+                     void* stream);
+int dic_nic_head_bwd(const float* pooled, const float* d_features, int B, float* g_enc_w, float* g_enc_b, void* stream);
+size_t dic_nic_workspace_bytes(int B, int Tmax, int V, int n_packed);
+int dic_nic_fwd(const dic_nic_weights* w, int V, const float* features, const int64_t* captions, int cap_stride,
+                const int* lengths, int B, const float* drop_mult, float* logits_packed, void* workspace, size_t workspace_bytes,
+                void* stream);
+int dic_nic_bwd(const dic_nic_weights* w, int V, const int64_t* captions, int cap_stride, const int* lengths, int B,
+                const float* drop_mult, const float* dlogits_packed, const dic_nic_grads* g, float* d_features, void* workspace,
+                size_t workspace_bytes, void* stream);
+int dic_nic_pack_targets(const int64_t* captions, int cap_stride, const int* lengths, int B, int64_t* targets, void* stream);
+size_t dic_nic_greedy_workspace_bytes(int B, int max_length, int V);
+int dic_nic_greedy(const dic_nic_weights* w, int V, const float* features, int B, int max_length, int64_t* out_ids, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* stand-alone attention module: Soft_Attention.forward (attention.py:81-95), Hard_Attention.forward (:132-148,
  *   mode 1, gumbel_u [B,196], temp) and Hard_Attention.Hard_sample (:150-167, mode 2): feats [B,196,2048],

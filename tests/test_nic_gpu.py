@@ -1,0 +1,234 @@
+"""GPU parity of the NIC / Show-and-Tell path (through the C ABI) against the CPU restatement (tests/nic_common.py) and the golden
+vectors captured from the reference's NIC_RNNDecoder.  Tolerances are the project's own for the attention decoder
+(tests/test_decoder_gpu.py): logits 1e-4 of their scale, loss within 1e-4, each gradient 1e-3 of its tensor's max; token-id
+argmax identical on the golden cases and on every decidable row (tests/nic_common.py) at full size."""
+import numpy as np
+import pytest
+import torch
+
+from depth_image_captioning_pub_amd import native, synthetic as syn
+from tests import nic_common as nc
+from tests.helpers import GOLDEN_THREADS, check_packed, load_golden, torch_threads
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _assert_close(name, got, ref, tol):
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, f"{name}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    scale = float(ref.abs().max()) + 1e-12
+    err = float((got - ref).abs().max())
+    print(f"{name}: max err {err:.3e}, scale {scale:.3e}, ratio {err / scale:.2e} (bound {tol:g})")
+    assert np.isfinite(err) and err <= tol * scale, f"{name}: max err {err:.3e} > {tol:g} * scale {scale:.3e}"
+
+
+def _to_dev(d):
+    return {k: v.to(DEV) for k, v in d.items()}
+
+
+def _reference(name):
+    """fp64 restatement of a case with torch autograd: logits, loss, pooled, features and the 13 gradients."""
+    w, hw, fmap, caps, lens, drop = nc.case_inputs(name)
+    wd = {k: v.double().requires_grad_(True) for k, v in w.items()}
+    hd = {k: v.double().requires_grad_(True) for k, v in hw.items()}
+    with torch_threads(GOLDEN_THREADS):
+        pooled, feats = nc.head(hd, fmap.double())
+        logits, bsz = nc.nic_forward(wd, feats, caps, lens, drop)
+        loss = nc.nic_loss(logits, caps, lens)
+        loss.backward()
+    grads = {k: v.grad for k, v in wd.items()}
+    grads.update({"encoder." + k: v.grad for k, v in hd.items()})
+    return dict(logits=logits.detach(), loss=float(loss.detach()), pooled=pooled.detach(), features=feats.detach(), grads=grads, bsz=bsz)
+
+
+def _device_run(name):
+    w, hw, fmap, caps, lens, drop = nc.case_inputs(name)
+    wg, hg = _to_dev(w), _to_dev(hw)
+    capd = caps.to(DEV)
+    pooled, feats = native.nic_head_forward(hg["linear.weight"], hg["linear.bias"], fmap.to(DEV))
+    logits, tape = native.nic_forward(wg, feats, capd, lens, drop.to(DEV) if drop is not None else None)
+    targets = native.nic_pack_targets(capd, lens)
+    loss, dlogits, _ = native.caption_loss(logits, targets, None)
+    grads, dfeat = native.nic_backward(tape, dlogits)
+    gw, gb = native.nic_head_backward(pooled, dfeat)
+    grads = dict(grads)
+    grads.update({"encoder.linear.weight": gw, "encoder.linear.bias": gb})
+    return dict(logits=logits, loss=loss, pooled=pooled, features=feats, grads=grads, targets=targets, tape=tape, d_features=dfeat)
+
+
+# ---- 7. forward + loss + backward ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["ragged_train", "ragged_eval", "equal_train", "odd", "single", "full"])
+def test_forward_loss_backward_against_the_restatement(lib, name):
+    ref, got = _reference(name), _device_run(name)
+    w, hw, fmap, caps, lens, drop = nc.case_inputs(name)
+    assert got["tape"].batch_sizes == ref["bsz"]
+    assert torch.equal(got["targets"].cpu(), nc.pack_targets(caps, lens))
+    _assert_close("pooled", got["pooled"], ref["pooled"], 1e-4)
+    _assert_close("features", got["features"], ref["features"], 1e-4)
+    _assert_close("logits", got["logits"], ref["logits"], 1e-4)
+    print(f"loss {float(got['loss']):.7f} vs {ref['loss']:.7f}")
+    assert abs(float(got["loss"]) - ref["loss"]) <= 1e-4
+    assert len(ref["grads"]) == 13
+    for k, r in ref["grads"].items():
+        _assert_close("grad." + k, got["grads"][k], r, 1e-3)
+    _, ok, eps = nc.case_decidable(name)
+    same = got["logits"].argmax(1).cpu() == ref["logits"].argmax(1)
+    assert bool(same[ok].all()), f"{int((~same[ok]).sum())} decidable rows differ"
+    if name in ("ragged_train", "ragged_eval", "equal_train"):
+        assert bool(same.all())
+
+
+@pytest.mark.parametrize("name", ["ragged_train", "ragged_eval", "equal_train"])
+def test_forward_loss_backward_against_the_goldens(lib, name):
+    g, got = load_golden("nic_" + name), _device_run(name)
+    assert list(g["batch_sizes"]) == got["tape"].batch_sizes
+    scale = float(np.abs(g["logits"]).max())
+    np.testing.assert_allclose(got["logits"].cpu().numpy(), g["logits"], rtol=0, atol=1e-4 * scale)
+    assert np.array_equal(got["logits"].argmax(1).cpu().numpy(), g["argmax"])          # identical on every row
+    assert abs(float(got["loss"]) - float(g["loss"])) <= 1e-4
+    if name == "ragged_eval":
+        return
+    for k, t in got["grads"].items():
+        a = t.cpu().numpy()
+        if "grad." + k in g:
+            gmax = float(np.abs(g["grad." + k]).max())
+            np.testing.assert_allclose(a, g["grad." + k], rtol=0, atol=1e-3 * gmax, err_msg=k)
+        else:      # stored as a strided subsample (tests.helpers.check_packed): the bound relative to the subsample's maximum
+            gmax = float(np.abs(g["grad." + k + "__sub"]).max())
+            check_packed(g, "grad." + k, t, 0, 1e-3 * gmax)
+
+
+# ---- 8. rows do not see each other ------------------------------------------------------------------------------------------------------
+def test_rows_are_independent(lib):
+    """Rows 0, 31 and 63 of the full-size batch, run alone as B = 1, give the batch's logits to within 16 * eps (rounding level:
+    only the tile choice of a batched product may differ between the two calls)."""
+    w, hw, fmap, caps, lens, drop = nc.case_inputs("full")
+    _, _, eps = nc.case_decidable("full")
+    wg, hg = _to_dev(w), _to_dev(hw)
+    _, feats = native.nic_head_forward(hg["linear.weight"], hg["linear.bias"], fmap.to(DEV))
+    capd, dropd = caps.to(DEV), drop.to(DEV)
+    logits, tape = native.nic_forward(wg, feats, capd, lens, dropd)
+    B, T = len(lens), lens[0]
+    batch = logits.view(T, B, -1)                         # equal lengths: packed row (t, b) = t * B + b
+    for b in (0, 31, 63):
+        alone, _ = native.nic_forward(wg, feats[b:b + 1].contiguous(), capd[b:b + 1].contiguous(), [lens[b]],
+                                      dropd[b:b + 1].contiguous())
+        err = float((alone - batch[:, b]).abs().max())
+        print(f"row {b}: |alone - in batch| {err:.3e} (bound {nc.GAP_FACTOR * eps:.3e})")
+        assert err <= nc.GAP_FACTOR * eps
+
+
+# ---- 9. bit-reproducible -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["odd", "full"])
+def test_two_runs_are_bit_identical(lib, name):
+    a, b = _device_run(name), _device_run(name)
+    assert torch.equal(a["logits"], b["logits"]) and torch.equal(a["d_features"], b["d_features"])
+    for k in a["grads"]:
+        assert torch.equal(a["grads"][k], b["grads"][k]), k
+
+
+# ---- 10. greedy decode ----------------------------------------------------------------------------------------------------------------
+def _greedy_on_device(name, max_length=30):
+    w, hw, fmap = nc.greedy_inputs(name)
+    hg = _to_dev(hw)
+    _, feats = native.nic_head_forward(hg["linear.weight"], hg["linear.bias"], fmap.to(DEV))
+    return native.nic_greedy(_to_dev(w), feats, max_length), feats
+
+
+def test_greedy_matches_the_reference_batch_sample(lib):
+    ids, _ = _greedy_on_device("golden")
+    assert ids.dtype == torch.int64 and tuple(ids.shape) == (4, 30)
+    assert np.array_equal(ids.cpu().numpy(), load_golden("nic_batch_sample")["ids"])
+
+
+def test_greedy_full_size_matches_the_fp64_restatement(lib):
+    ids, _ = _greedy_on_device("full")
+    ref, ok, eps, gap = nc.greedy_decidable("full")
+    same = (ids.cpu() == ref).all(1)
+    print(f"decidable rows {int(ok.sum())}/{ok.numel()}, identical rows {int(same.sum())}, eps {eps:.2e}")
+    assert float(ok.double().mean()) >= 1.0 - nc.MAX_UNDECIDABLE_GREEDY
+    assert bool(same[ok].all()), f"rows {torch.nonzero(ok & ~same).flatten().tolist()} differ"
+
+
+def test_shim_sample_is_row_zero_of_batch_sample(lib):
+    from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.nic import NIC_RNNDecoder
+    w, hw, fmap = nc.greedy_inputs("golden")
+    dec = NIC_RNNDecoder(300, 128, 50, 2, 0.5).to(DEV).eval()
+    dec.load_state_dict(w, strict=True)
+    hg = _to_dev(hw)
+    _, feats = native.nic_head_forward(hg["linear.weight"], hg["linear.bias"], fmap.to(DEV))
+    rows = dec.batch_sample(feats)
+    assert np.array_equal(np.asarray(rows, np.int64), load_golden("nic_batch_sample")["ids"])
+    assert dec.sample(feats) == rows[0] and len(rows[0]) == 30
+    assert dec.sample(feats, max_length=7) == rows[0][:7]
+
+
+def test_shims_backpropagate_into_decoder_and_head(lib):
+    """autograd through the two Function objects gives the gradients of the direct calls (eval mode: no dropout draw)."""
+    from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.nic import NIC_RNNDecoder, _NicHeadFn
+    name = "ragged_eval"
+    w, hw, fmap, caps, lens, _ = nc.case_inputs(name)
+    got = _device_run(name)
+    dec = NIC_RNNDecoder(300, 128, 50, 2, 0.5).to(DEV).eval()
+    dec.load_state_dict(w, strict=True)
+    lin_w, lin_b = (hw[k].to(DEV).requires_grad_(True) for k in ("linear.weight", "linear.bias"))
+    feats = _NicHeadFn.apply(fmap.to(DEV), lin_w, lin_b)
+    logits = dec(feats, caps.to(DEV), lens)
+    assert torch.equal(logits, got["logits"])
+    loss = torch.nn.functional.cross_entropy(logits, got["targets"])
+    loss.backward()
+    for k, p in dec.named_parameters():
+        _assert_close("shim grad." + k, p.grad, got["grads"][k], 1e-4)
+    _assert_close("shim grad.encoder.linear.weight", lin_w.grad, got["grads"]["encoder.linear.weight"], 1e-4)
+    _assert_close("shim grad.encoder.linear.bias", lin_b.grad, got["grads"]["encoder.linear.bias"], 1e-4)
+
+
+# ---- 11. three trainer steps -----------------------------------------------------------------------------------------------------------
+def test_trainer_three_steps_golden(lib):
+    """Bounds of tests/test_engine_gpu.py::test_decoder_adamw3_golden: losses atol 1e-4, weights rtol 2e-4 / atol 2e-5."""
+    from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.nic import NicTrainer
+    g = load_golden("nic_adamw3")
+    w, hw = syn.nic_weights(50, seed=73)
+    fmap = syn.nic_map(5, 1, 74).to(DEV)
+    caps, lens = syn.captions_ragged([9, 7, 7, 4, 3], 50, seed=73)
+    tr = NicTrainer(50, device=DEV, lr=1e-3, decoder_init=w, head_init=hw, resnet_layers=(1, 1, 1, 1))
+    losses = [float(tr.step_on_map(fmap, caps.to(DEV), lens, dropout=False).item()) for _ in range(3)]
+    np.testing.assert_allclose(losses, g["losses"], atol=1e-4)
+    sd = tr.state_dicts()
+    for k, v in sd["decoder"].items():
+        check_packed(g, "adamw3." + k, v, 2e-4, 2e-5)
+    for k in ("linear.weight", "linear.bias"):
+        check_packed(g, "adamw3.encoder." + k, sd["encoder"][k], 2e-4, 2e-5)
+
+
+# ---- 12. train_nic ------------------------------------------------------------------------------------------------------------------------
+def test_train_nic_synthetic_smoke(lib, tmp_path):
+    from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.nic import (NIC_CNNEncoder, NIC_RNNDecoder, NicTrainer,
+                                                                                         train_nic)
+    from depth_image_captioning_pub_amd.Captioning_models.config import ConfigTrain
+    cfg = ConfigTrain()
+    cfg.num_epochs, cfg.iters_per_epoch, cfg.batch_size, cfg.vocab_size, cfg.seq_len = 1, 2, 4, 200, 8
+    cfg.resnet_layers = (1, 1, 1, 1)
+    cfg.save_directory_nic = str(tmp_path / "NIC")
+    stats = {}
+    hist = train_nic(0, "synthetic", config=cfg, stats=stats)
+    assert len(hist) == 1 and all(np.isfinite(v) for v in hist[0]) and stats["steps"] == 2
+    enc = NIC_CNNEncoder(300, layers=(1, 1, 1, 1))
+    dec = NIC_RNNDecoder(300, 128, 200, 2, 0.5)
+    enc.load_state_dict(torch.load(str(tmp_path / "NIC" / "nic_encoder_best0.pth"), map_location="cpu"), strict=True)
+    dec.load_state_dict(torch.load(str(tmp_path / "NIC" / "nic_decoder_best0.pth"), map_location="cpu"), strict=True)
+    assert int(enc.backbone[1].num_batches_tracked) == 2
+    # the loss falls over a handful of steps on a repeated batch
+    tr = NicTrainer(200, device=DEV, lr=1e-3, resnet_layers=(1, 1, 1, 1))
+    imgs = syn.rgb_images(4, seed=9).to(DEV)
+    caps, lens = syn.captions_fixed(4, 200, 8, seed=9)
+    losses = [float(tr.train_step(imgs, caps.to(DEV), lens).item()) for _ in range(6)]
+    tr.check_status()
+    print("losses on a repeated batch:", losses)
+    assert all(np.isfinite(l) for l in losses) and losses[-1] < losses[0]
+    # the module path trains the same two parameter sets
+    enc, dec = enc.to(DEV).train(), dec.to(DEV).train()
+    out = dec(enc(imgs), caps.to(DEV), lens)
+    torch.nn.functional.cross_entropy(out, native.nic_pack_targets(caps.to(DEV), lens)).backward()
+    assert enc.linear.weight.grad is not None and dec.embed.weight.grad is not None and enc.backbone[0].weight.grad is None
