@@ -1,5 +1,5 @@
-"""NIC / Show-and-Tell baseline (Captioning_models/Base_caption_model/nic.py): drop-in NIC_CNNEncoder / NIC_RNNDecoder and
-train_nic.
+"""NIC / Show-and-Tell baseline (Captioning_models/Base_caption_model/nic.py): drop-in NIC_CNNEncoder / NIC_RNNDecoder,
+train_nic and evaluation_nic.
 
 Model (nic.py:23-118): frozen ResNet-152 -> global average pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) ->
 nn.Linear(128, V).  The image embedding is step 0 of the input sequence, states start at zero, dropout acts on the top layer's
@@ -8,13 +8,17 @@ modules keep the reference's parameter trees and state_dict keys (a checkpoint w
 and route forward / backward through torch.autograd.Function objects like the other shims.
 
 train_nic is the loop of nic.py:178-356 on synthetic batches (the COCO loaders and the vocabulary pickle are out of scope, as in
-depth_train.py).  Single GPU: data-parallel NIC is out of scope.  evaluation_nic (datasets, pycocoevalcap) is out of scope like
+depth_train.py).  Single GPU: data-parallel NIC is out of scope.  evaluation_nic is the decode loop of nic.py:360-455 on synthetic
+images, greedy like the reference or with NIC_RNNDecoder.beam_sample (dic_nic_beam: the decode rule the attention decoders are
+scored with); it returns and writes the hypotheses - the metric scorers (pycocoevalcap) stay out of scope like
 the other caption metrics."""
 from __future__ import annotations
 
+import json
 import os
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -138,6 +142,20 @@ class NIC_RNNDecoder(nn.Module):
     def batch_sample(self, features: torch.Tensor, states=None, max_length: int = 30):
         """Greedy captions of a batch: list of B lists of token ids (nic.py:150-175)."""
         return [[int(v) for v in row] for row in self._greedy(features, states, max_length).cpu().tolist()]
+
+    # ---- beam-search decoding (no counterpart in the reference, which decodes greedily; semantics: include/dic.h) ------------------
+    @torch.no_grad()
+    def beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, return_all=False):
+        """Beam-search captions of a batch: np.int64 [B,max_length], the best of `beam_size` hypotheses per image ranked by
+        score / length^length_penalty; positions behind the first '<end>' hold '<end>'.  return_all=True: (ids np.int64
+        [B,K,max_length], scores np.float32 [B,K] (sums of log-probabilities), lengths np.int32 [B,K]), best first.
+        beam_size=1 gives batch_sample's tokens up to the first '<end>'."""
+        ids, scores, lengths = native.nic_beam(self._weights(), _contig(features), word_to_id["<end>"], beam_size, max_length,
+                                               float(length_penalty))
+        if return_all:
+            return (ids.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return ids[:, 0].cpu().numpy().astype(np.int64)
 
 
 class NicTrainer(CaptionTrainer):
@@ -294,3 +312,64 @@ def train_nic(ext, useData: str = "synthetic", config=None, stats=None):
     if stats is not None:
         stats.update(steps=trainer.step_count, best_val_loss=val_loss_best)
     return history
+
+
+def nic_ids_to_captions(hypos_id, id_to_word: Dict[int, str]) -> List[str]:
+    """nic.py:432-440: words up to (not including) the first '<end>', '<start>' skipped."""
+    out = []
+    for ids in hypos_id:
+        line = []
+        for i in ids:
+            w = id_to_word[int(i)]
+            if w == "<end>":
+                break
+            if w != "<start>":
+                line.append(w)
+        out.append(" ".join(line))
+    return out
+
+
+@torch.no_grad()
+def evaluation_nic(useData: str = "synthetic", config=None, param_files: Optional[Dict[str, List[str]]] = None, n_batches: int = 2,
+                   beam_size: int = 1, length_penalty: float = 0.0):
+    """The decode loop of nic.py:360-455 on synthetic images: for every [encoder, decoder] checkpoint pair under
+    config.save_directory_nic (`param_files`: key -> the two file names; default = the best-validation files train_nic wrote for
+    run 0) load both with strict=True, switch to eval mode (eval-mode BatchNorm, dropout off), decode n_batches batches of
+    config.batch_size images and turn the ids into words (nic_ids_to_captions).  beam_size == 1 decodes with batch_sample like the
+    reference; beam_size > 1 with beam_sample - the best of `beam_size` hypotheses per image, ranked by
+    score / length^length_penalty.  Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} and writes the hypotheses to
+    {save_directory_nic}/{useData}_nic_hypotheses.json.  No metric scores (nic.py:444-455: pycocoevalcap, out of scope).
+    config.resnet_layers (optional, not in the reference) shrinks the backbone's block counts as in train_nic."""
+    from ...depth_evaluation import synthetic_vocabulary          # (that module imports this package)
+    if useData != "synthetic":
+        raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
+    if int(beam_size) < 1:
+        raise DicError(f"beam_size={beam_size!r} must be at least 1")
+    config = config or ConfigTrain()
+    dev = config.device
+    save_directory = config.save_directory_nic
+    if param_files is None:
+        param_files = {"run0": ["nic_encoder_best0.pth", "nic_decoder_best0.pth"]}
+    word_to_id, id_to_word = synthetic_vocabulary(config.vocab_size)
+    encoder = NIC_CNNEncoder(config.nic_dim_embedding, layers=tuple(getattr(config, "resnet_layers", None) or _LAYERS),
+                             conv_mode=getattr(config, "conv_mode", None))                   # nic.py:399-407
+    decoder = NIC_RNNDecoder(config.nic_dim_embedding, config.dim_hidden, config.vocab_size, config.num_layers, config.dropout)
+    for m in (encoder, decoder):
+        m.to(dev)
+        m.eval()
+    results = {}
+    for key, (f_enc, f_dec) in param_files.items():
+        encoder.load_state_dict(torch.load(f"{save_directory}/{f_enc}", weights_only=True), strict=True)      # nic.py:412-415
+        decoder.load_state_dict(torch.load(f"{save_directory}/{f_dec}", weights_only=True), strict=True)
+        hypos_id = []
+        for b in range(n_batches):
+            feature = encoder(syn.rgb_images(config.batch_size, seed=5000 + b).to(dev))      # nic.py:426
+            if int(beam_size) > 1:
+                hypos_id.append(decoder.beam_sample(feature, word_to_id, beam_size=int(beam_size), length_penalty=length_penalty))
+            else:
+                hypos_id.append(np.asarray(decoder.batch_sample(feature), dtype=np.int64))   # nic.py:427
+        hypos_id = np.concatenate(hypos_id)
+        results[key] = {"hypotheses": nic_ids_to_captions(hypos_id, id_to_word), "ids": hypos_id}
+    with open(os.path.join(save_directory, f"{useData}_nic_hypotheses.json"), "w") as f:
+        json.dump({k: v["hypotheses"] for k, v in results.items()}, f)
+    return results

@@ -4,7 +4,7 @@
 //   decoder.hip         what the routes share: workspace carving, set-up, the attention step and LSTM cell kernels + launchers
 //   decoder_fwd.hip     teacher-forced forward, stand-alone attention forward
 //   decoder_bwd.hip     BPTT backward, stand-alone attention backward
-//   decoder_decode.hip  greedy and beam-search decode
+//   decoder_decode.hip  greedy and beam-search decode (the selection kernels it shares with the NIC beam search: beam.h / beam.hip)
 #pragma once
 #include "dic.h"
 #include "gemm.h"

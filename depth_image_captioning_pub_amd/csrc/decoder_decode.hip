@@ -1,5 +1,5 @@
 // Decoding on the device: greedy (dic_decoder_greedy) and beam search (dic_decoder_beam).
-#include "decoder.h"
+#include "beam.h"
 #include <algorithm>
 
 namespace dic {
@@ -54,7 +54,6 @@ __global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ l
 // State: Hst / Cst [B*KB][2][kH] (slot 0 = state entering the step, slot 1 = state the LSTM cell wrote: lstm_fwd_kernel's
 // Hall / Call layout at T = 1), score / fin / length / prev [B*KB], token and back-pointer history [T][B*KB].
 // ------------------------------------------------------------------------------------------
-constexpr int kBeamMax = 8;
 // context pass of beam_attn_kernel: NFB batches of FB cells per wave (8 waves x NFB x FB >= 196 cells; the weights of the padding
 // cells are 0), each with 64 / NFB of the gate's K range.  Wide beams take smaller batches: the per-beam operands of a batch
 // (attention weights, hidden state) live in scalar registers, and there are about a hundred of those.
@@ -274,110 +273,8 @@ __global__ void __launch_bounds__(512, 4) beam_attn_kernel(
   }
 }
 
-// (value descending, flat index ascending): the order of the candidate list
-__device__ __forceinline__ bool beam_better(float av, long long ai, float bv, long long bi) {
-  return av > bv || (av == bv && ai < bi);
-}
-
-// Row b*KB+k: lsm = logits - max - log sum exp(logits - max) (fp32), then the KB best of score + lsm[v] (ties: lower v), best
-// first, into cand_val / cand_tok [row][KB].  A finished beam has the single candidate (score, id_end); unused slots get
-// token -1.  grid (B*KB), 256 threads; the first 256*kTopkNPT logits of the row stay in registers over the three passes
-// (max, sum, selection), any beyond that are read again (V > 10240).
-constexpr int kTopkNPT = 40;
-template <int KB>
-__global__ void __launch_bounds__(256) beam_topk_kernel(const float* __restrict__ logits, int V,
-                                                         const float* __restrict__ score, const int* __restrict__ fin,
-                                                         long long id_end, float* __restrict__ cand_val,
-                                                         int* __restrict__ cand_tok) {
-  __shared__ float sv[2][4];
-  __shared__ int si[2][4];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float sc = score[row];
-  if (fin[row]) {            // (uniform) frozen hypothesis: carried at unchanged score
-    if (tid < KB) {
-      cand_val[(long long)row * KB + tid] = tid == 0 ? sc : -INFINITY;
-      cand_tok[(long long)row * KB + tid] = tid == 0 ? (int)id_end : -1;
-    }
-    return;
-  }
-  const float* x = logits + (long long)row * V;
-  float xr[kTopkNPT];
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < kTopkNPT; ++i) {
-    const int v = tid + 256 * i;
-    xr[i] = v < V ? x[v] : -INFINITY;
-    m = fmaxf(m, xr[i]);
-  }
-  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) m = fmaxf(m, x[v]);
-  m = wave_max(m);
-  if (lane == 0) sv[0][w] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(sv[0][0], sv[0][1]), fmaxf(sv[0][2], sv[0][3]));
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kTopkNPT; ++i) s += expf(xr[i] - m);          // (exp(-inf) = 0 for the slots past V)
-  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) s += expf(x[v] - m);
-  s = wave_sum(s);
-  if (lane == 0) sv[1][w] = s;
-  __syncthreads();
-  const float ls = logf((sv[1][0] + sv[1][1]) + (sv[1][2] + sv[1][3]));
-  // this thread's KB best, sorted; its elements arrive in ascending v
-  float lv[KB];
-  int li[KB];
-#pragma unroll
-  for (int j = 0; j < KB; ++j) { lv[j] = -INFINITY; li[j] = 0x7fffffff; }
-  auto offer = [&](float c, int v) {
-    if (beam_better(c, v, lv[KB - 1], li[KB - 1])) {
-      lv[KB - 1] = c; li[KB - 1] = v;
-#pragma unroll
-      for (int j = KB - 1; j > 0; --j) {
-        if (beam_better(lv[j], li[j], lv[j - 1], li[j - 1])) {
-          const float tv = lv[j]; lv[j] = lv[j - 1]; lv[j - 1] = tv;
-          const int ti = li[j]; li[j] = li[j - 1]; li[j - 1] = ti;
-        }
-      }
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < kTopkNPT; ++i) {
-    const int v = tid + 256 * i;
-    if (v < V) offer(sc + ((xr[i] - m) - ls), v);
-  }
-  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) offer(sc + ((x[v] - m) - ls), v);
-  // KB rounds: the best head of the 256 lists wins and its thread moves on to its next element
-#pragma unroll
-  for (int r = 0; r < KB; ++r) {
-    float bv = lv[0];
-    int bi = li[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (beam_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    __syncthreads();                        // (the previous round's readers are done with sv / si)
-    if (lane == 0) { sv[r & 1][w] = bv; si[r & 1][w] = bi; }
-    __syncthreads();
-    bv = sv[r & 1][0]; bi = si[r & 1][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-      if (beam_better(sv[r & 1][i], si[r & 1][i], bv, bi)) { bv = sv[r & 1][i]; bi = si[r & 1][i]; }
-    if (li[0] == bi) {                      // (token ids are unique: one thread)
-#pragma unroll
-      for (int j = 0; j + 1 < KB; ++j) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
-      lv[KB - 1] = -INFINITY; li[KB - 1] = 0x7fffffff;
-    }
-    if (tid == 0) {
-      cand_val[(long long)row * KB + r] = bv;
-      cand_tok[(long long)row * KB + r] = bi == 0x7fffffff ? -1 : bi;
-    }
-  }
-}
-
-// Image b: the KB best of its KB x KB candidates by (value descending, flat index k*V + v ascending) become the new beams,
-// in that order; each takes over score, token, finished flag, length and - the state hand-over - h', c' of its parent (slot 1
-// of the parent -> slot 0 of the survivor).  grid (B), kH threads.
+// Image b: the KB best of its KB x KB candidates become the new beams (beam_select_rank, beam.h); each also takes over - the
+// state hand-over - h', c' of its parent (slot 1 of the parent -> slot 0 of the survivor).  grid (B), kH threads.
 template <int KB>
 __global__ void __launch_bounds__(kH) beam_select_kernel(const float* __restrict__ cand_val,
                                                           const int* __restrict__ cand_tok, int V, long long id_end, int t,
@@ -385,48 +282,13 @@ __global__ void __launch_bounds__(kH) beam_select_kernel(const float* __restrict
                                                           int* __restrict__ length, long long* __restrict__ prev,
                                                           int* __restrict__ tok_hist, int* __restrict__ bp_hist,
                                                           float* __restrict__ Hst, float* __restrict__ Cst) {
-  constexpr int NC = KB * KB;
-  __shared__ float cv_s[NC];
-  __shared__ long long cf_s[NC];
-  __shared__ float s_val[KB];
-  __shared__ int s_src[KB], s_tok[KB], fin_s[KB], len_s[KB];
+  __shared__ BeamSelectLds<KB> sel;
   const int b = blockIdx.x, tid = threadIdx.x;
   const long long row0 = (long long)b * KB;
-  int tok = -1;
-  float val = -INFINITY;
-  if (tid < NC) {
-    tok = cand_tok[row0 * KB + tid];
-    val = cand_val[row0 * KB + tid];
-    cv_s[tid] = val;
-    cf_s[tid] = tok < 0 ? 0x7fffffffffffffffLL : (long long)(tid / KB) * V + tok;
-  }
-  if (tid < KB) {
-    fin_s[tid] = fin[row0 + tid];
-    len_s[tid] = length[row0 + tid];
-    s_src[tid] = 0; s_tok[tid] = (int)id_end; s_val[tid] = -INFINITY;
-  }
-  __syncthreads();
-  if (tid < NC && tok >= 0) {
-    const long long mine = cf_s[tid];
-    int rank = 0;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) rank += (cf_s[c] != 0x7fffffffffffffffLL && beam_better(cv_s[c], cf_s[c], val, mine)) ? 1 : 0;
-    if (rank < KB) { s_src[rank] = tid / KB; s_tok[rank] = tok; s_val[rank] = val; }
-  }
-  __syncthreads();
-  if (tid < KB) {
-    const int src = s_src[tid], tk = s_tok[tid];
-    const int was = fin_s[src];
-    score[row0 + tid] = s_val[tid];
-    fin[row0 + tid] = (was || tk == (int)id_end) ? 1 : 0;
-    length[row0 + tid] = was ? len_s[src] : t + 1;
-    prev[row0 + tid] = tk;
-    tok_hist[(long long)t * BK + row0 + tid] = tk;
-    bp_hist[(long long)t * BK + row0 + tid] = src;
-  }
+  beam_select_rank<KB>(sel, cand_val, cand_tok, V, id_end, t, BK, row0, score, fin, length, prev, tok_hist, bp_hist);
 #pragma unroll
   for (int r = 0; r < KB; ++r) {
-    const long long from = ((row0 + s_src[r]) * 2 + 1) * kH + tid, to = (row0 + r) * 2 * kH + tid;
+    const long long from = ((row0 + sel.src[r]) * 2 + 1) * kH + tid, to = (row0 + r) * 2 * kH + tid;
     Hst[to] = Hst[from];
     Cst[to] = Cst[from];
   }
@@ -453,50 +315,6 @@ __global__ void __launch_bounds__(kH) beam_init_kernel(int KB, long long id_star
   }
 }
 
-// end of the search: rank the KB hypotheses of image b by score / length^length_penalty (descending, stable in the beam index)
-// and follow the back-pointers from each, last step first, to emit its tokens (and the attention weights its steps used).
-__global__ void __launch_bounds__(256) beam_backtrack_kernel(int KB, int T, int BK, float length_penalty,
-                                                              const float* __restrict__ score, const int* __restrict__ length,
-                                                              const int* __restrict__ tok_hist, const int* __restrict__ bp_hist,
-                                                              const float* __restrict__ alpha_hist, int* __restrict__ path,
-                                                              long long* __restrict__ out_ids, float* __restrict__ out_scores,
-                                                              int* __restrict__ out_lengths, float* __restrict__ alphas_out) {
-  __shared__ float rk[kBeamMax];
-  __shared__ int ord[kBeamMax];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const long long row0 = (long long)b * KB;
-  if (tid < KB) {
-    const float s = score[row0 + tid];
-    // length^penalty as exp(penalty * log(length)): the inlined powf compiles to packed fp32 forms the build audit refuses
-    rk[tid] = length_penalty > 0.f ? s / expf(length_penalty * logf((float)length[row0 + tid])) : s;
-  }
-  __syncthreads();
-  if (tid < KB) {
-    int rank = 0;
-    for (int k = 0; k < KB; ++k) rank += (rk[k] > rk[tid] || (rk[k] == rk[tid] && k < tid)) ? 1 : 0;
-    ord[rank] = tid;
-  }
-  __syncthreads();
-  if (tid < KB) {
-    int cur = ord[tid];
-    out_scores[row0 + tid] = score[row0 + cur];
-    out_lengths[row0 + tid] = length[row0 + cur];
-    for (int t = T - 1; t >= 0; --t) {
-      const long long at = (long long)t * BK + row0 + cur;
-      out_ids[(row0 + tid) * T + t] = tok_hist[at];
-      cur = bp_hist[at];                       // the beam that was extended at step t: its attention weights belong to the token
-      path[(row0 + tid) * T + t] = cur;
-    }
-  }
-  if (alphas_out == nullptr) return;
-  __syncthreads();
-  const int n = KB * T * kL;
-  for (int i = tid; i < n; i += 256) {
-    const int rt = i / kL, l = i - rt * kL;
-    const int t = rt % T;
-    alphas_out[(row0 * T + rt) * kL + l] = alpha_hist[((long long)t * BK + row0 + path[row0 * T + rt]) * kL + l];
-  }
-}
 
 }  // namespace dic
 
@@ -588,18 +406,6 @@ BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overf
   return w;
 }
 
-// runs STMT with the beam width as the compile-time constant KB_
-#define DIC_BEAM_SWITCH(K, STMT)                       \
-  switch (K) {                                         \
-    case 1: { constexpr int KB_ = 1; STMT } break;     \
-    case 2: { constexpr int KB_ = 2; STMT } break;     \
-    case 3: { constexpr int KB_ = 3; STMT } break;     \
-    case 4: { constexpr int KB_ = 4; STMT } break;     \
-    case 5: { constexpr int KB_ = 5; STMT } break;     \
-    case 6: { constexpr int KB_ = 6; STMT } break;     \
-    case 7: { constexpr int KB_ = 7; STMT } break;     \
-    default: { constexpr int KB_ = 8; STMT } break;    \
-  }
 
 bool beam_sizes_ok(int B, int K, int max_length, int V) {
   return B > 0 && K >= 1 && K <= kBeamMax && max_length >= 1 && V >= K;
@@ -647,16 +453,13 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
     // the state arrays are lstm_fwd_kernel's Hall / Call at T = 1, t = 0: c from slot 0, h' / c' into slot 1
     DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.Hdrop, kS_LSTM, BK, 0}, 0, 1, st));
     DIC_TRY(gemm(BK, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
-    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_topk_kernel<KB_>, dim3(BK), dim3(256), 0, st, ws.logits, V, ws.score, ws.fin,
-                                          id_end, ws.cand_val, ws.cand_tok);
-                    hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
-                                       BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
+    DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st));
+    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
+                                          BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
     DIC_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(beam_backtrack_kernel, dim3(B), dim3(256), 0, st, K, T, BK, length_penalty, ws.score, ws.length,
-                     ws.tok_hist, ws.bp_hist, ws.alpha_hist, ws.path, (long long*)out_ids, out_scores, out_lengths, alphas_out);
-  DIC_LAUNCH_CHECK();
-  return DIC_OK;
+  return launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, ws.alpha_hist, ws.path,
+                               (long long*)out_ids, out_scores, out_lengths, alphas_out, st);
 }
 
 }  // extern "C"

@@ -1,12 +1,13 @@
 // NIC / Show-and-Tell baseline (Base_caption_model/nic.py): encoder head, stacked two-layer LSTM over packed ragged sequences
-// (teacher-forced forward, BPTT backward) and greedy decode.  Semantics: include/dic.h; mapping and measurements: DESIGN.md 5.7.
+// (teacher-forced forward, BPTT backward), greedy and beam-search decode.  Semantics: include/dic.h; mapping and measurements:
+// DESIGN.md 5.7 (training, greedy) and 5.8 (beam search).
 //
 // The time loop of forward and backward is ONE launch each (nic_lstm2_seq_fwd / nic_lstm2_seq_bwd): workgroup g owns kNicR
 // consecutive batch rows for all their steps, h and c stay in LDS / registers, and nothing is exchanged between workgroups (no
 // attention, no per-step coupling between rows).  Everything that is not recurrent is hoisted out of the loop and batched over all
 // packed rows on the exact-fp32 gemm(): layer 0's input projection, the vocabulary projection, every weight gradient, dX.
 // The arithmetic of a row does not depend on which rows share its workgroup: a row run alone gives the same recurrence bit for bit.
-#include "decoder.h"
+#include "beam.h"
 #include "nn_kernels.h"
 #include <algorithm>
 #include <vector>
@@ -35,7 +36,7 @@ __global__ void __launch_bounds__(256) nic_bias_sum_kernel(const float* __restri
   if (i < n) out[i] = a[i] + b[i];
 }
 
-// acc[r] += sum_i W[col][i] * x_s[r][i0 + i] over n4 float4 groups starting at group g0 of the packed matrix (n_out columns).
+// acc[r] += sum_i W[col][i] * x_s[r][i0 + i] for R rows over n4 float4 groups starting at group g0 of the packed matrix (n_out columns).
 // The weights come in blocks of UNROLL groups (n4 % UNROLL == 0), each block's loads issued together: the sequence kernels are
 // bound by the latency of these L2 reads, not by their bytes, so they put a whole K = 128 product (32 groups, 128 vector registers)
 // in flight.  The fence ends a block: without it the scheduler pulls the loads of the following product forward as well, and
@@ -51,9 +52,9 @@ typedef unsigned int nic_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t nic_rsrc(const float* p, int floats) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, floats * 4, 0x00020000);
 }
-template <int UNROLL>
+template <int UNROLL, int R>
 __device__ __forceinline__ void nic_matvec(__amdgpu_buffer_rsrc_t W4, int g0, int n4, int n_out, int col,
-                                           const float* x_s, int xld, int x0, float (&acc)[kNicR]) {
+                                           const float* x_s, int xld, int x0, float (&acc)[R]) {
 #pragma unroll 1
   for (int gb = 0; gb < n4; gb += UNROLL) {
     float4 w[UNROLL];
@@ -65,7 +66,7 @@ __device__ __forceinline__ void nic_matvec(__amdgpu_buffer_rsrc_t W4, int g0, in
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
 #pragma unroll
-      for (int r = 0; r < kNicR; ++r) {
+      for (int r = 0; r < R; ++r) {
         const float4 x = *reinterpret_cast<const float4*>(x_s + r * xld + x0 + (gb + u) * 4);
         float a = acc[r];
         a = fmaf(w[u].x, x.x, a);
@@ -405,6 +406,123 @@ __global__ void __launch_bounds__(256) nic_argmax_kernel(const float* __restrict
   }
 }
 
+// One beam-search step for the KB hypotheses (rows b*KB + k) of image b = blockIdx.x: nic_step_kernel with the selection and
+// the state hand-over in front.  At t > 0 the workgroup first turns the image's KB x KB candidates of step t-1 into the new beams
+// (beam_select_rank), then loads h0, c0, h1, c1 of each survivor's PARENT row - h into LDS, c into registers - and only behind
+// the barrier that follows overwrites those rows with the survivors' new state: every parent read of an image happens in the
+// workgroup that owns its rows, before its first write.  At t == 0 the K beams start from zero state and features[b], beam 0 at
+// score 0 and the others at -inf.  Per row the products, their summation order and the cell are those of nic_step_kernel
+// (nic_matvec's arithmetic of a row does not depend on how many rows share the workgroup): K = 1 computes what the greedy step
+// computes.  Thread tid owns gate column tid in the products and (rows tid >> 7 and (tid >> 7) + 4, unit tid & 127) in the cells.
+struct NicBeamStep {
+  const float *features, *embed, *Wih0p, *Whh0p, *Wih1p, *Whh1p, *bsum0, *bsum1;
+  float *state, *Hout;                     // [B*K][4][H] = h0, c0, h1, c1 and the top-layer output [B*K][H]
+  const float* cand_val; const int* cand_tok;
+  float* score; int *fin, *length, *tok_hist, *bp_hist;
+  long long id_end; int V, t, BK;
+};
+template <int KB>
+__global__ void __launch_bounds__(kNicThreads) nic_beam_step_kernel(const NicBeamStep a) {
+  constexpr int NJ = (KB + kNicR - 1) / kNicR;
+  __shared__ __align__(16) float x_s[KB][kNicE];
+  __shared__ __align__(16) float h0_s[KB][kH];
+  __shared__ __align__(16) float h1_s[KB][kH];
+  __shared__ __align__(16) float g_s[KB][kG];
+  __shared__ BeamSelectLds<KB> sel;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int rc = tid >> 7, u = tid & (kH - 1);
+  const long long row0 = (long long)b * KB;
+  const __amdgpu_buffer_rsrc_t Wih0 = nic_rsrc(a.Wih0p, kG * kNicE), Whh0 = nic_rsrc(a.Whh0p, kG * kH),
+                               Wih1 = nic_rsrc(a.Wih1p, kG * kH), Whh1 = nic_rsrc(a.Whh1p, kG * kH);
+  float c0[NJ], c1[NJ];
+  if (a.t == 0) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int r = rc + kNicR * j;
+      c0[j] = 0.f; c1[j] = 0.f;
+      if (r < KB) { h0_s[r][u] = 0.f; h1_s[r][u] = 0.f; }
+    }
+    for (int i = tid; i < KB * kNicE; i += kNicThreads) {
+      const int r = i / kNicE, e = i - r * kNicE;
+      x_s[r][e] = a.features[(long long)b * kNicE + e];
+    }
+    if (tid < KB) {
+      a.score[row0 + tid] = tid == 0 ? 0.f : -INFINITY;
+      a.fin[row0 + tid] = 0;
+      a.length[row0 + tid] = 0;
+    }
+  } else {
+    beam_select_rank<KB>(sel, a.cand_val, a.cand_tok, a.V, a.id_end, a.t - 1, a.BK, row0, a.score, a.fin, a.length, nullptr,
+                         a.tok_hist, a.bp_hist);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int r = rc + kNicR * j;
+      c0[j] = 0.f; c1[j] = 0.f;
+      if (r < KB) {
+        const float* ps = a.state + (row0 + sel.src[r]) * 4 * kH;
+        h0_s[r][u] = ps[u];
+        c0[j] = ps[kH + u];
+        h1_s[r][u] = ps[2 * kH + u];
+        c1[j] = ps[3 * kH + u];
+      }
+    }
+    for (int i = tid; i < KB * kNicE; i += kNicThreads) {
+      const int r = i / kNicE, e = i - r * kNicE;
+      x_s[r][e] = a.embed[clamp_token(sel.tok[r], a.V) * kNicE + e];
+    }
+  }
+  __syncthreads();                // (every parent row has been read: from here on the rows of the image may be overwritten)
+  float acc[KB];
+#pragma unroll
+  for (int r = 0; r < KB; ++r) acc[r] = a.bsum0[tid];
+  nic_matvec<5>(Wih0, 0, kNicE / 4, kG, tid, &x_s[0][0], kNicE, 0, acc);
+  nic_matvec<8>(Whh0, 0, kH / 4, kG, tid, &h0_s[0][0], kH, 0, acc);
+#pragma unroll
+  for (int r = 0; r < KB; ++r) g_s[r][tid] = acc[r];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int r = rc + kNicR * j;
+    if (r < KB) {
+      float* st = a.state + (row0 + r) * 4 * kH;
+      const NicCellOut q = nic_cell(g_s[r], u, c0[j]);
+      st[u] = q.h;
+      st[kH + u] = q.c;
+      h0_s[r][u] = q.h;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < KB; ++r) acc[r] = a.bsum1[tid];
+  nic_matvec<8>(Wih1, 0, kH / 4, kG, tid, &h0_s[0][0], kH, 0, acc);
+  nic_matvec<8>(Whh1, 0, kH / 4, kG, tid, &h1_s[0][0], kH, 0, acc);
+#pragma unroll
+  for (int r = 0; r < KB; ++r) g_s[r][tid] = acc[r];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int r = rc + kNicR * j;
+    if (r < KB) {
+      float* st = a.state + (row0 + r) * 4 * kH;
+      const NicCellOut q = nic_cell(g_s[r], u, c1[j]);
+      st[2 * kH + u] = q.h;
+      st[3 * kH + u] = q.c;
+      a.Hout[(row0 + r) * kH + u] = q.h;
+    }
+  }
+}
+
+// the selection of the last step (no step kernel follows it).  grid (B), 64 threads
+template <int KB>
+__global__ void __launch_bounds__(64) nic_beam_last_select_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_tok,
+                                                                   int V, long long id_end, int t, int BK, float* __restrict__ score,
+                                                                   int* __restrict__ fin, int* __restrict__ length,
+                                                                   int* __restrict__ tok_hist, int* __restrict__ bp_hist) {
+  __shared__ BeamSelectLds<KB> sel;
+  beam_select_rank<KB>(sel, cand_val, cand_tok, V, id_end, t, BK, (long long)blockIdx.x * KB, score, fin, length, nullptr, tok_hist,
+                       bp_hist);
+}
+
 namespace {
 
 constexpr int kNicSplitDH = 8;     // split-K of dHdrop = dlogits W_out (K = V)
@@ -441,8 +559,18 @@ NicWs nic_carve(void* p, size_t bytes, int B, int T, int V, int N, bool* overflo
   return w;
 }
 
-struct NicGreedyWs {
-  float *Wih0F, *Whh0F, *Wih1F, *Whh1F, *bsum0, *bsum1, *state, *Hout, *logits;
+// what the decode step kernels read: the four weight matrices packed for nic_matvec and the summed biases of each layer
+struct NicStepWs { float *Wih0F, *Whh0F, *Wih1F, *Whh1F, *bsum0, *bsum1; };
+
+void nic_step_carve(Carver& c, NicStepWs& w) {
+  w.Wih0F = c.take<float>((size_t)kG * kNicE);
+  for (float** m : {&w.Whh0F, &w.Wih1F, &w.Whh1F}) *m = c.take<float>((size_t)kG * kH);
+  w.bsum0 = c.take<float>(kG);
+  w.bsum1 = c.take<float>(kG);
+}
+
+struct NicGreedyWs : NicStepWs {
+  float *state, *Hout, *logits;
   long long* ids;
   size_t bytes;
 };
@@ -450,10 +578,7 @@ struct NicGreedyWs {
 NicGreedyWs nic_greedy_carve(void* p, size_t bytes, int B, int V, bool* overflow) {
   Carver c(p, bytes);
   NicGreedyWs w{};
-  w.Wih0F = c.take<float>((size_t)kG * kNicE);
-  for (float** m : {&w.Whh0F, &w.Wih1F, &w.Whh1F}) *m = c.take<float>((size_t)kG * kH);
-  w.bsum0 = c.take<float>(kG);
-  w.bsum1 = c.take<float>(kG);
+  nic_step_carve(c, w);
   w.state = c.take<float>((size_t)B * 4 * kH);
   w.Hout = c.take<float>((size_t)B * kH);
   w.logits = c.take<float>((size_t)B * V);
@@ -479,6 +604,48 @@ int nic_pack4(const float* src, int n_out, int n_in, int so, int si, float* dst,
   hipLaunchKernelGGL(nic_pack4_kernel, dim3(ceil_div((long long)n_out * n_in, 256)), dim3(256), 0, st, src, n_out, n_in, so, si, dst);
   DIC_LAUNCH_CHECK();
   return DIC_OK;
+}
+
+int nic_step_setup(const dic_nic_weights* w, const NicStepWs& ws, hipStream_t st) {
+  DIC_TRY(nic_pack4(w->w_ih_l0, kG, kNicE, kNicE, 1, ws.Wih0F, st));
+  DIC_TRY(nic_pack4(w->w_hh_l0, kG, kH, kH, 1, ws.Whh0F, st));
+  DIC_TRY(nic_pack4(w->w_ih_l1, kG, kH, kH, 1, ws.Wih1F, st));
+  DIC_TRY(nic_pack4(w->w_hh_l1, kG, kH, kH, 1, ws.Whh1F, st));
+  hipLaunchKernelGGL(nic_bias_sum_kernel, dim3(kG / 256), dim3(256), 0, st, w->b_ih_l0, w->b_hh_l0, kG, ws.bsum0);
+  hipLaunchKernelGGL(nic_bias_sum_kernel, dim3(kG / 256), dim3(256), 0, st, w->b_ih_l1, w->b_hh_l1, kG, ws.bsum1);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
+
+struct NicBeamWs : NicStepWs {
+  float *state, *Hout, *logits, *cand_val, *score;
+  int *cand_tok, *fin, *length, *tok_hist, *bp_hist, *path;
+  size_t bytes;
+};
+
+NicBeamWs nic_beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overflow) {
+  Carver c(p, bytes);
+  NicBeamWs w{};
+  const size_t BK = (size_t)B * K;
+  nic_step_carve(c, w);
+  w.state = c.take<float>(BK * 4 * kH);
+  w.Hout = c.take<float>(BK * kH);
+  w.logits = c.take<float>(BK * V);
+  w.cand_val = c.take<float>(BK * K);
+  w.cand_tok = c.take<int>(BK * K);
+  w.score = c.take<float>(BK);
+  w.fin = c.take<int>(BK);
+  w.length = c.take<int>(BK);
+  w.tok_hist = c.take<int>(BK * T);
+  w.bp_hist = c.take<int>(BK * T);
+  w.path = c.take<int>(BK * T);
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+
+bool nic_beam_sizes_ok(int B, int K, int max_length, int V) {
+  return B > 0 && K >= 1 && K <= kBeamMax && max_length >= 1 && V >= K;
 }
 
 int nic_upload_plan(const NicWs& ws, const int* lengths, int B, const StepPlan& pl, hipStream_t st) {
@@ -646,13 +813,7 @@ int dic_nic_greedy(const dic_nic_weights* w, int V, const float* features, int B
     set_last_error("dic_nic_greedy: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
     return DIC_ERR_WORKSPACE;
   }
-  DIC_TRY(nic_pack4(w->w_ih_l0, kG, kNicE, kNicE, 1, ws.Wih0F, st));
-  DIC_TRY(nic_pack4(w->w_hh_l0, kG, kH, kH, 1, ws.Whh0F, st));
-  DIC_TRY(nic_pack4(w->w_ih_l1, kG, kH, kH, 1, ws.Wih1F, st));
-  DIC_TRY(nic_pack4(w->w_hh_l1, kG, kH, kH, 1, ws.Whh1F, st));
-  hipLaunchKernelGGL(nic_bias_sum_kernel, dim3(kG / 256), dim3(256), 0, st, w->b_ih_l0, w->b_hh_l0, kG, ws.bsum0);
-  hipLaunchKernelGGL(nic_bias_sum_kernel, dim3(kG / 256), dim3(256), 0, st, w->b_ih_l1, w->b_hh_l1, kG, ws.bsum1);
-  DIC_LAUNCH_CHECK();
+  DIC_TRY(nic_step_setup(w, ws, st));
   DIC_CHECK_HIP(hipMemsetAsync(ws.state, 0, sizeof(float) * (size_t)B * 4 * kH, st));      // h and c of both layers start at zero
   for (int t = 0; t < max_length; ++t) {
     hipLaunchKernelGGL(nic_step_kernel, dim3(ceil_div(B, kNicR)), dim3(kNicThreads), 0, st, features, w->embed,
@@ -665,6 +826,50 @@ int dic_nic_greedy(const dic_nic_weights* w, int V, const float* features, int B
     DIC_LAUNCH_CHECK();
   }
   return DIC_OK;
+}
+
+size_t dic_nic_beam_workspace_bytes(int B, int K, int max_length, int V) {
+  if (!nic_beam_sizes_ok(B, K, max_length, V)) return 0;
+  bool ov;
+  return nic_beam_carve(nullptr, 0, B, K, max_length, V, &ov).bytes;
+}
+
+int dic_nic_beam(const dic_nic_weights* w, int V, const float* features, int B, int K, long long id_end, int max_length,
+                 float length_penalty, int64_t* out_ids, float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes,
+                 void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call
+  DIC_REQUIRE(B > 0, "dic_nic_beam: bad batch size B=%d", B);
+  DIC_REQUIRE(V > 0, "dic_nic_beam: bad vocabulary size V=%d", V);
+  DIC_REQUIRE(K >= 1 && K <= kBeamMax, "dic_nic_beam: beam width K=%d is outside 1..%d", K, kBeamMax);
+  DIC_REQUIRE(V >= K, "dic_nic_beam: vocabulary V=%d is smaller than the beam width K=%d", V, K);
+  DIC_REQUIRE(max_length >= 1, "dic_nic_beam: max_length=%d is < 1", max_length);
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "dic_nic_beam: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(length_penalty >= 0.f, "dic_nic_beam: length_penalty=%g must be >= 0 (NaN is refused too)", (double)length_penalty);
+  DIC_REQUIRE(w && features && out_ids && out_scores && out_lengths && workspace, "dic_nic_beam: null pointer");
+  const int T = max_length, BK = B * K;
+  bool ov = false;
+  NicBeamWs ws = nic_beam_carve(workspace, workspace_bytes, B, K, T, V, &ov);
+  if (ov) {
+    set_last_error("dic_nic_beam: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  DIC_TRY(nic_step_setup(w, ws, st));
+  NicBeamStep a{features, w->embed, ws.Wih0F, ws.Whh0F, ws.Wih1F, ws.Whh1F, ws.bsum0, ws.bsum1, ws.state, ws.Hout, ws.cand_val,
+                ws.cand_tok, ws.score, ws.fin, ws.length, ws.tok_hist, ws.bp_hist, id_end, V, 0, BK};
+  // a step is three launches, like the greedy step: selection of step t-1 + hand-over + cells, vocabulary GEMM, top-K
+  for (int t = 0; t < T; ++t) {
+    a.t = t;
+    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(nic_beam_step_kernel<KB_>, dim3(B), dim3(kNicThreads), 0, st, a);)
+    DIC_LAUNCH_CHECK();
+    DIC_TRY(gemm(BK, V, kH, op_rowk(ws.Hout, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
+    DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st));
+  }
+  DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(nic_beam_last_select_kernel<KB_>, dim3(B), dim3(64), 0, st, ws.cand_val, ws.cand_tok, V, id_end,
+                                        T - 1, BK, ws.score, ws.fin, ws.length, ws.tok_hist, ws.bp_hist);)
+  DIC_LAUNCH_CHECK();
+  return launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, nullptr, ws.path,
+                               (long long*)out_ids, out_scores, out_lengths, nullptr, st);
 }
 
 }  // extern "C"

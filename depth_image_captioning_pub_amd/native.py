@@ -783,3 +783,27 @@ def nic_greedy(weights: Dict[str, torch.Tensor], features: torch.Tensor, max_len
     rc = lib.dic_nic_greedy(C.byref(wp), vocab, ptr(f), B, int(max_length), ptr(ids), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
     check(rc, "dic_nic_greedy")
     return ids
+
+
+def nic_beam(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, beam_size: int, max_length: int = 30,
+             length_penalty: float = 0.0):
+    """dic_nic_beam: fixed-width beam search of the NIC decoder, on the device (semantics: include/dic.h).
+    Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K]), best first."""
+    lib = _lib.load()
+    f = _dev_f32(features, "features")
+    B, K = int(f.shape[0]), int(beam_size)
+    if tuple(f.shape) != (B, NIC_EMB):
+        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    wp, keep = nic_ptrs(weights)
+    vocab = int(weights["linear.weight"].shape[0])
+    lib.dic_nic_beam_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_nic_beam_workspace_bytes(B, K, int(max_length), vocab)      # (0 for sizes the call below refuses with its text)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f.device)
+    kk, tt = max(K, 1), max(int(max_length), 1)
+    ids = torch.empty((B, kk, tt), dtype=torch.int64, device=f.device)
+    scores = torch.empty((B, kk), dtype=torch.float32, device=f.device)
+    lengths = torch.empty((B, kk), dtype=torch.int32, device=f.device)
+    rc = lib.dic_nic_beam(C.byref(wp), vocab, ptr(f), B, K, C.c_longlong(int(id_end)), int(max_length), C.c_float(length_penalty),
+                          ptr(ids), ptr(scores), ptr(lengths), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    check(rc, "dic_nic_beam")
+    return ids, scores, lengths

@@ -209,6 +209,33 @@ size_t dic_nic_greedy_workspace_bytes(int B, int max_length, int V);
 int dic_nic_greedy(const dic_nic_weights* w, int V, const float* features, int B, int max_length, int64_t* out_ids, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* fixed-width beam search for the NIC baseline, entirely on the device.  There is no reference implementation (the reference
+ *   decodes greedily, nic.py:126-175); this comment is the specification.  The candidate rule is dic_decoder_beam's, word for word.
+ *   Shape of the search: per image K hypotheses ("beams") are kept at every step, for exactly max_length steps.  Every launch is
+ *     enqueued on `stream`, nothing is copied to the host, nothing synchronises.
+ *   Start: there is no start token (NIC has none).  The step-0 input of all K beams of image b is features[b]; h and c of both
+ *     layers start at zero; beam 0 starts at score 0 and beams 1..K-1 at -inf, so step 0 picks K different first tokens.
+ *   One step, every beam: the body of dic_nic_greedy - both cells, gate order i, f, g, o, b_ih + b_hh, no dropout,
+ *     logits = linear(h_top) - then lsm = logits - max - log sum exp(logits - max) in fp32.
+ *   Candidates of an image: a live beam k offers score[k] + lsm[k,v] for every v; a finished beam offers exactly one, token
+ *     id_end at unchanged score.  The K best of them survive, ordered by value descending, ties broken by the lower flat index
+ *     k*V + v.  A survivor inherits all four state vectors (h and c of both layers) and the token history of its parent, sets
+ *     finished |= (token == id_end), and gets length = t + 1 from a live parent (a finished parent hands its length on: length
+ *     counts the tokens up to and including the first id_end, or max_length).  The survivor's token is its next input,
+ *     embed[token].
+ *   Result: hypotheses ranked by score / length^length_penalty (0: the raw score), descending, stable in the beam index.
+ *   out_ids int64 [B,K,max_length] (positions behind the first id_end hold id_end), out_scores float [B,K] (the raw sums),
+ *   out_lengths int [B,K].
+ *   1 <= K <= 8, K <= V, 0 <= id_end < V, length_penalty >= 0, max_length >= 1, B > 0, no null pointer, a workspace of at least
+ *   dic_nic_beam_workspace_bytes: a violation returns a negative code before anything is launched, with a dic_last_error() text
+ *   that starts with "dic_nic_beam".  The workspace query returns 0 for sizes the call refuses.
+ *   K = 1 returns the ids of dic_nic_greedy up to and including the first id_end (id_end behind it): the per-row arithmetic and
+ *   summation order of a step are those of the greedy step. */
+size_t dic_nic_beam_workspace_bytes(int B, int K, int max_length, int V);
+int dic_nic_beam(const dic_nic_weights* w, int V, const float* features, int B, int K, long long id_end, int max_length,
+                 float length_penalty, int64_t* out_ids, float* out_scores, int* out_lengths, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* stand-alone attention module: Soft_Attention.forward (attention.py:81-95), Hard_Attention.forward (:132-148,
  *   mode 1, gumbel_u [B,196], temp) and Hard_Attention.Hard_sample (:150-167, mode 2): feats [B,196,2048],
  *   h [B,128] -> ctx [B,2048], alpha [B,196] (float; one-hot in mode 2). */
