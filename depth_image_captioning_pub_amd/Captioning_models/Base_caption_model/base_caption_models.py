@@ -119,6 +119,11 @@ class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, return_all=False):
         return super().beam_sample(features, None, word_to_id, beam_size, max_length, length_penalty, return_all)
 
+    def stochastic_sample(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                          return_all=False):
+        return super().stochastic_sample(features, None, word_to_id, n_samples, max_length, temperature, top_k, top_p, seed,
+                                         return_all)
+
 
 class RNNDecoderWithHardAttention(_CaptionDecoderBase):
     """base-hard decoder (base_caption_models.py:257-508)."""
@@ -147,3 +152,8 @@ class RNNDecoderWithHardAttention(_CaptionDecoderBase):
 
     def beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, return_all=False):
         return super().beam_sample(features, None, word_to_id, beam_size, max_length, length_penalty, return_all)
+
+    def stochastic_sample(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                          return_all=False):
+        return super().stochastic_sample(features, None, word_to_id, n_samples, max_length, temperature, top_k, top_p, seed,
+                                         return_all)

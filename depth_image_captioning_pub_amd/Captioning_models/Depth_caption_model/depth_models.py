@@ -224,6 +224,32 @@ class _CaptionDecoderBase(nn.Module):
                     lengths.cpu().numpy().astype(np.int32))
         return ids[:, 0].cpu().numpy().astype(np.int64)
 
+    # ---- stochastic decoding (no counterpart in the reference; semantics: include/dic.h).  `sample` stays the greedy one-image call
+    @torch.no_grad()
+    def stochastic_sample(self, features, depth_features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0,
+                          top_p=1.0, seed=0, return_all=False):
+        """Captions drawn from the model's distribution (temperature, top-k, nucleus): np.int64 [B,max_length] for n_samples == 1,
+        [B,n_samples,max_length] otherwise; positions behind the first '<end>' hold '<end>'.  The draws are
+        torch.rand((max_length, B*n_samples)) of a generator on the features' device seeded with `seed`: one seed, one set of
+        captions.  return_all=True: (ids, logprobs np.float32 - the log-probability of every drawn token under the filtered
+        distribution, 0 behind '<end>' -, lengths np.int32)."""
+        if self.hard:
+            raise DicError("stochastic_sample: sampling is built for the soft-attention decoders only (a Gumbel-max decode draws "
+                           "its attention already); use batch_sample for hard attention")
+        features = _contig(features)
+        S = int(n_samples)
+        gen = torch.Generator(features.device).manual_seed(int(seed))
+        u = torch.rand((max_length, features.shape[0] * max(S, 1)), generator=gen, device=features.device)
+        ids, logprobs, lengths = native.decoder_sample(self._weights(), features, _contig(depth_features), word_to_id["<start>"],
+                                                       word_to_id["<end>"], S, u, max_length, float(temperature), int(top_k),
+                                                       float(top_p))
+        if S == 1:
+            ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
+        if return_all:
+            return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return ids.cpu().numpy().astype(np.int64)
+
 
 class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,

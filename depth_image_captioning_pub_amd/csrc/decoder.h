@@ -1,10 +1,11 @@
-// Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy and beam-search decode.
+// Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy, beam-search and sampling decode.
 // One translation unit per route, each with its kernels, host orchestration and C ABI entry points; this header declares only
 // what more than one of them uses:
 //   decoder.hip         what the routes share: workspace carving, set-up, the attention step and LSTM cell kernels + launchers
 //   decoder_fwd.hip     teacher-forced forward, stand-alone attention forward
 //   decoder_bwd.hip     BPTT backward, stand-alone attention backward
-//   decoder_decode.hip  greedy and beam-search decode (the selection kernels it shares with the NIC beam search: beam.h / beam.hip)
+//   decoder_decode.hip  greedy, beam-search and sampling decode (the selection kernels it shares with the NIC beam search: beam.h /
+//                       beam.hip; the kernel that draws a token from a row of logits: sample.h / sample.hip)
 #pragma once
 #include "dic.h"
 #include "gemm.h"

@@ -1,5 +1,7 @@
-// Decoding on the device: greedy (dic_decoder_greedy) and beam search (dic_decoder_beam).
+// Decoding on the device: greedy (dic_decoder_greedy), beam search (dic_decoder_beam) and sampling (dic_decoder_sample).
 #include "beam.h"
+#include "sample.h"
+#include <cmath>
 #include <algorithm>
 
 namespace dic {
@@ -315,6 +317,39 @@ __global__ void __launch_bounds__(kH) beam_init_kernel(int KB, long long id_star
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// sampling (dic_decoder_sample; semantics in include/dic.h, layout in DESIGN.md 5.9): S drawn captions per image, rows b*S + s.
+// A sampled row is a beam row whose parent is always itself: the state arrays and beam_attn_kernel<S> are the beam search's.
+// Per step: beam_attn_kernel -> gate GEMM slabs -> lstm_fwd_kernel -> vocabulary GEMM -> sample_token_kernel (sample.hip).
+// ------------------------------------------------------------------------------------------
+// start: h0 / c0 of the image (written by the init_linear GEMM into slot 1 of sample 0) for all S rows, previous token <start>
+__global__ void __launch_bounds__(kH) sample_init_kernel(int S, long long id_start, int* __restrict__ fin,
+                                                          int* __restrict__ length, long long* __restrict__ prev,
+                                                          float* __restrict__ Hst, float* __restrict__ Cst) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row0 = (long long)b * S;
+  const float h = Hst[(row0 * 2 + 1) * kH + tid], c = Cst[(row0 * 2 + 1) * kH + tid];
+  for (int s = 0; s < S; ++s) {
+    Hst[(row0 + s) * 2 * kH + tid] = h;
+    Cst[(row0 + s) * 2 * kH + tid] = c;
+  }
+  if (tid < S) {
+    fin[row0 + tid] = 0;
+    length[row0 + tid] = 0;
+    prev[row0 + tid] = id_start;
+  }
+}
+
+// end: the attention weights kept per step [T][R][196] -> alphas_out [R][T][196]
+__global__ void __launch_bounds__(256) sample_alpha_gather_kernel(const float* __restrict__ hist, int R, int T,
+                                                                   float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)R * T * kL) return;
+  const long long rt = i / kL;
+  const int l = (int)(i - rt * kL), t = (int)(rt % T);
+  const long long r = rt / T;
+  out[i] = hist[((long long)t * R + r) * kL + l];
+}
 
 }  // namespace dic
 
@@ -460,6 +495,101 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
   }
   return launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, ws.alpha_hist, ws.path,
                                (long long*)out_ids, out_scores, out_lengths, alphas_out, st);
+}
+
+// ---- sampling ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct SampleWs : SetupBufs {      // (no WcatT; BeamWs without the candidate, back-pointer and path arrays)
+  float *Hst, *Cst, *X, *slab, *Gact, *Hdrop, *logits, *alpha_hist;
+  int* fin;
+  long long* prev;
+  size_t bytes;
+};
+
+SampleWs sample_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* overflow) {
+  Carver c(p, bytes);
+  SampleWs w{};
+  const size_t R = (size_t)B * S;
+  w.F = c.take<float>((size_t)B * kL * kD);
+  w.P = c.take<float>((size_t)B * kL * kA);
+  w.mean = c.take<float>((size_t)B * kD);
+  w.Wcat = c.take<float>((size_t)kG * kXK);
+  w.bcat = c.take<float>(kG);
+  w.WhT = c.take<float>((size_t)kH * kA);
+  w.WbT = c.take<float>((size_t)kH * kD);
+  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
+  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
+  w.Hst = c.take<float>(R * 2 * kH);
+  w.Cst = c.take<float>(R * 2 * kH);
+  w.X = c.take<float>(R * kXK);
+  w.slab = c.take<float>((size_t)kS_LSTM * R * kG);
+  w.Gact = c.take<float>(R * kG);
+  w.Hdrop = c.take<float>(R * kH);
+  w.logits = c.take<float>(R * V);
+  w.fin = c.take<int>(R);
+  w.prev = c.take<long long>(R);
+  w.alpha_hist = c.take<float>(R * T * kL);
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+
+bool sample_sizes_ok(int B, int S, int max_length, int V) {
+  return B > 0 && S >= 1 && S <= kBeamMax && max_length >= 1 && V > 0;
+}
+}  // namespace
+
+size_t dic_decoder_sample_workspace_bytes(int B, int S, int max_length, int V) {
+  if (!sample_sizes_ok(B, S, max_length, V)) return 0;
+  bool ov;
+  return sample_carve(nullptr, 0, B, S, max_length, V, &ov).bytes;
+}
+
+int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                       long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                       const float* uniform_u, int64_t* out_ids, float* out_logprobs, int* out_lengths, float* alphas_out,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_sample: samples per image S=%d is outside 1..%d", S, kBeamMax);
+  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "decoder_sample: bad sizes (B=%d, V=%d, max_length=%d)", B, V, max_length);
+  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_sample: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_sample: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "decoder_sample: temperature=%g must be finite and > 0",
+              (double)temperature);
+  DIC_REQUIRE(top_k >= 0 && top_k <= V, "decoder_sample: top_k=%d is outside 0..V=%d (0: no limit)", top_k, V);
+  DIC_REQUIRE(top_p > 0.f && top_p <= 1.f, "decoder_sample: top_p=%g is outside (0, 1] (1: off; NaN is refused too)", (double)top_p);
+  DIC_REQUIRE(w && feat_rgb && uniform_u && out_ids && out_logprobs && out_lengths && workspace, "decoder_sample: null pointer");
+  const int T = max_length, R = B * S;
+  bool ov = false;
+  SampleWs ws = sample_carve(workspace, workspace_bytes, B, S, T, V, &ov);
+  if (ov) {
+    set_last_error("decoder_sample: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  // per image, never per sample.  [h0 | c0] -> slot 1 of sample 0, then copied to the S rows
+  DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
+  hipLaunchKernelGGL(sample_init_kernel, dim3(B), dim3(kH), 0, st, S, id_start, ws.fin, out_lengths, ws.prev, ws.Hst, ws.Cst);
+  DIC_LAUNCH_CHECK();
+  for (int t = 0; t < T; ++t) {
+    float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * R * kL : nullptr;
+    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P,
+                                          ws.Hst, ws.prev, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b,
+                                          ws.WbT, w->fbeta_b, alpha_t, ws.X, B);)
+    DIC_LAUNCH_CHECK();
+    DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
+    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.Hdrop, kS_LSTM, R, 0}, 0, 1, st));
+    DIC_TRY(gemm(R, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
+    DIC_TRY(launch_sample_token(SampleStep{ws.logits, R, V, temperature, top_k, top_p, uniform_u + (size_t)t * R, id_end, t, T,
+                                           ws.fin, out_lengths, ws.prev, (long long*)out_ids, out_logprobs, ws.Hst, ws.Cst, kH},
+                                st));
+  }
+  if (alphas_out) {
+    hipLaunchKernelGGL(sample_alpha_gather_kernel, dim3(ceil_div((long long)R * T * kL, 256)), dim3(256), 0, st, ws.alpha_hist, R,
+                       T, alphas_out);
+    DIC_LAUNCH_CHECK();
+  }
+  return DIC_OK;
 }
 
 }  // extern "C"

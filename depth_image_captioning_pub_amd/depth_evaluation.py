@@ -51,12 +51,16 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
 @torch.no_grad()
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
-                      length_penalty: float = 0.0):
+                      length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
+                      top_p: float = 1.0, seed: int = 0):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
     beam_size > 1 (soft attention only) decodes with decoder.beam_sample - the best of `beam_size` hypotheses per image, ranked
-    by score / length^length_penalty - instead of the reference's greedy batch_sample; 1 is the greedy loop itself."""
+    by score / length^length_penalty - instead of the reference's greedy batch_sample; 1 is the greedy loop itself.
+    n_samples > 0 (soft attention only) ADDS to each result "samples", a list of `n_samples` caption strings per image drawn with
+    decoder.stochastic_sample(temperature, top_k, top_p), and "sample_ids" np.int64 [N,n_samples,30]; batch b is seeded with
+    seed + b.  The hypotheses, the ids and the written file do not depend on it."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
@@ -65,6 +69,10 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
         raise DicError(f"beam_size={beam_size!r} must be at least 1")
     if int(beam_size) > 1 and atten != "soft":
         raise DicError("beam_size > 1 needs atten='soft': beam search is built for the soft-attention decoder only")
+    if int(n_samples) < 0:
+        raise DicError(f"n_samples={n_samples!r} must be at least 0")
+    if int(n_samples) > 0 and atten != "soft":
+        raise DicError("n_samples > 0 needs atten='soft': sampling is built for the soft-attention decoder only")
     config = config or ConfigTrain()
     dev = config.device
     tag = f"depth_{atten}"
@@ -90,7 +98,7 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
         encoder.load_state_dict(torch.load(f"{save_directory}/{f_enc}", weights_only=True))       # :139-144
         decoder.load_state_dict(torch.load(f"{save_directory}/{f_dec}", weights_only=True))
         depth_encoder.load_state_dict(torch.load(f"{save_directory}/{f_denc}", weights_only=True))
-        hypos_id = []
+        hypos_id, sample_ids = [], []
         for b in range(n_batches):
             raw = syn.raw_images(config.batch_size, seed=5000 + b).to(dev)
             imgs, imgs_for_dep = util.device_transforms(raw)
@@ -102,9 +110,17 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
                                                     length_penalty=length_penalty))
             else:
                 hypos_id.append(decoder.batch_sample(feature, depth_features, word_to_id))     # :165
+            if int(n_samples) > 0:
+                drawn = decoder.stochastic_sample(feature, depth_features, word_to_id, n_samples=int(n_samples),
+                                                  temperature=temperature, top_k=top_k, top_p=top_p, seed=int(seed) + b)
+                sample_ids.append(drawn.reshape(drawn.shape[0], int(n_samples), -1))
         hypos_id = np.concatenate(hypos_id)
         hypos_word = ids_to_captions(hypos_id, id_to_word)
         results[key] = {"hypotheses": hypos_word, "ids": hypos_id}
+        if int(n_samples) > 0:
+            sample_ids = np.concatenate(sample_ids)
+            results[key]["samples"] = [ids_to_captions(rows, id_to_word) for rows in sample_ids]
+            results[key]["sample_ids"] = sample_ids
         # depth_evaluation.py:178-184 scores the hypotheses with BLEU / METEOR / CIDEr (pycocoevalcap + Java): out of scope
         #  - the hypotheses are the product of this path.
     with open(os.path.join(save_directory, f"{useData}_hypotheses.json"), "w") as f:

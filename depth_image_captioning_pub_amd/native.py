@@ -571,6 +571,37 @@ def decoder_beam(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_
     return (ids, scores, lengths, alphas) if return_alphas else (ids, scores, lengths)
 
 
+def decoder_sample(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                   id_end: int, n_samples: int, uniform_u: torch.Tensor, max_length: int = 30, temperature: float = 1.0,
+                   top_k: int = 0, top_p: float = 1.0, return_alphas: bool = False):
+    """dic_decoder_sample: `n_samples` captions per image drawn from the soft-attention decoder's distribution, on the device
+    (semantics: include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1) - the draws are an input.
+    Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S][, alphas [B,S,max_length,196]])."""
+    lib = _lib.load()
+    f_rgb = _dev_f32(feat_rgb, "features")
+    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
+    B, S = f_rgb.shape[0], int(n_samples)
+    ss = max(S, 1)
+    u = _dev_f32(uniform_u, "uniform_u")
+    if tuple(u.shape) != (max_length, B * ss):
+        raise _lib.DicError(f"decoder_sample: uniform_u must be [max_length, B*n_samples] = [{max_length}, {B * ss}], got {tuple(u.shape)}")
+    vocab = weights["linear.weight"].shape[0]
+    wp, keep = decoder_ptrs(weights)
+    lib.dic_decoder_sample_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_decoder_sample_workspace_bytes(B, S, max_length, vocab)     # (0 for sizes the call below refuses with its text)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f_rgb.device)
+    ids = torch.empty((B, ss, max_length), dtype=torch.int64, device=f_rgb.device)
+    logprobs = torch.empty((B, ss, max_length), dtype=torch.float32, device=f_rgb.device)
+    lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
+    alphas = torch.empty((B, ss, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device) if return_alphas else None
+    rc = lib.dic_decoder_sample(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, C.c_longlong(int(id_start)),
+                                C.c_longlong(int(id_end)), max_length, C.c_float(temperature), int(top_k), C.c_float(top_p),
+                                ptr(u), ptr(ids), ptr(logprobs), ptr(lengths), ptr(alphas), ptr(ws), C.c_size_t(ws.numel()),
+                                stream_ptr())
+    check(rc, "dic_decoder_sample")
+    return (ids, logprobs, lengths, alphas) if return_alphas else (ids, logprobs, lengths)
+
+
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""

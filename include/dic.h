@@ -156,6 +156,40 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
                      float* out_scores, int* out_lengths, float* alphas_out, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* stochastic decoding for the soft-attention decoder (depth-soft, or base-soft with feat_depth = NULL): S captions per image
+ *   DRAWN from the model's distribution, with temperature, top-k and nucleus (top-p) filtering and the log-probability of every
+ *   drawn token.  Entirely on the device: every launch is enqueued on `stream`, nothing is copied to the host, nothing
+ *   synchronises.  There is no reference implementation; this comment is the specification.
+ *   Rows: row r = b*S + s is sample s of image b, 1 <= S <= 8.  All S rows of an image start from init_linear(mean_L F) and from
+ *     id_start; dropout off, soft attention over F = F_rgb (+ F_depth), 196 cells; exactly max_length = T steps.  One step of a
+ *     row is the decode-step body of dic_decoder_greedy up to logits = linear(h).
+ *   Draws are an input (quirk Q6, as gumbel_u): uniform_u float [T, B*S] on the device, values in [0,1); the library generates
+ *     no randomness, so the call is a pure function of its arguments.  Row r consumes u[t, r] at step t while it is live.  A value
+ *     >= 1 selects the last kept token; the values are not validated on the host.
+ *   One step of a live row, in fp32: z_v = logits_v / temperature, e_v = exp(z_v - max z).
+ *     top-k: if 0 < top_k < V keep {v : z_v >= the top_k-th largest z}; ties at the threshold are all kept.  top_k = 0 or V: no limit.
+ *     top-p: if top_p < 1, inside the top-k set of mass Z_k: tau = the largest logit value with
+ *       sum{e_v : kept, z_v >= tau} >= top_p * Z_k; keep {v : z_v >= tau}; ties at tau are all kept.  top_p = 1: off.
+ *     draw: with Z the mass of the kept set, the token is the first kept v in vocabulary index order whose inclusive running sum of
+ *       kept e exceeds u * Z; if rounding leaves none, the last kept token.  out_logprobs[r,t] = z_v - max z - log Z.
+ *     The association order of the sums is free.
+ *   Finished rows: after a row draws id_end at step t its length is t + 1 (otherwise T); later positions hold id_end with
+ *     log-probability 0 and the row's logits are no longer read.
+ *   out_ids int64 [B,S,T], out_logprobs float [B,S,T], out_lengths int [B,S], alphas_out (nullable) [B,S,T,196]: the attention
+ *   weights of each row's own steps (steps at or behind `length`: unspecified).
+ *   1 <= S <= 8, B, V > 0, max_length >= 1, 0 <= id_start, id_end < V, temperature finite and > 0, 0 <= top_k <= V,
+ *   0 < top_p <= 1 (NaN refused), no null pointer other than feat_depth and alphas_out, a workspace of sufficient size: a violation
+ *   returns a negative code and a dic_last_error() text that starts with "decoder_sample:", before anything is launched; the
+ *   workspace query returns 0 for sizes the call refuses.
+ *   Properties: row (b,s) depends only on image b and column b*S+s of uniform_u; the S rows of an image share one read of its F
+ *   and P per step; top_k = 1 decodes what dic_decoder_greedy decodes up to the first id_end whenever each step's
+ *   maximum is unique. */
+size_t dic_decoder_sample_workspace_bytes(int B, int S, int max_length, int V);
+int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                       long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                       const float* uniform_u, int64_t* out_ids, float* out_logprobs, int* out_lengths, float* alphas_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
  *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
  *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both
