@@ -20,7 +20,8 @@ __global__ void __launch_bounds__(256) normalize_images_kernel(const float* __re
 }
 
 // bilinear resize (align_corners=False, no antialias: identical to torchvision/F.interpolate when up-scaling),
-// optional centre crop window, then y = v*mul + add (T.Normalize(0.5,0.5): mul 2, add -1)   (util.py:14-17)
+// optional centre crop window, then y = v*mul + add (T.Normalize(0.5,0.5): mul 2, add -1)   (util.py:14-17).
+// The window's origin comes from center_crop_origin below: halves round to the EVEN neighbour, as in torchvision.
 __global__ void __launch_bounds__(256) resize_bilinear_kernel(const float* __restrict__ in, int planes, int H, int W,
                                                                int RH, int RW, int crop_y, int crop_x, int OH, int OW,
                                                                float mul, float add, float* __restrict__ out) {
@@ -82,6 +83,13 @@ __global__ void __launch_bounds__(256) bn_ema_update_kernel(float* __restrict__ 
 
 using namespace dic;
 
+// torchvision.transforms.functional.center_crop: origin = int(round((resized - crop) / 2.0)), and Python 3's round() rounds
+// halves to even (12.5 -> 12, 97.5 -> 98) where lroundf rounds them away from zero.  In integers: no float involved.
+static inline int center_crop_origin(int resized, int crop) {
+  const int d = resized - crop, q = d / 2;      // d >= 0 (checked by the caller)
+  return (d & 1) ? q + (q & 1) : q;
+}
+
 extern "C" {
 
 int dic_normalize_images(const float* in, float* out, int B, int C, int H, int W, const float* mean3, const float* std3,
@@ -103,7 +111,7 @@ int dic_resize_bilinear(const float* in, int planes, int H, int W, int resize_sh
   int RH, RW;
   if (H <= W) { RH = resize_short; RW = (int)((long long)resize_short * W / H); }
   else { RW = resize_short; RH = (int)((long long)resize_short * H / W); }
-  const int cy = (int)lroundf((RH - crop) / 2.0f), cx = (int)lroundf((RW - crop) / 2.0f);
+  const int cy = center_crop_origin(RH, crop), cx = center_crop_origin(RW, crop);
   const long long total = (long long)planes * crop * crop;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(resize_bilinear_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, planes, H, W, RH, RW, cy,

@@ -540,7 +540,10 @@ int dic_pointwise_dot(const float* x, long long rows, int C, const float* w, con
 int dic_normalize_images(const float* in, float* out, int B, int C, int H, int W, const float* mean3, const float* std3,
                          void* stream);
 /* T.Resize(resize_short, bilinear) + T.CenterCrop(crop) + y*mul+add over `planes` HxW planes (util.py:14-17;
- * align_corners=False, no antialias = torchvision's result when up-scaling 224 -> 384). out: [planes,crop,crop]. */
+ * align_corners=False, no antialias = torchvision's result when up-scaling 224 -> 384). out: [planes,crop,crop].
+ * Geometry: the short edge becomes resize_short, the long edge floor(resize_short * long / short); the crop window starts at
+ * round((resized - crop) / 2) with halves rounded to the EVEN neighbour (Python's round(), which torchvision's center_crop uses:
+ * 12.5 -> 12, 97.5 -> 98). */
 int dic_resize_bilinear(const float* in, int planes, int H, int W, int resize_short, int crop, float mul, float add,
                         float* out, void* stream);
 /* in place: NaN -> 0.5, then per-image (x-min)/(max-min)   (DPT_model.py:50-59); depth: [B, hw]. */
