@@ -124,6 +124,9 @@ class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
         return super().stochastic_sample(features, None, word_to_id, n_samples, max_length, temperature, top_k, top_p, seed,
                                          return_all)
 
+    def score_captions(self, features, captions, word_to_id, skip_start=False, return_all=False):
+        return super().score_captions(features, None, captions, word_to_id, skip_start, return_all)
+
 
 class RNNDecoderWithHardAttention(_CaptionDecoderBase):
     """base-hard decoder (base_caption_models.py:257-508)."""
@@ -157,3 +160,6 @@ class RNNDecoderWithHardAttention(_CaptionDecoderBase):
                           return_all=False):
         return super().stochastic_sample(features, None, word_to_id, n_samples, max_length, temperature, top_k, top_p, seed,
                                          return_all)
+
+    def score_captions(self, features, captions, word_to_id, skip_start=False, return_all=False):
+        return super().score_captions(features, None, captions, word_to_id, skip_start, return_all)

@@ -250,6 +250,29 @@ class _CaptionDecoderBase(nn.Module):
                     lengths.cpu().numpy().astype(np.int32))
         return ids.cpu().numpy().astype(np.int64)
 
+    # ---- scoring of given captions (no counterpart in the reference; semantics: include/dic.h) -----------------------------------
+    @torch.no_grad()
+    def score_captions(self, features, depth_features, captions, word_to_id, skip_start=False, return_all=False):
+        """Log-probability the model gives to GIVEN captions: np.float32 [B] for captions int64 [B,T], [B,S] for [B,S,T] (S <= 8
+        captions per image) - the sum over each caption's tokens up to and including its first '<end>'.  The captions carry no
+        '<start>'; skip_start=True drops column 0 (collated ground-truth captions begin with it).  return_all=True: (logprobs
+        np.float32 [B,(S,)T] - one entry per token, 0 behind '<end>' -, scores, lengths np.int32)."""
+        if self.hard:
+            raise DicError("score_captions: scoring is built for the soft-attention decoders only (the likelihood of a Gumbel-max "
+                           "decode is an expectation over its attention draws); there is no hard-attention counterpart")
+        caps = torch.as_tensor(captions)
+        if caps.dim() not in (2, 3):
+            raise DicError(f"score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        if skip_start:
+            caps = caps[..., 1:]
+        features = _contig(features)
+        logprobs, scores, lengths = native.decoder_score(self._weights(), features, _contig(depth_features), word_to_id["<start>"],
+                                                         word_to_id["<end>"], caps.to(features.device))
+        if return_all:
+            return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return scores.cpu().numpy().astype(np.float32)
+
 
 class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,

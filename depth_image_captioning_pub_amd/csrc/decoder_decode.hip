@@ -1,6 +1,8 @@
-// Decoding on the device: greedy (dic_decoder_greedy), beam search (dic_decoder_beam) and sampling (dic_decoder_sample).
+// Decoding on the device: greedy (dic_decoder_greedy), beam search (dic_decoder_beam), sampling (dic_decoder_sample) and the
+// scoring of given captions (dic_decoder_score).
 #include "beam.h"
 #include "sample.h"
+#include "score.h"
 #include <cmath>
 #include <algorithm>
 
@@ -351,6 +353,63 @@ __global__ void __launch_bounds__(256) sample_alpha_gather_kernel(const float* _
   out[i] = hist[((long long)t * R + r) * kL + l];
 }
 
+// ------------------------------------------------------------------------------------------
+// scoring given captions (dic_decoder_score; semantics in include/dic.h, layout in DESIGN.md 5.10): S captions per image, rows
+// b*S + s.  A scored row is a sampled row whose tokens are known in advance: the recurrence never looks at the logits, so the
+// loop only collects h of every step and ONE fused projection + log-sum-exp (score.hip) runs over all T*R rows afterwards.
+// Per step: beam_attn_kernel -> gate GEMM slabs -> lstm_fwd_kernel (h appended to the history) -> score_handover_kernel.
+// ------------------------------------------------------------------------------------------
+// start, grid (B), kH threads: h0 / c0 of the image (slot 1 of row 0, as sample_init_kernel) for all S rows; and per row the
+// transposed token arrays: tok_in [T][R] the input of every step (<start>, then the caption shifted by one), target [T][R] the
+// caption clamped into the vocabulary, -1 from the row's length on; length = index of the first id_end + 1, or T.
+__global__ void __launch_bounds__(kH) score_init_kernel(int S, int T, int V, long long id_start, long long id_end,
+                                                         const long long* __restrict__ captions, long long* __restrict__ tok_in,
+                                                         long long* __restrict__ target, int* __restrict__ length,
+                                                         float* __restrict__ Hst, float* __restrict__ Cst) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row0 = (long long)b * S, R = (long long)gridDim.x * S;
+  const float h = Hst[(row0 * 2 + 1) * kH + tid], c = Cst[(row0 * 2 + 1) * kH + tid];
+  for (int s = 0; s < S; ++s) {
+    Hst[(row0 + s) * 2 * kH + tid] = h;
+    Cst[(row0 + s) * 2 * kH + tid] = c;
+  }
+  if (tid < S) {
+    const long long r = row0 + tid;
+    const long long* cap = captions + r * T;
+    int n = T;
+    tok_in[r] = id_start;
+    for (int t = 0; t < T; ++t) {
+      const long long id = cap[t];
+      target[(long long)t * R + r] = t < n ? clamp_token(id, V) : -1;
+      if (t + 1 < T) tok_in[(long long)(t + 1) * R + r] = id;
+      if (t < n && id == id_end) n = t + 1;
+    }
+    length[r] = n;
+  }
+}
+
+// state hand-over of every row to itself: h', c' (slot 1, what the cell wrote) -> slot 0 (what the next step reads)
+__global__ void __launch_bounds__(kH) score_handover_kernel(float* __restrict__ Hst, float* __restrict__ Cst) {
+  const long long to = (long long)blockIdx.x * 2 * kH + threadIdx.x;
+  Hst[to] = Hst[to + kH];
+  Cst[to] = Cst[to + kH];
+}
+
+// end, one thread per row: log-probabilities [T][R] -> out_logprobs [R][T] (exactly 0 from the row's length on: the fused kernel
+// wrote 0 for the skipped targets) and their fp32 sum in ascending t
+__global__ void __launch_bounds__(256) score_finish_kernel(const float* __restrict__ lp, int R, int T,
+                                                            float* __restrict__ out_logprobs, float* __restrict__ out_scores) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  float sum = 0.f;
+  for (int t = 0; t < T; ++t) {
+    const float v = lp[(long long)t * R + r];
+    out_logprobs[(long long)r * T + t] = v;
+    sum += v;
+  }
+  out_scores[r] = sum;
+}
+
 }  // namespace dic
 
 using namespace dic;
@@ -589,6 +648,97 @@ int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rg
                        T, alphas_out);
     DIC_LAUNCH_CHECK();
   }
+  return DIC_OK;
+}
+
+// ---- scoring ----------------------------------------------------------------------------------------------------------------
+namespace {
+struct ScoreWs : SetupBufs {       // (no WcatT; SampleWs without the logits and the attention history, plus the h history)
+  float *Hst, *Cst, *X, *slab, *Gact, *hist, *lp;
+  long long *tok_in, *target;
+  void* lse_ws;
+  size_t bytes;
+};
+
+ScoreWs score_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* overflow) {
+  Carver c(p, bytes);
+  ScoreWs w{};
+  const size_t R = (size_t)B * S, M = R * T;
+  w.F = c.take<float>((size_t)B * kL * kD);
+  w.P = c.take<float>((size_t)B * kL * kA);
+  w.mean = c.take<float>((size_t)B * kD);
+  w.Wcat = c.take<float>((size_t)kG * kXK);
+  w.bcat = c.take<float>(kG);
+  w.WhT = c.take<float>((size_t)kH * kA);
+  w.WbT = c.take<float>((size_t)kH * kD);
+  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
+  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
+  w.Hst = c.take<float>(R * 2 * kH);
+  w.Cst = c.take<float>(R * 2 * kH);
+  w.X = c.take<float>(R * kXK);
+  w.slab = c.take<float>((size_t)kS_LSTM * R * kG);
+  w.Gact = c.take<float>(R * kG);
+  w.hist = c.take<float>(M * kH);                              // h of every step, rows t*R + r: the A operand of the fused launch
+  w.lp = c.take<float>(M);
+  w.tok_in = c.take<long long>(M);
+  w.target = c.take<long long>(M);
+  w.lse_ws = c.take<char>(token_logprobs_bytes((int)M, V));
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+
+bool score_sizes_ok(int B, int S, int max_length, int V) {
+  return B > 0 && S >= 1 && S <= kBeamMax && max_length >= 1 && V > 0 && (long long)B * S * max_length <= kScoreMaxM;
+}
+}  // namespace
+
+size_t dic_decoder_score_workspace_bytes(int B, int S, int max_length, int V) {
+  if (!score_sizes_ok(B, S, max_length, V)) return 0;
+  bool ov;
+  return score_carve(nullptr, 0, B, S, max_length, V, &ov).bytes;
+}
+
+int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                      long long id_start, long long id_end, int max_length, const int64_t* captions, float* out_logprobs,
+                      float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_score: captions per image S=%d is outside 1..%d", S, kBeamMax);
+  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "decoder_score: bad sizes (B=%d, V=%d, max_length=%d)", B, V, max_length);
+  DIC_REQUIRE((long long)B * S * max_length <= kScoreMaxM, "decoder_score: B*S*max_length=%lld exceeds %d token positions per call",
+              (long long)B * S * max_length, kScoreMaxM);
+  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_score: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_score: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(w && feat_rgb && captions && out_logprobs && out_scores && out_lengths && workspace, "decoder_score: null pointer");
+  const int T = max_length, R = B * S;
+  bool ov = false;
+  ScoreWs ws = score_carve(workspace, workspace_bytes, B, S, T, V, &ov);
+  if (ov) {
+    set_last_error("decoder_score: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  // per image, never per caption.  [h0 | c0] -> slot 1 of row 0 of the image, then copied to its S rows
+  DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
+  hipLaunchKernelGGL(score_init_kernel, dim3(B), dim3(kH), 0, st, S, T, V, id_start, id_end, (const long long*)captions, ws.tok_in,
+                     ws.target, out_lengths, ws.Hst, ws.Cst);
+  DIC_LAUNCH_CHECK();
+  for (int t = 0; t < T; ++t) {
+    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P,
+                                          ws.Hst, ws.tok_in + (size_t)t * R, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w,
+                                          w->full_att_b, ws.WbT, w->fbeta_b, (float*)nullptr, ws.X, B);)
+    DIC_LAUNCH_CHECK();
+    DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
+    // the cell writes h' / c' into slot 1 and appends h' to the history (its "dropped" output at packed row t*R + r, no dropout)
+    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.hist, kS_LSTM, R, t * R}, 0, 1, st));
+    if (t + 1 < T) {
+      hipLaunchKernelGGL(score_handover_kernel, dim3(R), dim3(kH), 0, st, ws.Hst, ws.Cst);
+      DIC_LAUNCH_CHECK();
+    }
+  }
+  DIC_TRY(launch_token_logprobs(ws.hist, w->out_w, w->out_b, ws.target, R * T, V, ws.lp, nullptr, ws.lse_ws, st));
+  hipLaunchKernelGGL(score_finish_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, st, ws.lp, R, T, out_logprobs, out_scores);
+  DIC_LAUNCH_CHECK();
   return DIC_OK;
 }
 

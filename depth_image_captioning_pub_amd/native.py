@@ -602,6 +602,71 @@ def decoder_sample(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
     return (ids, logprobs, lengths, alphas) if return_alphas else (ids, logprobs, lengths)
 
 
+def _dev_i64(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise _lib.DicError(f"{what}: tensor must live on the GPU (no CPU fallback)")
+    if t.dtype != torch.int64:
+        raise _lib.DicError(f"{what}: expected int64, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor):
+    """dic_token_logprobs: log-probability of targets[m] under softmax(hidden[m] @ weight.T + bias), the [M,V] logits never stored
+    (semantics: include/dic.h).  hidden float32 [M,128], weight [V,128], bias [V], targets int64 [M] (negative: the row is skipped
+    and gets 0 / 0).  Returns (logprobs float32 [M], lse float32 [M])."""
+    lib = _lib.load()
+    h, w, b = _dev_f32(hidden, "hidden"), _dev_f32(weight, "weight"), _dev_f32(bias, "bias")
+    tg = _dev_i64(targets, "targets")
+    if h.dim() != 2 or h.shape[1] != D_HID or w.dim() != 2 or w.shape[1] != D_HID:
+        raise _lib.DicError(f"token_logprobs: hidden must be [M,{D_HID}] and weight [V,{D_HID}], got {tuple(h.shape)} and {tuple(w.shape)}")
+    M, V = h.shape[0], w.shape[0]
+    if tuple(b.shape) != (V,) or tuple(tg.shape) != (M,):
+        raise _lib.DicError(f"token_logprobs: bias must be [{V}] and targets [{M}], got {tuple(b.shape)} and {tuple(tg.shape)}")
+    lib.dic_token_logprobs_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_token_logprobs_workspace_bytes(M, V)                       # (0 for sizes the call below refuses with its text)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=h.device)
+    logprobs = torch.empty((M,), dtype=torch.float32, device=h.device)
+    lse = torch.empty((M,), dtype=torch.float32, device=h.device)
+    rc = lib.dic_token_logprobs(ptr(h), ptr(w), ptr(b), ptr(tg), M, V, ptr(logprobs), ptr(lse), ptr(ws), C.c_size_t(ws.numel()),
+                                stream_ptr())
+    check(rc, "dic_token_logprobs")
+    return logprobs, lse
+
+
+def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                  id_end: int, captions: torch.Tensor):
+    """dic_decoder_score: the log-probability the soft-attention decoder gives every token of given captions, on the device
+    (semantics: include/dic.h).  captions: int64 [B,T] (one per image) or [B,S,T] (S <= 8 per image), without '<start>'.
+    Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
+    lib = _lib.load()
+    f_rgb = _dev_f32(feat_rgb, "features")
+    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
+    cap = _dev_i64(captions, "captions")
+    B = f_rgb.shape[0]
+    squeeze = cap.dim() == 2
+    if squeeze:
+        cap = cap.unsqueeze(1)
+    if cap.dim() != 3 or cap.shape[0] != B:
+        raise _lib.DicError(f"decoder_score: captions must be [B,T] or [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+    S, T = int(cap.shape[1]), int(cap.shape[2])
+    vocab = weights["linear.weight"].shape[0]
+    wp, keep = decoder_ptrs(weights)
+    lib.dic_decoder_score_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_decoder_score_workspace_bytes(B, S, T, vocab)              # (0 for sizes the call below refuses with its text)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f_rgb.device)
+    ss, tt = max(S, 1), max(T, 1)
+    logprobs = torch.empty((B, ss, tt), dtype=torch.float32, device=f_rgb.device)
+    scores = torch.empty((B, ss), dtype=torch.float32, device=f_rgb.device)
+    lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
+    rc = lib.dic_decoder_score(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, C.c_longlong(int(id_start)),
+                               C.c_longlong(int(id_end)), T, ptr(cap), ptr(logprobs), ptr(scores), ptr(lengths), ptr(ws),
+                               C.c_size_t(ws.numel()), stream_ptr())
+    check(rc, "dic_decoder_score")
+    if squeeze:
+        return logprobs[:, 0], scores[:, 0], lengths[:, 0]
+    return logprobs, scores, lengths
+
+
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""

@@ -190,6 +190,52 @@ int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rg
                        const float* uniform_u, int64_t* out_ids, float* out_logprobs, int* out_lengths, float* alphas_out,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* log-probability of one given token per row of hidden states: the vocabulary projection fused with a log-sum-exp and a target
+ *   pick.  Model-agnostic (K = DIC_H = 128); this comment is the specification.
+ *   hidden float [M,128], out_w float [V,128], out_b float [V], targets int64 [M] on the device.
+ *     x_v = hidden_m . out_w[v] + out_b[v]                      (exact fp32 on v_mfma_f32_32x32x2_f32, one fma chain per x_v)
+ *     lse_m = max_v x_v + log sum_v exp(x_v - max_v x_v)         (fp32)
+ *     out_logprob[m] = x_target - lse_m, evaluated as (x_target - max) - log sum
+ *   A target >= V is clamped to V-1 (as every token input is).  A NEGATIVE target marks a skipped row: out_logprob[m] = 0 and
+ *   out_lse[m] = 0 exactly, and the row's logits need not be computed.  out_lse (nullable) float [M].
+ *   The [M,V] logits are never written to memory: they exist as accumulator tiles, reduced on the fly to one (max, sum) pair per
+ *   row and chunk of 512 columns, which a second small kernel combines in ascending chunk order.  No float atomics.
+ *   Properties: row m depends only on hidden_m, targets[m], out_w, out_b and V - never on M or on the other rows (the chunking of
+ *   V and every summation order are functions of V alone), so a row scored alone returns the bytes it returns inside a batch;
+ *   two calls return identical bytes.
+ *   M, V > 0, M <= 65535 * 128, no null pointer other than out_lse, a workspace of sufficient size: a violation returns a negative
+ *   code and a dic_last_error() text that starts with "dic_token_logprobs:", before any HIP call; the workspace query returns 0
+ *   for sizes the call refuses. */
+size_t dic_token_logprobs_workspace_bytes(int M, int V);
+int dic_token_logprobs(const float* hidden, const float* out_w, const float* out_b, const int64_t* targets, int M, int V,
+                       float* out_logprob, float* out_lse, void* workspace, size_t workspace_bytes, void* stream);
+
+/* scoring of GIVEN captions by the soft-attention decoder (depth-soft, or base-soft with feat_depth = NULL): the log-probability
+ *   the model gives every token of S captions per image.  Entirely on the device: every launch is enqueued on `stream`, nothing
+ *   is copied to the host, nothing synchronises.  There is no reference implementation; this comment is the specification.
+ *   Rows: row r = b*S + s is caption s of image b, 1 <= S <= 8.  captions int64 [B,S,T] on the device, WITHOUT <start>,
+ *     T = max_length.  Dropout off; all S rows of an image start from init_linear(mean_L F), F = F_rgb (+ F_depth), 196 cells.
+ *   The input token of step t is id_start at t = 0 and captions[r, t-1] after that, clamped into the vocabulary like every token
+ *     input.  One step of a row is the decode-step body of dic_decoder_greedy up to h.
+ *   length[r] = (index of the first id_end in captions[r, :]) + 1, or T when there is none; derived on the device.
+ *   t <  length: out_logprobs[r,t] = log-probability of captions[r,t] (clamped) under the UNFILTERED distribution of step t:
+ *     dic_token_logprobs of the step's h with linear.weight / linear.bias.
+ *   t >= length: out_logprobs[r,t] = 0 exactly; the tokens there are never a target.
+ *   out_scores[r] = the fp32 sum of out_logprobs[r, 0..T-1] in ascending t.
+ *   out_logprobs float [B,S,T], out_scores float [B,S], out_lengths int [B,S].
+ *   1 <= S <= 8, B, V > 0, max_length >= 1, B*S*max_length <= 65535 * 128, 0 <= id_start, id_end < V, no null pointer other than
+ *   feat_depth, a workspace of sufficient size: a violation returns a negative code and a dic_last_error() text that starts with
+ *   "decoder_score:", before anything is launched; the workspace query returns 0 for sizes the call refuses.
+ *   Properties: the result agrees, up to fp32 rounding, with dic_decoder_sample's out_logprobs for the ids it drew at temperature 1
+ *   with the filters off, and with dic_decoder_beam's out_scores for the hypotheses it returned; row (b,s) depends only on image b
+ *   and caption (b,s); two calls return identical bytes.  The S rows of an image share one read of its F and P per step, the
+ *   vocabulary projection runs once over all B*S*T hidden states, and the workspace holds no [B*S,V] or [B*S*T,V] array
+ *   (DESIGN.md 5.10). */
+size_t dic_decoder_score_workspace_bytes(int B, int S, int max_length, int V);
+int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                      long long id_start, long long id_end, int max_length, const int64_t* captions, float* out_logprobs,
+                      float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
  *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
  *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both
