@@ -24,4 +24,19 @@ size_t token_logprobs_bytes(int M, int V);
 int launch_token_logprobs(const float* hidden, const float* out_w, const float* out_b, const long long* targets, int M, int V,
                           float* out_logprob, float* out_lse, void* ws, hipStream_t st);
 
+// ---- the backward, score_bwd.hip (the rule is the header comment of dic_token_logprobs_bwd in include/dic.h) ----
+constexpr int kScoreBwdSplit = 2560;    // columns per workgroup of the d_hidden sweep.  A constant: the split of V never depends on M
+constexpr int kScoreBwdGroup = 2048;    // rows per workgroup of the d_out_w / d_out_b sweep
+inline int score_bwd_splits(int V) { return (V + kScoreBwdSplit - 1) / kScoreBwdSplit; }
+inline int score_bwd_groups(int M) { return (M + kScoreBwdGroup - 1) / kScoreBwdGroup; }
+// per-row (lse, g, l - g, target) [M]; with more than one split / group the partial results [splits][M][128], [groups][V][128],
+// [groups][V].  Nothing of M * V elements.
+size_t token_logprobs_bwd_bytes(int M, int V);
+
+// lse [M]: the out_lse of launch_token_logprobs for the same inputs.  d_lse and each of the three outputs nullable.
+// ws: token_logprobs_bwd_bytes(M, V) bytes, 256-B aligned.  No argument checks here: the entry point makes them.
+int launch_token_logprobs_bwd(const float* hidden, const float* out_w, const float* out_b, const long long* targets,
+                              const float* lse, const float* d_logprob, const float* d_lse, int M, int V, float* d_hidden,
+                              float* d_out_w, float* d_out_b, void* ws, hipStream_t st);
+
 }  // namespace dic

@@ -1,0 +1,66 @@
+"""Differentiable token log-probabilities: torch autograd over dic_token_logprobs / dic_token_logprobs_bwd (include/dic.h).  The
+vocabulary projection, its log-sum-exp and both of their gradients run in the fused kernels of csrc/score.hip and
+csrc/score_bwd.hip; the [M,V] logits and their gradient are never stored.  Nothing here falls back to torch ops: tensors that
+do not live on the GPU raise DicError."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import _lib, native
+
+
+class _TokenLogprobs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, targets):
+        logprobs, lse = native.token_logprobs(hidden, weight, bias, targets)
+        ctx.save_for_backward(hidden, weight, bias, targets, lse)
+        ctx.set_materialize_grads(False)          # a gradient that does not arrive stays None: d_lse = NULL skips nothing but a read
+        return logprobs, lse
+
+    @staticmethod
+    def backward(ctx, d_logprobs, d_lse):
+        hidden, weight, bias, targets, lse = ctx.saved_tensors
+        need = tuple(ctx.needs_input_grad[:3])
+        if not any(need) or (d_logprobs is None and d_lse is None):
+            return None, None, None, None
+        if d_logprobs is None:
+            d_logprobs = torch.zeros_like(lse)
+        d_hidden, d_weight, d_bias = native.token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprobs, d_lse, need)
+        return d_hidden, d_weight, d_bias, None   # (targets: integer, no gradient)
+
+
+def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor):
+    """(logprobs [M], lse [M]) of native.token_logprobs, differentiable with respect to hidden [M,128], weight [V,128] and bias [V]:
+    logprobs[m] = log softmax(hidden[m] @ weight.T + bias)[targets[m]], lse[m] the row's log-sum-exp.  A negative target skips
+    the row (0, 0, and no gradient from it); a target >= V is clamped to V-1.  Gradients may arrive on either output or both."""
+    return _TokenLogprobs.apply(hidden, weight, bias, targets)
+
+
+def linear_cross_entropy(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor,
+                         weights: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
+    """Cross entropy of targets under softmax(hidden @ weight.T + bias) without the [M,V] logits: -(weights *) logprobs.
+    Rows with a negative target are ignored (F.cross_entropy's ignore_index).  weights: optional PER-ROW float32 [M] (a reward, a
+    mask, a per-token weight); gradients flow into it as well.
+    reduction: "none" -> [M] (0 on ignored rows); "sum"; "mean" -> the sum divided by the number of live rows, which is
+    F.cross_entropy(ignore_index=...)'s mean, or - with weights - by the sum of the live rows' weights, as
+    F.cross_entropy(weight=...) divides by the sum of its class weights over the live rows.  No live row: nan, as there."""
+    if reduction not in ("mean", "sum", "none"):
+        raise _lib.DicError(f"linear_cross_entropy: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    logprobs, _ = token_logprobs(hidden, weight, bias, targets)
+    return reduce_logprobs(logprobs, targets, weights, reduction)
+
+
+def reduce_logprobs(logprobs: torch.Tensor, targets: torch.Tensor, weights: Optional[torch.Tensor], reduction: str) -> torch.Tensor:
+    """The loss linear_cross_entropy makes of token_logprobs' first output (0 on rows with a negative target): see there."""
+    if weights is not None and tuple(weights.shape) != tuple(logprobs.shape):
+        raise _lib.DicError(f"linear_cross_entropy: weights must be [{logprobs.shape[0]}], got {tuple(weights.shape)}")
+    rows = -logprobs if weights is None else -(weights * logprobs)
+    if reduction == "none":
+        return rows
+    if reduction == "sum":
+        return rows.sum()
+    live = targets >= 0
+    denom = live.sum().to(rows.dtype) if weights is None else (weights * live.to(weights.dtype)).sum()
+    return rows.sum() / denom

@@ -633,6 +633,40 @@ def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     return logprobs, lse
 
 
+def token_logprobs_bwd(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor,
+                       d_logprob: torch.Tensor, d_lse: Optional[torch.Tensor] = None, need=(True, True, True)):
+    """dic_token_logprobs_bwd: the gradients of sum(d_logprob * logprobs) + sum(d_lse * lse) of token_logprobs with respect to
+    hidden, weight and bias, the [M,V] logits never stored (semantics: include/dic.h).  lse: what token_logprobs returned for the
+    same inputs.  d_logprob, d_lse (optional) float32 [M].  need: which of (d_hidden [M,128], d_weight [V,128], d_bias [V]) to
+    compute; one that was not requested is None."""
+    lib = _lib.load()
+    h, w, b = _dev_f32(hidden, "hidden"), _dev_f32(weight, "weight"), _dev_f32(bias, "bias")
+    tg = _dev_i64(targets, "targets")
+    ls, g = _dev_f32(lse, "lse"), _dev_f32(d_logprob, "d_logprob")
+    dl = _dev_f32(d_lse, "d_lse") if d_lse is not None else None
+    if h.dim() != 2 or h.shape[1] != D_HID or w.dim() != 2 or w.shape[1] != D_HID:
+        raise _lib.DicError(f"token_logprobs_bwd: hidden must be [M,{D_HID}] and weight [V,{D_HID}], got {tuple(h.shape)} and {tuple(w.shape)}")
+    M, V = h.shape[0], w.shape[0]
+    if tuple(b.shape) != (V,) or tuple(tg.shape) != (M,):
+        raise _lib.DicError(f"token_logprobs_bwd: bias must be [{V}] and targets [{M}], got {tuple(b.shape)} and {tuple(tg.shape)}")
+    if tuple(ls.shape) != (M,) or tuple(g.shape) != (M,) or (dl is not None and tuple(dl.shape) != (M,)):
+        raise _lib.DicError(f"token_logprobs_bwd: lse, d_logprob and d_lse must be [{M}], got {tuple(ls.shape)}, {tuple(g.shape)} and "
+                            f"{tuple(dl.shape) if dl is not None else None}")
+    need = tuple(bool(n) for n in need)
+    if len(need) != 3:
+        raise _lib.DicError(f"token_logprobs_bwd: need must name three outputs, got {len(need)}")
+    lib.dic_token_logprobs_bwd_workspace_bytes.restype = C.c_size_t
+    nbytes = lib.dic_token_logprobs_bwd_workspace_bytes(M, V)                 # (0 for sizes the call below refuses with its text)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=h.device)
+    d_hidden = torch.empty((M, D_HID), dtype=torch.float32, device=h.device) if need[0] else None
+    d_weight = torch.empty((V, D_HID), dtype=torch.float32, device=h.device) if need[1] else None
+    d_bias = torch.empty((V,), dtype=torch.float32, device=h.device) if need[2] else None
+    rc = lib.dic_token_logprobs_bwd(ptr(h), ptr(w), ptr(b), ptr(tg), ptr(ls), ptr(g), ptr(dl), M, V, ptr(d_hidden), ptr(d_weight),
+                                    ptr(d_bias), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    check(rc, "dic_token_logprobs_bwd")
+    return d_hidden, d_weight, d_bias
+
+
 def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
                   id_end: int, captions: torch.Tensor):
     """dic_decoder_score: the log-probability the soft-attention decoder gives every token of given captions, on the device

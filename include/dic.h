@@ -210,6 +210,35 @@ size_t dic_token_logprobs_workspace_bytes(int M, int V);
 int dic_token_logprobs(const float* hidden, const float* out_w, const float* out_b, const int64_t* targets, int M, int V,
                        float* out_logprob, float* out_lse, void* workspace, size_t workspace_bytes, void* stream);
 
+/* backward of dic_token_logprobs: the gradient of  sum_m g_m out_logprob[m] + l_m out_lse[m]  with respect to hidden, out_w and
+ *   out_b, the [M,V] logits and their gradient never written to memory.  Model-agnostic (K = DIC_H = 128); this comment is the
+ *   specification.
+ *   hidden float [M,128], out_w float [V,128], out_b float [V], targets int64 [M], lse float [M], d_logprob float [M],
+ *   d_lse (nullable) float [M] on the device.  lse is the out_lse dic_token_logprobs returned for the same inputs.
+ *     x_mv = hidden_m . out_w[v] + out_b[v]                     (recomputed: exact fp32 on v_mfma_f32_32x32x2_f32, the forward's chain)
+ *     p_mv = exp(x_mv - lse_m)
+ *     t_m = min(targets[m], V-1),  g_m = d_logprob[m],  l_m = d_lse ? d_lse[m] : 0
+ *     d_mv = g_m [v == t_m] + (l_m - g_m) p_mv
+ *   A row with targets[m] < 0 is skipped, as in the forward: d_mv = 0 for every v (selected, not multiplied), so its d_hidden row
+ *   is exactly 0 and it adds nothing to d_out_w / d_out_b whatever finite values its hidden, lse and d_* hold.
+ *     d_hidden[m,k] = sum_v d_mv out_w[v,k]      float [M,128]
+ *     d_out_w[v,k]  = sum_m d_mv hidden[m,k]     float [V,128]
+ *     d_out_b[v]    = sum_m d_mv                 float [V]
+ *   The outputs are written, not accumulated.  Each of the three may be NULL, in which case its work is not done; at least one
+ *   must be given.  Everything is enqueued on `stream`; nothing is copied to the host, nothing synchronises.
+ *   Properties: the workspace holds no array of M*V elements (one (lse, g, l-g, t) record per row, and partial results
+ *   [ceil(V/2560)][M][128], [ceil(M/2048)][V][128], [ceil(M/2048)][V] where there is more than one part).  No float atomics: every
+ *   summation order is a function of (M, V) alone, so two calls return identical bytes.  d_hidden row m depends only on row m's
+ *   inputs, out_w, out_b and V - never on M, on the other rows or on whether d_out_w / d_out_b were requested: a row
+ *   differentiated alone returns the bytes it returns inside a batch.
+ *   M, V > 0, M <= 65535 * 128, no null pointer other than d_lse and the three outputs, at least one output, a workspace of
+ *   sufficient size: a violation returns a negative code and a dic_last_error() text that starts with "dic_token_logprobs_bwd:",
+ *   before any HIP call; the workspace query returns 0 for sizes the call refuses. */
+size_t dic_token_logprobs_bwd_workspace_bytes(int M, int V);
+int dic_token_logprobs_bwd(const float* hidden, const float* out_w, const float* out_b, const int64_t* targets, const float* lse,
+                           const float* d_logprob, const float* d_lse, int M, int V, float* d_hidden, float* d_out_w,
+                           float* d_out_b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* scoring of GIVEN captions by the soft-attention decoder (depth-soft, or base-soft with feat_depth = NULL): the log-probability
  *   the model gives every token of S captions per image.  Entirely on the device: every launch is enqueued on `stream`, nothing
  *   is copied to the host, nothing synchronises.  There is no reference implementation; this comment is the specification.
