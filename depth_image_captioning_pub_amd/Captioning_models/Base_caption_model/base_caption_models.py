@@ -127,6 +127,9 @@ class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def score_captions(self, features, captions, word_to_id, skip_start=False, return_all=False):
         return super().score_captions(features, None, captions, word_to_id, skip_start, return_all)
 
+    def caption_logprobs(self, features, captions, word_to_id, skip_start=False):
+        return super().caption_logprobs(features, None, captions, word_to_id, skip_start)
+
 
 class RNNDecoderWithHardAttention(_CaptionDecoderBase):
     """base-hard decoder (base_caption_models.py:257-508)."""
@@ -163,3 +166,6 @@ class RNNDecoderWithHardAttention(_CaptionDecoderBase):
 
     def score_captions(self, features, captions, word_to_id, skip_start=False, return_all=False):
         return super().score_captions(features, None, captions, word_to_id, skip_start, return_all)
+
+    def caption_logprobs(self, features, captions, word_to_id, skip_start=False):
+        return super().caption_logprobs(features, None, captions, word_to_id, skip_start)

@@ -16,7 +16,7 @@ import torch
 from torch import nn
 from torch.nn.utils.rnn import PackedSequence
 
-from ... import native
+from ... import losses, native
 from ..._lib import DicError
 from ..attention import Hard_Attention, Soft_Attention
 
@@ -116,6 +116,34 @@ class _DecoderFn(torch.autograd.Function):
             d_logits = torch.zeros((tape.n_packed, tape.vocab), dtype=torch.float32, device=tape.alphas.device)
         grads, dfeat = native.decoder_backward(tape, _contig(d_logits), _contig(d_alphas))
         return (None, dfeat, dfeat if ctx.has_depth else None, None) + tuple(grads[k] for k in _DEC_KEYS)
+
+
+class _CaptionStatesFn(torch.autograd.Function):
+    """Hidden states of given captions (dic_decoder_states_fwd) and their backward through time (dic_decoder_states_bwd).  params:
+    the 15 decoder parameters other than linear.*, which enter through losses.token_logprobs."""
+
+    @staticmethod
+    def forward(ctx, cfg, features, depth_features, captions, *params):
+        ctx.set_materialize_grads(False)
+        weights = {k: p.detach() for k, p in zip(native.STATES_GRAD_KEYS, params)}
+        weights.update(cfg["linear"])
+        hidden, targets, lengths, tape = native.decoder_states_forward(
+            weights, _contig(features.detach()), _contig(depth_features.detach()) if depth_features is not None else None,
+            cfg["id_start"], cfg["id_end"], captions, cfg.get("drop_mult"))
+        ctx.tape = tape
+        ctx.has_depth = depth_features is not None
+        cfg["targets"], cfg["lengths"] = targets, lengths
+        return hidden
+
+    @staticmethod
+    def backward(ctx, d_hidden):
+        n = 4 + len(native.STATES_GRAD_KEYS)
+        if d_hidden is None:
+            return (None,) * n
+        need_rgb, need_depth = ctx.needs_input_grad[1], ctx.has_depth and ctx.needs_input_grad[2]
+        grads, dfeat = native.decoder_states_backward(ctx.tape, _contig(d_hidden), need_features=need_rgb or need_depth)
+        return (None, dfeat if need_rgb else None, dfeat if need_depth else None, None) + tuple(
+            grads[k] for k in native.STATES_GRAD_KEYS)
 
 
 class _CaptionDecoderBase(nn.Module):
@@ -236,19 +264,31 @@ class _CaptionDecoderBase(nn.Module):
         if self.hard:
             raise DicError("stochastic_sample: sampling is built for the soft-attention decoders only (a Gumbel-max decode draws "
                            "its attention already); use batch_sample for hard attention")
-        features = _contig(features)
         S = int(n_samples)
-        gen = torch.Generator(features.device).manual_seed(int(seed))
-        u = torch.rand((max_length, features.shape[0] * max(S, 1)), generator=gen, device=features.device)
-        ids, logprobs, lengths = native.decoder_sample(self._weights(), features, _contig(depth_features), word_to_id["<start>"],
-                                                       word_to_id["<end>"], S, u, max_length, float(temperature), int(top_k),
-                                                       float(top_p))
+        ids, logprobs, lengths = self.stochastic_sample_tensors(features, depth_features, word_to_id, S, max_length, temperature,
+                                                                top_k, top_p, seed)
         if S == 1:
             ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
         if return_all:
             return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
                     lengths.cpu().numpy().astype(np.int32))
         return ids.cpu().numpy().astype(np.int64)
+
+    @torch.no_grad()
+    def stochastic_sample_tensors(self, features, depth_features, word_to_id, n_samples=1, max_length=30, temperature=1.0,
+                                  top_k=0, top_p=1.0, seed=0):
+        """What stochastic_sample draws, left on the device: (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length],
+        lengths int32 [B,S]) - for callers that feed the captions to another device call (scst.scst_step)."""
+        if self.hard:
+            raise DicError("stochastic_sample: sampling is built for the soft-attention decoders only (a Gumbel-max decode draws "
+                           "its attention already); use batch_sample for hard attention")
+        features = _contig(features.detach())
+        depth_features = _contig(depth_features.detach()) if depth_features is not None else None
+        S = int(n_samples)
+        gen = torch.Generator(features.device).manual_seed(int(seed))
+        u = torch.rand((max_length, features.shape[0] * max(S, 1)), generator=gen, device=features.device)
+        return native.decoder_sample(self._weights(), features, depth_features, word_to_id["<start>"], word_to_id["<end>"], S, u,
+                                     max_length, float(temperature), int(top_k), float(top_p))
 
     # ---- scoring of given captions (no counterpart in the reference; semantics: include/dic.h) -----------------------------------
     @torch.no_grad()
@@ -272,6 +312,39 @@ class _CaptionDecoderBase(nn.Module):
             return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
                     lengths.cpu().numpy().astype(np.int32))
         return scores.cpu().numpy().astype(np.float32)
+
+    # ---- the same log-probabilities, differentiable (no counterpart in the reference; semantics: include/dic.h) ---
+    def caption_logprobs(self, features, depth_features, captions, word_to_id, skip_start=False):
+        """Differentiable log-probabilities of GIVEN captions: (logprobs float32 [B,(S,)T] on the device - one entry per token, 0
+        from each caption's length on -, lengths int32 [B(,S)]) for captions int64 [B,T] or [B,S,T] (S <= 8 per image, no
+        '<start>'; skip_start=True drops column 0).  backward() reaches every decoder parameter and the features (a depth encoder
+        upstream trains through it): the recurrence is dic_decoder_states_fwd / _bwd - the S captions of an image share its
+        feature map -, the vocabulary projection losses.token_logprobs.  In train() mode the hidden states that enter the
+        projection are dropped as in forward(); eval() has no dropout.  Frozen features or a frozen `linear` skip their kernels."""
+        if self.hard:
+            raise DicError("caption_logprobs: scoring is built for the soft-attention decoders only (the likelihood of a Gumbel-max "
+                           "decode is an expectation over its attention draws); there is no hard-attention counterpart")
+        caps = torch.as_tensor(captions)
+        if caps.dim() not in (2, 3):
+            raise DicError(f"caption_logprobs: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        if skip_start:
+            caps = caps[..., 1:]
+        squeeze = caps.dim() == 2
+        if squeeze:
+            caps = caps.unsqueeze(1)
+        caps = _contig(caps.to(features.device))
+        B, S, T = (int(v) for v in caps.shape)
+        cfg = {"id_start": word_to_id["<start>"], "id_end": word_to_id["<end>"],
+               "drop_mult": self._dropout_mult(B * S, T, features.device),
+               "linear": {"linear.weight": self.linear.weight.detach(), "linear.bias": self.linear.bias.detach()}}
+        params = [_param(self, k) for k in native.STATES_GRAD_KEYS]
+        hidden = _CaptionStatesFn.apply(cfg, features, depth_features, caps, *params)
+        logprobs, _ = losses.token_logprobs(hidden.view(T * B * S, native.D_HID), self.linear.weight, self.linear.bias,
+                                            cfg["targets"].view(-1))
+        logprobs = logprobs.view(T, B, S).permute(1, 2, 0)
+        if squeeze:
+            return logprobs[:, 0], cfg["lengths"][:, 0]
+        return logprobs, cfg["lengths"]
 
 
 class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):

@@ -116,6 +116,75 @@ __device__ __forceinline__ RowChunk attn_step_row() {
 __device__ __forceinline__ long long clamp_token(long long id, int V) { return id < 0 ? 0 : (id >= V ? V - 1 : id); }
 #endif
 
+// ---- parts of the BPTT backward (decoder_bwd.hip) that the shared-feature backward (decoder_states.hip) uses as well ----
+// LSTM cell backward of step t: assembles dh_t / dc_t (the carry from step t+1 out of that step's products) and writes dG_t
+struct LstmBwdArgs {
+  int t, T, B, nb_next, have_next, final_pass, nlch;
+  const float* dHd; int packed_off; const float* drop;
+  const float* slab_dx; int nslab_dx, nb_slab; const float* dqp;
+  const float* pbeta; const float* W_h /*[A][H]*/;
+  const float* Gact; const float* Call; float* carry_dc;
+  float* dG; float* dq_all; float* dinit;
+};
+#ifdef __HIPCC__
+// body: thread j of row b; `active` = this thread takes part (the fused kernel runs it on the first kH of 256 threads);
+// every thread of the workgroup must call it (it contains a barrier)
+__device__ __forceinline__ void lstm_bwd_body(const int b, const int j, const bool active, const LstmBwdArgs& la) {
+  __shared__ float dq_s[kA];
+  float dh = 0.f, dc = 0.f;
+  const bool carry = la.have_next && b < la.nb_next;          // row b was active at step t+1
+  if (carry && active) {
+    float q = 0.f;
+    for (int c = 0; c < la.nlch; ++c) q += la.dqp[((long long)c * la.B + b) * kA + j];
+    dq_s[j] = q;
+    la.dq_all[((long long)b * la.T + (la.t + 1)) * kA + j] = q;
+  }
+  __syncthreads();
+  if (!active) return;
+  if (carry) {
+    float s = 0.f;
+#pragma unroll
+    for (int z = 0; z < kS_DX; ++z) s += (z < la.nslab_dx) ? la.slab_dx[((long long)z * la.nb_slab + b) * kXK + kE + kD + j] : 0.f;
+#pragma unroll
+    for (int c = 0; c < kNCH; ++c) s += la.pbeta[((long long)c * la.B + b) * kH + j];
+#pragma unroll 32
+    for (int a = 0; a < kA; ++a) s += dq_s[a] * la.W_h[a * kH + j];
+    dh = s;
+    dc = la.carry_dc[b * kH + j];
+  }
+  if (la.final_pass) {
+    la.dinit[b * 2 * kH + j] = dh;
+    la.dinit[b * 2 * kH + kH + j] = dc;
+    return;
+  }
+  const float dm = la.drop ? la.drop[((long long)b * la.T + la.t) * kH + j] : 1.0f;
+  dh += la.dHd[((long long)la.packed_off + b) * kH + j] * dm;
+  const float* ga = la.Gact + ((long long)b * la.T + la.t) * kG;
+  const float ig = ga[j], fg = ga[kH + j], gg = ga[2 * kH + j], og = ga[3 * kH + j];
+  const long long hc = ((long long)b * (la.T + 1) + la.t) * kH + j;
+  const float cprev = la.Call[hc], tc = tanhf(la.Call[hc + kH]);
+  const float dog = dh * tc;
+  dc += dh * og * (1.f - tc * tc);
+  la.carry_dc[b * kH + j] = dc * fg;
+  float* dg = la.dG + ((long long)b * la.T + la.t) * kG;
+  dg[j] = dc * gg * ig * (1.f - ig);
+  dg[kH + j] = dc * cprev * fg * (1.f - fg);
+  dg[2 * kH + j] = dc * ig * (1.f - gg * gg);
+  dg[3 * kH + j] = dog * og * (1.f - og);
+}
+#endif
+
+// several independent column sums in two launches; ws: 64 partial rows per job, back to back
+struct ColsumJob { const float* X; long long ld; int M, N, rs; float* out; float* part; };
+struct ColsumBatch { ColsumJob j[8]; };
+int colsum_batch(ColsumBatch& b, int njobs, float* ws, hipStream_t st);
+
+// embed_grad_kernel: dembed[token] = the sum of the rows (b, t), t < dec_len[b], of dXe [B*T][E] that fed the token
+// cap[b*cap_stride + t], in increasing (b, t) order; dembed zeroed by the caller.  One 64-bit ballot per 64 rows in LDS.
+inline bool embed_grad_rows_ok(long long rows) { return (rows + kE - 1) / kE * 2 * 8 <= 60 * 1024; }
+int launch_embed_grad(const float* dXe, const long long* cap, int cap_stride, const int* dec_len, int B, int T, int V,
+                      float* dembed, hipStream_t st);
+
 // Experiments build only (-DDIC_EXPERIMENTS): one launch for all T forward steps (soft attention, B <= 64); see experiments/decoder_persist.hip.  Expects F, P, h0/c0 (slot 0 of
 // Hall/Call), the embedding columns of Xall, WhT / WbT / WcatT, Gemb and the device copy of the lengths in the workspace.
 bool decoder_persist_eligible(int B, int T, int mode);

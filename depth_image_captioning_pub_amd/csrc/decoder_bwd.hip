@@ -17,8 +17,6 @@ __global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ X
 
 // Several independent column sums in two launches (the seven bias gradients after BPTT were 14 dependent ~5-us launches).
 // Per job the arithmetic is exactly colsum()'s: `rs` strided partial rows, then their sum in order.
-struct ColsumJob { const float* X; long long ld; int M, N, rs; float* out; float* part; };
-struct ColsumBatch { ColsumJob j[8]; };
 __global__ void __launch_bounds__(256) colsum_batch_kernel(const ColsumBatch b, int stage) {
   const ColsumJob job = b.j[blockIdx.z];
   const int n = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
@@ -38,7 +36,7 @@ __global__ void __launch_bounds__(256) colsum_batch_kernel(const ColsumBatch b, 
   }
 }
 
-static int colsum_batch(ColsumBatch& b, int njobs, float* ws, hipStream_t st) {
+int colsum_batch(ColsumBatch& b, int njobs, float* ws, hipStream_t st) {
   int maxn = 1, maxrs = 1;
   float* part = ws;
   for (int i = 0; i < njobs; ++i) {
@@ -72,60 +70,6 @@ static int colsum(const float* X, long long ld, int M, int N, float* out, float*
 //   assembled here from step t+1's products:  dX[:,h slot] + W_h^T dq + W_beta^T dgpre.
 //   final=1: only assemble the carry into dinit (gradient of h0 | c0) after step 0.
 // ------------------------------------------------------------------------------------------
-struct LstmBwdArgs {
-  int t, T, B, nb_next, have_next, final_pass, nlch;
-  const float* dHd; int packed_off; const float* drop;
-  const float* slab_dx; int nslab_dx, nb_slab; const float* dqp;
-  const float* pbeta; const float* W_h /*[A][H]*/;
-  const float* Gact; const float* Call; float* carry_dc;
-  float* dG; float* dq_all; float* dinit;
-};
-// body: thread j of row b; `active` = this thread takes part (the fused kernel runs it on the first kH of 256 threads);
-// every thread of the workgroup must call it (it contains a barrier)
-__device__ __forceinline__ void lstm_bwd_body(const int b, const int j, const bool active, const LstmBwdArgs& la) {
-  __shared__ float dq_s[kA];
-  float dh = 0.f, dc = 0.f;
-  const bool carry = la.have_next && b < la.nb_next;          // row b was active at step t+1
-  if (carry && active) {
-    float q = 0.f;
-    for (int c = 0; c < la.nlch; ++c) q += la.dqp[((long long)c * la.B + b) * kA + j];
-    dq_s[j] = q;
-    la.dq_all[((long long)b * la.T + (la.t + 1)) * kA + j] = q;
-  }
-  __syncthreads();
-  if (!active) return;
-  if (carry) {
-    float s = 0.f;
-#pragma unroll
-    for (int z = 0; z < kS_DX; ++z) s += (z < la.nslab_dx) ? la.slab_dx[((long long)z * la.nb_slab + b) * kXK + kE + kD + j] : 0.f;
-#pragma unroll
-    for (int c = 0; c < kNCH; ++c) s += la.pbeta[((long long)c * la.B + b) * kH + j];
-#pragma unroll 32
-    for (int a = 0; a < kA; ++a) s += dq_s[a] * la.W_h[a * kH + j];
-    dh = s;
-    dc = la.carry_dc[b * kH + j];
-  }
-  if (la.final_pass) {
-    la.dinit[b * 2 * kH + j] = dh;
-    la.dinit[b * 2 * kH + kH + j] = dc;
-    return;
-  }
-  const float dm = la.drop ? la.drop[((long long)b * la.T + la.t) * kH + j] : 1.0f;
-  dh += la.dHd[((long long)la.packed_off + b) * kH + j] * dm;
-  const float* ga = la.Gact + ((long long)b * la.T + la.t) * kG;
-  const float ig = ga[j], fg = ga[kH + j], gg = ga[2 * kH + j], og = ga[3 * kH + j];
-  const long long hc = ((long long)b * (la.T + 1) + la.t) * kH + j;
-  const float cprev = la.Call[hc], tc = tanhf(la.Call[hc + kH]);
-  const float dog = dh * tc;
-  dc += dh * og * (1.f - tc * tc);
-  la.carry_dc[b * kH + j] = dc * fg;
-  float* dg = la.dG + ((long long)b * la.T + la.t) * kG;
-  dg[j] = dc * gg * ig * (1.f - ig);
-  dg[kH + j] = dc * cprev * fg * (1.f - fg);
-  dg[2 * kH + j] = dc * ig * (1.f - gg * gg);
-  dg[3 * kH + j] = dog * og * (1.f - og);
-}
-
 __global__ void __launch_bounds__(kH) lstm_bwd_kernel(const LstmBwdArgs la) { lstm_bwd_body(blockIdx.x, threadIdx.x, true, la); }
 
 // ------------------------------------------------------------------------------------------
@@ -265,6 +209,14 @@ __global__ void __launch_bounds__(kE) embed_grad_kernel(const float* __restrict_
     }
   }
   dembed[(long long)tok * kE + e] = acc;
+}
+
+int launch_embed_grad(const float* dXe, const long long* cap, int cap_stride, const int* dec_len, int B, int T, int V,
+                      float* dembed, hipStream_t st) {
+  const size_t bal_bytes = (size_t)((B * T + kE - 1) / kE) * 2 * sizeof(unsigned long long);
+  hipLaunchKernelGGL(embed_grad_kernel, dim3(B * T), dim3(kE), bal_bytes, st, dXe, cap, cap_stride, dec_len, B, T, V, dembed);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -612,11 +564,8 @@ static int decoder_bwd_impl(const dic_decoder_weights* w, int V, const int64_t* 
     }
   }
   // embedding gradient: per-token sum of the per-row gradients in a fixed order
-  const size_t bal_bytes = (size_t)((B * T + kE - 1) / kE) * 2 * sizeof(unsigned long long);
-  DIC_REQUIRE(bal_bytes <= 60 * 1024, "decoder_bwd: B*T too large for the embedding-gradient kernel");
-  hipLaunchKernelGGL(embed_grad_kernel, dim3(B * T), dim3(kE), bal_bytes, st, ws.dXe,
-                     (const long long*)captions, cap_stride, d_len, B, T, V, g->embed);
-  DIC_LAUNCH_CHECK();
+  DIC_REQUIRE(embed_grad_rows_ok((long long)B * T), "decoder_bwd: B*T too large for the embedding-gradient kernel");
+  DIC_TRY(launch_embed_grad(ws.dXe, (const long long*)captions, cap_stride, d_len, B, T, V, g->embed, st));
 
   // ---- bias gradients: seven column sums in two launches ------------------------------------------
   {

@@ -64,3 +64,27 @@ def reduce_logprobs(logprobs: torch.Tensor, targets: torch.Tensor, weights: Opti
     live = targets >= 0
     denom = live.sum().to(rows.dtype) if weights is None else (weights * live.to(weights.dtype)).sum()
     return rows.sum() / denom
+
+
+def self_critical_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: torch.Tensor, baseline="others") -> torch.Tensor:
+    """Self-critical sequence-training loss over the log-probabilities of SAMPLED captions (what the decoders' caption_logprobs
+    returns: logprobs [B,S,T] or [B,T], 0 from each caption's length on, and lengths):
+        -(sum over tokens of (rewards - baseline)[..., None] * logprobs) / lengths.sum()
+    rewards: float [B,S] (or [B]), one per caption.  baseline: "others" - per caption the mean reward of the image's other S - 1
+    captions (needs S >= 2); a tensor broadcastable to the rewards, for example the reward of the greedy caption; or None.
+    Plain torch reductions over [B,S,T] values; no gradient flows into rewards or baseline."""
+    r = rewards.detach().to(logprobs.dtype)
+    if tuple(r.shape) != tuple(logprobs.shape[:-1]):
+        raise _lib.DicError(f"self_critical_loss: rewards must be {tuple(logprobs.shape[:-1])}, one per caption, got {tuple(r.shape)}")
+    if isinstance(baseline, str):
+        if baseline != "others":
+            raise _lib.DicError(f"self_critical_loss: baseline must be 'others', a tensor or None, got {baseline!r}")
+        if r.dim() != 2 or r.shape[1] < 2:
+            raise _lib.DicError("self_critical_loss: the 'others' baseline is the mean reward of the image's other captions and "
+                                f"needs rewards [B,S] with S >= 2, got {tuple(r.shape)}")
+        adv = r - (r.sum(1, keepdim=True) - r) / (r.shape[1] - 1)
+    elif baseline is None:
+        adv = r
+    else:
+        adv = r - torch.as_tensor(baseline, device=r.device).detach().to(r.dtype)
+    return -(adv.unsqueeze(-1) * logprobs).sum() / lengths.sum().to(logprobs.dtype)

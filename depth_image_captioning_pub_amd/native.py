@@ -701,6 +701,87 @@ def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat
     return logprobs, scores, lengths
 
 
+# the 15 decoder gradients dic_decoder_states_bwd writes (linear.* come from token_logprobs_bwd)
+STATES_GRAD_KEYS = tuple(k for k, _ in DECODER_FIELDS if not k.startswith("linear."))
+
+
+@dataclass
+class StatesTape:
+    """Everything dic_decoder_states_bwd needs from the matching forward call."""
+    workspace: torch.Tensor
+    weights: Dict[str, torch.Tensor]
+    vocab: int
+    B: int
+    S: int
+    T: int
+    id_start: int
+    id_end: int
+    captions: torch.Tensor
+    drop_mult: Optional[torch.Tensor]
+
+
+def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, depth_features: Optional[torch.Tensor],
+                           id_start: int, id_end: int, captions: torch.Tensor, drop_mult: Optional[torch.Tensor] = None):
+    """dic_decoder_states_fwd: the hidden states of given captions, with a tape for decoder_states_backward (semantics:
+    include/dic.h).  captions int64 [B,S,T] without '<start>', S <= 8 per image; drop_mult float32 [B*S,T,128] or None (eval).
+    Returns (hidden float32 [T,R,128] - 0 from each row's length on -, targets int64 [T,R] - -1 there -, lengths int32 [B,S],
+    tape), R = B*S, rows b*S + s."""
+    lib = _lib.load()
+    f_rgb = _dev_f32(features, "features")
+    f_dep = _dev_f32(depth_features, "depth_features") if depth_features is not None else None
+    cap = _dev_i64(captions, "captions")
+    B = f_rgb.shape[0]
+    if cap.dim() != 3 or cap.shape[0] != B:
+        raise _lib.DicError(f"decoder_states: captions must be [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+    if tuple(f_rgb.shape[1:]) != (L_CELLS, D_ENC) or (f_dep is not None and tuple(f_dep.shape) != tuple(f_rgb.shape)):
+        raise _lib.DicError(f"decoder_states: features (and depth features) must be [B,{L_CELLS},{D_ENC}], got {tuple(f_rgb.shape)}")
+    S, T = int(cap.shape[1]), int(cap.shape[2])
+    R = B * S
+    dm = None
+    if drop_mult is not None:
+        dm = _dev_f32(drop_mult, "drop_mult")
+        if tuple(dm.shape) != (R, T, D_HID):
+            raise _lib.DicError(f"decoder_states: drop_mult must be [B*S,T,{D_HID}] = [{R},{T},{D_HID}], got {tuple(dm.shape)}")
+    vocab = weights["linear.weight"].shape[0]
+    wp, keep = decoder_ptrs(weights)
+    lib.dic_decoder_states_workspace_bytes.restype = C.c_size_t
+    need = lib.dic_decoder_states_workspace_bytes(B, S, T, vocab)             # (0 for sizes the call below refuses with its text)
+    dev = f_rgb.device
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    rr, tt = max(R, 1), max(T, 1)
+    hidden = torch.empty((tt, rr, D_HID), dtype=torch.float32, device=dev)
+    targets = torch.empty((tt, rr), dtype=torch.int64, device=dev)
+    lengths = torch.empty((B, max(S, 1)), dtype=torch.int32, device=dev)
+    rc = lib.dic_decoder_states_fwd(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, C.c_longlong(int(id_start)),
+                                    C.c_longlong(int(id_end)), T, ptr(cap), ptr(dm), ptr(hidden), ptr(targets), ptr(lengths),
+                                    ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    check(rc, "dic_decoder_states_fwd")
+    tape = StatesTape(ws, {k: t for (k, _), t in zip(DECODER_FIELDS, keep)}, vocab, B, S, T, int(id_start), int(id_end), cap, dm)
+    return hidden, targets, lengths, tape
+
+
+def decoder_states_backward(tape: StatesTape, d_hidden: torch.Tensor, need_features: bool = True):
+    """dic_decoder_states_bwd: backward through time of decoder_states_forward.  d_hidden float32 [T,R,128] (rows behind a
+    caption's length are ignored).  Returns (grads: dict over the 15 keys STATES_GRAD_KEYS, d_features [B,196,2048] or None)."""
+    lib = _lib.load()
+    dh = _dev_f32(d_hidden, "d_hidden")
+    R = tape.B * tape.S
+    if tuple(dh.shape) != (tape.T, R, D_HID):
+        raise _lib.DicError(f"decoder_states: d_hidden must be [T,R,{D_HID}] = [{tape.T},{R},{D_HID}], got {tuple(dh.shape)}")
+    wp, keep = decoder_ptrs(tape.weights)
+    dev = dh.device
+    grads = {k: torch.empty_like(tape.weights[k]) for k in STATES_GRAD_KEYS}
+    gp = DecoderPtrs()
+    for key, field in DECODER_FIELDS:
+        setattr(gp, field, grads[key].data_ptr() if key in grads else None)
+    d_features = torch.empty((tape.B, L_CELLS, D_ENC), dtype=torch.float32, device=dev) if need_features else None
+    rc = lib.dic_decoder_states_bwd(C.byref(wp), tape.vocab, tape.B, tape.S, C.c_longlong(tape.id_start), C.c_longlong(tape.id_end),
+                                    tape.T, ptr(tape.captions), ptr(tape.drop_mult), ptr(dh), C.byref(gp), ptr(d_features),
+                                    ptr(tape.workspace), C.c_size_t(tape.workspace.numel()), stream_ptr())
+    check(rc, "dic_decoder_states_bwd")
+    return grads, d_features
+
+
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""

@@ -265,6 +265,45 @@ int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb
                       long long id_start, long long id_end, int max_length, const int64_t* captions, float* out_logprobs,
                       float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* hidden states of GIVEN captions with a tape, and the backward through time: the differentiable form of dic_decoder_score's
+ *   recurrence (soft attention, 196 cells), S captions per image that SHARE the image's F, P = W_z F + b_z and mean.  Composed with
+ *   dic_token_logprobs / dic_token_logprobs_bwd it makes the log-probabilities of dic_decoder_score trainable (self-critical
+ *   sequence training).  There is no reference implementation; this comment is the specification.
+ *   Forward.  Rows, inputs and lengths are those of dic_decoder_score: row r = b*S + s, R = B*S; captions int64 [B,S,T] on the
+ *     device, WITHOUT <start>; the input token of step t is id_start at t = 0 and captions[r,t-1] after that, clamped into the
+ *     vocabulary; length[r] = (index of the first id_end in captions[r,:]) + 1, or T, derived on the device; feat_depth nullable.
+ *     drop_mult (nullable = eval) float [R,T,128]: an explicit multiplier of the hidden state that leaves the recurrence, as in
+ *     dic_decoder_fwd (quirk Q6: the mask is an input); the carried h is never dropped.
+ *     out_hidden  float [T,R,128], time-major (the packed row of (t,r) is t*R + r): h_t of row r (x drop_mult[r,t,:]) for
+ *                 t < length[r], exactly 0 for t >= length[r].
+ *     out_targets int64 [T,R]: captions[r,t] clamped for t < length[r], -1 from the length on - the targets dic_token_logprobs takes.
+ *     out_lengths int [B,S].
+ *     The workspace keeps the tape: attention weights, contexts, gates, gate activations, cell states, Q, the LSTM input rows.
+ *   Backward.  Consumes the workspace the forward left; same captions and drop_mult.  d_hidden float [T,R,128] is the gradient of
+ *     out_hidden; its rows with t >= length[r] are ignored (selected to 0, never multiplied: any finite bytes there change
+ *     nothing).  Writes (does not accumulate) the 15 gradients of dic_decoder_grads other than out_w / out_b - those two pointers
+ *     are not read and may be NULL: dic_token_logprobs_bwd gives them.  d_features (nullable) float [B,196,2048]: the gradient
+ *     with respect to BOTH feature inputs, summed over the S rows of the image in ascending s; when NULL that work is not done.
+ *     Embedding rows of tokens never fed are 0.
+ *   Properties: every launch is enqueued on `stream`, nothing is copied to the host, nothing synchronises - the lengths never
+ *     reach the host.  No float atomics: every summation order is a function of (B, S, T) alone, so two calls return identical
+ *     bytes.  Forward row (b,s) depends only on image b and caption (b,s).  The workspace holds F, P and the mean once per image,
+ *     not once per row, and no array with a V dimension: its size does not depend on V at all (the gradient of the embedding
+ *     table goes through a [R,T,128] array of per-row gradients that is summed per token into the caller's g->embed).
+ *     (row, step) pairs with t >= length[r] contribute exactly nothing: the backward's per-row kernels return on them.
+ *   1 <= S <= 8, B, V > 0, 1 <= T <= 64, B*S*T <= 491 520 (the embedding-gradient kernel keeps one ballot bit per (row, step) in
+ *   60 KB of LDS), 0 <= id_start, id_end < V, no null pointer other than feat_depth, drop_mult, d_features, g->out_w and g->out_b,
+ *   a workspace of sufficient size: a violation returns a negative code and a dic_last_error() text that starts with
+ *   "decoder_states:", before anything is launched; the workspace query returns 0 for sizes the calls refuse.  DESIGN.md 5.12. */
+size_t dic_decoder_states_workspace_bytes(int B, int S, int T, int V);
+int dic_decoder_states_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                           long long id_start, long long id_end, int T, const int64_t* captions, const float* drop_mult,
+                           float* out_hidden, int64_t* out_targets, int* out_lengths, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, long long id_start, long long id_end, int T,
+                           const int64_t* captions, const float* drop_mult, const float* d_hidden, const dic_decoder_grads* g,
+                           float* d_features, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
  *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
  *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both

@@ -1,0 +1,315 @@
+"""GPU: dic_decoder_states_fwd / dic_decoder_states_bwd (through native.decoder_states_forward / _backward), composed with
+dic_token_logprobs / _bwd, and the layers above them (caption_logprobs, losses.self_critical_loss, scst.scst_step) against the fp64
+CPU restatement of tests/states_common.py.
+
+Bounds, never taken from the code under test: log-probabilities 4 x the restatement's own fp32-to-fp64 distance (the rule of
+tests/test_score_gpu.py); gradients the rule of tests/test_decoder_gpu.py::_assert_close at 1e-3 of the tensor's scale (absolute
+1e-6 for full_att.bias, whose exact gradient is 0).  Every comparison prints what it measured beside the restatement's fp32
+distance (run with -s); DESIGN.md 5.12 is where the figures of an MI355X run belong."""
+import functools
+
+import pytest
+import torch
+
+from depth_image_captioning_pub_amd import _lib, losses, native, synthetic as syn
+from depth_image_captioning_pub_amd.Captioning_models import scst
+from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.base_caption_models import (RNNDecoderWithHardAttention,
+                                                                                                     RNNDecoderWithSoftAttention)
+from depth_image_captioning_pub_amd.Captioning_models.Depth_caption_model.depth_models import CD_RNNDecoderWithSoftAttention
+from tests import states_common as stc
+from tests.test_decoder_gpu import _assert_close
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+LW, LB = "linear.weight", "linear.bias"
+
+
+def _dev(w):
+    return {k: v.to(DEV) for k, v in w.items()}
+
+
+def _bytes(t):
+    return t.detach().cpu().numpy().tobytes()
+
+
+def _forward(name, mult=None, fr=None, fd="case", caps=None):
+    w, fr0, fd0, s, e, caps0 = stc.case_data(name)
+    fr = fr0 if fr is None else fr
+    fd = fd0 if isinstance(fd, str) else fd
+    caps = caps0 if caps is None else caps
+    wd = _dev(w)
+    hidden, targets, lengths, tape = native.decoder_states_forward(wd, fr.to(DEV), fd.to(DEV) if fd is not None else None, s, e,
+                                                                   caps.to(DEV), mult)
+    T, R = targets.shape
+    lp, lse = native.token_logprobs(hidden.view(T * R, 128), wd[LW], wd[LB], targets.view(-1))
+    return dict(w=wd, hidden=hidden, targets=targets, lengths=lengths, tape=tape, lp=lp, lse=lse, T=T, R=R, shape=tuple(caps.shape))
+
+
+def _logprobs(f):
+    B, S, T = f["shape"]
+    return f["lp"].view(T, B, S).permute(1, 2, 0).contiguous()
+
+
+def _backward(name, f, g=None, poison=None, need_features=True):
+    """The C route behind a forward `f`: dic_token_logprobs_bwd, then dic_decoder_states_bwd -> ({17 gradients}, d_features) on
+    the CPU.  g: d loss / d logprobs [T*R] (default: the loss of states_common.loss_of); poison: a value written over every row
+    of d_hidden at or behind its caption's length."""
+    T, R = f["T"], f["R"]
+    if g is None:
+        adv = stc.advantage(name).to(DEV).view(1, R)
+        g = (-adv / f["lengths"].sum().float()).expand(T, R).contiguous().view(-1)
+    d_hidden, d_w, d_b = native.token_logprobs_bwd(f["hidden"].view(T * R, 128), f["w"][LW], f["w"][LB], f["targets"].view(-1),
+                                                   f["lse"], g)
+    d_hidden = d_hidden.view(T, R, 128)
+    dead = torch.arange(T, device=DEV).view(T, 1) >= f["lengths"].view(1, R)
+    assert bool((d_hidden[dead] == 0).all())
+    if poison is not None:
+        d_hidden = torch.where(dead.unsqueeze(-1), torch.full_like(d_hidden, poison), d_hidden)
+    grads, dfeat = native.decoder_states_backward(f["tape"], d_hidden, need_features)
+    torch.cuda.synchronize()
+    grads = {k: v.cpu() for k, v in grads.items()}
+    grads[LW], grads[LB] = d_w.cpu(), d_b.cpu()
+    return grads, (dfeat.cpu() if dfeat is not None else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _case_run(name):
+    f = _forward(name)
+    return f, _backward(name, f)
+
+
+def _check_forward(name, f, r64, lp_dist):
+    B, S, T = f["shape"]
+    lp = _logprobs(f).cpu()
+    lengths = f["lengths"].cpu()
+    assert f["hidden"].dtype == torch.float32 and tuple(f["hidden"].shape) == (T, B * S, 128)
+    assert f["targets"].dtype == torch.int64 and lengths.dtype == torch.int32 and tuple(lengths.shape) == (B, S)
+    assert torch.equal(lengths.long(), r64["lengths"])
+    dead = (torch.arange(T).view(T, 1) >= lengths.view(1, B * S))
+    assert bool((f["hidden"].cpu()[dead] == 0).all())                     # exactly 0 from the row's length on
+    assert bool((f["targets"].cpu()[dead] == -1).all()) and bool((f["targets"].cpu()[~dead] >= 0).all())
+    err, bound = float((lp.double() - r64["logprobs"]).abs().max()), 4.0 * lp_dist
+    print(f"states forward {name}: log-probability error {err:.3e} (bound {bound:.3e}); rows ended early "
+          f"{int((lengths < T).sum())}/{B * S}")
+    assert err <= bound
+    return lp
+
+
+def _check_gradients(name, got, r32, r64):
+    grads, dfeat = got
+    _, gdist, fdist = stc.distances(r32, r64)
+    rows = [(k, grads[k], r64["grads"][k], gdist[k]) for k in stc.GRAD_KEYS] + [("d_features", dfeat, r64["d_features"], fdist)]
+    failed = []
+    print(f"states backward {name}:  tensor | error | 1e-3 x scale | fp32 distance of the restatement")
+    for key, a, r, d in rows:
+        assert a.dtype == torch.float32 and a.shape == r.shape, key
+        err, scale = float((a.double() - r).abs().max()), float(r.abs().max())
+        print(f"  {key:32s} {err:.3e}  {1e-3 * scale:.3e}  {d:.3e}")
+        try:
+            _assert_close(key, a, r, 1e-3)
+        except AssertionError as ex:
+            failed.append(str(ex))
+    assert not failed, failed
+
+
+# ---- 1, 2: forward and gradients against fp64 ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", stc.CASES)
+def test_forward_matches_fp64(lib, name):
+    r32, r64 = stc.case_grads(name, False), stc.case_grads(name, True)
+    lp_dist = stc.distances(r32, r64)[0]
+    f, _ = _case_run(name)
+    lp = _check_forward(name, f, r64, lp_dist)
+    # eval mode: what dic_decoder_score reports for the same captions, each side within its bound of the same fp64 numbers
+    w, fr, fd, s, e, caps = stc.case_data(name)
+    sc_lp, _, sc_len = native.decoder_score(f["w"], fr.to(DEV), fd.to(DEV) if fd is not None else None, s, e, caps.to(DEV))
+    assert torch.equal(sc_len.cpu(), f["lengths"].cpu())
+    diff = float((sc_lp.cpu().double() - lp.double()).abs().max())
+    print(f"states forward {name}: |difference to dic_decoder_score| {diff:.3e} (bound {8.0 * lp_dist:.3e})")
+    assert diff <= 8.0 * lp_dist
+
+
+@pytest.mark.parametrize("name", stc.CASES)
+def test_gradients_match_fp64(lib, name):
+    _check_gradients(name, _case_run(name)[1], stc.case_grads(name, False), stc.case_grads(name, True))
+    emb = _case_run(name)[1][0]["embed.weight"]
+    w, _, _, s, _, caps = stc.case_data(name)
+    fed = torch.zeros(emb.shape[0], dtype=torch.bool)
+    fed[caps.clamp(0, emb.shape[0] - 1).reshape(-1)] = True
+    fed[s] = True
+    assert bool((emb[~fed] == 0).all())                                  # embedding rows of tokens never fed: exactly 0
+
+
+# ---- 3: dropout -----------------------------------------------------------------------------------------------------------------------
+def test_dropout_multiplier(lib):
+    name = "base_soft"
+    B, S, T = stc.case_data(name)[5].shape
+    mult = native.dropout_mask((B * S, T, 128), 0.5, 1234, 0, DEV)
+    m = mult.cpu()
+    assert set(m.unique().tolist()) == {0.0, 2.0}
+    r32, r64 = stc.grads_of(name, False, m), stc.grads_of(name, True, m)
+    f = _forward(name, mult)
+    _check_forward(name + " p=0.5", f, r64, stc.distances(r32, r64)[0])
+    _check_gradients(name + " p=0.5", _backward(name, f), r32, r64)
+    assert _bytes(f["hidden"]) != _bytes(_case_run(name)[0]["hidden"])
+
+
+# ---- 4: dead rows of d_hidden ---------------------------------------------------------------------------------------------------------
+def test_dead_rows_of_d_hidden_are_ignored(lib):
+    name = "b5_k8_v333"
+    f, (grads, dfeat) = _case_run(name)
+    assert int((f["lengths"] < f["T"]).sum()) == f["R"]                    # every row has dead steps
+    g2, df2 = _backward(name, f, poison=1e30)
+    for k in stc.GRAD_KEYS:
+        assert _bytes(grads[k]) == _bytes(g2[k]), k
+    assert _bytes(dfeat) == _bytes(df2)
+    assert all(bool(torch.isfinite(v).all()) for v in g2.values())
+
+
+# ---- 5: determinism and row independence ------------------------------------------------------------------------------------------------
+def test_two_calls_return_identical_bytes(lib):
+    for name in ("b5_k8_v333", "base_soft"):
+        f1, (g1, d1) = _case_run(name)
+        f2 = _forward(name)
+        g2, d2 = _backward(name, f2)
+        for k in ("hidden", "targets", "lengths", "lp"):
+            assert _bytes(f1[k]) == _bytes(f2[k]), (name, k)
+        for k in stc.GRAD_KEYS:
+            assert _bytes(g1[k]) == _bytes(g2[k]), (name, k)
+        assert _bytes(d1) == _bytes(d2), name
+
+
+def test_forward_rows_depend_on_their_own_image_and_caption_only(lib):
+    name = "b5_k8_v333"
+    w, fr, fd, _, _, caps = stc.case_data(name)
+    B, S, T = caps.shape
+    base = _case_run(name)[0]
+    keep_b, keep_s = [0, 3], [0, 5, 7]
+    fr2, fd2 = syn.features(B, 501), syn.features(B, 502, scale=0.5)
+    fr2[keep_b], fd2[keep_b] = fr[keep_b], fd[keep_b]
+    caps2 = torch.randint(0, w[LW].shape[0], caps.shape, generator=torch.Generator().manual_seed(9))
+    for b in keep_b:
+        caps2[b, keep_s] = caps[b, keep_s]
+    other = _forward(name, fr=fr2, fd=fd2, caps=caps2)
+    for b in keep_b:
+        for s in keep_s:
+            r = b * S + s
+            assert _bytes(base["hidden"][:, r].contiguous()) == _bytes(other["hidden"][:, r].contiguous()), (b, s)
+            assert _bytes(base["targets"][:, r].contiguous()) == _bytes(other["targets"][:, r].contiguous()), (b, s)
+    assert _bytes(base["hidden"]) != _bytes(other["hidden"])
+
+
+# ---- 6: autograd ------------------------------------------------------------------------------------------------------------------------
+def _decoder(name, cls=CD_RNNDecoderWithSoftAttention):
+    w = stc.case_data(name)[0]
+    dec = cls(128, 128, 2048, 128, w[LW].shape[0], 0.5)
+    dec.load_state_dict(w)
+    return dec.to(DEV)
+
+
+def test_caption_logprobs_autograd_leaves_the_c_routes_bytes(lib):
+    name = "b5_k8_v333"
+    w, fr, fd, s, e, caps = stc.case_data(name)
+    B, S, T = caps.shape
+    tok = {"<start>": s, "<end>": e}
+    dec = _decoder(name).eval()
+    feats, depth = fr.to(DEV).requires_grad_(True), fd.to(DEV).requires_grad_(True)
+    logprobs, lengths = dec.caption_logprobs(feats, depth, caps, tok)           # (a CPU tensor of captions: the shim moves it)
+    assert tuple(logprobs.shape) == (B, S, T) and logprobs.dtype == torch.float32 and logprobs.is_cuda
+    f = _case_run(name)[0]
+    assert _bytes(logprobs.contiguous()) == _bytes(_logprobs(f)) and _bytes(lengths) == _bytes(f["lengths"])
+    logprobs.retain_grad()
+    loss = losses.self_critical_loss(logprobs, lengths, stc.advantage(name).to(DEV), None)
+    ref_loss = float(stc.case_grads(name, True)["loss"])
+    assert abs(float(loss.detach()) - ref_loss) <= 1e-4 * max(1.0, abs(ref_loss))
+    loss.backward()
+    g = logprobs.grad.permute(2, 0, 1).contiguous().view(-1)                   # [B,S,T] -> [T,R]
+    grads, dfeat = _backward(name, f, g=g)
+    for k in stc.GRAD_KEYS:
+        p = dec
+        for part in k.split("."):
+            p = getattr(p, part)
+        assert p.grad is not None and _bytes(p.grad) == _bytes(grads[k]), k
+    assert _bytes(feats.grad) == _bytes(dfeat) and _bytes(depth.grad) == _bytes(dfeat)
+    # one caption per image, [B,T], with <start> in column 0
+    with_start = torch.cat((torch.full((B, 1), s, dtype=torch.int64), caps[:, 1]), 1)
+    lp1, ln1 = dec.caption_logprobs(fr.to(DEV), fd.to(DEV), with_start, tok, skip_start=True)
+    assert tuple(lp1.shape) == (B, T) and tuple(ln1.shape) == (B,) and torch.equal(ln1, f["lengths"][:, 1])
+    assert float((lp1 - logprobs.detach()[:, 1]).abs().max()) <= 1e-4          # (S = 1 and S = 8 block their sums alike row by row)
+
+
+def test_frozen_inputs_skip_their_kernels(lib, monkeypatch):
+    name = "base_soft"
+    w, fr, _, s, e, caps = stc.case_data(name)
+    tok = {"<start>": s, "<end>": e}
+    dec = _decoder(name, RNNDecoderWithSoftAttention).eval()
+    for p in dec.linear.parameters():
+        p.requires_grad_(False)
+    seen = {}
+    real_bwd, real_states = native.token_logprobs_bwd, native.decoder_states_backward
+
+    def spy_bwd(*a, **k):
+        seen["need"] = tuple(a[7] if len(a) > 7 else k["need"])
+        return real_bwd(*a, **k)
+
+    def spy_states(tape, d_hidden, need_features=True):
+        seen["need_features"] = need_features
+        return real_states(tape, d_hidden, need_features)
+
+    monkeypatch.setattr(native, "token_logprobs_bwd", spy_bwd)
+    monkeypatch.setattr(native, "decoder_states_backward", spy_states)
+    logprobs, lengths = dec.caption_logprobs(fr.to(DEV), caps.to(DEV), tok)       # frozen features, frozen linear
+    losses.self_critical_loss(logprobs, lengths, stc.advantage(name).to(DEV)).backward()
+    assert seen["need"] == (True, False, False) and seen["need_features"] is False
+    assert dec.linear.weight.grad is None and dec.linear.bias.grad is None and dec.embed.weight.grad is not None
+    feats = fr.to(DEV).requires_grad_(True)
+    logprobs, lengths = dec.caption_logprobs(feats, caps.to(DEV), tok)
+    losses.self_critical_loss(logprobs, lengths, stc.advantage(name).to(DEV)).backward()
+    assert seen["need_features"] is True and feats.grad is not None and float(feats.grad.abs().max()) > 0
+
+
+def test_train_mode_draws_the_dropout_multiplier_and_hard_attention_raises(lib):
+    name = "b5_k2"
+    w, fr, fd, s, e, caps = stc.case_data(name)
+    B, S, T = caps.shape
+    tok = {"<start>": s, "<end>": e}
+    dec = _decoder(name).train()
+    seed, offset = dec._rng_seed, dec._rng_offset
+    logprobs, _ = dec.caption_logprobs(fr.to(DEV), fd.to(DEV), caps.to(DEV), tok)
+    assert dec._rng_offset > offset
+    mult = native.dropout_mask((B * S, T, 128), 0.5, seed, offset, DEV)
+    assert _bytes(logprobs.detach().contiguous()) == _bytes(_logprobs(_forward(name, mult)))
+    assert _bytes(dec.eval().caption_logprobs(fr.to(DEV), fd.to(DEV), caps.to(DEV), tok)[0].detach().contiguous()) == _bytes(
+        _logprobs(_case_run(name)[0]))
+    hard = RNNDecoderWithHardAttention(128, 128, 2048, 128, 300, DEV)
+    with pytest.raises(_lib.DicError, match="soft-attention"):
+        hard.caption_logprobs(fr.to(DEV), caps.to(DEV), tok)
+
+
+# ---- 7: training smoke ------------------------------------------------------------------------------------------------------------------
+def test_scst_steps_raise_the_reward(lib):
+    """20 self-critical steps on b5_k2's inputs, S 4, T 6, Adam(lr 1e-2); reward = the share of even token ids among each caption's
+    tokens up to its length.  The fp64 restatement with torch.multinomial draws goes from 0.54 .. 0.62 over the first five steps to
+    0.98 .. 0.99 over the last five (four seeds): the condition below fails only if the gradient is wrong.  eval() mode, as
+    there: no dropout between the recurrence and the projection."""
+    name = "b5_k2"
+    w, fr, fd, s, e, _ = stc.case_data(name)
+    tok = {"<start>": s, "<end>": e}
+    dec = _decoder(name).eval()
+    opt = torch.optim.Adam(dec.parameters(), lr=1e-2)
+    feats, depth = fr.to(DEV), fd.to(DEV)
+
+    def reward(ids, lengths):
+        assert ids.is_cuda and lengths.is_cuda and tuple(ids.shape) == (5, 4, 6) and tuple(lengths.shape) == (5, 4)
+        live = torch.arange(ids.shape[-1], device=ids.device).view(1, 1, -1) < lengths.unsqueeze(-1)
+        return ((ids % 2 == 0) & live).sum(-1).float() / lengths.float()
+
+    means, loss_vals = [], []
+    for step in range(20):
+        loss, mean = scst.scst_step(dec, opt, feats, depth, tok, reward, n_samples=4, max_length=6, seed=100 + step)
+        means.append(mean)
+        loss_vals.append(loss)
+    means = [float(m) for m in means]
+    first, last = sum(means[:5]) / 5, sum(means[-5:]) / 5
+    print("scst mean reward per step:", " ".join(f"{m:.2f}" for m in means), f"| first five {first:.3f}, last five {last:.3f}")
+    assert all(torch.isfinite(l) for l in loss_vals)
+    assert first <= 0.70 and last >= 0.80
