@@ -5,8 +5,11 @@ One step is five device calls and no host round trip of the captions: dic_decode
 function scores them, dic_decoder_states_fwd / dic_token_logprobs give their log-probabilities with a tape, and backward()
 runs dic_token_logprobs_bwd and dic_decoder_states_bwd.
 
-Out of scope here: the engine's flat parameter buffers and fused train step, the data-parallel gradient exchange, and metric
-rewards (CIDEr needs pycocoevalcap and host strings) - reward_fn is the seam for them."""
+The usual reward is CIDEr-D against the batch's reference captions: cider.CiderD.reward_fn scores the sampled ids on the device
+in one more launch (dic_cider_d), so the step stays free of host round trips with a real metric too.
+
+Out of scope here: the engine's flat parameter buffers and fused train step and the data-parallel gradient exchange; other
+metric rewards (BLEU, METEOR, ROUGE) - reward_fn is the seam for them."""
 from __future__ import annotations
 
 from .. import losses

@@ -5,9 +5,10 @@ encoder, decoder.batch_sample  (depth_evaluation.py:146-165), then turn the toke
 (:167-176).  Every tensor operation runs in libdic_hip.so; the decode keeps the previous token on the device (the reference
 copies it to the host every step, depth_models.py:298-299).
 
-Out of scope here as in SURVEY.md section 2: the COCO dataset / annotation files and the pycocoevalcap scorers
-(BLEU / METEOR (Java) / ROUGE / CIDEr, evaluate_metrix.py) - `useData` must be "synthetic" (procedural images, a procedural
-vocabulary); no scores are computed, the hypotheses are returned and written next to the checkpoints."""
+Out of scope here as in SURVEY.md section 2: the COCO dataset / annotation files and the pycocoevalcap scorers BLEU / METEOR
+(Java) / ROUGE (evaluate_metrix.py) - `useData` must be "synthetic" (procedural images, a procedural vocabulary); the hypotheses
+are returned and written next to the checkpoints.  CIDEr (evaluate_metrix.py:31) is computed on request, on the device, over
+token ids against procedural reference captions (cider.CiderD)."""
 from __future__ import annotations
 
 import json
@@ -19,6 +20,7 @@ import torch
 
 from . import synthetic as syn
 from ._lib import DicError
+from .cider import CiderD
 from .Captioning_models import util
 from .Captioning_models.Base_caption_model.base_caption_models import CNNEncoder_Atten
 from .Captioning_models.config import ConfigTrain
@@ -52,7 +54,7 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
                       length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0):
+                      top_p: float = 1.0, seed: int = 0, cider: bool = False):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
@@ -60,7 +62,10 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     by score / length^length_penalty - instead of the reference's greedy batch_sample; 1 is the greedy loop itself.
     n_samples > 0 (soft attention only) ADDS to each result "samples", a list of `n_samples` caption strings per image drawn with
     decoder.stochastic_sample(temperature, top_k, top_p), and "sample_ids" np.int64 [N,n_samples,30]; batch b is seeded with
-    seed + b.  The hypotheses, the ids and the written file do not depend on it."""
+    seed + b.  The hypotheses, the ids and the written file do not depend on it.
+    cider=True ADDS "CIDEr": the mean CIDEr-D (evaluate_metrix.py:31; x10 as pycocoevalcap reports it) of the hypotheses against
+    synthetic.reference_captions(batch_size, vocab_size, seed=5000 + b) of batch b, five per image, scored on the device as decoded
+    strings are (count_end=False); the idf table is that of all the evaluated images' references.  Nothing else depends on it."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
@@ -99,12 +104,15 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
         decoder.load_state_dict(torch.load(f"{save_directory}/{f_dec}", weights_only=True))
         depth_encoder.load_state_dict(torch.load(f"{save_directory}/{f_denc}", weights_only=True))
         hypos_id, sample_ids = [], []
+        references = []
         for b in range(n_batches):
             raw = syn.raw_images(config.batch_size, seed=5000 + b).to(dev)
             imgs, imgs_for_dep = util.device_transforms(raw)
             depth_maps = dpt.depth_maps_for_training(imgs_for_dep)                          # :155-159
             depth_features = depth_encoder(depth_maps)                                      # :161
             feature = encoder(imgs)                                                         # :164
+            if cider:
+                references += syn.reference_captions(config.batch_size, config.vocab_size, seed=5000 + b)
             if int(beam_size) > 1:
                 hypos_id.append(decoder.beam_sample(feature, depth_features, word_to_id, beam_size=int(beam_size),
                                                     length_penalty=length_penalty))
@@ -121,8 +129,12 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             sample_ids = np.concatenate(sample_ids)
             results[key]["samples"] = [ids_to_captions(rows, id_to_word) for rows in sample_ids]
             results[key]["sample_ids"] = sample_ids
-        # depth_evaluation.py:178-184 scores the hypotheses with BLEU / METEOR / CIDEr (pycocoevalcap + Java): out of scope
+        # depth_evaluation.py:178-184 scores the hypotheses with BLEU / METEOR / ROUGE too (pycocoevalcap + Java): out of scope
         #  - the hypotheses are the product of this path.
+        if cider:
+            scorer = CiderD.from_references(references, config.vocab_size, word_to_id["<end>"], count_end=False, device=dev)
+            ref_ids, ref_counts = scorer.pack_references(references)
+            results[key]["CIDEr"] = float(scorer.corpus_score(torch.from_numpy(hypos_id).long().to(dev), ref_ids, ref_counts))
     with open(os.path.join(save_directory, f"{useData}_hypotheses.json"), "w") as f:
         json.dump({k: v["hypotheses"] for k, v in results.items()}, f)
     return results

@@ -782,6 +782,44 @@ def decoder_states_backward(tape: StatesTape, d_hidden: torch.Tensor, need_featu
     return grads, d_features
 
 
+def cider_d(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor, id_end: int, vocab: int,
+            idf_keys: Optional[torch.Tensor], idf_vals: Optional[torch.Tensor], idf_unseen: float, count_end: bool = True,
+            sigma: float = 6.0):
+    """dic_cider_d: CIDEr-D of hypotheses against their image's references over token ids, one launch, on the device (semantics:
+    include/dic.h).  hyp_ids int64 [B,T] (one per image) or [B,S,T]; ref_ids int64 [B,R,Tr], R <= 8; ref_counts int32 [B]: how many
+    of the R reference rows of each image count; idf_keys int64 [n_keys] ascending and idf_vals float32 [n_keys] (both None or
+    empty: every n-gram is unseen).  Returns float32 [B] or [B,S]."""
+    lib = _lib.load()
+    hyp, ref = _dev_i64(hyp_ids, "hyp_ids"), _dev_i64(ref_ids, "ref_ids")
+    squeeze = hyp.dim() == 2
+    if squeeze:
+        hyp = hyp.unsqueeze(1)
+    if hyp.dim() != 3 or ref.dim() != 3 or ref.shape[0] != hyp.shape[0]:
+        raise _lib.DicError(f"cider_d: hyp_ids must be [B,T] or [B,S,T] and ref_ids [B,R,Tr] with the same B, got "
+                            f"{tuple(hyp_ids.shape)} and {tuple(ref_ids.shape)}")
+    B, S, T = (int(v) for v in hyp.shape)
+    R, Tr = int(ref.shape[1]), int(ref.shape[2])
+    if not ref_counts.is_cuda or ref_counts.dtype != torch.int32 or tuple(ref_counts.shape) != (B,):
+        raise _lib.DicError(f"cider_d: ref_counts must be int32 [{B}] on the GPU, got {ref_counts.dtype} {tuple(ref_counts.shape)} on "
+                            f"{ref_counts.device}")
+    cnt = ref_counts if ref_counts.is_contiguous() else ref_counts.contiguous()
+    if (idf_keys is None) != (idf_vals is None):
+        raise _lib.DicError("cider_d: idf_keys and idf_vals come together")
+    keys = vals = None
+    n_keys = 0
+    if idf_keys is not None:
+        if idf_keys.dim() != 1 or tuple(idf_vals.shape) != tuple(idf_keys.shape):
+            raise _lib.DicError(f"cider_d: idf_keys and idf_vals must be [n_keys], got {tuple(idf_keys.shape)} and {tuple(idf_vals.shape)}")
+        n_keys = int(idf_keys.shape[0])
+        if n_keys > 0:                                                               # (an empty table travels as NULL pointers)
+            keys, vals = _dev_i64(idf_keys, "idf_keys"), _dev_f32(idf_vals, "idf_vals")
+    out = torch.empty((max(B, 1), max(S, 1)), dtype=torch.float32, device=hyp.device)
+    rc = lib.dic_cider_d(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, C.c_longlong(int(id_end)), int(bool(count_end)), int(vocab),
+                         ptr(keys), ptr(vals), C.c_longlong(n_keys), C.c_float(idf_unseen), C.c_float(sigma), ptr(out), stream_ptr())
+    check(rc, "dic_cider_d")
+    return out[:, 0] if squeeze else out
+
+
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""

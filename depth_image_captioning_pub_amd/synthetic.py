@@ -159,6 +159,19 @@ def captions_ragged(lengths: Sequence[int], vocab: int, seed: int = 123) -> Tupl
     return torch.from_numpy(c), lengths
 
 
+def reference_captions(n_images: int, vocab: int, seed: int = 123, n_refs: int = 5, min_len: int = 5,
+                       max_len: int = 15) -> List[List[List[int]]]:
+    """Per image `n_refs` reference captions as lists of ordinary word ids (no <start> / <end>), min_len..max_len words drawn with
+    Zipf weights (word i: 1 / (i + 1)) - frequent words recur across captions, as in a real corpus, so n-gram metrics are not 0."""
+    r = _rng(seed + 4000)
+    n_words = vocab - 4
+    p = 1.0 / np.arange(1, n_words + 1)
+    p /= p.sum()
+    lengths = r.integers(min_len, max_len + 1, size=(n_images, n_refs))
+    words = iter(np.split(r.choice(n_words, size=int(lengths.sum()), p=p), np.cumsum(lengths.reshape(-1))[:-1]))
+    return [[next(words).tolist() for _ in range(n_refs)] for _ in range(n_images)]
+
+
 def features(batch: int, seed: int, replicate: bool = True, scale: float = 1.0) -> torch.Tensor:
     """Non-negative annotation map [B,196,2048] shaped like an encoder output (post-ReLU);
     replicate=True makes each 2x2 block of the 14x14 grid identical (quirk Q3)."""

@@ -304,6 +304,41 @@ int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, lo
                            const int64_t* captions, const float* drop_mult, const float* d_hidden, const dic_decoder_grads* g,
                            float* d_features, void* workspace, size_t workspace_bytes, void* stream);
 
+/* CIDEr-D (Vedantam et al. 2015) of S hypotheses per image against the image's references, over token ids, on the device: the reward
+ *   of self-critical training and the metric `Cider()` of Captioning_models/evaluate_metrix.py:31 reports.  This comment is the
+ *   specification: it restates pycocoevalcap's cider_scorer.py (whose `Cider` is CIDEr-D: clipping and a Gaussian length penalty),
+ *   which is not vendored in the reference and not installed here.  Token ids are a bijection of the tokenised words, so the scores
+ *   are those of the strings for in-vocabulary captions.  All pointers are device pointers; the call is ONE launch enqueued on
+ *   `stream`: no workspace, no host copy, no synchronisation.
+ *   hyp_ids int64 [B,S,T], ref_ids int64 [B,R,Tr], ref_counts int [B], out_scores float [B,S].
+ *   Tokens of a caption (hypotheses and references alike): len = (index of the first id_end in the row) + (count_end ? 1 : 0), or the
+ *     row's width when it holds no id_end (the ids are compared as given, as dic_decoder_score does); the caption is positions
+ *     [0, len).  Ids outside [0, V) are clamped into it, as every token input is.  count_end = 1 scores <end> as a word (the
+ *     self-critical.pytorch convention: ending the sentence is rewarded); count_end = 0 is what an evaluation of decoded strings sees.
+ *   References: image b has references 0 .. min(max(ref_counts[b], 0), R) - 1 = R_b of them; with R_b = 0 its scores are exactly 0.
+ *   n-gram key, n = 1..4: (t_0 .. t_{n-1}) packs into the int64  sum_j (t_j + 1) << 16 j, the first token in the low field: hence
+ *     V <= 65535, no hashing, no collisions.  Keys are ordered as SIGNED int64 on both sides (torch.unique's order): an n-gram
+ *     whose fourth field is above 32767 is a negative key.
+ *   idf of a key: idf_vals[i] where idf_keys[i] == key (idf_keys ascending, binary search), idf_unseen otherwise.  The table
+ *     already holds log N - log max(1, df), computed in fp64 on the host and rounded once: the kernel takes no logarithm.
+ *     n_keys = 0: every key is unseen, and only then may the two table pointers be NULL.
+ *   Per caption c and order n, in fp32: g_c,n(key) = tf * idf(key), tf the occurrences of key in c; norm_c,n = sqrt(sum over the
+ *     distinct keys of g^2); L_c = max(len - 1, 0), the number of BIGRAMS.  That is pycocoevalcap's length - it adds the term
+ *     frequencies where len(ngram) - 1 == 1 - and the quirk is kept.
+ *   Similarity of hypothesis h to reference r: delta = L_h - L_r; val_n = sum over the distinct keys of h of min(g_h, g_r) * g_r
+ *     (g_r = 0 for a key r does not hold: the clipping); val_n is divided by norm_h,n * norm_r,n only when both are non-zero, then
+ *     multiplied by exp(-delta^2 / (2 sigma^2)).
+ *   out_scores[b,s] = 10 / (4 R_b) * sum_r sum_n val_n.
+ *   Properties: no float atomics; every summation order is a function of (T, Tr, R_b) alone; row (b,s) depends only on its own
+ *   hypothesis, image b's references and the table - never on B, on S or on the other rows - so a row scored alone returns the bytes
+ *   it returns inside a batch; two calls return identical bytes.
+ *   B, S >= 1, 1 <= T, Tr <= 64, 1 <= R <= 8, 1 <= V <= 65535, 0 <= id_end < V, n_keys >= 0, sigma finite and > 0, idf_unseen finite
+ *   and >= 0, no null pointer other than the table when n_keys == 0: a violation returns a negative code and a dic_last_error() text
+ *   that starts with "cider_d:", before any HIP call.  DESIGN.md 5.13. */
+int dic_cider_d(const int64_t* hyp_ids, int B, int S, int T, const int64_t* ref_ids, const int* ref_counts, int R, int Tr,
+                long long id_end, int count_end, int V, const int64_t* idf_keys, const float* idf_vals, long long n_keys,
+                float idf_unseen, float sigma, float* out_scores, void* stream);
+
 /* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
  *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
  *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both
