@@ -13,6 +13,7 @@ from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.base_ca
 from depth_image_captioning_pub_amd.Captioning_models.Depth_caption_model.depth_models import (
     CD_RNNDecoderWithHardAttention, CD_RNNDecoderWithSoftAttention, Depth_CNN_endoder)
 from oracle import captioning_oracle as orc
+from tests import decoder_parity_common as dpc
 from tests.helpers import check_packed, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -63,45 +64,76 @@ def test_hard_attention_module_rng_and_onehot(lib):
     _close("ctx", ctx2, c_ref, 1e-4)
 
 
-@pytest.mark.parametrize("hard", [False, True])
-def test_attention_modules_are_differentiable(lib, hard):
-    """Soft_Attention.forward / Hard_Attention.forward are ordinary autograd modules in the reference
-    (attention.py:81-95, 132-148): gradients w.r.t. the six parameters, encoder_out and decoder_hidden vs the oracle's
-    autograd, for a loss that uses both outputs."""
+def _attention_gradients(hard, B):
+    """Soft_Attention.forward / Hard_Attention.forward on the device, and the oracle's autograd in fp32 and in fp64, for a loss that
+    uses both outputs: ((ctx, alpha, {gradient name: tensor}) of the device, of fp32, of fp64)."""
     w = syn.decoder_weights(50, seed=15)
     aw = {k[len("attention."):]: v for k, v in w.items() if k.startswith("attention.")}
     att = (Hard_Attention if hard else Soft_Attention)(2048, 128, 128)
     att.load_state_dict(aw)
     att.to(DEV)
-    B = 3
     rng = np.random.Generator(np.random.PCG64(16))
     feats = syn.features(B, 17, replicate=False)
     h = torch.from_numpy(rng.standard_normal((B, 128)).astype(np.float32))
     gc = torch.from_numpy(rng.standard_normal((B, 2048)).astype(np.float32))
     ga = torch.from_numpy(rng.standard_normal((B, 196)).astype(np.float32))
     fd, hd = feats.to(DEV).requires_grad_(True), h.to(DEV).requires_grad_(True)
-    wr = {k: v.clone().requires_grad_(True) for k, v in w.items()}
-    fr, hr = feats.clone().requires_grad_(True), h.clone().requires_grad_(True)
+    temp = torch.tensor(0.7)
     if hard:
-        temp = torch.tensor(0.7)
         torch.manual_seed(79)
         ctx, alpha = att(fd, hd, DEV, temp)
         torch.manual_seed(79)
-        c_ref, a_ref = orc.hard_attention_train(wr, fr, hr, torch.rand(B, 196), temp)
+        u = torch.rand(B, 196)                                   # the draw the module made
     else:
         ctx, alpha = att(fd, hd)
-        c_ref, a_ref = orc.soft_attention(wr, fr, hr)
     ((ctx * gc.to(DEV)).sum() + (alpha * ga.to(DEV)).sum()).backward()
-    ((c_ref * gc).sum() + (a_ref * ga).sum()).backward()
+    out = [(ctx, alpha, dict({k: p.grad for k, p in att.named_parameters()}, **{"d encoder_out": fd.grad, "d decoder_hidden": hd.grad}))]
+    for dt in (torch.float32, torch.float64):
+        wr = {k: v.clone().to(dt).requires_grad_(True) for k, v in w.items() if k.startswith("attention.")}
+        fr, hr = feats.clone().to(dt).requires_grad_(True), h.clone().to(dt).requires_grad_(True)
+        if hard:
+            c_ref, a_ref = orc.hard_attention_train(wr, fr, hr, u.to(dt), temp.to(dt))
+        else:
+            c_ref, a_ref = orc.soft_attention(wr, fr, hr)
+        ((c_ref * gc.to(dt)).sum() + (a_ref * ga.to(dt)).sum()).backward()
+        out.append((c_ref.detach(), a_ref.detach(), dict({k[len("attention."):]: v.grad for k, v in wr.items()},
+                                                         **{"d encoder_out": fr.grad, "d decoder_hidden": hr.grad})))
+    return out
+
+
+def _check_attention_gradients(hard, B):
+    (ctx, alpha, got), (c_ref, a_ref, g32), (_, _, g64) = _attention_gradients(hard, B)
     _close("ctx", ctx, c_ref, 1e-4)
     _close("alpha", alpha, a_ref, 1e-4)
-    _close("d encoder_out", fd.grad, fr.grad, 1e-3)
-    _close("d decoder_hidden", hd.grad, hr.grad, 1e-3)
-    for k, p in att.named_parameters():
+    _close("d encoder_out", got["d encoder_out"], g32["d encoder_out"], 1e-3)
+    _close("d decoder_hidden", got["d decoder_hidden"], g32["d decoder_hidden"], 1e-3)
+    for k in g32:
         if k == "full_att.bias":
-            _close("grad " + k, p.grad, wr["attention." + k].grad, 0.0, atol=1e-5)      # exactly zero true gradient (Q10)
-        else:
-            _close("grad " + k, p.grad, wr["attention." + k].grad, 1e-3)
+            if B == 3:
+                _close("grad " + k, got[k], g32[k], 0.0, atol=1e-5)      # exactly zero true gradient (Q10)
+        elif not k.startswith("d "):
+            _close("grad " + k, got[k], g32[k], 1e-3)
+    # beside the 1e-3 bar against fp32: fp64 as the reference, 4 x the oracle's pooled fp32-to-fp64 distance x the tensor's scale.
+    # full_att.bias holds rounding noise only, on both sides, and the noise grows with the rows and with |F . d ctx| (about 30 for this
+    # loss): held to 4 x the fp32 oracle's own noise (the rule of operators_common.bound on this tensor alone), at least the 1e-5 above
+    noise32 = float((g32["full_att.bias"].double() - g64["full_att.bias"]).abs().max())
+    assert float(g64["full_att.bias"].abs().max()) < 1e-10
+    dpc.check_pooled(f"attention module hard={hard} B={B}", got, g32, g64, zero_keys=("full_att.bias",), zero_atol=max(1e-5, 4.0 * noise32))
+
+
+@pytest.mark.parametrize("hard", [False, True])
+def test_attention_modules_are_differentiable(lib, hard):
+    """Soft_Attention.forward / Hard_Attention.forward are ordinary autograd modules in the reference
+    (attention.py:81-95, 132-148): gradients w.r.t. the six parameters, encoder_out and decoder_hidden vs the oracle's
+    autograd, for a loss that uses both outputs."""
+    _check_attention_gradients(hard, 3)
+
+
+@pytest.mark.parametrize("B", [1, 9])
+@pytest.mark.parametrize("hard", [False, True])
+def test_attention_modules_are_differentiable_at_one_row_and_nine(lib, hard, B):
+    """The same at B = 1 and at B = 9 (one row past a group of eight)."""
+    _check_attention_gradients(hard, B)
 
 
 def test_base_main_cli_smoke(lib, tmp_path, monkeypatch):

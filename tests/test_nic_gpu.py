@@ -1,17 +1,28 @@
 """GPU parity of the NIC / Show-and-Tell path (through the C ABI) against the CPU restatement (tests/nic_common.py) and the golden
 vectors captured from the reference's NIC_RNNDecoder.  Tolerances are the project's own for the attention decoder
-(tests/test_decoder_gpu.py): logits 1e-4 of their scale, loss within 1e-4, each gradient 1e-3 of its tensor's max; token-id
+(tests/test_decoder_gpu.py): logits 1e-4 of their scale, loss within 1e-4, each gradient 1e-3 of its tensor's max and, beside
+it, 4 x the restatement's pooled fp32-to-fp64 distance x the tensor's scale (tests/decoder_parity_common.py::pooled_bounds); token-id
 argmax identical on the golden cases and on every decidable row (tests/nic_common.py) at full size."""
 import numpy as np
 import pytest
 import torch
 
 from depth_image_captioning_pub_amd import native, synthetic as syn
+from tests import decoder_parity_common as dpc
 from tests import nic_common as nc
 from tests.helpers import GOLDEN_THREADS, check_packed, load_golden, torch_threads
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+
+# A factor above the rule's 4, with its cause.  dic_nic_bwd forms d lstm.weight_ih_l0 = dG0^T X as ONE product over the
+# K = n_packed rows, i.e. one fp32 fma chain of n_packed terms per element (exact-fp32 MFMA, no split-K); torch's autograd adds up one
+# product per step, chains of B terms.  At the full size (n_packed 1344, B 64) the chain alone measures 1.5e-6 of the scale on the
+# restatement's own fp32 operands (numpy, one fma per row in row order) against 4.6e-7 for the per-step sums, the restatement's r32:
+# a different, equally valid summation order.  The rounding of a chain grows like sqrt(K): sqrt(1344 / 64) = 4.6 times the per-step
+# sums', which would put the factor at 18; 16 is the ceiling for such a cause.
+CHAIN_FACTORS = {"lstm.weight_ih_l0": 16.0}
 
 
 def _assert_close(name, got, ref, tol):
@@ -27,13 +38,15 @@ def _to_dev(d):
     return {k: v.to(DEV) for k, v in d.items()}
 
 
-def _reference(name):
-    """fp64 restatement of a case with torch autograd: logits, loss, pooled, features and the 13 gradients."""
+def _reference(name, dbl=True):
+    """fp64 (or fp32) restatement of a case with torch autograd: logits, loss, pooled, features and the 13 gradients."""
     w, hw, fmap, caps, lens, drop = nc.case_inputs(name)
-    wd = {k: v.double().requires_grad_(True) for k, v in w.items()}
-    hd = {k: v.double().requires_grad_(True) for k, v in hw.items()}
+    dt = torch.float64 if dbl else torch.float32
+    wd = {k: v.clone().to(dt).requires_grad_(True) for k, v in w.items()}          # (clone: the inputs are cached)
+    hd = {k: v.clone().to(dt).requires_grad_(True) for k, v in hw.items()}
+    drop = drop.to(dt) if drop is not None else None
     with torch_threads(GOLDEN_THREADS):
-        pooled, feats = nc.head(hd, fmap.double())
+        pooled, feats = nc.head(hd, fmap.to(dt))
         logits, bsz = nc.nic_forward(wd, feats, caps, lens, drop)
         loss = nc.nic_loss(logits, caps, lens)
         loss.backward()
@@ -72,6 +85,9 @@ def test_forward_loss_backward_against_the_restatement(lib, name):
     assert len(ref["grads"]) == 13
     for k, r in ref["grads"].items():
         _assert_close("grad." + k, got["grads"][k], r, 1e-3)
+    # beside the 1e-3 bar: 4 x the restatement's pooled fp32-to-fp64 distance (tests/decoder_parity_common.py)
+    dpc.check_pooled(f"nic backward {name}", got["grads"], _reference(name, False)["grads"], ref["grads"], zero_keys=(),
+                     factors=CHAIN_FACTORS)
     _, ok, eps = nc.case_decidable(name)
     same = got["logits"].argmax(1).cpu() == ref["logits"].argmax(1)
     assert bool(same[ok].all()), f"{int((~same[ok]).sum())} decidable rows differ"

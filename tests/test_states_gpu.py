@@ -4,7 +4,8 @@ CPU restatement of tests/states_common.py.
 
 Bounds, never taken from the code under test: log-probabilities 4 x the restatement's own fp32-to-fp64 distance (the rule of
 tests/test_score_gpu.py); gradients the rule of tests/test_decoder_gpu.py::_assert_close at 1e-3 of the tensor's scale (absolute
-1e-6 for full_att.bias, whose exact gradient is 0).  Every comparison prints what it measured beside the restatement's fp32
+1e-6 for full_att.bias, whose exact gradient is 0) and, beside it, 4 x the restatement's pooled fp32-to-fp64 distance x the tensor's
+scale (tests/decoder_parity_common.py::pooled_bounds).  Every comparison prints what it measured beside the restatement's fp32
 distance (run with -s); DESIGN.md 5.12 is where the figures of an MI355X run belong."""
 import functools
 
@@ -16,6 +17,7 @@ from depth_image_captioning_pub_amd.Captioning_models import scst
 from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.base_caption_models import (RNNDecoderWithHardAttention,
                                                                                                      RNNDecoderWithSoftAttention)
 from depth_image_captioning_pub_amd.Captioning_models.Depth_caption_model.depth_models import CD_RNNDecoderWithSoftAttention
+from tests import decoder_parity_common as dpc
 from tests import states_common as stc
 from tests.test_decoder_gpu import _assert_close
 
@@ -110,6 +112,9 @@ def _check_gradients(name, got, r32, r64):
         except AssertionError as ex:
             failed.append(str(ex))
     assert not failed, failed
+    # beside the 1e-3 bar: 4 x the restatement's pooled fp32-to-fp64 distance (tests/decoder_parity_common.py)
+    dpc.check_pooled(f"states backward {name}", dict(grads, d_features=dfeat), dict(r32["grads"], d_features=r32["d_features"]),
+                     dict(r64["grads"], d_features=r64["d_features"]))
 
 
 # ---- 1, 2: forward and gradients against fp64 ---------------------------------------------------------------------------------------
