@@ -10,6 +10,7 @@
 #include "conv.h"
 #include "gemm_epilogue.h"
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <cstdlib>
 
@@ -2585,13 +2586,14 @@ int conv_dgrad_s1_bf3(const unsigned short* const dy_planes[3], const ConvDesc& 
 // The plan of one route's contraction without its operands (dic_debug_bf3_plan, api.hip): DIC_OK, or 1 when the route does not take the
 // shape.  route: 0 = planes (conv_fwd_bf3), 1 = on-the-fly 1x1 (conv1x1_fwd_bf3_bn, M = B * H * W), 2 = on-the-fly 3x3 (conv3x3_fwd_bf3_bn),
 // 3 = weight gradient (conv_wgrad_bf3), 4 = stem (conv_stem_bf3; B, H, W, CO); flags: 1 = residual, 2 = fp32 copy, 4 = BatchNorm of the
-// residual, 8 = bias, 16 = no BatchNorm statistics.  The plan reads only whether a pointer is there, so `t` stands for every one.
+// residual, 8 = bias, 16 = no BatchNorm statistics, 32 = no tail workspace (route 0: what dic_linear_* passes, Bf3Work{}).  The plan reads
+// only whether a pointer is there, so `t` stands for every one.
 int bf3_plan_route(int route, int fmt, const ConvDesc& d, int flags, int splitk, int tail_ws_slabs, const char** kernel, int out[6]) {
   static float t[1];
   unsigned short* const u = reinterpret_cast<unsigned short*>(t), * const pl3[3] = {u, u, fmt ? nullptr : u};
   float* const stats = (flags & 16) ? nullptr : t, * const rbn = (flags & 4) ? t : nullptr;
   Bf3Params p{};
-  Bf3Work w{route == 4 ? nullptr : t, tail_ws_slabs};
+  Bf3Work w{(route == 4 || (route == 0 && (flags & 32))) ? nullptr : t, tail_ws_slabs};
   if (route == 0) p = conv_fwd_bf3_params(pl3, d, pl3, t, stats, (flags & 8) ? t : nullptr, ACT_NONE, fmt, 1.0f);
   else if (route == 1 && conv1x1_bn_bf3_shape_ok(d.M(), d.C))
     p = conv1x1_bn_bf3_params(t, t, t, (flags & 1) ? t : nullptr, 1, (flags & 2) ? t : nullptr, d.M(), d.C, pl3, d.CO, t, stats, fmt, 1.0f, nullptr, rbn, rbn);
@@ -2690,15 +2692,48 @@ static int linear_bf3(int M, int N, int K, const uint16_t* const x_planes[], con
   if (fmt) { p.fmt = 1; p.ep.alpha = out_scale; }
   return launch_bf3(p, Bf3Work{}, (hipStream_t)stream);
 }
+/* Argument checks of the four entry points below, before anything is derived from the arguments (ConvDesc::OH() divides by the
+ * stride) and before the first HIP call.  nplanes: 3 (bf16x3) or 2 (f16x2). */
+static int linear_bf3_check(const char* who, int M, int N, int K, const uint16_t* const x_planes[], const uint16_t* const w_planes[], int nplanes,
+                            int act, const float* C, long long ldc, float out_scale) {
+  DIC_REQUIRE(x_planes && w_planes && C, "%s: null pointer (x_planes, w_planes, C)", who);
+  for (int i = 0; i < nplanes; ++i) DIC_REQUIRE(x_planes[i] && w_planes[i], "%s: null plane %d of %d", who, i, nplanes);
+  DIC_REQUIRE(M > 0 && N > 0 && K > 0, "%s: M=%d, N=%d, K=%d must be positive", who, M, N, K);
+  DIC_REQUIRE(K % 32 == 0, "%s: K=%d must be a multiple of 32 (K %% 32)", who, K);
+  DIC_REQUIRE(ldc >= N, "%s: ldc=%lld is below N=%d", who, ldc, N);
+  DIC_REQUIRE(act >= ACT_NONE && act <= ACT_GELU, "%s: act=%d is not one of 0 none, 1 ReLU, 2 sigmoid, 3 GELU", who, act);
+  DIC_REQUIRE(out_scale > 0.f && std::isfinite(out_scale), "%s: out_scale must be positive and finite", who);
+  DIC_REQUIRE((long long)M * N <= 0x7fffffffll, "%s: M * N = %lld output elements exceed int", who, (long long)M * N);
+  return DIC_OK;
+}
+static int conv2d_bf3_check(const char* who, const uint16_t* const x_planes[], int B, int H, int W, int Cin, const uint16_t* const w_planes[],
+                            int nplanes, int CO, int KH, int KW, int stride, int pad, int act, const float* y, float out_scale) {
+  DIC_REQUIRE(x_planes && w_planes && y, "%s: null pointer (x_planes, w_planes, y_nhwc)", who);
+  for (int i = 0; i < nplanes; ++i) DIC_REQUIRE(x_planes[i] && w_planes[i], "%s: null plane %d of %d", who, i, nplanes);
+  DIC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && CO > 0 && KH > 0 && KW > 0, "%s: B=%d, H=%d, W=%d, C=%d, CO=%d, KH=%d, KW=%d must be positive",
+              who, B, H, W, Cin, CO, KH, KW);
+  DIC_REQUIRE(Cin % 32 == 0, "%s: C=%d must be a multiple of 32 (C %% 32)", who, Cin);
+  DIC_REQUIRE((long long)KH * KW <= 32, "%s: KH * KW = %lld taps, at most 32", who, (long long)KH * KW);
+  DIC_REQUIRE(stride >= 1, "%s: stride=%d must be at least 1", who, stride);
+  DIC_REQUIRE(pad >= 0, "%s: pad=%d must not be negative", who, pad);
+  DIC_REQUIRE(act >= ACT_NONE && act <= ACT_GELU, "%s: act=%d is not one of 0 none, 1 ReLU, 2 sigmoid, 3 GELU", who, act);
+  DIC_REQUIRE(out_scale > 0.f && std::isfinite(out_scale), "%s: out_scale must be positive and finite", who);
+  const long long hp = (long long)H + 2ll * pad, wp = (long long)W + 2ll * pad;
+  DIC_REQUIRE(hp >= KH && wp >= KW, "%s: the %dx%d kernel is larger than the padded %lldx%lld map (empty output)", who, KH, KW, hp, wp);
+  const long long rows = (long long)B * ((hp - KH) / stride + 1) * ((wp - KW) / stride + 1);
+  DIC_REQUIRE(hp <= 0x7fffffffll && wp <= 0x7fffffffll && rows <= 0x7fffffffll && (long long)KH * KW * Cin <= 0x7fffffffll,
+              "%s: B * OH * OW = %lld output pixels (or the padded map, or KH * KW * C) exceed int", who, rows);
+  return DIC_OK;
+}
 int dic_linear_bf16x3(int M, int N, int K, const uint16_t* const x_planes[3], const uint16_t* const w_planes[3], const float* bias,
                       int act, int accumulate, float* C, long long ldc, void* stream) {
-  DIC_REQUIRE(x_planes && w_planes && C && M > 0 && N > 0 && K > 0 && K % 32 == 0, "linear_bf16x3: bad arguments (K %% 32)");
+  DIC_TRY(linear_bf3_check("linear_bf16x3", M, N, K, x_planes, w_planes, 3, act, C, ldc, 1.0f));
   return linear_bf3(M, N, K, x_planes, w_planes, bias, act, accumulate, C, ldc, 0, 1.0f, stream);
 }
 int dic_conv2d_bf16x3(const uint16_t* const x_planes[3], int B, int H, int W, int Cin, const uint16_t* const w_planes[3],
                       const float* bias, int CO, int KH, int KW, int stride, int pad, int act, float* y_nhwc, float* tail_ws,
                       void* stream) {
-  DIC_REQUIRE(x_planes && w_planes && y_nhwc && Cin % 32 == 0, "conv2d_bf16x3: bad arguments (C %% 32)");
+  DIC_TRY(conv2d_bf3_check("conv2d_bf16x3", x_planes, B, H, W, Cin, w_planes, 3, CO, KH, KW, stride, pad, act, y_nhwc, 1.0f));
   ConvDesc d{B, H, W, Cin, CO, KH, KW, stride, pad, 0};
   return conv_fwd_bf3(x_planes, d, w_planes, y_nhwc, nullptr, nullptr, tail_ws, (hipStream_t)stream, bias, nullptr, nullptr, act);
 }
@@ -2706,13 +2741,13 @@ int dic_conv2d_bf16x3(const uint16_t* const x_planes[3], int B, int H, int W, in
 /* the same two on the f16x2 operand format (planes from dic_split_f16x2_paired; out_scale = 1 / (scale of x * scale of W)) */
 int dic_linear_f16x2(int M, int N, int K, const uint16_t* const x_planes[2], const uint16_t* const w_planes[2], const float* bias,
                      int act, int accumulate, float* C, long long ldc, float out_scale, void* stream) {
-  DIC_REQUIRE(x_planes && w_planes && C && M > 0 && N > 0 && K > 0 && K % 32 == 0 && out_scale > 0.f, "linear_f16x2: bad arguments (K %% 32)");
+  DIC_TRY(linear_bf3_check("linear_f16x2", M, N, K, x_planes, w_planes, 2, act, C, ldc, out_scale));
   return linear_bf3(M, N, K, x_planes, w_planes, bias, act, accumulate, C, ldc, 1, out_scale, stream);
 }
 int dic_conv2d_f16x2(const uint16_t* const x_planes[2], int B, int H, int W, int Cin, const uint16_t* const w_planes[2],
                      const float* bias, int CO, int KH, int KW, int stride, int pad, int act, float* y_nhwc, float* tail_ws,
                      float out_scale, void* stream) {
-  DIC_REQUIRE(x_planes && w_planes && y_nhwc && Cin % 32 == 0 && out_scale > 0.f, "conv2d_f16x2: bad arguments (C %% 32)");
+  DIC_TRY(conv2d_bf3_check("conv2d_f16x2", x_planes, B, H, W, Cin, w_planes, 2, CO, KH, KW, stride, pad, act, y_nhwc, out_scale));
   ConvDesc d{B, H, W, Cin, CO, KH, KW, stride, pad, 0};
   const unsigned short* xp[3] = {x_planes[0], x_planes[1], nullptr};
   const unsigned short* wp[3] = {w_planes[0], w_planes[1], nullptr};

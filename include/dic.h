@@ -630,7 +630,11 @@ int dic_gemm_bf16x3_paired(int M, int N, int K, const uint16_t* a_hi, const uint
  *   y[B,OH,OW,CO] = act(conv(x NHWC, w OHWI) + bias) - the residual conv units, fusion-block and head convolutions
  *                                                  (blocks.py:231-341, dpt_depth.py:58-107), C % 32 == 0.
  * Operands are paired planes (dic_split_bf16x3_paired of x viewed as [rows][K] resp. [B*H*W][C], of W as [N][K] resp.
- * [CO][KH*KW*C]); act: 0 none, 1 ReLU, 2 sigmoid, 3 GELU; tail_ws (nullable): kGemmTailWsBytes of scratch as for dic_conv2d_fwd. */
+ * [CO][KH*KW*C]); act: 0 none, 1 ReLU, 2 sigmoid, 3 GELU; tail_ws (nullable): kGemmTailWsBytes of scratch as for dic_conv2d_fwd.
+ * Order of the epilogue: bias, then the activation, then (accumulate) the old value of C is added.
+ * Limits, checked before the first HIP call (non-zero return, dic_last_error() says which): every plane pointer (3 resp. 2), C / y_nhwc
+ * non-null; M, N, K resp. B, H, W, C, CO, KH, KW > 0; K % 32 == 0 resp. C % 32 == 0; KH * KW <= 32; stride >= 1; pad >= 0; the kernel no
+ * larger than the padded map (OH, OW >= 1); ldc >= N; act in 0..3; out_scale positive and finite; M * N resp. B * OH * OW within int. */
 int dic_linear_bf16x3(int M, int N, int K, const uint16_t* const x_planes[3], const uint16_t* const w_planes[3], const float* bias,
                       int act, int accumulate, float* C, long long ldc, void* stream);
 int dic_conv2d_bf16x3(const uint16_t* const x_planes[3], int B, int H, int W, int C, const uint16_t* const w_planes[3],
