@@ -1,11 +1,17 @@
-// Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy, beam-search and sampling decode.
+// Show-Attend-and-Tell decoder (soft + Gumbel "hard" attention): forward, BPTT backward, greedy, beam-search and sampling decode,
+// scoring of given captions and their hidden states with a tape.
 // One translation unit per route, each with its kernels, host orchestration and C ABI entry points; this header declares only
 // what more than one of them uses:
-//   decoder.hip         what the routes share: workspace carving, set-up, the attention step and LSTM cell kernels + launchers
+//   decoder.hip         what the routes share: workspace carving, set-up, the attention step and LSTM cell kernels + launchers,
+//                       the refusals the S-rows-per-image routes word alike
 //   decoder_fwd.hip     teacher-forced forward, stand-alone attention forward
-//   decoder_bwd.hip     BPTT backward, stand-alone attention backward
-//   decoder_decode.hip  greedy, beam-search and sampling decode (the selection kernels it shares with the NIC beam search: beam.h /
-//                       beam.hip; the kernel that draws a token from a row of logits: sample.h / sample.hip)
+//   decoder_bwd.hip     BPTT backward and its tail (bias / weight gradients, dP W_z), stand-alone attention backward
+//   decoder_decode.hip  greedy decode; beam search, sampling and the scoring of given captions over one row workspace (RowWs) and
+//                       one step head (launch_row_step).  The selection kernels shared with the NIC beam search: beam.h / beam.hip;
+//                       the kernel that draws a token from a row of logits: sample.h / sample.hip; the fused projection +
+//                       log-sum-exp of the scoring route: score.h / score.hip
+//   decoder_states.hip  hidden states of given captions with a tape and their backward through time, S captions per image that
+//                       share the image's F, P and mean (the tail of its backward is decoder_bwd.hip's)
 #pragma once
 #include "dic.h"
 #include "gemm.h"
@@ -50,6 +56,12 @@ struct DecoderWs : SetupBufs {
 };
 
 DecoderWs decoder_carve(void* ws, size_t ws_bytes, int B, int T, int V, int N, bool* overflow);
+
+// Refusals that the routes with S rows per image word alike; `route` is the message prefix ("decoder_beam", ...).  Each route
+// calls them at the place of its own order of checks, so the refusal that wins when several arguments are bad stays the route's.
+int check_row_sizes(const char* route, int B, int V, int max_length);
+int check_token_ids(const char* route, int V, long long id_start, long long id_end);
+int workspace_too_small(const char* route, size_t have, size_t need);      // sets the message, returns DIC_ERR_WORKSPACE
 
 // runs STMT with a compile-time cell count L_ (196 = reference layout, 49 = compact)
 #define DIC_CELLS_SWITCH(CELLS, STMT)   \
@@ -114,6 +126,32 @@ __device__ __forceinline__ RowChunk attn_step_row() {
   return {(lin & 7) + 8 * (lin >> 6), (lin >> 3) & 7};
 }
 __device__ __forceinline__ long long clamp_token(long long id, int V) { return id < 0 ? 0 : (id >= V ? V - 1 : id); }
+// Start of a route with several rows per image, thread j < kH: the image's h0 / c0, which the init_linear GEMM wrote at element
+// `src` of H / C, to n rows of the image: elements dst + i*ld, i < n.
+__device__ __forceinline__ void broadcast_state(float* __restrict__ H, float* __restrict__ C, long long src, long long dst,
+                                                long long ld, int n, int j) {
+  const float h = H[src + j], c = C[src + j];
+  for (int i = 0; i < n; ++i) {
+    H[dst + i * ld + j] = h;
+    C[dst + i * ld + j] = c;
+  }
+}
+// One given caption cap[T] -> tok[t * tok_ld] the input of every step (<start>, then the caption shifted by one, unclamped) and
+// target[t * target_ld] the caption clamped into the vocabulary, -1 from the row's length on.  Returns the length: the index of
+// the first id_end + 1, or T.
+__device__ __forceinline__ int parse_caption(const long long* __restrict__ cap, int T, int V, long long id_start, long long id_end,
+                                             long long* __restrict__ tok, long long tok_ld, long long* __restrict__ target,
+                                             long long target_ld) {
+  int n = T;
+  tok[0] = id_start;
+  for (int t = 0; t < T; ++t) {
+    const long long id = cap[t];
+    target[t * target_ld] = t < n ? clamp_token(id, V) : -1;
+    if (t + 1 < T) tok[(t + 1) * tok_ld] = id;
+    if (t < n && id == id_end) n = t + 1;
+  }
+  return n;
+}
 #endif
 
 // ---- parts of the BPTT backward (decoder_bwd.hip) that the shared-feature backward (decoder_states.hip) uses as well ----
@@ -178,6 +216,19 @@ __device__ __forceinline__ void lstm_bwd_body(const int b, const int j, const bo
 struct ColsumJob { const float* X; long long ld; int M, N, rs; float* out; float* part; };
 struct ColsumBatch { ColsumJob j[8]; };
 int colsum_batch(ColsumBatch& b, int njobs, float* ws, hipStream_t st);
+
+// Tail of BPTT, once the step loop has filled the per-step gradients: the seven bias gradients (one colsum_batch), the five
+// weight-gradient products (one grouped launch) and b_hh = b_ih.  rows: B*T (teacher-forced) or R*T (shared features) rows of
+// dG / dgpre / dq / Xall; acc_rows: rows of dwf_acc / dbf_acc; dP [B*cells][A] and dinit [B][2H] are per image, as F and mean.
+// gemm_ws holds the split-K partials of dW_q and dW_z side by side: 8 * kA * (kD + kH) floats.
+struct BpttTail {
+  int rows, acc_rows, B, cells;
+  const float *dP, *dinit, *dG, *dgpre, *dq, *dwf_acc, *dbf_acc, *Xall, *F, *mean;
+  float *colsum_ws, *gemm_ws;
+};
+int launch_bptt_tail(const BpttTail& a, const dic_decoder_grads* g, hipStream_t st);
+// d_features [rows][D] += dP [rows][A] W_z, rows = B*cells; WzT: kA*kD floats of workspace for W_z^T
+int launch_dP_Wz(const float* W_z, float* WzT, const float* dP, int rows, float* d_features, hipStream_t st);
 
 // embed_grad_kernel: dembed[token] = the sum of the rows (b, t), t < dec_len[b], of dXe [B*T][E] that fed the token
 // cap[b*cap_stride + t], in increasing (b, t) order; dembed zeroed by the caller.  One 64-bit ballot per 64 rows in LDS.

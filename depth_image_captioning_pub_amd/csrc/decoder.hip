@@ -80,6 +80,22 @@ DecoderWs decoder_carve(void* ws, size_t ws_bytes, int B, int T, int V, int N, b
   return w;
 }
 
+int check_row_sizes(const char* route, int B, int V, int max_length) {
+  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "%s: bad sizes (B=%d, V=%d, max_length=%d)", route, B, V, max_length);
+  return DIC_OK;
+}
+
+int check_token_ids(const char* route, int V, long long id_start, long long id_end) {
+  DIC_REQUIRE(id_start >= 0 && id_start < V, "%s: id_start=%lld is outside the vocabulary [0, %d)", route, id_start, V);
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "%s: id_end=%lld is outside the vocabulary [0, %d)", route, id_end, V);
+  return DIC_OK;
+}
+
+int workspace_too_small(const char* route, size_t have, size_t need) {
+  set_last_error("%s: workspace too small (%zu < %zu)", route, have, need);
+  return DIC_ERR_WORKSPACE;
+}
+
 // small utility kernels
 // out[c*R + r] = in[r*C + c]
 __global__ void __launch_bounds__(256) transpose_kernel(const float* __restrict__ in, float* __restrict__ out,

@@ -466,6 +466,47 @@ __global__ void __launch_bounds__(256) fold_dalphas_kernel(const float* __restri
   dc[i] = 0.25f * ((r[0] + r[1]) + (r[14] + r[15]));
 }
 
+int launch_bptt_tail(const BpttTail& a, const dic_decoder_grads* g, hipStream_t st) {
+  // ---- bias gradients: seven column sums in two launches ------------------------------------------
+  ColsumBatch cb{};
+  cb.j[0] = ColsumJob{a.dG, kG, a.rows, kG, 0, g->b_ih, nullptr};
+  cb.j[1] = ColsumJob{a.dgpre, kD, a.rows, kD, 0, g->fbeta_b, nullptr};
+  cb.j[2] = ColsumJob{a.dq, kA, a.rows, kA, 0, g->dec_att_b, nullptr};
+  cb.j[3] = ColsumJob{a.dwf_acc, kA, a.acc_rows, kA, 0, g->full_att_w, nullptr};
+  cb.j[4] = ColsumJob{a.dbf_acc, 1, a.acc_rows, 1, 0, g->full_att_b, nullptr};
+  cb.j[5] = ColsumJob{a.dP, kA, a.B * a.cells, kA, 0, g->enc_att_b, nullptr};
+  cb.j[6] = ColsumJob{a.dinit, 2 * kH, a.B, 2 * kH, 0, g->init_b, nullptr};
+  DIC_TRY(colsum_batch(cb, 7, a.colsum_ws, st));
+  // ---- batched weight gradients ---------------------------------------------------------------
+  const float* Hprev = a.Xall + kE + kD;                     // h_{t-1} rows, ld = kXK
+  // Five independent products with K-major operands, one launch (gemm_launch_group_colk; until round 4 five launches + three
+  // split-K reduces, 0.26 ms of the main stream per step):
+  //   [dW_ih | dW_hh] = dG^T [X | h_prev]     f_beta: dgpre^T h_prev     decoder_att: dq^T h_prev     encoder_att: dP^T F
+  //   init_linear: dinit^T mean
+  GemmParams gp[5] = {};
+  auto set = [&](int i, int M, int N, int K, GemmOperand A, GemmOperand Bop, GemmEpilogue ep, int splitk, float* wsp) {
+    gp[i].M = M; gp[i].N = N; gp[i].K = K; gp[i].A = A; gp[i].B = Bop; gp[i].ep = ep; gp[i].splitk = splitk; gp[i].ws = wsp;
+  };
+  GemmEpilogue ep = ep_store(g->w_ih, kE + kD);
+  ep.C2 = g->w_hh; ep.ldc2 = kH; ep.nsplit = kE + kD;
+  set(0, kG, kXK, a.rows, op_colk(a.dG, kG), op_colk(a.Xall, kXK), ep, 1, nullptr);
+  set(1, kD, kH, a.rows, op_colk(a.dgpre, kD), op_colk(Hprev, kXK), ep_store(g->fbeta_w, kH), 1, nullptr);
+  set(2, kA, kH, a.rows, op_colk(a.dq, kA), op_colk(Hprev, kXK), ep_store(g->dec_att_w, kH), 8, a.gemm_ws);
+  set(3, kA, kD, a.B * a.cells, op_colk(a.dP, kA), op_colk(a.F, kD), ep_store(g->enc_att_w, kD), 8, a.gemm_ws + (size_t)8 * kA * kH);
+  set(4, 2 * kH, kD, a.B, op_colk(a.dinit, 2 * kH), op_colk(a.mean, kD), ep_store(g->init_w, kD), 1, nullptr);
+  DIC_TRY(gemm_launch_group_colk(gp, 5, st));
+  DIC_CHECK_HIP(hipMemcpyAsync(g->b_hh, g->b_ih, sizeof(float) * kG, hipMemcpyDeviceToDevice, st));
+  return DIC_OK;
+}
+
+int launch_dP_Wz(const float* W_z, float* WzT, const float* dP, int rows, float* d_features, hipStream_t st) {
+  GemmEpilogue ep = ep_store(d_features, kD);
+  ep.accumulate = 1;
+  // dF += dP W_z: W_z^T ([D][A], K-contiguous rows) keeps this 6.6-GFLOP product on the LDS-DMA kernel
+  DIC_TRY(launch_transpose(W_z, WzT, kA, kD, st));
+  return gemm(rows, kD, kA, op_rowk(dP, kA), op_rowk(WzT, kA), ep, st);
+}
+
 }  // namespace dic
 
 using namespace dic;
@@ -567,39 +608,8 @@ static int decoder_bwd_impl(const dic_decoder_weights* w, int V, const int64_t* 
   DIC_REQUIRE(embed_grad_rows_ok((long long)B * T), "decoder_bwd: B*T too large for the embedding-gradient kernel");
   DIC_TRY(launch_embed_grad(ws.dXe, (const long long*)captions, cap_stride, d_len, B, T, V, g->embed, st));
 
-  // ---- bias gradients: seven column sums in two launches ------------------------------------------
-  {
-    ColsumBatch cb{};
-    cb.j[0] = ColsumJob{ws.dG, kG, (int)BT, kG, 0, g->b_ih, nullptr};
-    cb.j[1] = ColsumJob{ws.dgpre, kD, (int)BT, kD, 0, g->fbeta_b, nullptr};
-    cb.j[2] = ColsumJob{ws.dq, kA, (int)BT, kA, 0, g->dec_att_b, nullptr};
-    cb.j[3] = ColsumJob{ws.dwf_acc, kA, nlch * B, kA, 0, g->full_att_w, nullptr};
-    cb.j[4] = ColsumJob{ws.dbf_acc, 1, nlch * B, 1, 0, g->full_att_b, nullptr};
-    cb.j[5] = ColsumJob{ws.dPacc, kA, B * cells, kA, 0, g->enc_att_b, nullptr};
-    cb.j[6] = ColsumJob{ws.dinit, 2 * kH, B, 2 * kH, 0, g->init_b, nullptr};
-    DIC_TRY(colsum_batch(cb, 7, cs, st));
-  }
-  // ---- batched weight gradients ---------------------------------------------------------------
-  const float* Hprev = ws.Xall + kE + kD;                     // h_{t-1} rows, ld = kXK
-  // Five independent products with K-major operands, one launch (gemm_launch_group_colk; until round 4 five launches + three
-  // split-K reduces, 0.26 ms of the main stream per step):
-  //   [dW_ih | dW_hh] = dG^T [X | h_prev]     f_beta: dgpre^T h_prev     decoder_att: dq^T h_prev     encoder_att: dP^T F
-  //   init_linear: dinit^T mean
-  {
-    GemmParams gp[5] = {};
-    auto set = [&](int i, int M, int N, int K, GemmOperand A, GemmOperand Bop, GemmEpilogue ep, int splitk, float* wsp) {
-      gp[i].M = M; gp[i].N = N; gp[i].K = K; gp[i].A = A; gp[i].B = Bop; gp[i].ep = ep; gp[i].splitk = splitk; gp[i].ws = wsp;
-    };
-    GemmEpilogue ep = ep_store(g->w_ih, kE + kD);
-    ep.C2 = g->w_hh; ep.ldc2 = kH; ep.nsplit = kE + kD;
-    set(0, kG, kXK, (int)BT, op_colk(ws.dG, kG), op_colk(ws.Xall, kXK), ep, 1, nullptr);
-    set(1, kD, kH, (int)BT, op_colk(ws.dgpre, kD), op_colk(Hprev, kXK), ep_store(g->fbeta_w, kH), 1, nullptr);
-    set(2, kA, kH, (int)BT, op_colk(ws.dq, kA), op_colk(Hprev, kXK), ep_store(g->dec_att_w, kH), 8, ws.gemm_ws);
-    set(3, kA, kD, B * cells, op_colk(ws.dPacc, kA), op_colk(ws.F, kD), ep_store(g->enc_att_w, kD), 8, ws.gemm_ws + (size_t)8 * kA * kH);
-    set(4, 2 * kH, kD, B, op_colk(ws.dinit, 2 * kH), op_colk(ws.mean, kD), ep_store(g->init_w, kD), 1, nullptr);
-    DIC_TRY(gemm_launch_group_colk(gp, 5, st));
-    DIC_CHECK_HIP(hipMemcpyAsync(g->b_hh, g->b_ih, sizeof(float) * kG, hipMemcpyDeviceToDevice, st));
-  }
+  DIC_TRY(launch_bptt_tail(BpttTail{(int)BT, nlch * B, B, cells, ws.dPacc, ws.dinit, ws.dG, ws.dgpre, ws.dq, ws.dwf_acc, ws.dbf_acc,
+                                    ws.Xall, ws.F, ws.mean, cs, ws.gemm_ws}, g, st));
   DIC_TRY(gemm(B, kD, 2 * kH, op_rowk(ws.dinit, 2 * kH), op_colk(w->init_w, kD), ep_store(ws.dmean, kD), st, 8,
                ws.gemm_ws, 64));
   // ---- gradient w.r.t. the fused feature map (same for F_rgb and F_depth: F = F_rgb + F_depth) ----
@@ -612,11 +622,7 @@ static int decoder_bwd_impl(const dic_decoder_weights* w, int V, const int64_t* 
                                                  st, alphas, ws.dctx, ws.dmean, T, d_len, d_features);)
     }
     DIC_LAUNCH_CHECK();
-    GemmEpilogue ep = ep_store(d_features, kD);
-    ep.accumulate = 1;
-    // dF += dP W_z: W_z^T ([D][A], K-contiguous rows) keeps this 6.6-GFLOP product on the LDS-DMA kernel
-    DIC_TRY(launch_transpose(w->enc_att_w, ws.WzT, kA, kD, st));
-    DIC_TRY(gemm(B * cells, kD, kA, op_rowk(ws.dPacc, kA), op_rowk(ws.WzT, kA), ep, st));
+    DIC_TRY(launch_dP_Wz(w->enc_att_w, ws.WzT, ws.dPacc, B * cells, d_features, st));
   }
   return DIC_OK;
 }

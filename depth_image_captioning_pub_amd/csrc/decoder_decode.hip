@@ -1,5 +1,7 @@
 // Decoding on the device: greedy (dic_decoder_greedy), beam search (dic_decoder_beam), sampling (dic_decoder_sample) and the
-// scoring of given captions (dic_decoder_score).
+// scoring of given captions (dic_decoder_score).  The last three keep S rows per image that share the image's F, P and mean:
+// their workspaces begin with one RowWs (row_carve), their start kernels call broadcast_state (and parse_caption) of decoder.h,
+// and every step begins with launch_row_step; what follows the LSTM cell - vocabulary GEMM, selection, hand-over - is the route's.
 #include "beam.h"
 #include "sample.h"
 #include "score.h"
@@ -306,11 +308,7 @@ __global__ void __launch_bounds__(kH) beam_init_kernel(int KB, long long id_star
                                                         float* __restrict__ Cst) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const long long row0 = (long long)b * KB;
-  const float h = Hst[(row0 * 2 + 1) * kH + tid], c = Cst[(row0 * 2 + 1) * kH + tid];
-  for (int k = 0; k < KB; ++k) {
-    Hst[(row0 + k) * 2 * kH + tid] = h;
-    Cst[(row0 + k) * 2 * kH + tid] = c;
-  }
+  broadcast_state(Hst, Cst, (row0 * 2 + 1) * kH, row0 * 2 * kH, 2 * kH, KB, tid);
   if (tid < KB) {
     score[row0 + tid] = tid == 0 ? 0.f : -INFINITY;
     fin[row0 + tid] = 0;
@@ -330,11 +328,7 @@ __global__ void __launch_bounds__(kH) sample_init_kernel(int S, long long id_sta
                                                           float* __restrict__ Hst, float* __restrict__ Cst) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const long long row0 = (long long)b * S;
-  const float h = Hst[(row0 * 2 + 1) * kH + tid], c = Cst[(row0 * 2 + 1) * kH + tid];
-  for (int s = 0; s < S; ++s) {
-    Hst[(row0 + s) * 2 * kH + tid] = h;
-    Cst[(row0 + s) * 2 * kH + tid] = c;
-  }
+  broadcast_state(Hst, Cst, (row0 * 2 + 1) * kH, row0 * 2 * kH, 2 * kH, S, tid);
   if (tid < S) {
     fin[row0 + tid] = 0;
     length[row0 + tid] = 0;
@@ -368,23 +362,10 @@ __global__ void __launch_bounds__(kH) score_init_kernel(int S, int T, int V, lon
                                                          float* __restrict__ Hst, float* __restrict__ Cst) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const long long row0 = (long long)b * S, R = (long long)gridDim.x * S;
-  const float h = Hst[(row0 * 2 + 1) * kH + tid], c = Cst[(row0 * 2 + 1) * kH + tid];
-  for (int s = 0; s < S; ++s) {
-    Hst[(row0 + s) * 2 * kH + tid] = h;
-    Cst[(row0 + s) * 2 * kH + tid] = c;
-  }
+  broadcast_state(Hst, Cst, (row0 * 2 + 1) * kH, row0 * 2 * kH, 2 * kH, S, tid);
   if (tid < S) {
     const long long r = row0 + tid;
-    const long long* cap = captions + r * T;
-    int n = T;
-    tok_in[r] = id_start;
-    for (int t = 0; t < T; ++t) {
-      const long long id = cap[t];
-      target[(long long)t * R + r] = t < n ? clamp_token(id, V) : -1;
-      if (t + 1 < T) tok_in[(long long)(t + 1) * R + r] = id;
-      if (t < n && id == id_end) n = t + 1;
-    }
-    length[r] = n;
+    length[r] = parse_caption(captions + r * T, T, V, id_start, id_end, tok_in + r, R, target + r, R);
   }
 }
 
@@ -455,10 +436,49 @@ int dic_decoder_greedy(const dic_decoder_weights* w, int V, const float* feat_rg
   return DIC_OK;
 }
 
+// ---- what beam search, sampling and scoring share: S rows per image, rows b*S + s ---------------------------------------------
+namespace {
+// the leading part of the three workspaces (no WcatT): the set-up buffers and the per-row state of one step
+struct RowWs : SetupBufs {
+  float *Hst, *Cst, *X, *slab, *Gact;
+};
+
+void row_carve(Carver& c, RowWs& w, int B, size_t R) {
+  w.F = c.take<float>((size_t)B * kL * kD);
+  w.P = c.take<float>((size_t)B * kL * kA);
+  w.mean = c.take<float>((size_t)B * kD);
+  w.Wcat = c.take<float>((size_t)kG * kXK);
+  w.bcat = c.take<float>(kG);
+  w.WhT = c.take<float>((size_t)kH * kA);
+  w.WbT = c.take<float>((size_t)kH * kD);
+  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
+  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
+  w.Hst = c.take<float>(R * 2 * kH);
+  w.Cst = c.take<float>(R * 2 * kH);
+  w.X = c.take<float>(R * kXK);
+  w.slab = c.take<float>((size_t)kS_LSTM * R * kG);
+  w.Gact = c.take<float>(R * kG);
+}
+
+// Head of a step over the R = B*S rows: beam_attn_kernel<S> (input token of row r: tok[r]; attention weights to alpha_t when
+// not null) -> gate GEMM slabs -> lstm_fwd_kernel.  The state arrays are lstm_fwd_kernel's Hall / Call at T = 1, t = 0: c from
+// slot 0, h' / c' into slot 1; h' also goes to packed row packed_off + r of h_out (its "dropped" output, no dropout).
+int launch_row_step(const RowWs& ws, const dic_decoder_weights* w, int V, int B, int S, const long long* tok, float* alpha_t,
+                    float* h_out, int packed_off, hipStream_t st) {
+  const int R = B * S;
+  DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P, ws.Hst, tok,
+                                        w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b, ws.WbT, w->fbeta_b,
+                                        alpha_t, ws.X, B);)
+  DIC_LAUNCH_CHECK();
+  DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
+  return launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, h_out, kS_LSTM, R, packed_off}, 0, 1, st);
+}
+}  // namespace
+
 // ---- beam search ------------------------------------------------------------------------------------------------------------
 namespace {
-struct BeamWs : SetupBufs {      // (no WcatT)
-  float *Hst, *Cst, *X, *slab, *Gact, *Hdrop, *logits, *cand_val, *score;
+struct BeamWs : RowWs {
+  float *Hdrop, *logits, *cand_val, *score;
   float* alpha_hist;
   int *cand_tok, *fin, *length, *tok_hist, *bp_hist, *path;
   long long* prev;
@@ -469,20 +489,7 @@ BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overf
   Carver c(p, bytes);
   BeamWs w{};
   const size_t BK = (size_t)B * K;
-  w.F = c.take<float>((size_t)B * kL * kD);
-  w.P = c.take<float>((size_t)B * kL * kA);
-  w.mean = c.take<float>((size_t)B * kD);
-  w.Wcat = c.take<float>((size_t)kG * kXK);
-  w.bcat = c.take<float>(kG);
-  w.WhT = c.take<float>((size_t)kH * kA);
-  w.WbT = c.take<float>((size_t)kH * kD);
-  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
-  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
-  w.Hst = c.take<float>(BK * 2 * kH);
-  w.Cst = c.take<float>(BK * 2 * kH);
-  w.X = c.take<float>(BK * kXK);
-  w.slab = c.take<float>((size_t)kS_LSTM * BK * kG);
-  w.Gact = c.take<float>(BK * kG);
+  row_carve(c, w, B, BK);
   w.Hdrop = c.take<float>(BK * kH);
   w.logits = c.take<float>(BK * V);
   w.cand_val = c.take<float>(BK * K);
@@ -499,7 +506,6 @@ BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overf
   if (overflow) *overflow = c.overflow;
   return w;
 }
-
 
 bool beam_sizes_ok(int B, int K, int max_length, int V) {
   return B > 0 && K >= 1 && K <= kBeamMax && max_length >= 1 && V >= K;
@@ -519,19 +525,15 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
   hipStream_t st = (hipStream_t)stream;
   // every argument check comes before the first HIP call
   DIC_REQUIRE(K >= 1 && K <= kBeamMax, "decoder_beam: beam width K=%d is outside 1..%d", K, kBeamMax);
-  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "decoder_beam: bad sizes (B=%d, V=%d, max_length=%d)", B, V, max_length);
+  DIC_TRY(check_row_sizes("decoder_beam", B, V, max_length));
   DIC_REQUIRE(V >= K, "decoder_beam: vocabulary V=%d is smaller than the beam width K=%d", V, K);
-  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_beam: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
-  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_beam: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_TRY(check_token_ids("decoder_beam", V, id_start, id_end));
   DIC_REQUIRE(length_penalty >= 0.f, "decoder_beam: length_penalty=%g must be >= 0 (NaN is refused too)", (double)length_penalty);
   DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace, "decoder_beam: null pointer");
   const int T = max_length, BK = B * K;
   bool ov = false;
   BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov);
-  if (ov) {
-    set_last_error("decoder_beam: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
-    return DIC_ERR_WORKSPACE;
-  }
+  if (ov) return workspace_too_small("decoder_beam", workspace_bytes, ws.bytes);
   // per image, never per beam.  [h0 | c0] -> slot 1 of beam 0, then copied to the KB beams
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)K * 2 * kH, false}, st));
   hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
@@ -539,13 +541,7 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
   DIC_LAUNCH_CHECK();
   for (int t = 0; t < T; ++t) {
     float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * BK * kL : nullptr;
-    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P,
-                                          ws.Hst, ws.prev, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b,
-                                          ws.WbT, w->fbeta_b, alpha_t, ws.X, B);)
-    DIC_LAUNCH_CHECK();
-    DIC_TRY(gemm_slabs(BK, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
-    // the state arrays are lstm_fwd_kernel's Hall / Call at T = 1, t = 0: c from slot 0, h' / c' into slot 1
-    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.Hdrop, kS_LSTM, BK, 0}, 0, 1, st));
+    DIC_TRY(launch_row_step(ws, w, V, B, K, ws.prev, alpha_t, ws.Hdrop, 0, st));
     DIC_TRY(gemm(BK, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
     DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st));
     DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
@@ -558,8 +554,8 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------
 namespace {
-struct SampleWs : SetupBufs {      // (no WcatT; BeamWs without the candidate, back-pointer and path arrays)
-  float *Hst, *Cst, *X, *slab, *Gact, *Hdrop, *logits, *alpha_hist;
+struct SampleWs : RowWs {      // (BeamWs without the candidate, back-pointer and path arrays)
+  float *Hdrop, *logits, *alpha_hist;
   int* fin;
   long long* prev;
   size_t bytes;
@@ -569,20 +565,7 @@ SampleWs sample_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* o
   Carver c(p, bytes);
   SampleWs w{};
   const size_t R = (size_t)B * S;
-  w.F = c.take<float>((size_t)B * kL * kD);
-  w.P = c.take<float>((size_t)B * kL * kA);
-  w.mean = c.take<float>((size_t)B * kD);
-  w.Wcat = c.take<float>((size_t)kG * kXK);
-  w.bcat = c.take<float>(kG);
-  w.WhT = c.take<float>((size_t)kH * kA);
-  w.WbT = c.take<float>((size_t)kH * kD);
-  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
-  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
-  w.Hst = c.take<float>(R * 2 * kH);
-  w.Cst = c.take<float>(R * 2 * kH);
-  w.X = c.take<float>(R * kXK);
-  w.slab = c.take<float>((size_t)kS_LSTM * R * kG);
-  w.Gact = c.take<float>(R * kG);
+  row_carve(c, w, B, R);
   w.Hdrop = c.take<float>(R * kH);
   w.logits = c.take<float>(R * V);
   w.fin = c.take<int>(R);
@@ -611,9 +594,8 @@ int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rg
   hipStream_t st = (hipStream_t)stream;
   // every argument check comes before the first HIP call
   DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_sample: samples per image S=%d is outside 1..%d", S, kBeamMax);
-  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "decoder_sample: bad sizes (B=%d, V=%d, max_length=%d)", B, V, max_length);
-  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_sample: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
-  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_sample: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_TRY(check_row_sizes("decoder_sample", B, V, max_length));
+  DIC_TRY(check_token_ids("decoder_sample", V, id_start, id_end));
   DIC_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "decoder_sample: temperature=%g must be finite and > 0",
               (double)temperature);
   DIC_REQUIRE(top_k >= 0 && top_k <= V, "decoder_sample: top_k=%d is outside 0..V=%d (0: no limit)", top_k, V);
@@ -622,22 +604,14 @@ int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rg
   const int T = max_length, R = B * S;
   bool ov = false;
   SampleWs ws = sample_carve(workspace, workspace_bytes, B, S, T, V, &ov);
-  if (ov) {
-    set_last_error("decoder_sample: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
-    return DIC_ERR_WORKSPACE;
-  }
+  if (ov) return workspace_too_small("decoder_sample", workspace_bytes, ws.bytes);
   // per image, never per sample.  [h0 | c0] -> slot 1 of sample 0, then copied to the S rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
   hipLaunchKernelGGL(sample_init_kernel, dim3(B), dim3(kH), 0, st, S, id_start, ws.fin, out_lengths, ws.prev, ws.Hst, ws.Cst);
   DIC_LAUNCH_CHECK();
   for (int t = 0; t < T; ++t) {
     float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * R * kL : nullptr;
-    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P,
-                                          ws.Hst, ws.prev, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b,
-                                          ws.WbT, w->fbeta_b, alpha_t, ws.X, B);)
-    DIC_LAUNCH_CHECK();
-    DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
-    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.Hdrop, kS_LSTM, R, 0}, 0, 1, st));
+    DIC_TRY(launch_row_step(ws, w, V, B, S, ws.prev, alpha_t, ws.Hdrop, 0, st));
     DIC_TRY(gemm(R, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
     DIC_TRY(launch_sample_token(SampleStep{ws.logits, R, V, temperature, top_k, top_p, uniform_u + (size_t)t * R, id_end, t, T,
                                            ws.fin, out_lengths, ws.prev, (long long*)out_ids, out_logprobs, ws.Hst, ws.Cst, kH},
@@ -653,8 +627,8 @@ int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rg
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------------
 namespace {
-struct ScoreWs : SetupBufs {       // (no WcatT; SampleWs without the logits and the attention history, plus the h history)
-  float *Hst, *Cst, *X, *slab, *Gact, *hist, *lp;
+struct ScoreWs : RowWs {       // (SampleWs without the logits and the attention history, plus the h history)
+  float *hist, *lp;
   long long *tok_in, *target;
   void* lse_ws;
   size_t bytes;
@@ -664,20 +638,7 @@ ScoreWs score_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* ove
   Carver c(p, bytes);
   ScoreWs w{};
   const size_t R = (size_t)B * S, M = R * T;
-  w.F = c.take<float>((size_t)B * kL * kD);
-  w.P = c.take<float>((size_t)B * kL * kA);
-  w.mean = c.take<float>((size_t)B * kD);
-  w.Wcat = c.take<float>((size_t)kG * kXK);
-  w.bcat = c.take<float>(kG);
-  w.WhT = c.take<float>((size_t)kH * kA);
-  w.WbT = c.take<float>((size_t)kH * kD);
-  w.gemm_ws_floats = (size_t)16 * B * 2 * kH;                  // init_linear split-K
-  w.gemm_ws = c.take<float>(w.gemm_ws_floats);
-  w.Hst = c.take<float>(R * 2 * kH);
-  w.Cst = c.take<float>(R * 2 * kH);
-  w.X = c.take<float>(R * kXK);
-  w.slab = c.take<float>((size_t)kS_LSTM * R * kG);
-  w.Gact = c.take<float>(R * kG);
+  row_carve(c, w, B, R);
   w.hist = c.take<float>(M * kH);                              // h of every step, rows t*R + r: the A operand of the fused launch
   w.lp = c.take<float>(M);
   w.tok_in = c.take<long long>(M);
@@ -705,32 +666,23 @@ int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb
   hipStream_t st = (hipStream_t)stream;
   // every argument check comes before the first HIP call
   DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_score: captions per image S=%d is outside 1..%d", S, kBeamMax);
-  DIC_REQUIRE(V > 0 && B > 0 && max_length >= 1, "decoder_score: bad sizes (B=%d, V=%d, max_length=%d)", B, V, max_length);
+  DIC_TRY(check_row_sizes("decoder_score", B, V, max_length));
   DIC_REQUIRE((long long)B * S * max_length <= kScoreMaxM, "decoder_score: B*S*max_length=%lld exceeds %d token positions per call",
               (long long)B * S * max_length, kScoreMaxM);
-  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_score: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
-  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_score: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_TRY(check_token_ids("decoder_score", V, id_start, id_end));
   DIC_REQUIRE(w && feat_rgb && captions && out_logprobs && out_scores && out_lengths && workspace, "decoder_score: null pointer");
   const int T = max_length, R = B * S;
   bool ov = false;
   ScoreWs ws = score_carve(workspace, workspace_bytes, B, S, T, V, &ov);
-  if (ov) {
-    set_last_error("decoder_score: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
-    return DIC_ERR_WORKSPACE;
-  }
+  if (ov) return workspace_too_small("decoder_score", workspace_bytes, ws.bytes);
   // per image, never per caption.  [h0 | c0] -> slot 1 of row 0 of the image, then copied to its S rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
   hipLaunchKernelGGL(score_init_kernel, dim3(B), dim3(kH), 0, st, S, T, V, id_start, id_end, (const long long*)captions, ws.tok_in,
                      ws.target, out_lengths, ws.Hst, ws.Cst);
   DIC_LAUNCH_CHECK();
   for (int t = 0; t < T; ++t) {
-    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P,
-                                          ws.Hst, ws.tok_in + (size_t)t * R, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w,
-                                          w->full_att_b, ws.WbT, w->fbeta_b, (float*)nullptr, ws.X, B);)
-    DIC_LAUNCH_CHECK();
-    DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
-    // the cell writes h' / c' into slot 1 and appends h' to the history (its "dropped" output at packed row t*R + r, no dropout)
-    DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, ws.hist, kS_LSTM, R, t * R}, 0, 1, st));
+    // the cell writes h' / c' into slot 1 and appends h' to the history (packed row t*R + r)
+    DIC_TRY(launch_row_step(ws, w, V, B, S, ws.tok_in + (size_t)t * R, nullptr, ws.hist, t * R, st));
     if (t + 1 < T) {
       hipLaunchKernelGGL(score_handover_kernel, dim3(R), dim3(kH), 0, st, ws.Hst, ws.Cst);
       DIC_LAUNCH_CHECK();

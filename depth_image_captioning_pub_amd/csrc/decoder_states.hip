@@ -4,7 +4,8 @@
 // R = B*S rows (or all B images) and a (row, step) pair behind the row's length returns or is selected to 0.
 //   forward, per step:  states_attn_kernel<S> -> gate GEMM slabs -> lstm_fwd_kernel (h x drop_mult straight into out_hidden)
 //   backward, per step: states_lstm_bwd_kernel -> dX GEMM slabs -> states_attn_bwd_a_kernel<S> -> states_attn_bwd_b_kernel
-//   then: embed_grad_kernel, per-image folds of dP / dinit, the bias column sums, the grouped weight-gradient GEMMs, dF.
+//   then: embed_grad_kernel, per-image folds of dP / dinit, the tail of the teacher-forced backward (launch_bptt_tail: bias column
+//   sums, grouped weight-gradient GEMMs), dF (states_dF_kernel, then launch_dP_Wz).
 // Tape layouts are those of the teacher-forced route with its batch row replaced by r ([R][T][...], Hall / Call [R][T+1][H]), so
 // the LSTM cell kernels, embed_grad_kernel and the weight-gradient GEMMs are that route's; F, P and mean stay [B][...].
 #include "beam.h"
@@ -88,8 +89,9 @@ bool states_sizes_ok(int B, int S, int T, int V) {
 
 // ------------------------------------------------------------------------------------------
 // start, grid (B), kH threads: h0 / c0 of the image (slot 0 of its row 0, written by the init_linear GEMM) for its other S - 1
-// rows; and per row the token arrays with score_init_kernel's rule: tok [R][T] the input of every step, target [T][R] the caption
-// clamped into the vocabulary, -1 from the row's length on; length = index of the first id_end + 1, or T.
+// rows (broadcast_state); and per row the token arrays (parse_caption, the scoring route's rule): tok [R][T] the input of every
+// step, target [T][R] the caption clamped into the vocabulary, -1 from the row's length on; length = index of the first id_end + 1,
+// or T.
 // ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kH) states_init_kernel(int S, int T, int V, long long id_start, long long id_end,
                                                           const long long* __restrict__ captions, long long* __restrict__ tok,
@@ -98,22 +100,11 @@ __global__ void __launch_bounds__(kH) states_init_kernel(int S, int T, int V, lo
                                                           float* __restrict__ Call) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const long long row0 = (long long)b * S, R = (long long)gridDim.x * S;
-  const float h = Hall[row0 * (T + 1) * kH + tid], c = Call[row0 * (T + 1) * kH + tid];
-  for (int s = 1; s < S; ++s) {
-    Hall[(row0 + s) * (T + 1) * kH + tid] = h;
-    Call[(row0 + s) * (T + 1) * kH + tid] = c;
-  }
+  const long long ld = (long long)(T + 1) * kH;
+  broadcast_state(Hall, Call, row0 * ld, (row0 + 1) * ld, ld, S - 1, tid);
   if (tid < S) {
     const long long r = row0 + tid;
-    const long long* cap = captions + r * T;
-    int n = T;
-    tok[r * T] = id_start;
-    for (int t = 0; t < T; ++t) {
-      const long long id = cap[t];
-      target[(long long)t * R + r] = t < n ? clamp_token(id, V) : -1;
-      if (t + 1 < T) tok[r * T + t + 1] = id;
-      if (t < n && id == id_end) n = t + 1;
-    }
+    const int n = parse_caption(captions + r * T, T, V, id_start, id_end, tok + r * T, 1, target + r, R);
     len[r] = n;
     out_lengths[r] = n;
   }
@@ -542,9 +533,7 @@ static int states_check(int V, int B, int S, long long id_start, long long id_en
   DIC_REQUIRE(embed_grad_rows_ok((long long)B * S * T),
               "decoder_states: B*S*T=%lld exceeds the %d (row, step) pairs of the embedding-gradient kernel", (long long)B * S * T,
               60 * 1024 / 16 * kE);
-  DIC_REQUIRE(id_start >= 0 && id_start < V, "decoder_states: id_start=%lld is outside the vocabulary [0, %d)", id_start, V);
-  DIC_REQUIRE(id_end >= 0 && id_end < V, "decoder_states: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
-  return DIC_OK;
+  return check_token_ids("decoder_states", V, id_start, id_end);
 }
 
 int dic_decoder_states_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
@@ -557,10 +546,7 @@ int dic_decoder_states_fwd(const dic_decoder_weights* w, int V, const float* fea
   const int R = B * S;
   bool ov = false;
   StatesWs ws = states_carve(workspace, workspace_bytes, B, S, T, &ov);
-  if (ov) {
-    set_last_error("decoder_states: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
-    return DIC_ERR_WORKSPACE;
-  }
+  if (ov) return workspace_too_small("decoder_states", workspace_bytes, ws.bytes);
   // per image, never per caption.  [h0 | c0] -> slot 0 of row 0 of the image, then copied to its other rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hall, ws.Call, (long long)S * (T + 1) * kH, true}, st));
   hipLaunchKernelGGL(states_init_kernel, dim3(B), dim3(kH), 0, st, S, T, V, id_start, id_end, (const long long*)captions, ws.tok,
@@ -594,10 +580,7 @@ int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, lo
   const int R = B * S;
   bool ov = false;
   StatesWs ws = states_carve(workspace, workspace_bytes, B, S, T, &ov);
-  if (ov) {
-    set_last_error("decoder_states: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
-    return DIC_ERR_WORKSPACE;
-  }
+  if (ov) return workspace_too_small("decoder_states", workspace_bytes, ws.bytes);
   const size_t RT = (size_t)R * T;
   // (row, step) pairs behind the row's length keep zero gradients: dG, dctx, dgpre, dq are carved back to back
   DIC_CHECK_HIP(hipMemsetAsync(ws.dG, 0, (size_t)((char*)(ws.dq + RT * kA) - (char*)ws.dG), st));
@@ -635,41 +618,14 @@ int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, lo
   hipLaunchKernelGGL(states_fold_kernel, dim3(ceil_div(kL * kA, 256), B), dim3(256), 0, st, ws.dPacc, ws.dPimg, S, kL * kA);
   hipLaunchKernelGGL(states_fold_kernel, dim3(ceil_div(2 * kH, 256), B), dim3(256), 0, st, ws.dinit, ws.dinit_img, S, 2 * kH);
   DIC_LAUNCH_CHECK();
-  {
-    ColsumBatch cb{};
-    cb.j[0] = ColsumJob{ws.dG, kG, (int)RT, kG, 0, g->b_ih, nullptr};
-    cb.j[1] = ColsumJob{ws.dgpre, kD, (int)RT, kD, 0, g->fbeta_b, nullptr};
-    cb.j[2] = ColsumJob{ws.dq, kA, (int)RT, kA, 0, g->dec_att_b, nullptr};
-    cb.j[3] = ColsumJob{ws.dwf_acc, kA, kLCH * R, kA, 0, g->full_att_w, nullptr};
-    cb.j[4] = ColsumJob{ws.dbf_acc, 1, kLCH * R, 1, 0, g->full_att_b, nullptr};
-    cb.j[5] = ColsumJob{ws.dPimg, kA, B * kL, kA, 0, g->enc_att_b, nullptr};
-    cb.j[6] = ColsumJob{ws.dinit_img, 2 * kH, B, 2 * kH, 0, g->init_b, nullptr};
-    DIC_TRY(colsum_batch(cb, 7, ws.colsum_ws, st));
-  }
-  {  // the five weight-gradient products of the teacher-forced backward, one launch; F and mean are per image
-    const float* Hprev = ws.Xall + kE + kD;                     // h_{t-1} rows, ld = kXK
-    GemmParams gp[5] = {};
-    auto set = [&](int i, int M, int N, int K, GemmOperand A, GemmOperand Bop, GemmEpilogue ep, int splitk, float* wsp) {
-      gp[i].M = M; gp[i].N = N; gp[i].K = K; gp[i].A = A; gp[i].B = Bop; gp[i].ep = ep; gp[i].splitk = splitk; gp[i].ws = wsp;
-    };
-    GemmEpilogue ep = ep_store(g->w_ih, kE + kD);
-    ep.C2 = g->w_hh; ep.ldc2 = kH; ep.nsplit = kE + kD;
-    set(0, kG, kXK, (int)RT, op_colk(ws.dG, kG), op_colk(ws.Xall, kXK), ep, 1, nullptr);
-    set(1, kD, kH, (int)RT, op_colk(ws.dgpre, kD), op_colk(Hprev, kXK), ep_store(g->fbeta_w, kH), 1, nullptr);
-    set(2, kA, kH, (int)RT, op_colk(ws.dq, kA), op_colk(Hprev, kXK), ep_store(g->dec_att_w, kH), 8, ws.gemm_ws);
-    set(3, kA, kD, B * kL, op_colk(ws.dPimg, kA), op_colk(ws.F, kD), ep_store(g->enc_att_w, kD), 8, ws.gemm_ws + (size_t)8 * kA * kH);
-    set(4, 2 * kH, kD, B, op_colk(ws.dinit_img, 2 * kH), op_colk(ws.mean, kD), ep_store(g->init_w, kD), 1, nullptr);
-    DIC_TRY(gemm_launch_group_colk(gp, 5, st));
-    DIC_CHECK_HIP(hipMemcpyAsync(g->b_hh, g->b_ih, sizeof(float) * kG, hipMemcpyDeviceToDevice, st));
-  }
+  // the tail of the teacher-forced backward; dP, dinit, F and mean are per image
+  DIC_TRY(launch_bptt_tail(BpttTail{(int)RT, kLCH * R, B, kL, ws.dPimg, ws.dinit_img, ws.dG, ws.dgpre, ws.dq, ws.dwf_acc, ws.dbf_acc,
+                                    ws.Xall, ws.F, ws.mean, ws.colsum_ws, ws.gemm_ws}, g, st));
   if (d_features) {
     DIC_TRY(gemm(B, kD, 2 * kH, op_rowk(ws.dinit_img, 2 * kH), op_colk(w->init_w, kD), ep_store(ws.dmean, kD), st, 8, ws.gemm_ws, 64));
     hipLaunchKernelGGL(states_dF_kernel, dim3(kNCH, B), dim3(256), 0, st, ws.alpha, ws.dctx, ws.dmean, S, T, ws.len, d_features);
     DIC_LAUNCH_CHECK();
-    GemmEpilogue ep = ep_store(d_features, kD);
-    ep.accumulate = 1;
-    DIC_TRY(launch_transpose(w->enc_att_w, ws.WzT, kA, kD, st));
-    DIC_TRY(gemm(B * kL, kD, kA, op_rowk(ws.dPimg, kA), op_rowk(ws.WzT, kA), ep, st));
+    DIC_TRY(launch_dP_Wz(w->enc_att_w, ws.WzT, ws.dPimg, B * kL, d_features, st));
   }
   return DIC_OK;
 }

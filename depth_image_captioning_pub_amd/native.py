@@ -524,18 +524,29 @@ class ResNetRunner:
 # ---------------------------------------------------------------------------------------------
 # greedy decode + stand-alone attention
 # ---------------------------------------------------------------------------------------------
-def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
-                   id_start: int, max_length: int = 30, mode: int = 0, gumbel_u: Optional[torch.Tensor] = None):
-    """dic_decoder_greedy. Returns (ids int64 [B,max_length] on device, alphas [B,max_length,196])."""
+def _workspace(query, device, *sizes) -> torch.Tensor:
+    """Workspace of query(*sizes) bytes, at least 256: a query returns 0 for sizes its call refuses, and the call needs a
+    non-null pointer to get as far as the refusal with its text."""
+    query.restype = C.c_size_t
+    return torch.empty(max(query(*sizes), 256), dtype=torch.uint8, device=device)
+
+
+def _decoder_prologue(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor]):
+    """What every decode / score / states call starts with.  Returns (lib, features, depth features or None, B, vocab,
+    weight pointers, the tensors they point to - to be kept alive across the call)."""
     lib = _lib.load()
     f_rgb = _dev_f32(feat_rgb, "features")
     f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
-    B = f_rgb.shape[0]
     vocab = weights["linear.weight"].shape[0]
     wp, keep = decoder_ptrs(weights)
-    lib.dic_decoder_greedy_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_decoder_greedy_workspace_bytes(B, max_length, vocab)
-    ws = torch.empty(need, dtype=torch.uint8, device=f_rgb.device)
+    return lib, f_rgb, f_dep, f_rgb.shape[0], vocab, wp, keep
+
+
+def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
+                   id_start: int, max_length: int = 30, mode: int = 0, gumbel_u: Optional[torch.Tensor] = None):
+    """dic_decoder_greedy. Returns (ids int64 [B,max_length] on device, alphas [B,max_length,196])."""
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    ws = _workspace(lib.dic_decoder_greedy_workspace_bytes, f_rgb.device, B, max_length, vocab)
     ids = torch.empty((B, max_length), dtype=torch.int64, device=f_rgb.device)
     alphas = torch.empty((B, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device)
     gu = _dev_f32(gumbel_u, "gumbel_u") if gumbel_u is not None else None
@@ -550,15 +561,9 @@ def decoder_beam(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_
                  return_alphas: bool = False):
     """dic_decoder_beam: fixed-width beam search of the soft-attention decoder, on the device (semantics: include/dic.h).
     Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K][, alphas [B,K,max_length,196]]), best first."""
-    lib = _lib.load()
-    f_rgb = _dev_f32(feat_rgb, "features")
-    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
-    B, K = f_rgb.shape[0], int(beam_size)
-    vocab = weights["linear.weight"].shape[0]
-    wp, keep = decoder_ptrs(weights)
-    lib.dic_decoder_beam_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_decoder_beam_workspace_bytes(B, K, max_length, vocab)      # (0 for sizes the call below refuses with its text)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f_rgb.device)
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    K = int(beam_size)
+    ws = _workspace(lib.dic_decoder_beam_workspace_bytes, f_rgb.device, B, K, max_length, vocab)
     kk = max(K, 1)
     ids = torch.empty((B, kk, max_length), dtype=torch.int64, device=f_rgb.device)
     scores = torch.empty((B, kk), dtype=torch.float32, device=f_rgb.device)
@@ -577,19 +582,13 @@ def decoder_sample(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
     """dic_decoder_sample: `n_samples` captions per image drawn from the soft-attention decoder's distribution, on the device
     (semantics: include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1) - the draws are an input.
     Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S][, alphas [B,S,max_length,196]])."""
-    lib = _lib.load()
-    f_rgb = _dev_f32(feat_rgb, "features")
-    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
-    B, S = f_rgb.shape[0], int(n_samples)
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    S = int(n_samples)
     ss = max(S, 1)
     u = _dev_f32(uniform_u, "uniform_u")
     if tuple(u.shape) != (max_length, B * ss):
         raise _lib.DicError(f"decoder_sample: uniform_u must be [max_length, B*n_samples] = [{max_length}, {B * ss}], got {tuple(u.shape)}")
-    vocab = weights["linear.weight"].shape[0]
-    wp, keep = decoder_ptrs(weights)
-    lib.dic_decoder_sample_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_decoder_sample_workspace_bytes(B, S, max_length, vocab)     # (0 for sizes the call below refuses with its text)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f_rgb.device)
+    ws = _workspace(lib.dic_decoder_sample_workspace_bytes, f_rgb.device, B, S, max_length, vocab)
     ids = torch.empty((B, ss, max_length), dtype=torch.int64, device=f_rgb.device)
     logprobs = torch.empty((B, ss, max_length), dtype=torch.float32, device=f_rgb.device)
     lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
@@ -622,9 +621,7 @@ def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     M, V = h.shape[0], w.shape[0]
     if tuple(b.shape) != (V,) or tuple(tg.shape) != (M,):
         raise _lib.DicError(f"token_logprobs: bias must be [{V}] and targets [{M}], got {tuple(b.shape)} and {tuple(tg.shape)}")
-    lib.dic_token_logprobs_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_token_logprobs_workspace_bytes(M, V)                       # (0 for sizes the call below refuses with its text)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=h.device)
+    ws = _workspace(lib.dic_token_logprobs_workspace_bytes, h.device, M, V)
     logprobs = torch.empty((M,), dtype=torch.float32, device=h.device)
     lse = torch.empty((M,), dtype=torch.float32, device=h.device)
     rc = lib.dic_token_logprobs(ptr(h), ptr(w), ptr(b), ptr(tg), M, V, ptr(logprobs), ptr(lse), ptr(ws), C.c_size_t(ws.numel()),
@@ -672,22 +669,15 @@ def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat
     """dic_decoder_score: the log-probability the soft-attention decoder gives every token of given captions, on the device
     (semantics: include/dic.h).  captions: int64 [B,T] (one per image) or [B,S,T] (S <= 8 per image), without '<start>'.
     Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
-    lib = _lib.load()
-    f_rgb = _dev_f32(feat_rgb, "features")
-    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
     cap = _dev_i64(captions, "captions")
-    B = f_rgb.shape[0]
     squeeze = cap.dim() == 2
     if squeeze:
         cap = cap.unsqueeze(1)
     if cap.dim() != 3 or cap.shape[0] != B:
         raise _lib.DicError(f"decoder_score: captions must be [B,T] or [B,S,T] with B = {B}, got {tuple(captions.shape)}")
     S, T = int(cap.shape[1]), int(cap.shape[2])
-    vocab = weights["linear.weight"].shape[0]
-    wp, keep = decoder_ptrs(weights)
-    lib.dic_decoder_score_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_decoder_score_workspace_bytes(B, S, T, vocab)              # (0 for sizes the call below refuses with its text)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f_rgb.device)
+    ws = _workspace(lib.dic_decoder_score_workspace_bytes, f_rgb.device, B, S, T, vocab)
     ss, tt = max(S, 1), max(T, 1)
     logprobs = torch.empty((B, ss, tt), dtype=torch.float32, device=f_rgb.device)
     scores = torch.empty((B, ss), dtype=torch.float32, device=f_rgb.device)
@@ -726,11 +716,8 @@ def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Ten
     include/dic.h).  captions int64 [B,S,T] without '<start>', S <= 8 per image; drop_mult float32 [B*S,T,128] or None (eval).
     Returns (hidden float32 [T,R,128] - 0 from each row's length on -, targets int64 [T,R] - -1 there -, lengths int32 [B,S],
     tape), R = B*S, rows b*S + s."""
-    lib = _lib.load()
-    f_rgb = _dev_f32(features, "features")
-    f_dep = _dev_f32(depth_features, "depth_features") if depth_features is not None else None
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, features, depth_features)
     cap = _dev_i64(captions, "captions")
-    B = f_rgb.shape[0]
     if cap.dim() != 3 or cap.shape[0] != B:
         raise _lib.DicError(f"decoder_states: captions must be [B,S,T] with B = {B}, got {tuple(captions.shape)}")
     if tuple(f_rgb.shape[1:]) != (L_CELLS, D_ENC) or (f_dep is not None and tuple(f_dep.shape) != tuple(f_rgb.shape)):
@@ -742,12 +729,8 @@ def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Ten
         dm = _dev_f32(drop_mult, "drop_mult")
         if tuple(dm.shape) != (R, T, D_HID):
             raise _lib.DicError(f"decoder_states: drop_mult must be [B*S,T,{D_HID}] = [{R},{T},{D_HID}], got {tuple(dm.shape)}")
-    vocab = weights["linear.weight"].shape[0]
-    wp, keep = decoder_ptrs(weights)
-    lib.dic_decoder_states_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_decoder_states_workspace_bytes(B, S, T, vocab)             # (0 for sizes the call below refuses with its text)
     dev = f_rgb.device
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.dic_decoder_states_workspace_bytes, dev, B, S, T, vocab)
     rr, tt = max(R, 1), max(T, 1)
     hidden = torch.empty((tt, rr, D_HID), dtype=torch.float32, device=dev)
     targets = torch.empty((tt, rr), dtype=torch.int64, device=dev)

@@ -1,6 +1,8 @@
 """CPU: the C-ABI library builds, loads and exports every symbol include/dic.h declares."""
 import ctypes
 
+import pytest
+
 from depth_image_captioning_pub_amd import _lib, build
 
 
@@ -30,6 +32,41 @@ def test_ctypes_mirrors_have_the_size_of_the_library_structs():
         assert lib.dic_struct_bytes(which) == ctypes.sizeof(mirror) > 0, (which, mirror.__name__)
         _lib.check_struct(lib, which, mirror)
     assert ctypes.sizeof(native.ConvBnLayer) == 72 and lib.dic_struct_bytes(99) == 0
+
+
+# Workspace sizes are part of what a caller sees (it allocates them): pinned exactly, as commit 2ccc799 returned them, so that a
+# change to a carve - its order, a count, a new slice - shows here before it shows as a "workspace too small" elsewhere.
+_WORKSPACE_BYTES = [
+    ("dic_decoder_beam_workspace_bytes", (1, 1, 1, 8), 7619584),                 # (B, K, max_length, V)
+    ("dic_decoder_beam_workspace_bytes", (3, 3, 5, 300), 11531264),
+    ("dic_decoder_beam_workspace_bytes", (2, 8, 7, 1000), 10262272),
+    ("dic_decoder_beam_workspace_bytes", (64, 5, 30, 10000), 153271552),
+    ("dic_decoder_sample_workspace_bytes", (1, 1, 1, 8), 7617792),               # (B, S, max_length, V)
+    ("dic_decoder_sample_workspace_bytes", (3, 3, 5, 300), 11529472),
+    ("dic_decoder_sample_workspace_bytes", (2, 8, 7, 1000), 10259200),
+    ("dic_decoder_sample_workspace_bytes", (64, 5, 30, 10000), 153140992),
+    ("dic_decoder_score_workspace_bytes", (1, 1, 1, 8), 7617280),                # (B, S, max_length, V)
+    ("dic_decoder_score_workspace_bytes", (3, 3, 5, 300), 11503104),
+    ("dic_decoder_score_workspace_bytes", (2, 8, 7, 1000), 10160896),
+    ("dic_decoder_score_workspace_bytes", (64, 5, 30, 10000), 139328512),
+    ("dic_decoder_states_workspace_bytes", (1, 1, 1, 8), 23416320),              # (B, S, T, V)
+    ("dic_decoder_states_workspace_bytes", (3, 3, 5, 300), 30789888),
+    ("dic_decoder_states_workspace_bytes", (2, 8, 7, 1000), 33649920),
+    ("dic_decoder_states_workspace_bytes", (64, 5, 30, 10000), 678692096),
+    ("dic_decoder_greedy_workspace_bytes", (1, 1, 8), 23315200),                 # (B, max_length, V)
+    ("dic_decoder_greedy_workspace_bytes", (3, 5, 300), 27846656),
+    ("dic_decoder_greedy_workspace_bytes", (64, 30, 10000), 244206336),
+    ("dic_decoder_workspace_bytes", (1, 1, 8, 1), 23315200),                     # (B, Tmax, V, n_packed)
+    ("dic_decoder_workspace_bytes", (3, 5, 300, 12), 27843584),
+    ("dic_decoder_workspace_bytes", (64, 30, 10000, 1500), 243776256),
+]
+
+
+@pytest.mark.parametrize("query,sizes,want", _WORKSPACE_BYTES, ids=[f"{q[4:-16]}-{'x'.join(map(str, a))}" for q, a, _ in _WORKSPACE_BYTES])
+def test_decoder_workspace_sizes_are_pinned(query, sizes, want):
+    fn = getattr(ctypes.CDLL(build.build()), query)
+    fn.restype = ctypes.c_size_t
+    assert fn(*sizes) == want
 
 
 def test_loader_refuses_a_library_of_another_abi_version(monkeypatch):
