@@ -7,9 +7,11 @@ runs dic_token_logprobs_bwd and dic_decoder_states_bwd.
 
 The usual reward is CIDEr-D against the batch's reference captions: cider.CiderD.reward_fn scores the sampled ids on the device
 in one more launch (dic_cider_d), so the step stays free of host round trips with a real metric too.
+metrics.reward_fn mixes it with per-caption BLEU-1..4 and ROUGE-L (dic_bleu, dic_rouge_l, DESIGN.md 5.16: one more launch per
+metric of non-zero weight), e.g. CIDEr-D + 0.5 BLEU-4, as a device tensor as well.
 
-Out of scope here: the engine's flat parameter buffers and fused train step and the data-parallel gradient exchange; other
-metric rewards (BLEU, METEOR, ROUGE) - reward_fn is the seam for them."""
+Out of scope here: the engine's flat parameter buffers and fused train step and the data-parallel gradient exchange; a METEOR
+reward (a Java jar and WordNet, not a rule over token ids) - reward_fn is the seam for any other reward."""
 from __future__ import annotations
 
 from .. import losses

@@ -5,10 +5,11 @@ encoder, decoder.batch_sample  (depth_evaluation.py:146-165), then turn the toke
 (:167-176).  Every tensor operation runs in libdic_hip.so; the decode keeps the previous token on the device (the reference
 copies it to the host every step, depth_models.py:298-299).
 
-Out of scope here as in SURVEY.md section 2: the COCO dataset / annotation files and the pycocoevalcap scorers BLEU / METEOR
-(Java) / ROUGE (evaluate_metrix.py) - `useData` must be "synthetic" (procedural images, a procedural vocabulary); the hypotheses
-are returned and written next to the checkpoints.  CIDEr (evaluate_metrix.py:31) is computed on request, on the device, over
-token ids against procedural reference captions (cider.CiderD)."""
+Out of scope here as in SURVEY.md section 2: the COCO dataset / annotation files and pycocoevalcap's METEOR scorer (a Java jar and
+WordNet, evaluate_metrix.py:29) - `useData` must be "synthetic" (procedural images, a procedural vocabulary); the hypotheses
+are returned and written next to the checkpoints.  CIDEr (evaluate_metrix.py:31) and, with it, Bleu_1..4 and ROUGE_L
+(evaluate_metrix.py:28,30) are computed on request, on the device, over token ids against procedural reference captions
+(cider.CiderD; metrics.evaluation_scores)."""
 from __future__ import annotations
 
 import json
@@ -18,6 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from . import metrics as metrics_mod
 from . import synthetic as syn
 from ._lib import DicError
 from .cider import CiderD
@@ -54,7 +56,7 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
                       length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0, cider: bool = False):
+                      top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
@@ -65,7 +67,9 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     seed + b.  The hypotheses, the ids and the written file do not depend on it.
     cider=True ADDS "CIDEr": the mean CIDEr-D (evaluate_metrix.py:31; x10 as pycocoevalcap reports it) of the hypotheses against
     synthetic.reference_captions(batch_size, vocab_size, seed=5000 + b) of batch b, five per image, scored on the device as decoded
-    strings are (count_end=False); the idf table is that of all the evaluated images' references.  Nothing else depends on it."""
+    strings are (count_end=False); the idf table is that of all the evaluated images' references.  Nothing else depends on it.
+    metrics=True ADDS the reference's report without METEOR - "Bleu_1" .. "Bleu_4" (corpus BLEU), "ROUGE_L" (mean over the images)
+    and "CIDEr" (as cider=True) - over the same references, by metrics.evaluation_scores.  Nothing else depends on it."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
@@ -111,7 +115,7 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             depth_maps = dpt.depth_maps_for_training(imgs_for_dep)                          # :155-159
             depth_features = depth_encoder(depth_maps)                                      # :161
             feature = encoder(imgs)                                                         # :164
-            if cider:
+            if cider or metrics:
                 references += syn.reference_captions(config.batch_size, config.vocab_size, seed=5000 + b)
             if int(beam_size) > 1:
                 hypos_id.append(decoder.beam_sample(feature, depth_features, word_to_id, beam_size=int(beam_size),
@@ -129,9 +133,12 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             sample_ids = np.concatenate(sample_ids)
             results[key]["samples"] = [ids_to_captions(rows, id_to_word) for rows in sample_ids]
             results[key]["sample_ids"] = sample_ids
-        # depth_evaluation.py:178-184 scores the hypotheses with BLEU / METEOR / ROUGE too (pycocoevalcap + Java): out of scope
-        #  - the hypotheses are the product of this path.
-        if cider:
+        # depth_evaluation.py:178-184 scores the hypotheses with pycocoevalcap: BLEU, ROUGE-L and CIDEr are computed here on request,
+        # over token ids on the device; METEOR (a Java jar and WordNet) is out of scope.
+        if metrics:
+            results[key].update(metrics_mod.evaluation_scores(torch.from_numpy(hypos_id), references, config.vocab_size,
+                                                              word_to_id["<end>"], dev))
+        elif cider:
             scorer = CiderD.from_references(references, config.vocab_size, word_to_id["<end>"], count_end=False, device=dev)
             ref_ids, ref_counts = scorer.pack_references(references)
             results[key]["CIDEr"] = float(scorer.corpus_score(torch.from_numpy(hypos_id).long().to(dev), ref_ids, ref_counts))

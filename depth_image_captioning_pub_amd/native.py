@@ -803,6 +803,55 @@ def cider_d(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tens
     return out[:, 0] if squeeze else out
 
 
+def _metric_args(what: str, hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor):
+    """The checks native.cider_d makes of its caption arguments: (hyp [B,S,T], ref, counts, squeeze, B, S, T, R, Tr)."""
+    hyp, ref = _dev_i64(hyp_ids, "hyp_ids"), _dev_i64(ref_ids, "ref_ids")
+    squeeze = hyp.dim() == 2
+    if squeeze:
+        hyp = hyp.unsqueeze(1)
+    if hyp.dim() != 3 or ref.dim() != 3 or ref.shape[0] != hyp.shape[0]:
+        raise _lib.DicError(f"{what}: hyp_ids must be [B,T] or [B,S,T] and ref_ids [B,R,Tr] with the same B, got "
+                            f"{tuple(hyp_ids.shape)} and {tuple(ref_ids.shape)}")
+    B, S, T = (int(v) for v in hyp.shape)
+    R, Tr = int(ref.shape[1]), int(ref.shape[2])
+    if not ref_counts.is_cuda or ref_counts.dtype != torch.int32 or tuple(ref_counts.shape) != (B,):
+        raise _lib.DicError(f"{what}: ref_counts must be int32 [{B}] on the GPU, got {ref_counts.dtype} {tuple(ref_counts.shape)} on "
+                            f"{ref_counts.device}")
+    cnt = ref_counts if ref_counts.is_contiguous() else ref_counts.contiguous()
+    return hyp, ref, cnt, squeeze, B, S, T, R, Tr
+
+
+def bleu(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor, id_end: int, vocab: int, count_end: bool = True):
+    """dic_bleu: BLEU-1..4 of hypotheses against their image's references over token ids, one launch, on the device (semantics:
+    include/dic.h).  hyp_ids int64 [B,T] (one per image) or [B,S,T]; ref_ids int64 [B,R,Tr], R <= 8; ref_counts int32 [B].
+    Returns (scores float32 [B,4] or [B,S,4], stats int32 [B,10] or [B,S,10] = correct_1..4, guess_1..4, testlen, reflen)."""
+    lib = _lib.load()
+    hyp, ref, cnt, squeeze, B, S, T, R, Tr = _metric_args("bleu", hyp_ids, ref_ids, ref_counts)
+    scores = torch.empty((max(B, 1), max(S, 1), 4), dtype=torch.float32, device=hyp.device)
+    stats = torch.empty((max(B, 1), max(S, 1), 10), dtype=torch.int32, device=hyp.device)
+    rc = lib.dic_bleu(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, C.c_longlong(int(id_end)), int(bool(count_end)), int(vocab),
+                      ptr(scores), ptr(stats), stream_ptr())
+    check(rc, "dic_bleu")
+    return (scores[:, 0], stats[:, 0]) if squeeze else (scores, stats)
+
+
+def rouge_l(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor, id_end: int, vocab: int, count_end: bool = True,
+            beta: float = 1.2, return_lcs: bool = False):
+    """dic_rouge_l: ROUGE-L of hypotheses against their image's references over token ids, one launch, on the device (semantics:
+    include/dic.h).  Arguments as native.bleu.  Returns scores float32 [B] or [B,S]; with return_lcs (scores, lcs int32 [B,R] or
+    [B,S,R]: the longest common subsequence with every reference, 0 behind the image's count)."""
+    lib = _lib.load()
+    hyp, ref, cnt, squeeze, B, S, T, R, Tr = _metric_args("rouge_l", hyp_ids, ref_ids, ref_counts)
+    scores = torch.empty((max(B, 1), max(S, 1)), dtype=torch.float32, device=hyp.device)
+    lcs = torch.empty((max(B, 1), max(S, 1), max(R, 1)), dtype=torch.int32, device=hyp.device) if return_lcs else None
+    rc = lib.dic_rouge_l(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, C.c_longlong(int(id_end)), int(bool(count_end)), int(vocab),
+                         C.c_float(beta), ptr(scores), ptr(lcs), stream_ptr())
+    check(rc, "dic_rouge_l")
+    if squeeze:
+        scores, lcs = scores[:, 0], (lcs[:, 0] if return_lcs else None)
+    return (scores, lcs) if return_lcs else scores
+
+
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""

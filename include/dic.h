@@ -339,6 +339,42 @@ int dic_cider_d(const int64_t* hyp_ids, int B, int S, int T, const int64_t* ref_
                 long long id_end, int count_end, int V, const int64_t* idf_keys, const float* idf_vals, long long n_keys,
                 float idf_unseen, float sigma, float* out_scores, void* stream);
 
+/* BLEU-1..4 (Papineni et al. 2002) and ROUGE-L (Lin 2004) of S hypotheses per image against the image's references, over token ids,
+ *   on the device: the metrics `Bleu(4)` and `Rouge()` of Captioning_models/evaluate_metrix.py:28,30 report, and rewards that can be
+ *   mixed with CIDEr-D in self-critical training.  This comment is the specification: it restates pycocoevalcap's bleu_scorer.py
+ *   (option='closest') and rouge.py, which are not vendored in the reference and not installed here.  All pointers are device
+ *   pointers; each call is ONE launch enqueued on `stream`: no workspace, no host copy, no synchronisation.
+ *   hyp_ids int64 [B,S,T], ref_ids int64 [B,R,Tr], ref_counts int [B].
+ *   Tokens of a caption, references of an image: the rule of dic_cider_d, word for word - len = (index of the first id_end in the
+ *     row) + (count_end ? 1 : 0), or the row's width when it holds no id_end; ids are compared with id_end as given and clamped into
+ *     [0, V) afterwards; image b has R_b = min(max(ref_counts[b], 0), R) references, rows 0 .. R_b - 1.
+ *   dic_bleu, out_stats int [B,S,10] and out_scores float [B,S,4].  Per hypothesis h, k = 0..3 for the orders 1..4:
+ *     guess_k   = max(0, len_h - k), the (k+1)-grams of h;
+ *     correct_k = sum over the DISTINCT (k+1)-grams g of h of min(count_h(g), max over the R_b references r of count_r(g));
+ *     testlen   = len_h;  reflen = the len_r that minimises (|len_r - len_h|, len_r) lexicographically: the closest reference length,
+ *                 the shorter one on a tie;
+ *     out_stats[b,s,:] = (correct_0..3, guess_0..3, testlen, reflen), exact integers.
+ *     With tiny = 1e-15 and small = 1e-9 (pycocoevalcap's constants; the quirk is kept: an order without a match contributes
+ *     1e-15 / guess, not 0), in fp32:  p_k = prod_{j<=k} (correct_j + tiny) / (guess_j + small);  ratio = (testlen + tiny) /
+ *     (reflen + small);  bp = ratio < 1 ? exp(1 - 1 / ratio) : 1;  out_scores[b,s,k] = p_k^(1/(k+1)) * bp.  An empty hypothesis scores
+ *     exactly 0 (exp underflows).  With R_b = 0 all ten statistics and all four scores are exactly 0, so the image adds nothing to a
+ *     corpus sum (this library's own rule: pycocoevalcap cannot score such an image).
+ *     The CORPUS BLEU an evaluation reports is the same formula over the ten statistics summed over the images (metrics.corpus_bleu).
+ *   dic_rouge_l, out_scores float [B,S], out_lcs int [B,S,R] or NULL; beta finite and > 0 (pycocoevalcap: 1.2; the rule is that of
+ *     the float passed).  Per hypothesis h and reference r: lcs_r = the length of the longest common subsequence of the two token
+ *     rows;  prec_max = max_r lcs_r / len_h;  rec_max = max_r lcs_r / len_r (the two maxima may come from different references; a
+ *     reference of length 0 contributes 0 to both);  out_scores[b,s] = (1 + beta^2) prec_max rec_max / (rec_max + beta^2 prec_max)
+ *     in fp32 when both maxima are non-zero, else exactly 0: an empty hypothesis scores exactly 0, and so does R_b = 0.
+ *     out_lcs[b,s,r] = lcs_r for r < R_b and 0 for the other r, exact integers.
+ *   Properties: no float atomics; row (b,s) depends only on its own hypothesis and image b's references - never on B, on S or on the
+ *   other rows - so a row scored alone returns the bytes it returns inside a batch; two calls return identical bytes.
+ *   B, S >= 1, 1 <= T, Tr <= 64, 1 <= R <= 8, 1 <= V <= 65535, 0 <= id_end < V, no null pointer other than out_lcs: a violation
+ *   returns a negative code and a dic_last_error() text that starts with "bleu:" / "rouge_l:", before any HIP call.  DESIGN.md 5.16. */
+int dic_bleu(const int64_t* hyp_ids, int B, int S, int T, const int64_t* ref_ids, const int* ref_counts, int R, int Tr,
+             long long id_end, int count_end, int V, float* out_scores, int* out_stats, void* stream);
+int dic_rouge_l(const int64_t* hyp_ids, int B, int S, int T, const int64_t* ref_ids, const int* ref_counts, int R, int Tr,
+                long long id_end, int count_end, int V, float beta, float* out_scores, int* out_lcs, void* stream);
+
 /* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
  *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
  *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both
