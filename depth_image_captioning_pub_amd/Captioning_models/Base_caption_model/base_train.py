@@ -17,13 +17,13 @@ lam = 0.7             # base_train.py:22
 tqdm_disable = True   # base_train.py:21
 
 
-def train_base_soft(ext, useData, config=None, process_group=None, stats=None):
+def train_base_soft(ext, useData, config=None, process_group=None, stats=None, scst_epochs=None):
     config = config or ConfigTrain()
     return _train(ext, useData, hard=False, config=config, process_group=process_group, stats=stats, depth_branch=False,
-                  tag="base_soft", save_directory=config.save_directory_soft)
+                  tag="base_soft", save_directory=config.save_directory_soft, scst_epochs=scst_epochs)
 
 
-def train_base_hard(ext, useData, config=None, process_group=None, stats=None):
+def train_base_hard(ext, useData, config=None, process_group=None, stats=None, scst_epochs=None):
     config = config or ConfigTrain()
     return _train(ext, useData, hard=True, config=config, process_group=process_group, stats=stats, depth_branch=False,
-                  tag="base_hard", save_directory=config.save_directory_soft)      # (sic: base_train.py:253)
+                  tag="base_hard", save_directory=config.save_directory_soft, scst_epochs=scst_epochs)      # (sic: base_train.py:253)

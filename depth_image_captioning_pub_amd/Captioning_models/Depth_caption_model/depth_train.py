@@ -16,7 +16,8 @@ from collections import deque
 import numpy as np
 import torch
 
-from ... import native, synthetic as syn
+from ... import metrics, native, synthetic as syn
+from ...cider import CiderD
 from ..._lib import DicError
 from ...engine import CaptionTrainer
 from ..config import ConfigTrain
@@ -75,11 +76,64 @@ def _gumbel_draws(tmax: int, batch: int, epoch: int, iteration: int, rank: int, 
     return syn.gumbel_uniforms(tmax, batch, seed=seed)
 
 
+def _scst_epochs(trainer, config, rank: int, first_epoch: int, n_epochs: int, reward_file: str):
+    """`n_epochs` epochs of CaptionTrainer.scst_step behind the cross-entropy epochs (no counterpart in the reference).  The
+    reward of a batch is metrics.reward_fn (config.scst_reward_weights; CIDEr-D by default) against the batch's
+    synthetic.reference_captions, with the idf table of those references; sampled captions, rewards and token counts stay on the
+    device.  Appends "epoch, mean reward" per epoch to `reward_file`; returns the means."""
+    dev = config.device
+    ids = syn.special_token_ids(config.vocab_size)
+    id_start, id_end = ids["<start>"], ids["<end>"]
+    depth_branch = trainer.use_depth
+    means = []
+    for epoch in range(first_epoch, first_epoch + n_epochs):
+        def on_device():
+            for it, (imgs, depth, _, lens) in enumerate(_synthetic_batches(config, rank, config.iters_per_epoch, 1000 * epoch)):
+                refs = syn.reference_captions(len(lens), config.vocab_size, seed=1000 * epoch + 7919 * it + rank,
+                                              max_len=max(5, min(15, config.seq_len - 1)))
+                scorer = CiderD.from_references(refs, config.vocab_size, id_end, device=dev)
+                ref_ids, ref_counts = scorer.pack_references(refs)
+                reward = metrics.reward_fn(ref_ids, ref_counts, id_end=id_end, vocab=config.vocab_size, cider=scorer,
+                                           weights=config.scst_reward_weights)
+                yield imgs.to(dev), (depth.to(dev) if depth_branch else None), reward
+        ahead, stream_it = [], on_device()
+        for nxt in stream_it:
+            ahead.append(nxt)
+            if len(ahead) > 2:
+                break
+        rewards = []
+        while ahead:
+            imgs, depth, reward = ahead.pop(0)
+            nxt = next(stream_it, None)
+            if nxt is not None:
+                ahead.append(nxt)
+            _, mean = trainer.scst_step(imgs, depth, reward, id_start=id_start, id_end=id_end, n_samples=config.scst_samples,
+                                        max_length=config.seq_len, next_imgs=[a[0] for a in ahead[:2]])
+            rewards.append(mean)                                        # device tensors: no per-iteration host sync
+        trainer.check_status()
+        means.append(float(torch.cat(rewards).mean().item()))
+        if rank == 0:
+            with open(reward_file, "a") as f:
+                print(f"{epoch}, {means[-1]}", file=f)
+    return means
+
+
 def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None, depth_branch: bool = True,
-           tag: str = None, save_directory: str = None):
+           tag: str = None, save_directory: str = None, scst_epochs: int = None):
     """Shared loop of train_Cdepth_{soft,hard} and (depth_branch=False: no depth encoder, decoder-only optimiser, two
-    checkpoints) of train_base_{soft,hard} (Base_caption_model/base_train.py:24-234, 248-460)."""
+    checkpoints) of train_base_{soft,hard} (Base_caption_model/base_train.py:24-234, 248-460).
+    scst_epochs (default: config.scst_epochs, 0): further epochs of self-critical training behind the cross-entropy epochs, soft
+    attention only; their mean reward per epoch goes to <tag>_scst_reward_<useData><ext>.csv."""
     config = config or ConfigTrain()
+    scst_epochs = int(getattr(config, "scst_epochs", 0) if scst_epochs is None else scst_epochs)
+    if scst_epochs < 0:
+        raise DicError(f"scst_epochs={scst_epochs} must be >= 0")
+    if scst_epochs > 0 and hard:
+        raise DicError("scst_epochs > 0 with hard attention: self-critical training samples and scores with the soft-attention "
+                       "decoders only (CaptionTrainer.scst_step); there is no hard-attention counterpart")
+    if scst_epochs > 0 and bool(getattr(config, "use_dpt", False)):
+        raise DicError("scst_epochs > 0 with config.use_dpt: the self-critical epochs take their depth maps from the synthetic "
+                       "batches, not from the DPT front-end's cache")
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: the MSCOCO / original-dataset loaders and the vocabulary pickle are outside "
                        "this build's scope (SURVEY.md 8f) and not available offline; use useData='synthetic' "
@@ -167,6 +221,11 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
                 torch.save(sd["decoder"], f"{save_directory}/{tag}_decoder_best_{useData}{ext}.pth")
                 if depth_branch:
                     torch.save(sd["depth_encoder"], f"{save_directory}/{tag}_D_encoder_best_{useData}{ext}.pth")
+    if scst_epochs > 0:
+        means = _scst_epochs(trainer, config, rank, config.num_epochs, scst_epochs,
+                             f"{save_directory}/{tag}_scst_reward_{useData}{ext}.csv")
+        if stats is not None:
+            stats.update(scst_mean_rewards=means)
     if stats is not None:
         stats.update(prefetch_dropped=trainer.prefetch_dropped)
     if stats is not None and front is not None:
@@ -176,9 +235,9 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
     return history
 
 
-def train_Cdepth_soft(ext, useData, config=None, process_group=None, stats=None):
-    return _train(ext, useData, hard=False, config=config, process_group=process_group, stats=stats)
+def train_Cdepth_soft(ext, useData, config=None, process_group=None, stats=None, scst_epochs=None):
+    return _train(ext, useData, hard=False, config=config, process_group=process_group, stats=stats, scst_epochs=scst_epochs)
 
 
-def train_Cdepth_hard(ext, useData, config=None, process_group=None, stats=None):
-    return _train(ext, useData, hard=True, config=config, process_group=process_group, stats=stats)
+def train_Cdepth_hard(ext, useData, config=None, process_group=None, stats=None, scst_epochs=None):
+    return _train(ext, useData, hard=True, config=config, process_group=process_group, stats=stats, scst_epochs=scst_epochs)

@@ -36,3 +36,7 @@ class ConfigTrain(object):
         self.iters_per_epoch = 20
         self.use_dpt = False            # True = BASELINE config 5: depth maps predicted by the DPT-Hybrid front-end in epoch 0
         self.dpt_config = None          # synthetic.DptConfig (None = vitb_rn50_384)
+        # self-critical sequence training after the cross-entropy epochs (not in the reference; soft attention only)
+        self.scst_epochs = 0            # further epochs of CaptionTrainer.scst_step; 0 = none, nothing differs
+        self.scst_samples = 5           # captions sampled per image
+        self.scst_reward_weights = {"CIDEr": 1.0}       # metrics.reward_fn weights: CIDEr, Bleu_1..4, ROUGE_L

@@ -10,8 +10,10 @@ in one more launch (dic_cider_d), so the step stays free of host
 metrics.reward_fn mixes it with per-caption BLEU-1..4 and ROUGE-L (dic_bleu, dic_rouge_l, DESIGN.md 5.16: one more launch per
 metric of non-zero weight), e.g. CIDEr-D + 0.5 BLEU-4, as a device tensor as well.
 
-Out of scope here: the engine's flat parameter buffers and fused train step and the data-parallel gradient exchange; a METEOR
-reward (a Java jar and WordNet, not a rule over token ids) - reward_fn is the seam for any other reward."""
+The same step on the engine's flat parameter buffers - one AdamW launch, the depth encoder trained through it, the data-parallel
+gradient exchange with a global token count - is engine.CaptionTrainer.scst_step; this module stays the route
+for nn.Module decoders and torch optimisers.  Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
+reward_fn is the seam for any other reward."""
 from __future__ import annotations
 
 from .. import losses

@@ -1,7 +1,9 @@
 """CLI with the reference's argument convention (depth_main.py:14-35):
-    python -m depth_image_captioning_pub_amd.depth_main {soft,hard} cnn {coco,original,synthetic}
+    python -m depth_image_captioning_pub_amd.depth_main {soft,hard} cnn {coco,original,synthetic} [--scst-epochs N]
 (the reference script itself does not run as shipped - quirk Q5 - so this keeps its intent: 3 repetitions of
-train_Cdepth_{soft,hard}(i, useData)).  `mlp` is a no-op in the reference (depth_main.py:27-28,34-35) and here."""
+train_Cdepth_{soft,hard}(i, useData)).  `mlp` is a no-op in the reference (depth_main.py:27-28,34-35) and here.
+--scst-epochs N (not in the reference): N further epochs of self-critical training behind the cross-entropy epochs
+(CaptionTrainer.scst_step, soft attention only; default: config.scst_epochs = 0)."""
 from __future__ import annotations
 
 import sys
@@ -22,11 +24,40 @@ def torch_seed(seed=123):                      # depth_main.py:7-12
     np.random.seed(seed)
 
 
+def take_scst_epochs(args):
+    """(args without `--scst-epochs N` / `--scst-epochs=N`, N or None when the option is absent); ValueError on a bad value."""
+    rest, n, i = [], None, 0
+    while i < len(args):
+        a = str(args[i])
+        if a == "--scst-epochs" or a.startswith("--scst-epochs="):
+            if "=" in a:
+                value = a.split("=", 1)[1]
+            else:
+                i += 1
+                if i >= len(args):
+                    raise ValueError("--scst-epochs needs a value")
+                value = str(args[i])
+            try:
+                n = int(value)
+            except ValueError:
+                raise ValueError(f"--scst-epochs needs a non-negative integer, got {value!r}") from None
+            if n < 0:
+                raise ValueError(f"--scst-epochs needs a non-negative integer, got {value!r}")
+        else:
+            rest.append(args[i])
+        i += 1
+    return rest, n
+
+
 def main(argv=None):
     torch_seed()
     exp_time = EXP_TIME
     datas = ["coco", "original", "synthetic"]
-    args = list(sys.argv if argv is None else argv)
+    try:
+        args, scst_epochs = take_scst_epochs(list(sys.argv if argv is None else argv))
+    except ValueError as e:
+        print(e)
+        return 1
     if len(args) < 4:
         print("input {soft/hard} {cnn/mlp} {coco/original/synthetic}")
         return 1
@@ -41,7 +72,7 @@ def main(argv=None):
         print("input {soft/hard} {cnn/mlp} {coco/original/synthetic}")
         return 1
     for i in range(exp_time):
-        fn(i, use_data)
+        fn(i, use_data, scst_epochs=scst_epochs)
     return 0
 
 

@@ -106,6 +106,54 @@ def exchange_gradients(flat_grad: torch.Tensor, spans, group, between=None) -> N
         w.wait()
 
 
+SCST_MAX_CELLS = 491520      # B * S * T: the limit of dic_decoder_states_fwd / _bwd and dic_scst_loss (include/dic.h)
+
+
+def scst_arguments(hard: bool, B: int, n_samples: int, max_length: int, baseline, uniform_u=None, drop_mult=None,
+                   global_tokens=None, virtual_world=None, reward_fn=None) -> int:
+    """The argument checks of CaptionTrainer.scst_step, made before anything is launched (no device needed).  Returns the
+    baseline mode of dic_scst_loss: 0 none | 1 others | 2 per caption | 3 per image ("greedy", or a tensor [B])."""
+    if hard:
+        raise DicError("scst_step: sampling and scoring are built for the soft-attention decoders only (a Gumbel-max decode draws "
+                       "its attention already, and its likelihood is an expectation over those draws); there is no "
+                       "hard-attention counterpart")
+    S, T = int(n_samples), int(max_length)
+    if reward_fn is not None and not callable(reward_fn):
+        raise DicError("scst_step: reward_fn must be callable: reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S]")
+    if not 1 <= S <= 8:
+        raise DicError(f"scst_step: n_samples={S} is outside 1 .. 8 (the S-row routes share one feature read among at most 8 rows)")
+    if not 1 <= T <= 64:
+        raise DicError(f"scst_step: max_length={T} is outside 1 .. 64")
+    if B < 1 or B * S * T > SCST_MAX_CELLS:
+        raise DicError(f"scst_step: B*n_samples*max_length = {B * S * T} is outside 1 .. {SCST_MAX_CELLS} (the states route's limit)")
+    if isinstance(baseline, str):
+        if baseline not in ("others", "greedy"):
+            raise DicError(f"scst_step: baseline must be 'others', 'greedy', a tensor [B,S] or [B], or None, got {baseline!r}")
+        if baseline == "others" and S < 2:
+            raise DicError("scst_step: the 'others' baseline is the mean reward of the image's other captions and needs "
+                           f"n_samples >= 2, got {S}")
+        mode = 1 if baseline == "others" else 3
+    elif baseline is None:
+        mode = 0
+    elif torch.is_tensor(baseline) and tuple(baseline.shape) in ((B, S), (B,)):
+        mode = 3 if baseline.dim() == 1 else 2
+    else:
+        raise DicError(f"scst_step: baseline must be 'others', 'greedy', a tensor [{B},{S}] or [{B}], or None, got "
+                       f"{tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__}")
+    if uniform_u is not None and tuple(uniform_u.shape) != (T, B * S):
+        raise DicError(f"scst_step: uniform_u must be [max_length, B*n_samples] = [{T}, {B * S}], got {tuple(uniform_u.shape)}")
+    if drop_mult is not None and tuple(drop_mult.shape) != (B * S, T, native.D_HID):
+        raise DicError(f"scst_step: drop_mult must be [B*n_samples, max_length, {native.D_HID}] = [{B * S}, {T}, {native.D_HID}], got "
+                       f"{tuple(drop_mult.shape)}")
+    if global_tokens is not None and not (torch.is_tensor(global_tokens) and global_tokens.dtype == torch.int64
+                                          and global_tokens.numel() == 1 and global_tokens.is_cuda):
+        raise DicError("scst_step: global_tokens must be an int64 device tensor of one element (the token count never visits the "
+                       "host; train_step's host integer has no place here)")
+    if virtual_world is not None and int(virtual_world) < 1:
+        raise DicError(f"scst_step: virtual_world={virtual_world} must be >= 1")
+    return mode
+
+
 class _PrefetchSlot:
     """One frozen-ResNet forward in flight: own HIP stream, own runner (shared weights, own workspace, BatchNorm
     running-statistic pointers redirected to `delta`), own feature buffer, static input buffer and captured graphs."""
@@ -234,6 +282,8 @@ class CaptionTrainer:
         self.depth_fwd_count = 0       # train-mode depth-encoder forwards (= BatchNorm num_batches_tracked)
         self.rng_offset = 0
         self.seed = seed
+        self.sample_count = 0          # scst_step calls that drew their own uniforms: part of the sampling generator's key
+        self._expand_idx = {}          # B -> int64 [B*196] row indices of the 49 -> 196 cell replication (scst_step)
         # every rank draws its own dropout masks: the rank is mixed into the Philox key (same key on all ranks would
         # apply one mask pattern to every shard of the global batch)
         self.drop_seed = (seed + 0x9E3779B97F4A7C15 * self.rank) & 0xFFFFFFFFFFFFFFFF
@@ -501,6 +551,140 @@ class CaptionTrainer:
         if self.keep_outputs:
             self.last["decoder_tape"] = tape           # parity tests: native.decoder_attention_relu_mask(tape)
         return loss
+
+    # ---- self-critical sequence training -----------------------------------------------------------
+    def _expand_cells(self, feats: torch.Tensor) -> torch.Tensor:
+        """[B,49,2048] -> [B,196,2048] by the 2x2 replication AdaptiveAvgPool2d(14) performs on a 7x7 map: cell (i,j) <- (i//2, j//2),
+        one gather (dic_gather_rows).  The ResNet is frozen: nothing flows back through it."""
+        B = feats.shape[0]
+        idx = self._expand_idx.get(B)
+        if idx is None:
+            i = torch.arange(14)
+            cell = ((i // 2).view(14, 1) * 7 + (i // 2).view(1, 14)).reshape(-1)                      # [196] -> its 7x7 cell
+            idx = (torch.arange(B).view(B, 1) * native.L_COMPACT + cell.view(1, -1)).reshape(-1).to(self.device)
+            self._expand_idx[B] = idx
+        return native.gather_rows(feats.reshape(B * native.L_COMPACT, native.D_ENC), idx).view(B, native.L_CELLS, native.D_ENC)
+
+    def scst_step(self, imgs: Optional[torch.Tensor], depth_map: Optional[torch.Tensor], reward_fn, *, id_start: int, id_end: int,
+                  n_samples: int = 5, max_length: int = 30, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  baseline="others", uniform_u: Optional[torch.Tensor] = None, drop_mult: Optional[torch.Tensor] = None,
+                  precomputed_features: Optional[torch.Tensor] = None, next_imgs=None,
+                  global_tokens: Optional[torch.Tensor] = None, apply_update: bool = True, virtual_world: Optional[int] = None):
+        """One self-critical step (Rennie et al. 2017; no counterpart in the reference) on the engine's flat buffers: sample
+        n_samples captions per image (dic_decoder_sample), reward them, score them with a tape (dic_decoder_states_fwd +
+        dic_token_logprobs), dic_scst_loss, back through dic_token_logprobs_bwd, dic_decoder_states_bwd and the depth encoder,
+        the bucketed exchange, one guarded AdamW.  Soft attention only.  Everything is enqueued on the current stream; ids,
+        lengths, rewards and token counts never visit the host.  Returns (loss, mean reward) as 1-element device tensors.
+        reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S] on the device (metrics.reward_fn, CiderD.reward_fn).
+        baseline: "others" | "greedy" (the reward of dic_decoder_greedy's caption of the same features, per image) | a tensor
+          [B,S] or [B] | None.
+        uniform_u: float32 [max_length, B*n_samples] draws in [0,1); default: a device generator keyed by (seed, call number, rank).
+        drop_mult: float32 [B*n_samples, max_length, 128]; default: dic_dropout_mask at the trainer's rate (none at rate 0).
+          Dropout acts on the scored hidden states only; sampling runs without it.
+        The S-row routes run on 196 cells: both encoders run in that layout here (next_imgs are prefetched in it too); a map an
+          earlier train_step prefetched compact is expanded by replication.
+        Normaliser: the loss is -(sum adv * logprob) / N with N the token count of the GLOBAL batch - with a process group the
+          all-reduced sum of the ranks' counts (launched right after sampling, waited for before the loss head), so the ranks'
+          gradients are shares whose exchanged sum is the single-device gradient; `global_tokens` (int64 device tensor, one
+          element) overrides it; with neither, this batch's own count, times virtual_world when that is given.
+        next_imgs, precomputed_features, apply_update, virtual_world: as in train_step.  The returned loss is this rank's share."""
+        B = imgs.shape[0] if imgs is not None else (precomputed_features.shape[0] if precomputed_features is not None else 0)
+        mode = scst_arguments(self.hard, B, n_samples, max_length, baseline, uniform_u, drop_mult, global_tokens, virtual_world,
+                              reward_fn)
+        if self.use_depth and depth_map is None:
+            raise DicError("scst_step: this trainer has a depth encoder: depth_map is required")
+        S, T = int(n_samples), int(max_length)
+        R = B * S
+        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
+        self.marks = []
+        self._mark("start")
+        if precomputed_features is None:
+            feats = self._take_prefetched(imgs)
+            if feats is None:
+                feats = self._resnet_eager(imgs, True, False)
+                self._guard_take(self.resnet)
+            if next_imgs is not None:
+                upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
+                for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
+                    if k >= len(self.queue):
+                        self.prefetch_features(nxt, compact=False)
+            self._mark("resnet152_fwd")
+        else:
+            feats = precomputed_features
+            self._guard_take(None)
+        if feats.shape[1] == native.L_COMPACT:
+            feats = self._expand_cells(feats)
+        fdep = dtape = None
+        if self.use_depth:
+            fdep, dtape = native.depth_encoder_forward(self.enc_w, self.enc_state, depth_map.detach(), True,
+                                                       workspace=self.enc_ws, compact=False)
+            self.enc_ws = dtape.workspace
+            self.depth_fwd_count += 1
+            self.guard.bitwise_or_(native.depth_status_word(dtape))
+        self._mark("depth_encoder_fwd")
+        if uniform_u is None:
+            gen = torch.Generator(self.device)
+            gen.manual_seed((((self.seed * 1000003 + self.sample_count) * 64 + self.rank) ^ 0x5C57) & 0x7FFFFFFFFFFFFFFF)
+            self.sample_count += 1
+            uniform_u = torch.rand((T, R), generator=gen, device=self.device)
+        ids, _, lengths = native.decoder_sample(self.dec_w, feats, fdep, id_start, id_end, S, uniform_u, T, float(temperature),
+                                                int(top_k), float(top_p))
+        nworld = virtual_world if virtual_world is not None else self.world
+        tokens, pending = global_tokens, None
+        if tokens is None and (self.world > 1 and virtual_world is None):
+            tokens = lengths.sum(dtype=torch.int64).view(1)
+            pending = torch.distributed.all_reduce(tokens, op=torch.distributed.ReduceOp.SUM, group=self.pg, async_op=True)
+        elif tokens is None and nworld > 1:          # no collective: every rank is taken to hold this rank's count
+            tokens = lengths.sum(dtype=torch.int64).view(1) * int(nworld)
+        self._mark("sample")
+        rewards = reward_fn(ids, lengths)
+        base = None
+        if isinstance(baseline, str) and baseline == "greedy":
+            g_ids, _ = native.decoder_greedy(self.dec_w, feats, fdep, id_start, T)
+            ended = g_ids == int(id_end)
+            g_len = torch.where(ended.any(1), ended.int().argmax(1) + 1, torch.full_like(g_ids[:, 0], T)).to(torch.int32)
+            base = reward_fn(g_ids.unsqueeze(1), g_len.unsqueeze(1))
+            if tuple(base.shape) != (B, 1):
+                raise DicError(f"scst_step: reward_fn must return [B,S] = [{B}, 1] for the greedy captions, got {tuple(base.shape)}")
+            base = base.detach().float().reshape(B).contiguous()
+        elif torch.is_tensor(baseline):
+            base = baseline.detach().to(self.device, torch.float32).contiguous()
+        if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
+            raise DicError(f"scst_step: reward_fn must return a tensor [B,S] = [{B}, {S}], got "
+                           f"{tuple(rewards.shape) if torch.is_tensor(rewards) else type(rewards).__name__}")
+        rewards = rewards.detach().to(self.device, torch.float32).contiguous()
+        self._mark("reward")
+        if drop_mult is None and self.p_drop > 0:
+            drop_mult = native.dropout_mask((R, T, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset, self.device)
+            self.rng_offset += R * T * native.D_HID // 4 + 1
+        hidden, targets, lens, tape = native.decoder_states_forward(self.dec_w, feats, fdep, id_start, id_end, ids, drop_mult)
+        logprobs, lse = native.token_logprobs(hidden.view(T * R, native.D_HID), self.dec_w["linear.weight"],
+                                              self.dec_w["linear.bias"], targets.view(-1))
+        self._mark("states_fwd")
+        if pending is not None:
+            pending.wait()
+        loss, d_logprob, _ = native.scst_loss(logprobs.view(T, R), lens, rewards, base, mode, tokens)
+        self._mark("loss")
+        d_hidden = native.token_logprobs_bwd_into(self.dec_g, hidden.view(T * R, native.D_HID), self.dec_w["linear.weight"],
+                                                  self.dec_w["linear.bias"], targets.view(-1), lse, d_logprob.view(-1))
+        dfeat = native.decoder_states_backward_into(self.dec_g, tape, d_hidden.view(T, R, native.D_HID),
+                                                    need_features=self.use_depth)
+        self._mark("states_bwd")
+        if not self.use_depth:
+            if self.world > 1:
+                exchange_gradients(self.flat.grad, [self.dec_span], self.pg)
+        elif self.world > 1:   # decoder bucket goes out while the depth-encoder backward still runs
+            exchange_gradients(self.flat.grad, [self.dec_span, self.enc_span], self.pg,
+                               between=lambda: native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g))
+        else:
+            native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g)
+        self._mark("depth_encoder_bwd+allreduce")
+        if apply_update:
+            self.apply_update()
+        self._mark("adamw")
+        self.last = {"ids": ids, "lengths": lengths, "rewards": rewards, "logprobs": logprobs.view(T, B, S).permute(1, 2, 0),
+                     "features": feats, "depth_features": fdep}
+        return loss, rewards.mean().view(1)
 
     def apply_update(self) -> None:
         """AdamW on the flat buffer with whatever self.flat.grad holds (depth_train.py:221)."""

@@ -630,12 +630,35 @@ def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     return logprobs, lse
 
 
+def _grad_out(grads: Dict[str, torch.Tensor], key: str, shape, what: str) -> torch.Tensor:
+    """grads[key] as an output a kernel may write: float32, on the GPU, contiguous (never a copy: the caller reads ITS tensor)."""
+    g = grads.get(key)
+    if g is None:
+        raise _lib.DicError(f"{what}: grads has no entry {key!r}")
+    if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == tuple(shape)):
+        raise _lib.DicError(f"{what}: grads[{key!r}] must be a contiguous float32 GPU tensor {tuple(shape)}, got {g.dtype} "
+                            f"{tuple(g.shape)} on {g.device}")
+    return g
+
+
 def token_logprobs_bwd(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor,
                        d_logprob: torch.Tensor, d_lse: Optional[torch.Tensor] = None, need=(True, True, True)):
     """dic_token_logprobs_bwd: the gradients of sum(d_logprob * logprobs) + sum(d_lse * lse) of token_logprobs with respect to
     hidden, weight and bias, the [M,V] logits never stored (semantics: include/dic.h).  lse: what token_logprobs returned for the
     same inputs.  d_logprob, d_lse (optional) float32 [M].  need: which of (d_hidden [M,128], d_weight [V,128], d_bias [V]) to
     compute; one that was not requested is None."""
+    return _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, need, None)
+
+
+def token_logprobs_bwd_into(grads: Dict[str, torch.Tensor], hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                            targets: torch.Tensor, lse: torch.Tensor, d_logprob: torch.Tensor, d_lse: Optional[torch.Tensor] = None):
+    """token_logprobs_bwd with d_weight / d_bias written (not accumulated) into the caller's contiguous float32 GPU tensors
+    grads["linear.weight"] [V,128] / grads["linear.bias"] [V] - the engine's views of its flat gradient buffer - instead of new
+    ones.  Returns d_hidden [M,128]."""
+    return _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, (True, True, True), grads)[0]
+
+
+def _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, need, grads):
     lib = _lib.load()
     h, w, b = _dev_f32(hidden, "hidden"), _dev_f32(weight, "weight"), _dev_f32(bias, "bias")
     tg = _dev_i64(targets, "targets")
@@ -658,6 +681,11 @@ def token_logprobs_bwd(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.T
     d_hidden = torch.empty((M, D_HID), dtype=torch.float32, device=h.device) if need[0] else None
     d_weight = torch.empty((V, D_HID), dtype=torch.float32, device=h.device) if need[1] else None
     d_bias = torch.empty((V,), dtype=torch.float32, device=h.device) if need[2] else None
+    if grads is not None:
+        if need[1]:
+            d_weight = _grad_out(grads, "linear.weight", (V, D_HID), "token_logprobs_bwd")
+        if need[2]:
+            d_bias = _grad_out(grads, "linear.bias", (V,), "token_logprobs_bwd")
     rc = lib.dic_token_logprobs_bwd(ptr(h), ptr(w), ptr(b), ptr(tg), ptr(ls), ptr(g), ptr(dl), M, V, ptr(d_hidden), ptr(d_weight),
                                     ptr(d_bias), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
     check(rc, "dic_token_logprobs_bwd")
@@ -746,6 +774,18 @@ def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Ten
 def decoder_states_backward(tape: StatesTape, d_hidden: torch.Tensor, need_features: bool = True):
     """dic_decoder_states_bwd: backward through time of decoder_states_forward.  d_hidden float32 [T,R,128] (rows behind a
     caption's length are ignored).  Returns (grads: dict over the 15 keys STATES_GRAD_KEYS, d_features [B,196,2048] or None)."""
+    return _decoder_states_backward(tape, d_hidden, need_features, None)
+
+
+def decoder_states_backward_into(grads: Dict[str, torch.Tensor], tape: StatesTape, d_hidden: torch.Tensor,
+                                 need_features: bool = True):
+    """decoder_states_backward with the 15 gradients written (not accumulated) into the caller's contiguous float32 GPU tensors
+    grads[k], k in STATES_GRAD_KEYS (further keys are left alone) - the engine's views of its flat gradient buffer.  Returns
+    d_features [B,196,2048] or None."""
+    return _decoder_states_backward(tape, d_hidden, need_features, grads)[1]
+
+
+def _decoder_states_backward(tape, d_hidden, need_features, grads):
     lib = _lib.load()
     dh = _dev_f32(d_hidden, "d_hidden")
     R = tape.B * tape.S
@@ -753,7 +793,10 @@ def decoder_states_backward(tape: StatesTape, d_hidden: torch.Tensor, need_featu
         raise _lib.DicError(f"decoder_states: d_hidden must be [T,R,{D_HID}] = [{tape.T},{R},{D_HID}], got {tuple(dh.shape)}")
     wp, keep = decoder_ptrs(tape.weights)
     dev = dh.device
-    grads = {k: torch.empty_like(tape.weights[k]) for k in STATES_GRAD_KEYS}
+    if grads is None:
+        grads = {k: torch.empty_like(tape.weights[k]) for k in STATES_GRAD_KEYS}
+    else:
+        grads = {k: _grad_out(grads, k, tape.weights[k].shape, "decoder_states") for k in STATES_GRAD_KEYS}
     gp = DecoderPtrs()
     for key, field in DECODER_FIELDS:
         setattr(gp, field, grads[key].data_ptr() if key in grads else None)
@@ -850,6 +893,62 @@ def rouge_l(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tens
     if squeeze:
         scores, lcs = scores[:, 0], (lcs[:, 0] if return_lcs else None)
     return (scores, lcs) if return_lcs else scores
+
+
+def gather_rows(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """dic_gather_rows: out[r,:] = table[idx[r],:] for table float32 [N,W] (W a multiple of 4) and idx int64 [n], n <= 65535."""
+    t, i = _dev_f32(table, "table"), _dev_i64(idx, "idx")
+    if t.dim() != 2 or i.dim() != 1 or not 0 < i.shape[0] <= 65535:
+        raise _lib.DicError(f"gather_rows: table must be [N,W] and idx [n] with 0 < n <= 65535, got {tuple(t.shape)} and {tuple(i.shape)}")
+    out = torch.empty((i.shape[0], t.shape[1]), dtype=torch.float32, device=t.device)
+    check(_lib.load().dic_gather_rows(ptr(t), ptr(i), int(i.shape[0]), C.c_longlong(t.shape[1]), ptr(out), stream_ptr()),
+          "dic_gather_rows")
+    return out
+
+
+def scst_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: torch.Tensor, baseline: Optional[torch.Tensor] = None,
+              baseline_mode: int = 1, total_tokens: Optional[torch.Tensor] = None, return_advantage: bool = False):
+    """dic_scst_loss: the self-critical loss head over time-major log-probabilities, one launch, on the device (semantics:
+    include/dic.h).  logprobs float32 [T,R] or [T,B,S] (token_logprobs' output viewed so), lengths int32 [B,S], rewards float32
+    [B,S]; baseline_mode 0 none | 1 others | 2 per caption (baseline [B,S]) | 3 per image (baseline [B]); total_tokens: int64
+    device tensor of one element, the normaliser N (None: this call's own sum of lengths).
+    Returns (loss float32 [1], d_logprob float32 [T,R], tokens int64 [1][, advantage float32 [B,S]])."""
+    lib = _lib.load()
+    lp, rw = _dev_f32(logprobs, "logprobs"), _dev_f32(rewards, "rewards")
+    if not lengths.is_cuda or lengths.dtype != torch.int32 or lengths.dim() != 2:
+        raise _lib.DicError(f"scst_loss: lengths must be int32 [B,S] on the GPU, got {lengths.dtype} {tuple(lengths.shape)} on "
+                            f"{lengths.device}")
+    ln = lengths if lengths.is_contiguous() else lengths.contiguous()
+    B, S = int(ln.shape[0]), int(ln.shape[1])
+    R = B * S
+    if lp.dim() not in (2, 3) or lp.numel() != lp.shape[0] * R or (lp.dim() == 3 and tuple(lp.shape[1:]) != (B, S)):
+        raise _lib.DicError(f"scst_loss: logprobs must be time-major [T,{R}] (or [T,{B},{S}]), got {tuple(lp.shape)}")
+    T = int(lp.shape[0])
+    if tuple(rw.shape) != (B, S):
+        raise _lib.DicError(f"scst_loss: rewards must be [{B},{S}], one per caption, got {tuple(rw.shape)}")
+    mode = int(baseline_mode)
+    bl = None
+    if mode in (2, 3):
+        want = (B, S) if mode == 2 else (B,)
+        if baseline is None or tuple(baseline.shape) != want:
+            raise _lib.DicError(f"scst_loss: baseline_mode {mode} needs a baseline {want}, got "
+                                f"{None if baseline is None else tuple(baseline.shape)}")
+        bl = _dev_f32(baseline, "baseline")
+    tt = None
+    if total_tokens is not None:
+        if not (total_tokens.is_cuda and total_tokens.dtype == torch.int64 and total_tokens.numel() == 1):
+            raise _lib.DicError(f"scst_loss: total_tokens must be an int64 GPU tensor of one element, got {total_tokens.dtype} "
+                                f"{tuple(total_tokens.shape)} on {total_tokens.device}")
+        tt = total_tokens
+    dev = lp.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    d_logprob = torch.empty((max(T, 1), max(R, 1)), dtype=torch.float32, device=dev)
+    tokens = torch.empty(1, dtype=torch.int64, device=dev)
+    adv = torch.empty((max(B, 1), max(S, 1)), dtype=torch.float32, device=dev) if return_advantage else None
+    rc = lib.dic_scst_loss(ptr(lp), ptr(ln), ptr(rw), ptr(bl), B, S, T, mode, ptr(tt), ptr(loss), ptr(d_logprob), ptr(adv),
+                           ptr(tokens), stream_ptr())
+    check(rc, "dic_scst_loss")
+    return (loss, d_logprob, tokens, adv) if return_advantage else (loss, d_logprob, tokens)
 
 
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,

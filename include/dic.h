@@ -375,6 +375,42 @@ int dic_bleu(const int64_t* hyp_ids, int B, int S, int T, const int64_t* ref_ids
 int dic_rouge_l(const int64_t* hyp_ids, int B, int S, int T, const int64_t* ref_ids, const int* ref_counts, int R, int Tr,
                 long long id_end, int count_end, int V, float beta, float* out_scores, int* out_lcs, void* stream);
 
+/* the loss head of self-critical sequence training (Rennie et al. 2017) over the log-probabilities of SAMPLED captions: baseline,
+ *   advantage, per-caption weight, the gradient with respect to every log-probability and the loss value, in ONE launch enqueued on
+ *   `stream`: no workspace, no host copy, no synchronisation.  The loss is losses.self_critical_loss's,
+ *   -(sum over tokens of adv_r * logprob[t,r]) / N; what this entry point adds is a normaliser N that is a DEVICE scalar (the token
+ *   count of a global batch of which this call holds one rank's rows), the gradient in the time-major layout
+ *   dic_token_logprobs_bwd takes as d_logprob, and a loss value of a fixed summation order.  This comment is the specification.
+ *   logprobs float [T,R] time-major, R = B*S, row r = b*S + s: what dic_token_logprobs returns for dic_decoder_states_fwd's
+ *   out_hidden / out_targets.  lengths int [B,S], rewards float [B,S]; baseline float [B,S] (mode 2) or [B] (mode 3), not read in
+ *   modes 0 and 1.  total_tokens (nullable) long long [1] on the device.  All pointers are device pointers.
+ *   In fp32 unless said otherwise, per row r of image b:
+ *     len_r = min(max(lengths[r], 1), T)
+ *     b_r   = 0                                                             baseline_mode 0 (none)
+ *           = ((sum over s' of rewards[b,s'], ascending s') - rewards[r]) / (float)(S - 1)      1 (others; needs S >= 2)
+ *           = baseline[r]                                                                 2 (per caption)
+ *           = baseline[b]                                                                 3 (per image, e.g. the greedy caption's reward)
+ *     adv_r = rewards[r] - b_r    (mode 0: rewards[r] itself)
+ *     N     = total_tokens ? total_tokens[0] : sum over r of len_r   (integers; >= R >= 1.  A given N must be >= 1: it is a device
+ *             value and is not checked)
+ *     w_r   = -adv_r / (float)N   (one correctly rounded division)
+ *     out_d_logprob[t,r] = w_r for t < len_r, exactly 0 for t >= len_r (selected, not multiplied)          float [T,R]
+ *     out_loss[0] = sum over r of (double)w_r * (double)(the fp32 sum of logprobs[t,r] over t < len_r in ascending t): the products
+ *             are exact, their sum runs in fp64 in ascending r on one accumulator and is rounded to fp32 once            float [1]
+ *     out_advantage[r] = adv_r  (nullable)  float [B,S];   out_tokens[0] = sum over r of len_r  (nullable)  long long [1]
+ *   logprobs[t,r] with t >= len_r is never read: any bytes there, NaN included, change nothing.  No gradient flows into rewards or
+ *   baseline.  With ranks that each pass the all-reduced sum of their out_tokens as total_tokens, the ranks' out_loss and
+ *   out_d_logprob are shares whose sum over ranks is the single-device loss and gradient of the global batch.
+ *   Properties: no float atomics and no hand-over between workgroups; every order is a function of (B, S, T) alone, so two calls
+ *   return identical bytes; row r of out_d_logprob and out_advantage depends only on image b's rewards, its own length and
+ *   baseline entry, and N.
+ *   B, S, T >= 1, B*S*T <= 491 520 (dic_decoder_states_fwd's limit), 0 <= baseline_mode <= 3, S >= 2 in mode 1, a baseline in modes
+ *   2 and 3, no null pointer other than baseline, total_tokens, out_advantage and out_tokens: a violation returns a negative code
+ *   and a dic_last_error() text that starts with "scst_loss:", before any HIP call.  DESIGN.md 5.17. */
+int dic_scst_loss(const float* logprobs, const int* lengths, const float* rewards, const float* baseline, int B, int S, int T,
+                  int baseline_mode, const long long* total_tokens, float* out_loss, float* out_d_logprob, float* out_advantage,
+                  long long* out_tokens, void* stream);
+
 /* ---- NIC / Show-and-Tell baseline (Base_caption_model/nic.py:23-175; `base_main.py nic`): frozen ResNet-152 -> global average
  *      pool -> nn.Linear(2048, 300) -> 2-layer nn.LSTM(300, 128) -> nn.Linear(128, V).  This comment is the specification.
  *   Sizes: E = DIC_NIC_E = 300 (config.py:28), H = DIC_H = 128, two layers (config.py:29), D = DIC_D.  Gate order i, f, g, o; both

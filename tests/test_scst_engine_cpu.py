@@ -1,0 +1,193 @@
+"""CPU: dic_scst_loss's fp64 restatement (tests/scst_engine_common.py) against losses.self_critical_loss + autograd, every refusal
+of the entry point before a launch, the preconditions of CaptionTrainer.scst_step, and the harness / CLI plumbing of
+`--scst-epochs`.  Nothing here needs a GPU."""
+import ctypes
+import inspect
+import types
+
+import pytest
+import torch
+
+from depth_image_captioning_pub_amd import _lib, build, engine, losses, native
+from depth_image_captioning_pub_amd.engine import CaptionTrainer
+from tests import scst_engine_common as sec
+
+
+def _lib_cpu():
+    lib = ctypes.CDLL(build.build())
+    lib.dic_last_error.restype = ctypes.c_char_p
+    return lib
+
+
+# ---- 1. the restatement is losses.self_critical_loss ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+@pytest.mark.parametrize("given_n", [False, True])
+def test_restatement_is_self_critical_loss_and_its_autograd(mode, given_n):
+    B, S, T = 4, 3, 9
+    g = torch.Generator().manual_seed(50 + mode)
+    lengths = torch.randint(1, T + 1, (B, S), generator=g, dtype=torch.int32)
+    lengths[0, 0], lengths[1, 2] = 1, T
+    rewards = torch.rand((B, S), generator=g, dtype=torch.float64) * 2 - 0.5
+    raw = (-torch.rand((B, S, T), generator=g, dtype=torch.float64) * 5).requires_grad_(True)
+    baseline = {0: None, 1: "others", 2: torch.rand((B, S), generator=g, dtype=torch.float64),
+                3: torch.rand((B,), generator=g, dtype=torch.float64)}[mode]
+    live = torch.arange(T).view(1, 1, T) < lengths.unsqueeze(-1)
+    lp = torch.where(live, raw, torch.zeros_like(raw))                  # what caption_logprobs returns: 0 from the length on
+    loss = losses.self_critical_loss(lp, lengths, rewards, baseline.unsqueeze(1) if mode == 3 else baseline)
+    total = int(lengths.sum())
+    n = 3 * total + 7 if given_n else None
+    if given_n:                                                          # the loss is linear in 1/N
+        loss = loss * total / n
+    loss.backward()
+    poisoned = torch.where(live, raw.detach(), torch.full_like(raw, float("nan")))      # never read behind the length
+    ref = sec.scst_loss_reference(poisoned.permute(2, 0, 1).reshape(T, B * S), lengths, rewards,
+                                  baseline if mode >= 2 else None, mode, n)
+    assert abs(float(ref["loss"]) - float(loss.detach())) <= 1e-12
+    d = ref["d_logprob"].view(T, B, S).permute(1, 2, 0)
+    assert float((d - raw.grad).abs().max()) <= 1e-12
+    assert bool((d[~live] == 0).all()) and ref["tokens"] == total
+    assert bool(torch.isfinite(ref["abs_sum"])) and float(ref["abs_sum"]) >= abs(float(ref["loss"]))
+
+
+def test_restatement_on_written_out_numbers():
+    """B 1, S 2, T 3; lengths 2 and 3; rewards 1 and 0: advantages +1 / -1 under "others", N = 5."""
+    lp = torch.tensor([[-1.0, -2.0], [-3.0, -4.0], [float("nan"), -5.0]])
+    ref = sec.scst_loss_reference(lp, torch.tensor([[2, 3]]), torch.tensor([[1.0, 0.0]]), None, 1)
+    assert ref["tokens"] == 5 and ref["advantage"].tolist() == [[1.0, -1.0]]
+    assert ref["d_logprob"].tolist() == [[-0.2, 0.2], [-0.2, 0.2], [0.0, 0.2]]
+    assert abs(float(ref["loss"]) - (-(1.0 * -4.0) - (-1.0 * -11.0)) / 5) <= 1e-15       # = (4 - 11) / 5
+    # a length outside 1 .. T is clamped: 0 -> 1, 9 -> 3
+    ref = sec.scst_loss_reference(lp.nan_to_num(0.0), torch.tensor([[0, 9]]), torch.tensor([[1.0, 0.0]]), None, 0)
+    assert ref["tokens"] == 4 and ref["d_logprob"][:, 0].tolist() == [-0.25, 0.0, 0.0]
+
+
+# ---- 2. the entry point: declared, exported, bound, and its refusals ----------------------------------------------------------------
+def test_entry_point_is_declared_exported_and_bound():
+    names = _lib.declared_symbols()
+    lib = _lib_cpu()
+    assert "dic_scst_loss" in names and hasattr(lib, "dic_scst_loss")
+    lib.dic_version.restype = ctypes.c_int
+    assert lib.dic_version() == 200 == _lib.ABI_VERSION                 # additive: no existing signature or struct changed
+    assert list(inspect.signature(native.scst_loss).parameters) == ["logprobs", "lengths", "rewards", "baseline", "baseline_mode",
+                                                                    "total_tokens", "return_advantage"]
+    # the writing-in-place siblings of the two backward bindings, whose own parameter lists stay as they were
+    assert list(inspect.signature(native.token_logprobs_bwd_into).parameters)[:2] == ["grads", "hidden"]
+    assert list(inspect.signature(native.decoder_states_backward_into).parameters) == ["grads", "tape", "d_hidden", "need_features"]
+    assert list(inspect.signature(native.decoder_states_backward).parameters) == ["tape", "d_hidden", "need_features"]
+    with pytest.raises(_lib.DicError, match="GPU"):                     # no GPU here: the binding refuses host tensors
+        native.scst_loss(torch.zeros(3, 2), torch.ones((1, 2), dtype=torch.int32), torch.zeros(1, 2))
+    found = build.audit_packed_fp32()
+    assert found.get("scst_loss") == 0
+    assert not [k for k in build.audit_register_spills() if "scst_loss" in k]
+
+
+def _call(lib, *, B=2, S=3, T=5, mode=1, null=()):
+    """dic_scst_loss with a host dummy nobody dereferences for every pointer: every refusal comes before the first HIP call."""
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    a = {k: p for k in ("logprobs", "lengths", "rewards", "baseline", "total_tokens", "out_loss", "out_d_logprob", "out_advantage",
+                        "out_tokens")}
+    for k in null:
+        a[k] = None
+    rc = lib.dic_scst_loss(a["logprobs"], a["lengths"], a["rewards"], a["baseline"], B, S, T, mode, a["total_tokens"], a["out_loss"],
+                           a["out_d_logprob"], a["out_advantage"], a["out_tokens"], None)
+    return rc, lib.dic_last_error().decode()
+
+
+_REFUSALS = [
+    (dict(B=0), "bad sizes"), (dict(S=0), "bad sizes"), (dict(T=0), "bad sizes"), (dict(B=-3), "bad sizes"), (dict(T=-1), "bad sizes"),
+    (dict(B=64, S=8, T=961), "beyond 491520"), (dict(B=491521, S=1, T=1), "beyond 491520"),
+    (dict(B=65536, S=65536, T=1), "beyond 491520"),                     # (the product is taken in 64 bits)
+    (dict(mode=-1), "baseline_mode=-1"), (dict(mode=4), "baseline_mode=4"),
+    (dict(mode=1, S=1), "S >= 2"),
+    (dict(null=("logprobs",)), "null pointer"), (dict(null=("lengths",)), "null pointer"), (dict(null=("rewards",)), "null pointer"),
+    (dict(null=("out_loss",)), "null pointer"), (dict(null=("out_d_logprob",)), "null pointer"),
+    (dict(mode=2, null=("baseline",)), "needs a baseline"), (dict(mode=3, null=("baseline",)), "needs a baseline"),
+]
+
+
+@pytest.mark.parametrize("kwargs,needle", _REFUSALS, ids=[str(i) for i in range(len(_REFUSALS))])
+def test_scst_loss_refuses_before_any_launch(kwargs, needle):
+    rc, msg = _call(_lib_cpu(), **kwargs)
+    assert rc < 0 and msg.startswith("scst_loss:") and needle in msg, (rc, msg)
+
+
+# ---- 3. scst_step's preconditions -----------------------------------------------------------------------------------------------------
+def test_scst_step_signature_and_hard_refusal():
+    sig = inspect.signature(CaptionTrainer.scst_step).parameters
+    assert list(sig) == ["self", "imgs", "depth_map", "reward_fn", "id_start", "id_end", "n_samples", "max_length", "temperature",
+                         "top_k", "top_p", "baseline", "uniform_u", "drop_mult", "precomputed_features", "next_imgs",
+                         "global_tokens", "apply_update", "virtual_world"]
+    assert all(sig[k].kind is inspect.Parameter.KEYWORD_ONLY for k in list(sig)[4:])
+    assert (sig["n_samples"].default, sig["max_length"].default, sig["baseline"].default) == (5, 30, "others")
+    assert sig["apply_update"].default is True and sig["global_tokens"].default is None
+    # the refusal is the first thing the step does: nothing of a trainer but `hard` is looked at
+    with pytest.raises(_lib.DicError, match="soft-attention decoders only"):
+        CaptionTrainer.scst_step(types.SimpleNamespace(hard=True), None, None, None, id_start=0, id_end=1,
+                                 precomputed_features=torch.zeros(2, 196, 2048))
+    assert list(inspect.signature(CaptionTrainer.train_step).parameters)[:5] == ["self", "imgs", "depth_map", "captions", "lengths"]
+
+
+_BAD_ARGUMENTS = [
+    (dict(hard=True), "soft-attention"),
+    (dict(n_samples=0), "n_samples=0"), (dict(n_samples=9), "n_samples=9"),
+    (dict(max_length=0), "max_length=0"), (dict(max_length=65), "max_length=65"),
+    (dict(B=0), "outside 1 .. 491520"), (dict(B=2000, n_samples=8, max_length=40), "outside 1 .. 491520"),
+    (dict(baseline="mean"), "baseline must be"), (dict(baseline="others", n_samples=1), "n_samples >= 2"),
+    (dict(baseline=torch.zeros(3, 3)), "baseline must be"), (dict(baseline=0.5), "baseline must be"),
+    (dict(uniform_u=torch.zeros(5, 7)), "uniform_u must be"), (dict(drop_mult=torch.zeros(8, 5, 64)), "drop_mult must be"),
+    (dict(global_tokens=17), "global_tokens must be"), (dict(global_tokens=torch.tensor([17])), "global_tokens must be"),
+    (dict(virtual_world=0), "virtual_world=0"), (dict(reward_fn=3), "reward_fn must be callable"),
+]
+
+
+@pytest.mark.parametrize("kwargs,needle", _BAD_ARGUMENTS, ids=[str(i) for i in range(len(_BAD_ARGUMENTS))])
+def test_scst_step_argument_checks(kwargs, needle):
+    a = dict(hard=False, B=4, n_samples=2, max_length=5, baseline="others")
+    a.update(kwargs)
+    with pytest.raises(_lib.DicError, match=needle):
+        engine.scst_arguments(**a)
+
+
+def test_scst_step_baseline_modes():
+    ok = dict(hard=False, B=4, n_samples=2, max_length=5)
+    assert engine.scst_arguments(baseline=None, **ok) == 0 and engine.scst_arguments(baseline="others", **ok) == 1
+    assert engine.scst_arguments(baseline=torch.zeros(4, 2), **ok) == 2
+    assert engine.scst_arguments(baseline=torch.zeros(4), **ok) == 3 and engine.scst_arguments(baseline="greedy", **ok) == 3
+    assert engine.scst_arguments(False, 4, 1, 5, "greedy", uniform_u=torch.zeros(5, 4), drop_mult=torch.zeros(4, 5, 128)) == 3
+
+
+# ---- 4. harness and CLI ---------------------------------------------------------------------------------------------------------------
+def test_scst_epochs_option_is_parsed():
+    from depth_image_captioning_pub_amd import base_main, depth_main
+    take = depth_main.take_scst_epochs
+    assert take(["depth_main", "soft", "cnn", "synthetic"]) == (["depth_main", "soft", "cnn", "synthetic"], None)
+    assert take(["depth_main", "soft", "cnn", "synthetic", "--scst-epochs", "2"]) == (["depth_main", "soft", "cnn", "synthetic"], 2)
+    assert take(["depth_main", "--scst-epochs=0", "soft", "cnn", "synthetic"]) == (["depth_main", "soft", "cnn", "synthetic"], 0)
+    for bad in (["--scst-epochs"], ["--scst-epochs", "two"], ["--scst-epochs", "-1"], ["--scst-epochs=1.5"]):
+        with pytest.raises(ValueError, match="--scst-epochs"):
+            take(["depth_main", "soft", "cnn", "synthetic"] + bad)
+        assert depth_main.main(["depth_main", "soft", "cnn", "synthetic"] + bad) == 1
+        assert base_main.main(["base_main", "soft", "synthetic"] + bad) == 1
+    assert depth_main.main(["depth_main", "soft", "--scst-epochs", "1"]) == 1          # the three positional arguments are still needed
+    # hard attention has no self-critical step: refused before a trainer is built (no GPU is touched)
+    with pytest.raises(_lib.DicError, match="hard attention"):
+        depth_main.main(["depth_main", "hard", "cnn", "synthetic", "--scst-epochs", "1"])
+    with pytest.raises(_lib.DicError, match="hard attention"):
+        base_main.main(["base_main", "hard", "synthetic", "--scst-epochs=1"])
+
+
+def test_config_and_harness_defaults():
+    from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model import base_train
+    from depth_image_captioning_pub_amd.Captioning_models.Depth_caption_model import depth_train
+    from depth_image_captioning_pub_amd.Captioning_models.config import ConfigTrain
+    cfg = ConfigTrain()
+    assert cfg.scst_epochs == 0 and cfg.scst_samples == 5 and cfg.scst_reward_weights == {"CIDEr": 1.0}
+    for fn in (depth_train.train_Cdepth_soft, depth_train.train_Cdepth_hard, base_train.train_base_soft, base_train.train_base_hard):
+        sig = inspect.signature(fn).parameters
+        assert list(sig) == ["ext", "useData", "config", "process_group", "stats", "scst_epochs"] and sig["scst_epochs"].default is None
+    cfg.scst_epochs = 2
+    with pytest.raises(_lib.DicError, match="hard attention"):
+        depth_train.train_Cdepth_hard(0, "synthetic", config=cfg)
+    with pytest.raises(_lib.DicError, match="must be >= 0"):
+        depth_train.train_Cdepth_soft(0, "synthetic", config=cfg, scst_epochs=-2)
