@@ -44,8 +44,8 @@ def dep_trans(imgs: torch.Tensor) -> torch.Tensor:
     x = imgs.contiguous()
     B, Cc, H, W = x.shape
     out = torch.empty((B, Cc, image_size, image_size), dtype=torch.float32, device=x.device)
-    check(_lib.load().dic_resize_bilinear(ptr(x), B * Cc, H, W, image_size, image_size, C.c_float(2.0), C.c_float(-1.0),
-                                          ptr(out), stream_ptr()), "dic_resize_bilinear")
+    check(_lib.load().dic_resize_bilinear(ptr(x), B * Cc, H, W, image_size, image_size, 2.0, -1.0, ptr(out), stream_ptr()),
+          "dic_resize_bilinear")
     return out
 
 
@@ -57,8 +57,8 @@ def resize_planes(x: torch.Tensor, size: int) -> torch.Tensor:
     x = x.contiguous()
     B, Cc, H, W = x.shape
     out = torch.empty((B, Cc, size, size), dtype=torch.float32, device=x.device)
-    check(_lib.load().dic_resize_bilinear(ptr(x), B * Cc, H, W, size, size, C.c_float(1.0), C.c_float(0.0), ptr(out),
-                                          stream_ptr()), "dic_resize_bilinear")
+    check(_lib.load().dic_resize_bilinear(ptr(x), B * Cc, H, W, size, size, 1.0, 0.0, ptr(out), stream_ptr()),
+          "dic_resize_bilinear")
     return out
 
 
@@ -66,8 +66,7 @@ def standardize_depth_map(depth: torch.Tensor) -> torch.Tensor:
     """Per-image min-max to [0,1], NaN -> 0.5 first (DPT_model.py:43-61). depth: [B,1,H,W] on the GPU."""
     d = depth.contiguous().clone()
     B = d.shape[0]
-    check(_lib.load().dic_depth_standardize(ptr(d), B, C.c_longlong(d.numel() // B), stream_ptr()),
-          "dic_depth_standardize")
+    check(_lib.load().dic_depth_standardize(ptr(d), B, d.numel() // B, stream_ptr()), "dic_depth_standardize")
     return d
 
 
@@ -153,6 +152,5 @@ class DepthCache:
         idx = torch.tensor([self.slot[k] for k in keys], dtype=torch.int64, device=self.table.device)
         out = torch.empty((len(keys),) + tuple(self.table.shape[1:]), dtype=torch.float32, device=self.table.device)
         row = self.table[0].numel()
-        check(_lib.load().dic_gather_rows(ptr(self.table), ptr(idx), len(keys), C.c_longlong(row), ptr(out),
-                                          stream_ptr()), "dic_gather_rows")
+        check(_lib.load().dic_gather_rows(ptr(self.table), ptr(idx), len(keys), row, ptr(out), stream_ptr()), "dic_gather_rows")
         return out

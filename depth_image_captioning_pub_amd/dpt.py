@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .native import f16x2_weight_scale
 from .synthetic import DptConfig, dpt_stage_spec
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 3
@@ -62,7 +63,7 @@ class DptRunner:
             co, ci, kh, kw = w.shape
             if key in std_keys:                              # [timm] StdConv2dSame.get_weight, eps = 1e-8
                 ws = torch.empty_like(w)
-                check(self.lib.dic_weight_standardize(ptr(w), co, ci * kh * kw, C.c_float(1e-8), ptr(ws), stream_ptr()),
+                check(self.lib.dic_weight_standardize(ptr(w), co, ci * kh * kw, 1e-8, ptr(ws), stream_ptr()),
                       "dic_weight_standardize")
                 w = ws
             if kh > 1 and ci > 1:
@@ -90,10 +91,10 @@ class DptRunner:
         if out is None or out[0].numel() < n:
             out = [torch.empty(n, dtype=torch.int16, device=self.dev) for _ in range(3)]
         if self.arith == "f16x2":
-            check(self.lib.dic_split_f16x2_paired_checked(ptr(x2d), C.c_longlong(rows), k, C.c_float(scale), ptr(out[0]), ptr(out[1]),
-                                                          ptr(self.overflow), stream_ptr()), "dic_split_f16x2_paired_checked")
+            check(self.lib.dic_split_f16x2_paired_checked(ptr(x2d), rows, k, scale, ptr(out[0]), ptr(out[1]), ptr(self.overflow),
+                                                          stream_ptr()), "dic_split_f16x2_paired_checked")
             return out
-        check(self.lib.dic_split_bf16x3_paired(ptr(x2d), C.c_longlong(rows), k, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()),
+        check(self.lib.dic_split_bf16x3_paired(ptr(x2d), rows, k, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()),
               "dic_split_bf16x3_paired")
         return out
 
@@ -101,16 +102,13 @@ class DptRunner:
         if key not in self.w_planes:
             scale = 1.0
             if self.arith == "f16x2":                        # (once per layer: the weights are frozen)
-                wmax = float(w2d.abs().max())
-                if not (wmax > 0.0 and math.isfinite(wmax)):
-                    raise _lib.DicError(f"DptRunner: {key}: f16x2 needs finite, non-zero weights")
-                scale = 2.0 ** math.floor(14 - math.log2(wmax))
+                scale = f16x2_weight_scale(w2d, f"DptRunner: {key}: f16x2 needs finite, non-zero weights")
             self.w_scale[key] = scale
             self.w_planes[key] = self._split(w2d.contiguous(), scale=scale)
         return self.w_planes[key]
 
     def _out_scale(self, key: str):
-        return C.c_float(1.0 / (self.ACT_SCALE * self.w_scale[key]))
+        return 1.0 / (self.ACT_SCALE * self.w_scale[key])
 
     def _input_planes(self, x2d: torch.Tensor) -> list:
         self.x_planes = self._split(x2d, self.x_planes)      # one scratch set, grown to the largest layer input
@@ -145,15 +143,14 @@ class DptRunner:
             check(self.lib.dic_conv2d_bf16x3(self._p3(xp), B, H, W, ci, self._p3(wp), ptr(b), co, kh, kw, stride, pad, ACT_NONE, ptr(y),
                                              ptr(self.tail_ws), stream_ptr()), "dic_conv2d_bf16x3")
             return y
-        check(self.lib.dic_conv2d_fwd(ptr(x), B, H, W, ci, 1 if nchw else 0, ptr(w), ptr(b), co, kh, kw, stride, pad, ptr(y),
-                                      C.c_void_p(0), C.c_void_p(0), 0, C.c_void_p(0), stream_ptr()), "dic_conv2d_fwd")
+        check(self.lib.dic_conv2d_fwd(ptr(x), B, H, W, ci, 1 if nchw else 0, ptr(w), ptr(b), co, kh, kw, stride, pad, ptr(y), None,
+                                      None, 0, None, stream_ptr()), "dic_conv2d_fwd")
         return y
 
     def pad(self, x: torch.Tensor, top: int, left: int, bottom: int, right: int, value: float = 0.0) -> torch.Tensor:
         B, H, W, Cc = x.shape
         y = self._new(B, H + top + bottom, W + left + right, Cc)
-        check(self.lib.dic_pad_nhwc(ptr(x), B, H, W, Cc, top, left, bottom, right, C.c_float(value), ptr(y), stream_ptr()),
-              "dic_pad_nhwc")
+        check(self.lib.dic_pad_nhwc(ptr(x), B, H, W, Cc, top, left, bottom, right, value, ptr(y), stream_ptr()), "dic_pad_nhwc")
         return y
 
     def std_conv_same(self, x: torch.Tensor, key: str, stride: int = 1) -> torch.Tensor:
@@ -168,20 +165,19 @@ class DptRunner:
         """[timm] GroupNormAct(32, eps 1e-5) [+ residual] [+ ReLU]."""
         B, H, W, Cc = x.shape
         y = torch.empty_like(x)
-        self.lib.dic_groupnorm_workspace_bytes.restype = C.c_size_t
         need = self.lib.dic_groupnorm_workspace_bytes(B, 32)
         if self.gn_ws is None or self.gn_ws.numel() < need:
             self.gn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        check(self.lib.dic_groupnorm_nhwc(ptr(x), B, C.c_longlong(H * W), Cc, 32, ptr(self.w[prefix + "weight"]),
-                                          ptr(self.w[prefix + "bias"]), C.c_float(1e-5), ptr(residual), 1 if relu else 0, ptr(y),
-                                          ptr(self.gn_ws), stream_ptr()), "dic_groupnorm_nhwc")
+        check(self.lib.dic_groupnorm_nhwc(ptr(x), B, H * W, Cc, 32, ptr(self.w[prefix + "weight"]), ptr(self.w[prefix + "bias"]),
+                                          1e-5, ptr(residual), 1 if relu else 0, ptr(y), ptr(self.gn_ws), stream_ptr()),
+              "dic_groupnorm_nhwc")
         return y
 
     def layer_norm(self, x: torch.Tensor, prefix: str) -> torch.Tensor:
         y = torch.empty_like(x)
         rows = x.numel() // x.shape[-1]
-        check(self.lib.dic_layernorm(ptr(x), C.c_longlong(rows), x.shape[-1], ptr(self.w[prefix + "weight"]),
-                                     ptr(self.w[prefix + "bias"]), C.c_float(1e-6), ptr(y), stream_ptr()), "dic_layernorm")
+        check(self.lib.dic_layernorm(ptr(x), rows, x.shape[-1], ptr(self.w[prefix + "weight"]), ptr(self.w[prefix + "bias"]), 1e-6,
+                                     ptr(y), stream_ptr()), "dic_layernorm")
         return y
 
     def linear(self, x: torch.Tensor, key: str, act: int = ACT_NONE, out: Optional[torch.Tensor] = None,
@@ -197,22 +193,20 @@ class DptRunner:
             wp = self._weight_planes(key, w.reshape(n, k))
             if self.arith == "f16x2":
                 check(self.lib.dic_linear_f16x2(m, n, k, self._p3(xp), self._p3(wp), ptr(self.w[key + ".bias"]), act,
-                                                1 if accumulate else 0, ptr(out), C.c_longlong(n), self._out_scale(key), stream_ptr()),
+                                                1 if accumulate else 0, ptr(out), n, self._out_scale(key), stream_ptr()),
                       "dic_linear_f16x2")
                 return out
             check(self.lib.dic_linear_bf16x3(m, n, k, self._p3(xp), self._p3(wp), ptr(self.w[key + ".bias"]), act,
-                                             1 if accumulate else 0, ptr(out), C.c_longlong(n), stream_ptr()), "dic_linear_bf16x3")
+                                             1 if accumulate else 0, ptr(out), n, stream_ptr()), "dic_linear_bf16x3")
             return out
-        check(self.lib.dic_gemm_f32(m, n, k, ptr(x), C.c_longlong(k), 0, ptr(w), C.c_longlong(k), 0, ptr(out), C.c_longlong(n),
-                                    ptr(self.w[key + ".bias"]), act, 1 if accumulate else 0, 1, C.c_void_p(0), C.c_size_t(0), 0,
-                                    stream_ptr()), "dic_gemm_f32")
+        check(self.lib.dic_gemm_f32(m, n, k, ptr(x), k, 0, ptr(w), k, 0, ptr(out), n, ptr(self.w[key + ".bias"]), act,
+                                    1 if accumulate else 0, 1, None, 0, 0, stream_ptr()), "dic_gemm_f32")
         return out
 
     def add_act(self, a: torch.Tensor, b: Optional[torch.Tensor], act: int = ACT_NONE, out: Optional[torch.Tensor] = None):
         out = torch.empty_like(a) if out is None else out
         period = b.numel() if b is not None else 1
-        check(self.lib.dic_add_act(ptr(a), ptr(b), C.c_longlong(a.numel()), C.c_longlong(period), act, ptr(out), stream_ptr()),
-              "dic_add_act")
+        check(self.lib.dic_add_act(ptr(a), ptr(b), a.numel(), period, act, ptr(out), stream_ptr()), "dic_add_act")
         return out
 
     def upsample2x(self, x: torch.Tensor) -> torch.Tensor:
@@ -235,8 +229,8 @@ class DptRunner:
                     raise _lib.DicError("DptRunner: square inputs only")
                 planes = pe[0, 1:].reshape(g, g, -1).permute(2, 0, 1).contiguous()           # [C, g, g]
                 out = self._new(planes.shape[0], gh, gw)
-                check(self.lib.dic_resize_bilinear(ptr(planes), planes.shape[0], g, g, gh, gh, C.c_float(1.0), C.c_float(0.0),
-                                                   ptr(out), stream_ptr()), "dic_resize_bilinear")
+                check(self.lib.dic_resize_bilinear(ptr(planes), planes.shape[0], g, g, gh, gh, 1.0, 0.0, ptr(out), stream_ptr()),
+                      "dic_resize_bilinear")
                 grid = out.permute(1, 2, 0).reshape(gh * gw, -1)
                 self.pos_cache[key] = torch.cat([pe[0, :1], grid], dim=0).contiguous()
         return self.pos_cache[key]
@@ -277,14 +271,12 @@ class DptRunner:
         # computes in bf16x3; the exact-fp32 runner keeps the plain fp32 vector kernel (workspace = NULL)
         ws = None
         if self.arith != "fp32":
-            self.lib.dic_vit_attention_workspace_bytes.restype = C.c_size_t
             need = self.lib.dic_vit_attention_workspace_bytes(B, N, self.cfg.heads)
             if getattr(self, "_attn_ws", None) is None or self._attn_ws.numel() < need:
                 self._attn_ws = torch.empty(need, dtype=torch.uint8, device=x.device)
             ws = self._attn_ws
         check(self.lib.dic_vit_attention(ptr(qkv), B, N, self.cfg.heads, Cc // self.cfg.heads, ptr(a), ptr(ws),
-                                         C.c_size_t(ws.numel() if ws is not None else 0), stream_ptr()),
-              "dic_vit_attention")
+                                         ws.numel() if ws is not None else 0, stream_ptr()), "dic_vit_attention")
         self.linear(a, p + "attn.proj", out=x, accumulate=True)
         h = self.layer_norm(x, p + "norm2.")
         m = self.linear(h, p + "mlp.fc1", act=ACT_GELU)
@@ -348,9 +340,8 @@ class DptRunner:
         y = self.conv(y, "scratch.output_conv.2", pad=1)
         self.add_act(y, None, ACT_RELU, out=y)
         out = self._new(B, H, W)
-        check(self.lib.dic_pointwise_dot(ptr(y), C.c_longlong(B * H * W), y.shape[-1], ptr(self.w["scratch.output_conv.4.weight"]),
-                                         ptr(self.w["scratch.output_conv.4.bias"]), 1, ptr(out), stream_ptr()),
-              "dic_pointwise_dot")
+        check(self.lib.dic_pointwise_dot(ptr(y), B * H * W, y.shape[-1], ptr(self.w["scratch.output_conv.4.weight"]),
+                                         ptr(self.w["scratch.output_conv.4.bias"]), 1, ptr(out), stream_ptr()), "dic_pointwise_dot")
         if self.arith == "f16x2" and (int(self.overflow.item()) != 0 or not bool(torch.isfinite(out).all())):
             # (the reference's post-processing maps NaN to 0.5, and the ReLUs on the way turn the NaN of an overflowed product into 0:
             #  the guard word raised by the split kernels is what sees it.  The estimator runs in epoch 0 only, one host

@@ -3,6 +3,7 @@ streams; every number is produced by libdic_hip.so.  Nothing here falls back to 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -38,21 +39,60 @@ class DecoderPtrs(C.Structure):
         "w_ih", "w_hh", "b_ih", "b_hh", "init_w", "init_b", "fbeta_w", "fbeta_b", "out_w", "out_b")]
 
 
-def _dev_f32(t: torch.Tensor, what: str) -> torch.Tensor:
+_mirrors_checked = False
+
+
+def _load() -> C.CDLL:
+    """The library; on first use every ctypes mirror of STRUCT_MIRRORS (below, behind the last of them) is held to the size the
+    library compiled: a mirror that lags include/dic.h would stride a layer table wrongly - wild pointers on the device."""
+    global _mirrors_checked
+    lib = _lib.load()
+    if not _mirrors_checked:
+        for which, mirror in STRUCT_MIRRORS:
+            _lib.check_struct(lib, which, mirror)
+        _mirrors_checked = True
+    return lib
+
+
+def _dev(t: torch.Tensor, what: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     if not t.is_cuda:
         raise _lib.DicError(f"{what}: tensor must live on the GPU (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise _lib.DicError(f"{what}: expected float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise _lib.DicError(f"{what}: expected {str(dtype).split('.')[-1]}, got {t.dtype}")
     return t if t.is_contiguous() else t.contiguous()
 
 
-def decoder_ptrs(tensors: Dict[str, torch.Tensor]) -> Tuple[DecoderPtrs, list]:
-    keep, s = [], DecoderPtrs()
-    for key, field in DECODER_FIELDS:
-        t = _dev_f32(tensors[key], key)
+def _inplace_f32(t: torch.Tensor, message: str) -> torch.Tensor:
+    """A buffer a kernel updates, or whose address a table keeps: contiguous fp32 on the GPU as it stands (never a copy)."""
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+        raise _lib.DicError(message)
+    return t
+
+
+def _fill_ptrs(struct, fields, tensors: Dict[str, torch.Tensor], shapes=None, built_for: str = ""):
+    """(struct of device pointers, the tensors they point to - to be kept alive across the call): tensors[key] -> field for every
+    (key, field); with `shapes`, a tensor of another shape than shapes[key] is refused."""
+    keep, s = [], struct()
+    for key, field in fields:
+        t = _dev(tensors[key], key)
+        if shapes is not None and tuple(t.shape) != shapes[key]:
+            raise _lib.DicError(f"{key}: expected {shapes[key]}, got {tuple(t.shape)}{built_for}")
         keep.append(t)
         setattr(s, field, t.data_ptr())
     return s, keep
+
+
+def decoder_ptrs(tensors: Dict[str, torch.Tensor]) -> Tuple[DecoderPtrs, list]:
+    return _fill_ptrs(DecoderPtrs, DECODER_FIELDS, tensors)
+
+
+def _workspace(query, device, *sizes, reuse: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Workspace of query(*sizes) bytes, at least 256: a query returns 0 for sizes its call refuses, and the call needs a
+    non-null pointer to get as far as the refusal with its text.  `reuse` is returned instead when it is large enough."""
+    need = max(query(*sizes), 256)
+    if reuse is not None and reuse.numel() >= need:
+        return reuse
+    return torch.empty(need, dtype=torch.uint8, device=device)
 
 
 def _i32_host(values: Sequence[int]):
@@ -81,16 +121,16 @@ class DecoderTape:
 def decoder_attention_relu_mask(tape: DecoderTape) -> torch.Tensor:
     """dic_decoder_inspect: which units of the attention ReLU passed in the forward that produced `tape`, bool
     [B, Tmax, cells, D_ATT] (rows of finished captions are meaningless).  For the parity tests' decision replay."""
-    lib = _lib.load()
+    lib = _load()
     B, T = len(tape.dec_len), tape.tmax
     dev = tape.workspace.device
     out = []
     for which, shape in ((1, (B, 1, tape.cells, D_ATT)), (2, (B, T, 1, D_ATT))):
         t = torch.empty(shape, dtype=torch.float32, device=dev)
-        n = C.c_longlong(0)
-        check(lib.dic_decoder_inspect(ptr(tape.workspace), C.c_size_t(tape.workspace.numel()), B, T, tape.vocab, tape.n_packed,
-                                      tape.cells, which, ptr(t), C.byref(n), stream_ptr()), "dic_decoder_inspect")
-        assert n.value == t.numel()
+        n = (C.c_longlong * 1)()
+        check(lib.dic_decoder_inspect(ptr(tape.workspace), tape.workspace.numel(), B, T, tape.vocab, tape.n_packed, tape.cells,
+                                      which, ptr(t), n, stream_ptr()), "dic_decoder_inspect")
+        assert n[0] == t.numel()
         out.append(t)
     return (out[0] + out[1]) > 0
 
@@ -106,7 +146,7 @@ def decoder_forward(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fe
     """dic_decoder_fwd. Returns (logits_packed [N,V], alphas [B,Tmax,196], tape).
     Features of shape [B,49,2048] (the encoders' 7x7 maps before the 2x2 replication to 14x14) select the compact
     layout (dic_decoder_fwd_cells, soft attention only): same logits / alphas / gradients, 4x less feature traffic."""
-    lib = _lib.load()
+    lib = _load()
     B = feat_rgb.shape[0]
     cells = int(feat_rgb.shape[1])
     if cells not in (L_CELLS, L_COMPACT) or feat_rgb.shape[2] != D_ENC:
@@ -122,28 +162,25 @@ def decoder_forward(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fe
     vocab = weights["linear.weight"].shape[0]
     dev = feat_rgb.device
     wp, keep = decoder_ptrs(weights)
-    f_rgb = _dev_f32(feat_rgb, "features")
-    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
+    f_rgb = _dev(feat_rgb, "features")
+    f_dep = _dev(feat_depth, "depth_features") if feat_depth is not None else None
     caps = captions if captions.is_contiguous() else captions.contiguous()
     if caps.dtype != torch.int64 or not caps.is_cuda:
         raise _lib.DicError("captions must be an int64 GPU tensor")
-    lib.dic_decoder_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_decoder_workspace_bytes(B, tmax, vocab, n_packed)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    workspace = _workspace(lib.dic_decoder_workspace_bytes, dev, B, tmax, vocab, n_packed, reuse=workspace)
     logits = torch.empty((n_packed, vocab), dtype=torch.float32, device=dev)
     alphas = torch.empty((B, tmax, L_CELLS), dtype=torch.float32, device=dev)
-    dm = _dev_f32(drop_mult, "drop_mult") if drop_mult is not None else None
-    gu = _dev_f32(gumbel_u, "gumbel_u") if gumbel_u is not None else None
+    dm = _dev(drop_mult, "drop_mult") if drop_mult is not None else None
+    gu = _dev(gumbel_u, "gumbel_u") if gumbel_u is not None else None
     if cells == L_CELLS:
         rc = lib.dic_decoder_fwd(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), ptr(caps), caps.stride(0),
-                                 _i32_host(dec_len), B, ptr(dm), mode, ptr(gu), C.c_float(temp), ptr(logits), ptr(alphas),
-                                 ptr(workspace), C.c_size_t(workspace.numel()), stream_ptr())
+                                 _i32_host(dec_len), B, ptr(dm), mode, ptr(gu), temp, ptr(logits), ptr(alphas),
+                                 ptr(workspace), workspace.numel(), stream_ptr())
         check(rc, "dic_decoder_fwd")
     else:
         rc = lib.dic_decoder_fwd_cells(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), cells, ptr(caps), caps.stride(0),
                                        _i32_host(dec_len), B, ptr(dm), ptr(logits), ptr(alphas), ptr(workspace),
-                                       C.c_size_t(workspace.numel()), stream_ptr())
+                                       workspace.numel(), stream_ptr())
         check(rc, "dic_decoder_fwd_cells")
     tape = DecoderTape(workspace, dec_len, bsz, n_packed, tmax, vocab, caps, dm, mode, float(temp), alphas,
                        {k: t for (k, _), t in zip(DECODER_FIELDS, keep)}, cells)
@@ -153,7 +190,7 @@ def decoder_forward(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fe
 def decoder_backward(tape: DecoderTape, dlogits: torch.Tensor, dalphas: Optional[torch.Tensor],
                      grads: Optional[Dict[str, torch.Tensor]] = None, want_dfeatures: bool = True):
     """dic_decoder_bwd. Returns (grads dict keyed like state_dict, d_features [B,196,2048] or None)."""
-    lib = _lib.load()
+    lib = _load()
     dev = dlogits.device
     B = len(tape.dec_len)
     if grads is None:
@@ -161,25 +198,25 @@ def decoder_backward(tape: DecoderTape, dlogits: torch.Tensor, dalphas: Optional
     gp, keep_g = decoder_ptrs(grads)
     wp, keep_w = decoder_ptrs(tape.weights)
     dfeat = torch.empty((B, tape.cells, D_ENC), dtype=torch.float32, device=dev) if want_dfeatures else None
-    dl = _dev_f32(dlogits, "dlogits")
-    da = _dev_f32(dalphas, "dalphas") if dalphas is not None else None
+    dl = _dev(dlogits, "dlogits")
+    da = _dev(dalphas, "dalphas") if dalphas is not None else None
     if tape.cells == L_CELLS:
         rc = lib.dic_decoder_bwd(C.byref(wp), tape.vocab, ptr(tape.captions), tape.captions.stride(0),
-                                 _i32_host(tape.dec_len), B, ptr(tape.drop_mult), tape.mode, C.c_float(tape.temp), ptr(dl),
+                                 _i32_host(tape.dec_len), B, ptr(tape.drop_mult), tape.mode, tape.temp, ptr(dl),
                                  ptr(da), ptr(tape.alphas), C.byref(gp), ptr(dfeat), ptr(tape.workspace),
-                                 C.c_size_t(tape.workspace.numel()), stream_ptr())
+                                 tape.workspace.numel(), stream_ptr())
         check(rc, "dic_decoder_bwd")
     else:       # d_features is then the gradient w.r.t. the 7x7 maps
         rc = lib.dic_decoder_bwd_cells(C.byref(wp), tape.vocab, tape.cells, ptr(tape.captions), tape.captions.stride(0),
                                        _i32_host(tape.dec_len), B, ptr(tape.drop_mult), ptr(dl), ptr(da), ptr(tape.alphas),
-                                       C.byref(gp), ptr(dfeat), ptr(tape.workspace), C.c_size_t(tape.workspace.numel()),
+                                       C.byref(gp), ptr(dfeat), ptr(tape.workspace), tape.workspace.numel(),
                                        stream_ptr())
         check(rc, "dic_decoder_bwd_cells")
     return grads, dfeat
 
 
 def pack_targets(captions: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
-    lib = _lib.load()
+    lib = _load()
     dec_len = [int(l) - 1 for l in lengths]
     n = sum(batch_sizes_of(dec_len))
     buf = torch.empty(n + (len(dec_len) + 1) // 2 + 2, dtype=torch.int64, device=captions.device)   # + int32 lengths
@@ -194,7 +231,7 @@ def caption_loss(logits: torch.Tensor, targets: torch.Tensor, alphas: Optional[t
     """dic_caption_loss. Returns (loss [1] device tensor, dlogits, dalphas or None).
     grad_scale multiplies dlogits, reg_grad_scale (default: the same value) multiplies dalphas - data parallel passes
     n_packed_r / sum n_packed and 1 / world (see include/dic.h)."""
-    lib = _lib.load()
+    lib = _load()
     n, v = logits.shape
     dev = logits.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
@@ -203,8 +240,8 @@ def caption_loss(logits: torch.Tensor, targets: torch.Tensor, alphas: Optional[t
     T = alphas.shape[1] if alphas is not None else 0
     dalphas = torch.empty_like(alphas) if alphas is not None else None
     scratch = torch.empty(n + B + 8, dtype=torch.float32, device=dev)
-    rc = lib.dic_caption_loss(ptr(logits), ptr(targets), n, v, ptr(alphas), B, T, C.c_float(lam), C.c_float(grad_scale),
-                              C.c_float(grad_scale if reg_grad_scale is None else reg_grad_scale),
+    rc = lib.dic_caption_loss(ptr(logits), ptr(targets), n, v, ptr(alphas), B, T, lam, grad_scale,
+                              grad_scale if reg_grad_scale is None else reg_grad_scale,
                               ptr(loss), ptr(dlogits), ptr(dalphas), ptr(scratch), stream_ptr())
     check(rc, "dic_caption_loss")
     return loss, dlogits, dalphas
@@ -212,7 +249,7 @@ def caption_loss(logits: torch.Tensor, targets: torch.Tensor, alphas: Optional[t
 
 def _guard_ptr(word: Optional[torch.Tensor]):
     if word is None:
-        return C.c_void_p(0)
+        return None
     if not (word.is_cuda and word.dtype == torch.int32 and word.numel() >= 1 and word.is_contiguous()):
         raise _lib.DicError("the overflow guard word must be a contiguous int32 GPU tensor")
     return ptr(word)
@@ -223,12 +260,11 @@ def adamw_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor,
                weight_decay: float = 0.01, skip_if_raised: Optional[torch.Tensor] = None) -> None:
     """dic_adamw_step_guarded: `skip_if_raised` (int32 device word, optional) = the f16x2 overflow guard of the forward behind these
     gradients; when it is non-zero the kernel leaves parameters and moments untouched."""
-    lib = _lib.load()
+    lib = _load()
     for t in (params, grads, exp_avg, exp_avg_sq):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-            raise _lib.DicError("adamw_step needs contiguous fp32 GPU buffers")
-    rc = lib.dic_adamw_step_guarded(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), C.c_longlong(params.numel()), step,
-                                    C.c_float(lr), C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_float(weight_decay),
+        _inplace_f32(t, "adamw_step needs contiguous fp32 GPU buffers")
+    rc = lib.dic_adamw_step_guarded(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), step,
+                                    lr, beta1, beta2, eps, weight_decay,
                                     _guard_ptr(skip_if_raised), stream_ptr())
     check(rc, "dic_adamw_step_guarded")
 
@@ -239,14 +275,14 @@ def bn_ema_update(running: torch.Tensor, delta: torch.Tensor, momentum: float = 
     device when the guard word `skip_if_raised` is non-zero."""
     if not (running.is_cuda and running.is_contiguous() and delta.is_contiguous() and running.numel() == delta.numel()):
         raise _lib.DicError("bn_ema_update needs two contiguous GPU buffers of equal length")
-    check(_lib.load().dic_bn_ema_update_guarded(ptr(running), ptr(delta), C.c_longlong(running.numel()), C.c_float(momentum),
+    check(_load().dic_bn_ema_update_guarded(ptr(running), ptr(delta), running.numel(), momentum,
                                                 _guard_ptr(skip_if_raised), stream_ptr()), "dic_bn_ema_update_guarded")
 
 
 def dropout_mask(shape, p: float, seed: int, offset: int, device) -> torch.Tensor:
-    lib = _lib.load()
+    lib = _load()
     out = torch.empty(shape, dtype=torch.float32, device=device)
-    rc = lib.dic_dropout_mask(ptr(out), C.c_longlong(out.numel()), C.c_float(p), C.c_uint64(seed), C.c_uint64(offset),
+    rc = lib.dic_dropout_mask(ptr(out), out.numel(), p, seed, offset,
                               stream_ptr())
     check(rc, "dic_dropout_mask")
     return out
@@ -270,12 +306,7 @@ class DepthBnState(C.Structure):
 
 
 def depth_ptrs(tensors: Dict[str, torch.Tensor]):
-    keep, s = [], DepthPtrs()
-    for key, field in DEPTH_FIELDS:
-        t = _dev_f32(tensors[key], key)
-        keep.append(t)
-        setattr(s, field, t.data_ptr())
-    return s, keep
+    return _fill_ptrs(DepthPtrs, DEPTH_FIELDS, tensors)
 
 
 @dataclass
@@ -290,8 +321,8 @@ def depth_encoder_forward(weights: Dict[str, torch.Tensor], state: Dict[str, tor
                           train: bool, workspace: Optional[torch.Tensor] = None, compact: bool = False):
     """dic_depth_encoder_fwd: depth [B,1,H,W] -> (features [B,196,2048], tape). `state` holds
     bn{1,2,3}.running_{mean,var} (updated in place when train)."""
-    lib = _lib.load()
-    d = _dev_f32(depth, "depth_map")
+    lib = _load()
+    d = _dev(depth, "depth_map")
     B, c, H, W = d.shape
     if c != 1:
         raise _lib.DicError("depth map must be [B,1,H,W]")
@@ -299,25 +330,20 @@ def depth_encoder_forward(weights: Dict[str, torch.Tensor], state: Dict[str, tor
     st = DepthBnState()
     for i in (1, 2, 3):
         for short, name in (("rm", "running_mean"), ("rv", "running_var")):
-            t = state[f"bn{i}.{name}"]
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                raise _lib.DicError("BatchNorm running statistics must be contiguous fp32 GPU tensors")
+            t = _inplace_f32(state[f"bn{i}.{name}"], "BatchNorm running statistics must be contiguous fp32 GPU tensors")
             setattr(st, f"{short}{i}", t.data_ptr())
-    lib.dic_depth_encoder_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_depth_encoder_workspace_bytes(B, H, W)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=d.device)
+    workspace = _workspace(lib.dic_depth_encoder_workspace_bytes, d.device, B, H, W, reuse=workspace)
     if compact:          # the 7x7 map before the 2x2 replication (dic_depth_encoder_fwd_map; 224x224 inputs)
         if (H, W) != (224, 224):
             raise _lib.DicError("compact depth features need 224x224 inputs (a 7x7 final map)")
         out = torch.empty((B, L_COMPACT, D_ENC), dtype=torch.float32, device=d.device)
         rc = lib.dic_depth_encoder_fwd_map(C.byref(wp), C.byref(st), ptr(d), B, H, W, 1 if train else 0, ptr(out),
-                                           ptr(workspace), C.c_size_t(workspace.numel()), stream_ptr())
+                                           ptr(workspace), workspace.numel(), stream_ptr())
         check(rc, "dic_depth_encoder_fwd_map")
     else:
         out = torch.empty((B, L_CELLS, D_ENC), dtype=torch.float32, device=d.device)
         rc = lib.dic_depth_encoder_fwd(C.byref(wp), C.byref(st), ptr(d), B, H, W, 1 if train else 0, ptr(out),
-                                       ptr(workspace), C.c_size_t(workspace.numel()), stream_ptr())
+                                       ptr(workspace), workspace.numel(), stream_ptr())
         check(rc, "dic_depth_encoder_fwd")
     return out, DepthTape(workspace, d, {k: t for (k, _), t in zip(DEPTH_FIELDS, keep)}, compact)
 
@@ -329,18 +355,18 @@ def depth_status_word(tape: DepthTape) -> torch.Tensor:
 
 
 def depth_encoder_backward(tape: DepthTape, d_features: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]] = None):
-    lib = _lib.load()
+    lib = _load()
     if grads is None:
         grads = {k: torch.empty_like(t) for k, t in tape.weights.items()}
     gp, keep_g = depth_ptrs(grads)
     wp, keep_w = depth_ptrs(tape.weights)
-    df = _dev_f32(d_features, "d_features")
+    df = _dev(d_features, "d_features")
     B, _, H, W = tape.depth.shape
     fn = lib.dic_depth_encoder_bwd_map if tape.compact else lib.dic_depth_encoder_bwd
     if tuple(df.shape) != (B, L_COMPACT if tape.compact else L_CELLS, D_ENC):
         raise _lib.DicError(f"d_features has shape {tuple(df.shape)}")
     rc = fn(C.byref(wp), ptr(tape.depth), ptr(df), B, H, W, C.byref(gp), ptr(tape.workspace),
-            C.c_size_t(tape.workspace.numel()), stream_ptr())
+            tape.workspace.numel(), stream_ptr())
     check(rc, "dic_depth_encoder_bwd")
     return grads
 
@@ -348,16 +374,16 @@ def depth_encoder_backward(tape: DepthTape, d_features: torch.Tensor, grads: Opt
 def depth_encoder_decisions(tape: DepthTape) -> Dict[str, torch.Tensor]:
     """dic_depth_encoder_inspect: the max-pool arg-max indices and pooled maps of the forward that produced `tape`
     (NHWC), for the parity tests' decision replay.  Keys: pooled1, argmax1, pooled2, argmax2, relu3."""
-    lib = _lib.load()
+    lib = _load()
     B, _, H, W = tape.depth.shape
     out = {}
     for which, name in ((1, "pooled1"), (2, "argmax1"), (3, "pooled2"), (4, "argmax2"), (5, "relu3")):
-        n = C.c_longlong(0)
-        check(lib.dic_depth_encoder_inspect(ptr(tape.workspace), C.c_size_t(tape.workspace.numel()), B, H, W, which,
-                                            C.c_void_p(0), C.byref(n), stream_ptr()), "dic_depth_encoder_inspect")
-        t = torch.empty(n.value, dtype=torch.float32 if which in (1, 3) else torch.uint8, device=tape.depth.device)
-        check(lib.dic_depth_encoder_inspect(ptr(tape.workspace), C.c_size_t(tape.workspace.numel()), B, H, W, which,
-                                            ptr(t), C.byref(n), stream_ptr()), "dic_depth_encoder_inspect")
+        n = (C.c_longlong * 1)()
+        check(lib.dic_depth_encoder_inspect(ptr(tape.workspace), tape.workspace.numel(), B, H, W, which,
+                                            None, n, stream_ptr()), "dic_depth_encoder_inspect")
+        t = torch.empty(n[0], dtype=torch.float32 if which in (1, 3) else torch.uint8, device=tape.depth.device)
+        check(lib.dic_depth_encoder_inspect(ptr(tape.workspace), tape.workspace.numel(), B, H, W, which,
+                                            ptr(t), n, stream_ptr()), "dic_depth_encoder_inspect")
         ch = 128 if which <= 2 else 512 if which <= 4 else 2048
         out[name] = t.view(B, -1, ch)          # [B, PH*PW, C]
     return out
@@ -373,6 +399,15 @@ class ConvBnLayer(C.Structure):
 CONV_MODES = {"fp32": 0, "bf16x3": 1, "f16x2": 2}
 
 
+def f16x2_weight_scale(w: torch.Tensor, message: str) -> float:
+    """2^floor(14 - log2 max|w|): the power of two that puts the largest magnitude of a weight matrix into (2^13, 2^14] for the
+    f16x2 operand planes.  Weights that are all zero or not finite are refused with `message`."""
+    wmax = float(w.abs().max())
+    if not (wmax > 0.0 and math.isfinite(wmax)):
+        raise _lib.DicError(message)
+    return 2.0 ** math.floor(14 - math.log2(wmax))
+
+
 class ResNetRunner:
     """Holds the OHWI copies of the (frozen) ResNet conv weights and the layer table for dic_resnet_fwd.
     `tensors` is keyed like CNNEncoder_Atten.state_dict() ('backbone.0.weight', 'backbone.1.running_mean', ...)."""
@@ -384,8 +419,7 @@ class ResNetRunner:
         envelope of an fp32 evaluation of the network; weights scaled per layer so that their largest magnitude lands in
         (2^13, 2^14] - scale = 2^floor(14 - log2 max|w|) -, activations by 4)."""
         from .synthetic import resnet152_spec
-        lib = _lib.load()
-        _lib.check_struct(lib, 0, ConvBnLayer)
+        lib = _load()
         if conv_mode not in CONV_MODES:
             raise _lib.DicError(f"conv_mode must be one of {list(CONV_MODES)}")
         self.mode = CONV_MODES[conv_mode]
@@ -395,7 +429,7 @@ class ResNetRunner:
         self.table = (ConvBnLayer * self.n_layers)()
         self.keep = []
         for i, (key, bn, co, ci, k, _s, _p) in enumerate(self.spec):
-            w = _dev_f32(tensors[key], key)
+            w = _dev(tensors[key], key)
             if tuple(w.shape) != (co, ci, k, k):
                 raise _lib.DicError(f"{key}: expected {(co, ci, k, k)}, got {tuple(w.shape)}")
             if k == 1 or ci == 1:
@@ -408,14 +442,10 @@ class ResNetRunner:
             tens = [w, w_ohwi]
             if self.mode == 2 and i == 0 and (co, ci, k) == (64, 3, 7):
                 # 7x7 stem in the f16x2 format (round 4): two strip-ordered fp16 planes of scale * w (dic_resnet_pack_stem_weights_f16x2)
-                import math
-                wmax = float(w.abs().max())
-                if not (wmax > 0.0 and math.isfinite(wmax)):
-                    raise _lib.DicError(f"{key}: f16x2 mode needs finite, non-zero weights")
-                scale = 2.0 ** math.floor(14 - math.log2(wmax))
+                scale = f16x2_weight_scale(w, f"{key}: f16x2 mode needs finite, non-zero weights")
                 scratch = torch.empty(64 * 224, dtype=torch.float32, device=w.device)
                 planes = [torch.empty(64 * 224, dtype=torch.int16, device=w.device) for _ in range(2)]
-                check(lib.dic_resnet_pack_stem_weights_f16x2(ptr(w), ptr(scratch), ptr(planes[0]), ptr(planes[1]), C.c_float(scale),
+                check(lib.dic_resnet_pack_stem_weights_f16x2(ptr(w), ptr(scratch), ptr(planes[0]), ptr(planes[1]), scale,
                                                              stream_ptr()), "dic_resnet_pack_stem_weights_f16x2")
                 ent.w_hi, ent.w_mid, ent.w_lo, ent.w_scale = planes[0].data_ptr(), planes[1].data_ptr(), None, scale
                 tens += planes + [scratch]
@@ -429,27 +459,21 @@ class ResNetRunner:
                 tens += planes + [scratch]
             if self.mode == 1 and i > 0:             # (other C_in % 32 != 0 layers would stay on the exact-fp32 kernel)
                 planes = [torch.empty(w_ohwi.numel(), dtype=torch.int16, device=w_ohwi.device) for _ in range(3)]
-                check(lib.dic_split_bf16x3_paired(ptr(w_ohwi), C.c_longlong(co), ci * k * k, ptr(planes[0]),
+                check(lib.dic_split_bf16x3_paired(ptr(w_ohwi), co, ci * k * k, ptr(planes[0]),
                                                   ptr(planes[1]), ptr(planes[2]), stream_ptr()),
                       "dic_split_bf16x3_paired")
                 ent.w_hi, ent.w_mid, ent.w_lo = (pl.data_ptr() for pl in planes)
                 tens += planes
             if self.mode == 2 and i > 0:
-                import math
-                wmax = float(w_ohwi.abs().max())
-                if not (wmax > 0.0 and math.isfinite(wmax)):
-                    raise _lib.DicError(f"{key}: f16x2 mode needs finite, non-zero weights")
-                scale = 2.0 ** math.floor(14 - math.log2(wmax))
+                scale = f16x2_weight_scale(w_ohwi, f"{key}: f16x2 mode needs finite, non-zero weights")
                 planes = [torch.empty(w_ohwi.numel(), dtype=torch.int16, device=w_ohwi.device) for _ in range(2)]
-                check(lib.dic_split_f16x2_paired(ptr(w_ohwi), C.c_longlong(co), ci * k * k, C.c_float(scale), ptr(planes[0]),
+                check(lib.dic_split_f16x2_paired(ptr(w_ohwi), co, ci * k * k, scale, ptr(planes[0]),
                                                  ptr(planes[1]), stream_ptr()), "dic_split_f16x2_paired")
                 ent.w_hi, ent.w_mid, ent.w_lo, ent.w_scale = planes[0].data_ptr(), planes[1].data_ptr(), None, scale
                 tens += planes
             for field, name in (("gamma", "weight"), ("beta", "bias"), ("running_mean", "running_mean"),
                                 ("running_var", "running_var")):
-                t = tensors[bn + name]
-                if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                    raise _lib.DicError(f"{bn + name} must be a contiguous fp32 GPU tensor")
+                t = _inplace_f32(tensors[bn + name], f"{bn + name} must be a contiguous fp32 GPU tensor")
                 setattr(ent, field, t.data_ptr())
                 tens.append(t)
             self.keep.append(tens)
@@ -467,9 +491,7 @@ class ResNetRunner:
         for i, (_key, bn, *_rest) in enumerate(self.spec):
             other.table[i] = self.table[i]
             for field, name in (("running_mean", "running_mean"), ("running_var", "running_var")):
-                t = stats[bn + name]
-                if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                    raise _lib.DicError(f"{bn + name} must be a contiguous fp32 GPU tensor")
+                t = _inplace_f32(stats[bn + name], f"{bn + name} must be a contiguous fp32 GPU tensor")
                 setattr(other.table[i], field, t.data_ptr())
         other.keep = [self.keep, list(stats.values())]
         other.workspace = None
@@ -480,15 +502,12 @@ class ResNetRunner:
                 compact: bool = False) -> torch.Tensor:
         """compact=True (224x224 inputs): returns the final 7x7 map [B,49,2048] itself instead of its 2x2 replication
         to [B,196,2048] (dic_resnet_fwd_map) - the input of the compact decoder layout."""
-        lib = _lib.load()
-        x = _dev_f32(imgs, "imgs")
+        lib = _load()
+        x = _dev(imgs, "imgs")
         B, c, H, W = x.shape
         if c != 3:
             raise _lib.DicError("images must be [B,3,H,W]")
-        lib.dic_resnet_workspace_bytes.restype = C.c_size_t
-        need = lib.dic_resnet_workspace_bytes(B, H, W, self.blocks, self.mode)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        self.workspace = _workspace(lib.dic_resnet_workspace_bytes, x.device, B, H, W, self.blocks, self.mode, reuse=self.workspace)
         if compact and (H, W) != (224, 224):
             raise _lib.DicError("compact RGB features need 224x224 inputs (a 7x7 final map)")
         cells = L_COMPACT if compact else L_CELLS
@@ -498,7 +517,7 @@ class ResNetRunner:
             raise _lib.DicError(f"out must be {(B, cells, D_ENC)}, got {tuple(out.shape)}")
         fn = lib.dic_resnet_fwd_map if compact else lib.dic_resnet_fwd
         rc = fn(self.table, self.n_layers, self.blocks, ptr(x), B, H, W, 1 if train_bn else 0, self.mode, ptr(out),
-                ptr(self.workspace), C.c_size_t(self.workspace.numel()), stream_ptr())
+                ptr(self.workspace), self.workspace.numel(), stream_ptr())
         check(rc, "dic_resnet_fwd")
         if train_bn and not torch.cuda.is_current_stream_capturing():
             self.train_forwards += 1
@@ -524,19 +543,12 @@ class ResNetRunner:
 # ---------------------------------------------------------------------------------------------
 # greedy decode + stand-alone attention
 # ---------------------------------------------------------------------------------------------
-def _workspace(query, device, *sizes) -> torch.Tensor:
-    """Workspace of query(*sizes) bytes, at least 256: a query returns 0 for sizes its call refuses, and the call needs a
-    non-null pointer to get as far as the refusal with its text."""
-    query.restype = C.c_size_t
-    return torch.empty(max(query(*sizes), 256), dtype=torch.uint8, device=device)
-
-
 def _decoder_prologue(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor]):
     """What every decode / score / states call starts with.  Returns (lib, features, depth features or None, B, vocab,
     weight pointers, the tensors they point to - to be kept alive across the call)."""
-    lib = _lib.load()
-    f_rgb = _dev_f32(feat_rgb, "features")
-    f_dep = _dev_f32(feat_depth, "depth_features") if feat_depth is not None else None
+    lib = _load()
+    f_rgb = _dev(feat_rgb, "features")
+    f_dep = _dev(feat_depth, "depth_features") if feat_depth is not None else None
     vocab = weights["linear.weight"].shape[0]
     wp, keep = decoder_ptrs(weights)
     return lib, f_rgb, f_dep, f_rgb.shape[0], vocab, wp, keep
@@ -549,9 +561,9 @@ def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
     ws = _workspace(lib.dic_decoder_greedy_workspace_bytes, f_rgb.device, B, max_length, vocab)
     ids = torch.empty((B, max_length), dtype=torch.int64, device=f_rgb.device)
     alphas = torch.empty((B, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device)
-    gu = _dev_f32(gumbel_u, "gumbel_u") if gumbel_u is not None else None
-    rc = lib.dic_decoder_greedy(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, C.c_longlong(int(id_start)), max_length,
-                                mode, ptr(gu), ptr(ids), ptr(alphas), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    gu = _dev(gumbel_u, "gumbel_u") if gumbel_u is not None else None
+    rc = lib.dic_decoder_greedy(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, int(id_start), max_length, mode, ptr(gu), ptr(ids),
+                                ptr(alphas), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_decoder_greedy")
     return ids, alphas
 
@@ -569,9 +581,8 @@ def decoder_beam(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_
     scores = torch.empty((B, kk), dtype=torch.float32, device=f_rgb.device)
     lengths = torch.empty((B, kk), dtype=torch.int32, device=f_rgb.device)
     alphas = torch.empty((B, kk, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device) if return_alphas else None
-    rc = lib.dic_decoder_beam(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, C.c_longlong(int(id_start)),
-                              C.c_longlong(int(id_end)), max_length, C.c_float(length_penalty), ptr(ids), ptr(scores),
-                              ptr(lengths), ptr(alphas), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    rc = lib.dic_decoder_beam(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, int(id_start), int(id_end), max_length,
+                              length_penalty, ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_decoder_beam")
     return (ids, scores, lengths, alphas) if return_alphas else (ids, scores, lengths)
 
@@ -585,7 +596,7 @@ def decoder_sample(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
     S = int(n_samples)
     ss = max(S, 1)
-    u = _dev_f32(uniform_u, "uniform_u")
+    u = _dev(uniform_u, "uniform_u")
     if tuple(u.shape) != (max_length, B * ss):
         raise _lib.DicError(f"decoder_sample: uniform_u must be [max_length, B*n_samples] = [{max_length}, {B * ss}], got {tuple(u.shape)}")
     ws = _workspace(lib.dic_decoder_sample_workspace_bytes, f_rgb.device, B, S, max_length, vocab)
@@ -593,29 +604,20 @@ def decoder_sample(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
     logprobs = torch.empty((B, ss, max_length), dtype=torch.float32, device=f_rgb.device)
     lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
     alphas = torch.empty((B, ss, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device) if return_alphas else None
-    rc = lib.dic_decoder_sample(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, C.c_longlong(int(id_start)),
-                                C.c_longlong(int(id_end)), max_length, C.c_float(temperature), int(top_k), C.c_float(top_p),
-                                ptr(u), ptr(ids), ptr(logprobs), ptr(lengths), ptr(alphas), ptr(ws), C.c_size_t(ws.numel()),
-                                stream_ptr())
+    rc = lib.dic_decoder_sample(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), max_length,
+                                temperature, int(top_k), top_p, ptr(u), ptr(ids), ptr(logprobs), ptr(lengths), ptr(alphas), ptr(ws),
+                                ws.numel(), stream_ptr())
     check(rc, "dic_decoder_sample")
     return (ids, logprobs, lengths, alphas) if return_alphas else (ids, logprobs, lengths)
-
-
-def _dev_i64(t: torch.Tensor, what: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise _lib.DicError(f"{what}: tensor must live on the GPU (no CPU fallback)")
-    if t.dtype != torch.int64:
-        raise _lib.DicError(f"{what}: expected int64, got {t.dtype}")
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor):
     """dic_token_logprobs: log-probability of targets[m] under softmax(hidden[m] @ weight.T + bias), the [M,V] logits never stored
     (semantics: include/dic.h).  hidden float32 [M,128], weight [V,128], bias [V], targets int64 [M] (negative: the row is skipped
     and gets 0 / 0).  Returns (logprobs float32 [M], lse float32 [M])."""
-    lib = _lib.load()
-    h, w, b = _dev_f32(hidden, "hidden"), _dev_f32(weight, "weight"), _dev_f32(bias, "bias")
-    tg = _dev_i64(targets, "targets")
+    lib = _load()
+    h, w, b = _dev(hidden, "hidden"), _dev(weight, "weight"), _dev(bias, "bias")
+    tg = _dev(targets, "targets", torch.int64)
     if h.dim() != 2 or h.shape[1] != D_HID or w.dim() != 2 or w.shape[1] != D_HID:
         raise _lib.DicError(f"token_logprobs: hidden must be [M,{D_HID}] and weight [V,{D_HID}], got {tuple(h.shape)} and {tuple(w.shape)}")
     M, V = h.shape[0], w.shape[0]
@@ -624,8 +626,7 @@ def token_logprobs(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     ws = _workspace(lib.dic_token_logprobs_workspace_bytes, h.device, M, V)
     logprobs = torch.empty((M,), dtype=torch.float32, device=h.device)
     lse = torch.empty((M,), dtype=torch.float32, device=h.device)
-    rc = lib.dic_token_logprobs(ptr(h), ptr(w), ptr(b), ptr(tg), M, V, ptr(logprobs), ptr(lse), ptr(ws), C.c_size_t(ws.numel()),
-                                stream_ptr())
+    rc = lib.dic_token_logprobs(ptr(h), ptr(w), ptr(b), ptr(tg), M, V, ptr(logprobs), ptr(lse), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_token_logprobs")
     return logprobs, lse
 
@@ -659,11 +660,11 @@ def token_logprobs_bwd_into(grads: Dict[str, torch.Tensor], hidden: torch.Tensor
 
 
 def _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, need, grads):
-    lib = _lib.load()
-    h, w, b = _dev_f32(hidden, "hidden"), _dev_f32(weight, "weight"), _dev_f32(bias, "bias")
-    tg = _dev_i64(targets, "targets")
-    ls, g = _dev_f32(lse, "lse"), _dev_f32(d_logprob, "d_logprob")
-    dl = _dev_f32(d_lse, "d_lse") if d_lse is not None else None
+    lib = _load()
+    h, w, b = _dev(hidden, "hidden"), _dev(weight, "weight"), _dev(bias, "bias")
+    tg = _dev(targets, "targets", torch.int64)
+    ls, g = _dev(lse, "lse"), _dev(d_logprob, "d_logprob")
+    dl = _dev(d_lse, "d_lse") if d_lse is not None else None
     if h.dim() != 2 or h.shape[1] != D_HID or w.dim() != 2 or w.shape[1] != D_HID:
         raise _lib.DicError(f"token_logprobs_bwd: hidden must be [M,{D_HID}] and weight [V,{D_HID}], got {tuple(h.shape)} and {tuple(w.shape)}")
     M, V = h.shape[0], w.shape[0]
@@ -675,9 +676,7 @@ def _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, ne
     need = tuple(bool(n) for n in need)
     if len(need) != 3:
         raise _lib.DicError(f"token_logprobs_bwd: need must name three outputs, got {len(need)}")
-    lib.dic_token_logprobs_bwd_workspace_bytes.restype = C.c_size_t
-    nbytes = lib.dic_token_logprobs_bwd_workspace_bytes(M, V)                 # (0 for sizes the call below refuses with its text)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=h.device)
+    ws = _workspace(lib.dic_token_logprobs_bwd_workspace_bytes, h.device, M, V)
     d_hidden = torch.empty((M, D_HID), dtype=torch.float32, device=h.device) if need[0] else None
     d_weight = torch.empty((V, D_HID), dtype=torch.float32, device=h.device) if need[1] else None
     d_bias = torch.empty((V,), dtype=torch.float32, device=h.device) if need[2] else None
@@ -687,7 +686,7 @@ def _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, ne
         if need[2]:
             d_bias = _grad_out(grads, "linear.bias", (V,), "token_logprobs_bwd")
     rc = lib.dic_token_logprobs_bwd(ptr(h), ptr(w), ptr(b), ptr(tg), ptr(ls), ptr(g), ptr(dl), M, V, ptr(d_hidden), ptr(d_weight),
-                                    ptr(d_bias), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+                                    ptr(d_bias), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_token_logprobs_bwd")
     return d_hidden, d_weight, d_bias
 
@@ -698,7 +697,7 @@ def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat
     (semantics: include/dic.h).  captions: int64 [B,T] (one per image) or [B,S,T] (S <= 8 per image), without '<start>'.
     Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
-    cap = _dev_i64(captions, "captions")
+    cap = _dev(captions, "captions", torch.int64)
     squeeze = cap.dim() == 2
     if squeeze:
         cap = cap.unsqueeze(1)
@@ -710,9 +709,8 @@ def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat
     logprobs = torch.empty((B, ss, tt), dtype=torch.float32, device=f_rgb.device)
     scores = torch.empty((B, ss), dtype=torch.float32, device=f_rgb.device)
     lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
-    rc = lib.dic_decoder_score(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, C.c_longlong(int(id_start)),
-                               C.c_longlong(int(id_end)), T, ptr(cap), ptr(logprobs), ptr(scores), ptr(lengths), ptr(ws),
-                               C.c_size_t(ws.numel()), stream_ptr())
+    rc = lib.dic_decoder_score(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), T, ptr(cap),
+                               ptr(logprobs), ptr(scores), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_decoder_score")
     if squeeze:
         return logprobs[:, 0], scores[:, 0], lengths[:, 0]
@@ -745,7 +743,7 @@ def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Ten
     Returns (hidden float32 [T,R,128] - 0 from each row's length on -, targets int64 [T,R] - -1 there -, lengths int32 [B,S],
     tape), R = B*S, rows b*S + s."""
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, features, depth_features)
-    cap = _dev_i64(captions, "captions")
+    cap = _dev(captions, "captions", torch.int64)
     if cap.dim() != 3 or cap.shape[0] != B:
         raise _lib.DicError(f"decoder_states: captions must be [B,S,T] with B = {B}, got {tuple(captions.shape)}")
     if tuple(f_rgb.shape[1:]) != (L_CELLS, D_ENC) or (f_dep is not None and tuple(f_dep.shape) != tuple(f_rgb.shape)):
@@ -754,7 +752,7 @@ def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Ten
     R = B * S
     dm = None
     if drop_mult is not None:
-        dm = _dev_f32(drop_mult, "drop_mult")
+        dm = _dev(drop_mult, "drop_mult")
         if tuple(dm.shape) != (R, T, D_HID):
             raise _lib.DicError(f"decoder_states: drop_mult must be [B*S,T,{D_HID}] = [{R},{T},{D_HID}], got {tuple(dm.shape)}")
     dev = f_rgb.device
@@ -763,9 +761,8 @@ def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Ten
     hidden = torch.empty((tt, rr, D_HID), dtype=torch.float32, device=dev)
     targets = torch.empty((tt, rr), dtype=torch.int64, device=dev)
     lengths = torch.empty((B, max(S, 1)), dtype=torch.int32, device=dev)
-    rc = lib.dic_decoder_states_fwd(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, C.c_longlong(int(id_start)),
-                                    C.c_longlong(int(id_end)), T, ptr(cap), ptr(dm), ptr(hidden), ptr(targets), ptr(lengths),
-                                    ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    rc = lib.dic_decoder_states_fwd(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), T, ptr(cap),
+                                    ptr(dm), ptr(hidden), ptr(targets), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_decoder_states_fwd")
     tape = StatesTape(ws, {k: t for (k, _), t in zip(DECODER_FIELDS, keep)}, vocab, B, S, T, int(id_start), int(id_end), cap, dm)
     return hidden, targets, lengths, tape
@@ -786,8 +783,8 @@ def decoder_states_backward_into(grads: Dict[str, torch.Tensor], tape: StatesTap
 
 
 def _decoder_states_backward(tape, d_hidden, need_features, grads):
-    lib = _lib.load()
-    dh = _dev_f32(d_hidden, "d_hidden")
+    lib = _load()
+    dh = _dev(d_hidden, "d_hidden")
     R = tape.B * tape.S
     if tuple(dh.shape) != (tape.T, R, D_HID):
         raise _lib.DicError(f"decoder_states: d_hidden must be [T,R,{D_HID}] = [{tape.T},{R},{D_HID}], got {tuple(dh.shape)}")
@@ -801,9 +798,9 @@ def _decoder_states_backward(tape, d_hidden, need_features, grads):
     for key, field in DECODER_FIELDS:
         setattr(gp, field, grads[key].data_ptr() if key in grads else None)
     d_features = torch.empty((tape.B, L_CELLS, D_ENC), dtype=torch.float32, device=dev) if need_features else None
-    rc = lib.dic_decoder_states_bwd(C.byref(wp), tape.vocab, tape.B, tape.S, C.c_longlong(tape.id_start), C.c_longlong(tape.id_end),
-                                    tape.T, ptr(tape.captions), ptr(tape.drop_mult), ptr(dh), C.byref(gp), ptr(d_features),
-                                    ptr(tape.workspace), C.c_size_t(tape.workspace.numel()), stream_ptr())
+    rc = lib.dic_decoder_states_bwd(C.byref(wp), tape.vocab, tape.B, tape.S, tape.id_start, tape.id_end, tape.T, ptr(tape.captions),
+                                    ptr(tape.drop_mult), ptr(dh), C.byref(gp), ptr(d_features), ptr(tape.workspace),
+                                    tape.workspace.numel(), stream_ptr())
     check(rc, "dic_decoder_states_bwd")
     return grads, d_features
 
@@ -815,20 +812,8 @@ def cider_d(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tens
     include/dic.h).  hyp_ids int64 [B,T] (one per image) or [B,S,T]; ref_ids int64 [B,R,Tr], R <= 8; ref_counts int32 [B]: how many
     of the R reference rows of each image count; idf_keys int64 [n_keys] ascending and idf_vals float32 [n_keys] (both None or
     empty: every n-gram is unseen).  Returns float32 [B] or [B,S]."""
-    lib = _lib.load()
-    hyp, ref = _dev_i64(hyp_ids, "hyp_ids"), _dev_i64(ref_ids, "ref_ids")
-    squeeze = hyp.dim() == 2
-    if squeeze:
-        hyp = hyp.unsqueeze(1)
-    if hyp.dim() != 3 or ref.dim() != 3 or ref.shape[0] != hyp.shape[0]:
-        raise _lib.DicError(f"cider_d: hyp_ids must be [B,T] or [B,S,T] and ref_ids [B,R,Tr] with the same B, got "
-                            f"{tuple(hyp_ids.shape)} and {tuple(ref_ids.shape)}")
-    B, S, T = (int(v) for v in hyp.shape)
-    R, Tr = int(ref.shape[1]), int(ref.shape[2])
-    if not ref_counts.is_cuda or ref_counts.dtype != torch.int32 or tuple(ref_counts.shape) != (B,):
-        raise _lib.DicError(f"cider_d: ref_counts must be int32 [{B}] on the GPU, got {ref_counts.dtype} {tuple(ref_counts.shape)} on "
-                            f"{ref_counts.device}")
-    cnt = ref_counts if ref_counts.is_contiguous() else ref_counts.contiguous()
+    lib = _load()
+    hyp, ref, cnt, squeeze, B, S, T, R, Tr = _metric_args("cider_d", hyp_ids, ref_ids, ref_counts)
     if (idf_keys is None) != (idf_vals is None):
         raise _lib.DicError("cider_d: idf_keys and idf_vals come together")
     keys = vals = None
@@ -838,17 +823,17 @@ def cider_d(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tens
             raise _lib.DicError(f"cider_d: idf_keys and idf_vals must be [n_keys], got {tuple(idf_keys.shape)} and {tuple(idf_vals.shape)}")
         n_keys = int(idf_keys.shape[0])
         if n_keys > 0:                                                               # (an empty table travels as NULL pointers)
-            keys, vals = _dev_i64(idf_keys, "idf_keys"), _dev_f32(idf_vals, "idf_vals")
+            keys, vals = _dev(idf_keys, "idf_keys", torch.int64), _dev(idf_vals, "idf_vals")
     out = torch.empty((max(B, 1), max(S, 1)), dtype=torch.float32, device=hyp.device)
-    rc = lib.dic_cider_d(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, C.c_longlong(int(id_end)), int(bool(count_end)), int(vocab),
-                         ptr(keys), ptr(vals), C.c_longlong(n_keys), C.c_float(idf_unseen), C.c_float(sigma), ptr(out), stream_ptr())
+    rc = lib.dic_cider_d(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, int(id_end), int(bool(count_end)), int(vocab), ptr(keys),
+                         ptr(vals), n_keys, idf_unseen, sigma, ptr(out), stream_ptr())
     check(rc, "dic_cider_d")
     return out[:, 0] if squeeze else out
 
 
 def _metric_args(what: str, hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor):
-    """The checks native.cider_d makes of its caption arguments: (hyp [B,S,T], ref, counts, squeeze, B, S, T, R, Tr)."""
-    hyp, ref = _dev_i64(hyp_ids, "hyp_ids"), _dev_i64(ref_ids, "ref_ids")
+    """The checks the metrics make of their caption arguments: (hyp [B,S,T], ref, counts, squeeze, B, S, T, R, Tr)."""
+    hyp, ref = _dev(hyp_ids, "hyp_ids", torch.int64), _dev(ref_ids, "ref_ids", torch.int64)
     squeeze = hyp.dim() == 2
     if squeeze:
         hyp = hyp.unsqueeze(1)
@@ -868,12 +853,12 @@ def bleu(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor,
     """dic_bleu: BLEU-1..4 of hypotheses against their image's references over token ids, one launch, on the device (semantics:
     include/dic.h).  hyp_ids int64 [B,T] (one per image) or [B,S,T]; ref_ids int64 [B,R,Tr], R <= 8; ref_counts int32 [B].
     Returns (scores float32 [B,4] or [B,S,4], stats int32 [B,10] or [B,S,10] = correct_1..4, guess_1..4, testlen, reflen)."""
-    lib = _lib.load()
+    lib = _load()
     hyp, ref, cnt, squeeze, B, S, T, R, Tr = _metric_args("bleu", hyp_ids, ref_ids, ref_counts)
     scores = torch.empty((max(B, 1), max(S, 1), 4), dtype=torch.float32, device=hyp.device)
     stats = torch.empty((max(B, 1), max(S, 1), 10), dtype=torch.int32, device=hyp.device)
-    rc = lib.dic_bleu(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, C.c_longlong(int(id_end)), int(bool(count_end)), int(vocab),
-                      ptr(scores), ptr(stats), stream_ptr())
+    rc = lib.dic_bleu(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, int(id_end), int(bool(count_end)), int(vocab), ptr(scores),
+                      ptr(stats), stream_ptr())
     check(rc, "dic_bleu")
     return (scores[:, 0], stats[:, 0]) if squeeze else (scores, stats)
 
@@ -883,12 +868,12 @@ def rouge_l(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tens
     """dic_rouge_l: ROUGE-L of hypotheses against their image's references over token ids, one launch, on the device (semantics:
     include/dic.h).  Arguments as native.bleu.  Returns scores float32 [B] or [B,S]; with return_lcs (scores, lcs int32 [B,R] or
     [B,S,R]: the longest common subsequence with every reference, 0 behind the image's count)."""
-    lib = _lib.load()
+    lib = _load()
     hyp, ref, cnt, squeeze, B, S, T, R, Tr = _metric_args("rouge_l", hyp_ids, ref_ids, ref_counts)
     scores = torch.empty((max(B, 1), max(S, 1)), dtype=torch.float32, device=hyp.device)
     lcs = torch.empty((max(B, 1), max(S, 1), max(R, 1)), dtype=torch.int32, device=hyp.device) if return_lcs else None
-    rc = lib.dic_rouge_l(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, C.c_longlong(int(id_end)), int(bool(count_end)), int(vocab),
-                         C.c_float(beta), ptr(scores), ptr(lcs), stream_ptr())
+    rc = lib.dic_rouge_l(ptr(hyp), B, S, T, ptr(ref), ptr(cnt), R, Tr, int(id_end), int(bool(count_end)), int(vocab), beta,
+                         ptr(scores), ptr(lcs), stream_ptr())
     check(rc, "dic_rouge_l")
     if squeeze:
         scores, lcs = scores[:, 0], (lcs[:, 0] if return_lcs else None)
@@ -897,12 +882,11 @@ def rouge_l(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tens
 
 def gather_rows(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """dic_gather_rows: out[r,:] = table[idx[r],:] for table float32 [N,W] (W a multiple of 4) and idx int64 [n], n <= 65535."""
-    t, i = _dev_f32(table, "table"), _dev_i64(idx, "idx")
+    t, i = _dev(table, "table"), _dev(idx, "idx", torch.int64)
     if t.dim() != 2 or i.dim() != 1 or not 0 < i.shape[0] <= 65535:
         raise _lib.DicError(f"gather_rows: table must be [N,W] and idx [n] with 0 < n <= 65535, got {tuple(t.shape)} and {tuple(i.shape)}")
     out = torch.empty((i.shape[0], t.shape[1]), dtype=torch.float32, device=t.device)
-    check(_lib.load().dic_gather_rows(ptr(t), ptr(i), int(i.shape[0]), C.c_longlong(t.shape[1]), ptr(out), stream_ptr()),
-          "dic_gather_rows")
+    check(_load().dic_gather_rows(ptr(t), ptr(i), int(i.shape[0]), t.shape[1], ptr(out), stream_ptr()), "dic_gather_rows")
     return out
 
 
@@ -913,8 +897,8 @@ def scst_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: torch.Tens
     [B,S]; baseline_mode 0 none | 1 others | 2 per caption (baseline [B,S]) | 3 per image (baseline [B]); total_tokens: int64
     device tensor of one element, the normaliser N (None: this call's own sum of lengths).
     Returns (loss float32 [1], d_logprob float32 [T,R], tokens int64 [1][, advantage float32 [B,S]])."""
-    lib = _lib.load()
-    lp, rw = _dev_f32(logprobs, "logprobs"), _dev_f32(rewards, "rewards")
+    lib = _load()
+    lp, rw = _dev(logprobs, "logprobs"), _dev(rewards, "rewards")
     if not lengths.is_cuda or lengths.dtype != torch.int32 or lengths.dim() != 2:
         raise _lib.DicError(f"scst_loss: lengths must be int32 [B,S] on the GPU, got {lengths.dtype} {tuple(lengths.shape)} on "
                             f"{lengths.device}")
@@ -933,7 +917,7 @@ def scst_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: torch.Tens
         if baseline is None or tuple(baseline.shape) != want:
             raise _lib.DicError(f"scst_loss: baseline_mode {mode} needs a baseline {want}, got "
                                 f"{None if baseline is None else tuple(baseline.shape)}")
-        bl = _dev_f32(baseline, "baseline")
+        bl = _dev(baseline, "baseline")
     tt = None
     if total_tokens is not None:
         if not (total_tokens.is_cuda and total_tokens.dtype == torch.int64 and total_tokens.numel() == 1):
@@ -954,22 +938,21 @@ def scst_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: torch.Tens
 def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, mode: int = 0,
                       gumbel_u: Optional[torch.Tensor] = None, temp: float = 1.0):
     """dic_attention_fwd. `att` holds encoder_att/decoder_att/full_att weight+bias. Returns (ctx [B,2048], alpha [B,196])."""
-    lib = _lib.load()
-    f = _dev_f32(feats, "encoder_out")
-    hh = _dev_f32(h, "decoder_hidden")
+    lib = _load()
+    f = _dev(feats, "encoder_out")
+    hh = _dev(h, "decoder_hidden")
     B = f.shape[0]
     if tuple(f.shape[1:]) != (L_CELLS, D_ENC) or tuple(hh.shape) != (B, D_HID):
         raise _lib.DicError("attention_forward: expected encoder_out [B,196,2048] and decoder_hidden [B,128]")
-    t = {k: _dev_f32(v, k) for k, v in att.items()}
-    lib.dic_attention_workspace_bytes.restype = C.c_size_t
-    ws = torch.empty(lib.dic_attention_workspace_bytes(B), dtype=torch.uint8, device=f.device)
+    t = {k: _dev(v, k) for k, v in att.items()}
+    ws = _workspace(lib.dic_attention_workspace_bytes, f.device, B)
     ctx = torch.empty((B, D_ENC), dtype=torch.float32, device=f.device)
     alpha = torch.empty((B, L_CELLS), dtype=torch.float32, device=f.device)
-    gu = _dev_f32(gumbel_u, "gumbel_u") if gumbel_u is not None else None
+    gu = _dev(gumbel_u, "gumbel_u") if gumbel_u is not None else None
     rc = lib.dic_attention_fwd(ptr(t["encoder_att.weight"]), ptr(t["encoder_att.bias"]), ptr(t["decoder_att.weight"]),
                                ptr(t["decoder_att.bias"]), ptr(t["full_att.weight"]), ptr(t["full_att.bias"]), ptr(f),
-                               ptr(hh), B, mode, ptr(gu), C.c_float(temp), ptr(ctx), ptr(alpha), ptr(ws),
-                               C.c_size_t(ws.numel()), stream_ptr())
+                               ptr(hh), B, mode, ptr(gu), temp, ptr(ctx), ptr(alpha), ptr(ws),
+                               ws.numel(), stream_ptr())
     check(rc, "dic_attention_fwd")
     return ctx, alpha
 
@@ -977,20 +960,19 @@ def attention_forward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torc
 def attention_backward(att: Dict[str, torch.Tensor], feats: torch.Tensor, h: torch.Tensor, alpha: torch.Tensor,
                        d_ctx: torch.Tensor, d_alpha: Optional[torch.Tensor], mode: int = 0, temp: float = 1.0):
     """dic_attention_bwd. Returns (grads dict keyed like `att`, d_feats [B,196,2048], d_h [B,128])."""
-    lib = _lib.load()
-    f, hh, al, dc = _dev_f32(feats, "encoder_out"), _dev_f32(h, "decoder_hidden"), _dev_f32(alpha, "alpha"), _dev_f32(d_ctx, "d_ctx")
-    da = _dev_f32(d_alpha, "d_alpha") if d_alpha is not None else None
+    lib = _load()
+    f, hh, al, dc = _dev(feats, "encoder_out"), _dev(h, "decoder_hidden"), _dev(alpha, "alpha"), _dev(d_ctx, "d_ctx")
+    da = _dev(d_alpha, "d_alpha") if d_alpha is not None else None
     B = f.shape[0]
-    t = {k: _dev_f32(v, k) for k, v in att.items()}
+    t = {k: _dev(v, k) for k, v in att.items()}
     g = {k: torch.empty_like(v) for k, v in t.items()}
-    lib.dic_attention_bwd_workspace_bytes.restype = C.c_size_t
-    ws = torch.empty(lib.dic_attention_bwd_workspace_bytes(B), dtype=torch.uint8, device=f.device)
+    ws = _workspace(lib.dic_attention_bwd_workspace_bytes, f.device, B)
     d_feats, d_h = torch.empty_like(f), torch.empty_like(hh)
     rc = lib.dic_attention_bwd(ptr(t["encoder_att.weight"]), ptr(t["encoder_att.bias"]), ptr(t["decoder_att.weight"]),
                                ptr(t["decoder_att.bias"]), ptr(t["full_att.weight"]), ptr(f), ptr(hh), ptr(al), B, mode,
-                               C.c_float(temp), ptr(dc), ptr(da), ptr(g["encoder_att.weight"]), ptr(g["encoder_att.bias"]),
+                               temp, ptr(dc), ptr(da), ptr(g["encoder_att.weight"]), ptr(g["encoder_att.bias"]),
                                ptr(g["decoder_att.weight"]), ptr(g["decoder_att.bias"]), ptr(g["full_att.weight"]),
-                               ptr(g["full_att.bias"]), ptr(d_feats), ptr(d_h), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+                               ptr(g["full_att.bias"]), ptr(d_feats), ptr(d_h), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_attention_bwd")
     return g, d_feats, d_h
 
@@ -1021,19 +1003,21 @@ def nic_shapes(vocab: int) -> Dict[str, Tuple[int, ...]]:
 
 
 def nic_ptrs(tensors: Dict[str, torch.Tensor]) -> Tuple[NicPtrs, list]:
-    lib = _lib.load()
-    _lib.check_struct(lib, 6, NicPtrs)
-    _lib.check_struct(lib, 7, NicPtrs)
-    shapes = nic_shapes(tensors["linear.weight"].shape[0])
-    keep, s = [], NicPtrs()
-    for key, field in NIC_FIELDS:
-        t = _dev_f32(tensors[key], key)
-        if tuple(t.shape) != shapes[key]:
-            raise _lib.DicError(f"{key}: expected {shapes[key]}, got {tuple(t.shape)} (the native NIC path is built for "
-                                f"dim_embedding {NIC_EMB}, dim_hidden {D_HID}, 2 layers)")
-        keep.append(t)
-        setattr(s, field, t.data_ptr())
-    return s, keep
+    return _fill_ptrs(NicPtrs, NIC_FIELDS, tensors, nic_shapes(tensors["linear.weight"].shape[0]),
+                      f" (the native NIC path is built for dim_embedding {NIC_EMB}, dim_hidden {D_HID}, 2 layers)")
+
+
+# which of dic_struct_bytes -> the ctypes mirror of that struct of include/dic.h (_load checks them all, once)
+STRUCT_MIRRORS = ((0, ConvBnLayer), (1, DecoderPtrs), (2, DecoderPtrs), (3, DepthPtrs), (4, DepthPtrs), (5, DepthBnState),
+                  (6, NicPtrs), (7, NicPtrs))
+
+
+def _nic_features(features: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    f = _dev(features, "features")
+    B = int(f.shape[0])
+    if tuple(f.shape) != (B, NIC_EMB):
+        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    return f, B
 
 
 def _nic_captions(captions: torch.Tensor) -> torch.Tensor:
@@ -1059,13 +1043,13 @@ class NicTape:
 
 def nic_head_forward(enc_w: torch.Tensor, enc_b: torch.Tensor, fmap: torch.Tensor):
     """dic_nic_head_fwd: map [B,cells,2048] (or an already pooled [B,2048]) -> (pooled [B,2048], features [B,300])."""
-    lib = _lib.load()
-    m = _dev_f32(fmap, "map")
+    lib = _load()
+    m = _dev(fmap, "map")
     if m.dim() == 2:
         m = m.unsqueeze(1)
     if m.dim() != 3 or m.shape[2] != D_ENC:
         raise _lib.DicError(f"map must be [B,cells,{D_ENC}], got {tuple(fmap.shape)}")
-    w, b = _dev_f32(enc_w, "encoder.linear.weight"), _dev_f32(enc_b, "encoder.linear.bias")
+    w, b = _dev(enc_w, "encoder.linear.weight"), _dev(enc_b, "encoder.linear.bias")
     if tuple(w.shape) != (NIC_EMB, D_ENC) or tuple(b.shape) != (NIC_EMB,):
         raise _lib.DicError(f"encoder.linear must be [{NIC_EMB},{D_ENC}] / [{NIC_EMB}]")
     B, cells = int(m.shape[0]), int(m.shape[1])
@@ -1077,8 +1061,8 @@ def nic_head_forward(enc_w: torch.Tensor, enc_b: torch.Tensor, fmap: torch.Tenso
 
 def nic_head_backward(pooled: torch.Tensor, d_features: torch.Tensor):
     """dic_nic_head_bwd: (gradient of encoder.linear.weight [300,2048], of encoder.linear.bias [300])."""
-    lib = _lib.load()
-    p, d = _dev_f32(pooled, "pooled"), _dev_f32(d_features, "d_features")
+    lib = _load()
+    p, d = _dev(pooled, "pooled"), _dev(d_features, "d_features")
     B = int(p.shape[0])
     if tuple(p.shape) != (B, D_ENC) or tuple(d.shape) != (B, NIC_EMB):
         raise _lib.DicError("nic_head_backward: expected pooled [B,2048] and d_features [B,300]")
@@ -1091,11 +1075,8 @@ def nic_head_backward(pooled: torch.Tensor, d_features: torch.Tensor):
 def nic_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int],
                 drop_mult: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
     """dic_nic_fwd.  Returns (logits_packed [n_packed,V], tape); `lengths` are the full caption lengths (descending)."""
-    lib = _lib.load()
-    f = _dev_f32(features, "features")
-    B = int(f.shape[0])
-    if tuple(f.shape) != (B, NIC_EMB):
-        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    lib = _load()
+    f, B = _nic_features(features)
     lens = [int(l) for l in lengths]
     if len(lens) != B:
         raise _lib.DicError("one length per batch row")
@@ -1105,40 +1086,37 @@ def nic_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, captio
     tmax = max(lens) if lens else 0
     bsz = batch_sizes_of(lens) if tmax > 0 else []
     n_packed = sum(bsz)
-    lib.dic_nic_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_nic_workspace_bytes(B, tmax, vocab, n_packed)       # (0 for sizes the call below refuses with its text)
-    if workspace is None or workspace.numel() < max(need, 256):
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=f.device)
-    dm = _dev_f32(drop_mult, "drop_mult") if drop_mult is not None else None
+    workspace = _workspace(lib.dic_nic_workspace_bytes, f.device, B, tmax, vocab, n_packed, reuse=workspace)
+    dm = _dev(drop_mult, "drop_mult") if drop_mult is not None else None
     if dm is not None and tuple(dm.shape) != (B, tmax, D_HID):
         raise _lib.DicError(f"drop_mult must be [B,Tmax,{D_HID}] = {(B, tmax, D_HID)}, got {tuple(dm.shape)}")
     logits = torch.empty((max(n_packed, 1), vocab), dtype=torch.float32, device=f.device)[:n_packed]
     rc = lib.dic_nic_fwd(C.byref(wp), vocab, ptr(f), ptr(caps), caps.stride(0), _i32_host(lens), B, ptr(dm), ptr(logits),
-                         ptr(workspace), C.c_size_t(workspace.numel()), stream_ptr())
+                         ptr(workspace), workspace.numel(), stream_ptr())
     check(rc, "dic_nic_fwd")
     return logits, NicTape(workspace, lens, bsz, n_packed, tmax, vocab, caps, dm, {k: t for (k, _), t in zip(NIC_FIELDS, keep)})
 
 
 def nic_backward(tape: NicTape, dlogits: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]] = None):
     """dic_nic_bwd.  Returns (grads dict keyed like state_dict, d_features [B,300])."""
-    lib = _lib.load()
+    lib = _load()
     if grads is None:
         grads = {k: torch.empty_like(t) for k, t in tape.weights.items()}
     gp, keep_g = nic_ptrs(grads)
     wp, keep_w = nic_ptrs(tape.weights)
-    dl = _dev_f32(dlogits, "dlogits")
+    dl = _dev(dlogits, "dlogits")
     B = len(tape.lengths)
     dfeat = torch.empty((B, NIC_EMB), dtype=torch.float32, device=dl.device)
     rc = lib.dic_nic_bwd(C.byref(wp), tape.vocab, ptr(tape.captions), tape.captions.stride(0), _i32_host(tape.lengths), B,
                          ptr(tape.drop_mult), ptr(dl), C.byref(gp), ptr(dfeat), ptr(tape.workspace),
-                         C.c_size_t(tape.workspace.numel()), stream_ptr())
+                         tape.workspace.numel(), stream_ptr())
     check(rc, "dic_nic_bwd")
     return grads, dfeat
 
 
 def nic_pack_targets(captions: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
     """dic_nic_pack_targets: pack_padded_sequence(captions, lengths).data - all len_b tokens of a row."""
-    lib = _lib.load()
+    lib = _load()
     lens = [int(l) for l in lengths]
     caps = _nic_captions(captions)
     out = torch.empty(max(sum(max(l, 0) for l in lens), 1), dtype=torch.int64, device=caps.device)
@@ -1149,18 +1127,13 @@ def nic_pack_targets(captions: torch.Tensor, lengths: Sequence[int]) -> torch.Te
 
 def nic_greedy(weights: Dict[str, torch.Tensor], features: torch.Tensor, max_length: int = 30) -> torch.Tensor:
     """dic_nic_greedy.  Returns ids int64 [B,max_length] on the device."""
-    lib = _lib.load()
-    f = _dev_f32(features, "features")
-    B = int(f.shape[0])
-    if tuple(f.shape) != (B, NIC_EMB):
-        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    lib = _load()
+    f, B = _nic_features(features)
     wp, keep = nic_ptrs(weights)
     vocab = int(weights["linear.weight"].shape[0])
-    lib.dic_nic_greedy_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_nic_greedy_workspace_bytes(B, int(max_length), vocab)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f.device)
+    ws = _workspace(lib.dic_nic_greedy_workspace_bytes, f.device, B, int(max_length), vocab)
     ids = torch.empty((B, max(int(max_length), 1)), dtype=torch.int64, device=f.device)
-    rc = lib.dic_nic_greedy(C.byref(wp), vocab, ptr(f), B, int(max_length), ptr(ids), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    rc = lib.dic_nic_greedy(C.byref(wp), vocab, ptr(f), B, int(max_length), ptr(ids), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_nic_greedy")
     return ids
 
@@ -1169,21 +1142,16 @@ def nic_beam(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: i
              length_penalty: float = 0.0):
     """dic_nic_beam: fixed-width beam search of the NIC decoder, on the device (semantics: include/dic.h).
     Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K]), best first."""
-    lib = _lib.load()
-    f = _dev_f32(features, "features")
-    B, K = int(f.shape[0]), int(beam_size)
-    if tuple(f.shape) != (B, NIC_EMB):
-        raise _lib.DicError(f"features must be [B,{NIC_EMB}], got {tuple(f.shape)}")
+    lib = _load()
+    (f, B), K = _nic_features(features), int(beam_size)
     wp, keep = nic_ptrs(weights)
     vocab = int(weights["linear.weight"].shape[0])
-    lib.dic_nic_beam_workspace_bytes.restype = C.c_size_t
-    need = lib.dic_nic_beam_workspace_bytes(B, K, int(max_length), vocab)      # (0 for sizes the call below refuses with its text)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=f.device)
+    ws = _workspace(lib.dic_nic_beam_workspace_bytes, f.device, B, K, int(max_length), vocab)
     kk, tt = max(K, 1), max(int(max_length), 1)
     ids = torch.empty((B, kk, tt), dtype=torch.int64, device=f.device)
     scores = torch.empty((B, kk), dtype=torch.float32, device=f.device)
     lengths = torch.empty((B, kk), dtype=torch.int32, device=f.device)
-    rc = lib.dic_nic_beam(C.byref(wp), vocab, ptr(f), B, K, C.c_longlong(int(id_end)), int(max_length), C.c_float(length_penalty),
-                          ptr(ids), ptr(scores), ptr(lengths), ptr(ws), C.c_size_t(ws.numel()), stream_ptr())
+    rc = lib.dic_nic_beam(C.byref(wp), vocab, ptr(f), B, K, int(id_end), int(max_length), length_penalty,
+                          ptr(ids), ptr(scores), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_nic_beam")
     return ids, scores, lengths
