@@ -1,6 +1,7 @@
 // extern "C" surface of libdic_hip.so (declared in include/dic.h).
 #include "dic.h"
 #include "conv.h"
+#include "nn_kernels.h"
 
 #include <cstdio>
 
@@ -157,6 +158,179 @@ int dic_debug_conv1x1_bn(const float* raw, const float* scale, const float* shif
                          int tail_ws_slabs, void* stream) {
   return conv1x1_fwd_bf3_bn(raw, scale, shift, res, relu, act_out, M, C, w_planes, CO, y, bn_partial, mtiles_out, tail_ws, tail_ws_slabs,
                             (hipStream_t)stream, nullptr, nullptr);
+}
+/* ---- debug entry points of the BatchNorm / pooling / element-wise kernels (nn_kernels.h; declared in include/dic.h): thin wrappers,
+ *      every argument checked before the first launch.  A BnBuf travels as its four pointers, an F16Scale as its two. */
+static int bn_buf(const float* scale, const float* shift, const float* mean, const float* invstd, BnBuf* out, const char* who) {
+  DIC_REQUIRE(scale && shift && mean && invstd, "%s: a BatchNorm buffer (scale, shift, mean, invstd) is NULL", who);
+  *out = BnBuf{const_cast<float*>(scale), const_cast<float*>(shift), const_cast<float*>(mean), const_cast<float*>(invstd)};
+  return DIC_OK;
+}
+// an optional BatchNorm: all four NULL (-> *have = false) or all four given
+static int bn_buf_opt(const float* scale, const float* shift, const float* mean, const float* invstd, BnBuf* out, bool* have, const char* who) {
+  *have = scale || shift || mean || invstd;
+  *out = BnBuf{};
+  return *have ? bn_buf(scale, shift, mean, invstd, out, who) : DIC_OK;
+}
+// plane output: NULL (none), {hi, mid, lo} (bf16x3) or {h1, h2, NULL} (f16x2)
+static int plane_list(uint16_t* const planes[3], const char* who) {
+  DIC_REQUIRE(!planes || (planes[0] && planes[1]), "%s: planes[0] / planes[1] is NULL", who);
+  return DIC_OK;
+}
+int dic_debug_bn_backward_ws_floats(int C) {
+  DIC_REQUIRE(C > 0 && C % 64 == 0, "dic_debug_bn_backward_ws_floats: C=%d must be a positive multiple of 64", C);
+  const size_t n = bn_backward_ws_floats(C);
+  DIC_REQUIRE(n < ((size_t)1 << 31), "dic_debug_bn_backward_ws_floats: C=%d is out of range", C);
+  return (int)n;
+}
+int dic_debug_bn_finalize(const float* partial, int mtiles, long long count, int C, const float* gamma, const float* beta,
+                          float* running_mean, float* running_var, float* scale, float* shift, float* mean, float* invstd, double* red,
+                          size_t red_doubles, uint32_t* status, void* stream) {
+  BnBuf bn;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_bn_finalize"));
+  DIC_REQUIRE(partial && gamma && beta, "dic_debug_bn_finalize: partial / gamma / beta is NULL");
+  DIC_REQUIRE(mtiles >= 1 && count >= 1 && C >= 1, "dic_debug_bn_finalize: mtiles=%d count=%lld C=%d must be positive", mtiles, count, C);
+  DIC_REQUIRE(!running_mean == !running_var, "dic_debug_bn_finalize: running_mean and running_var go together");
+  DIC_REQUIRE(!red || red_doubles >= bn_finalize_ws_doubles(mtiles, C), "dic_debug_bn_finalize: red holds %zu doubles, %zu needed", red_doubles,
+              bn_finalize_ws_doubles(mtiles, C));
+  return bn_finalize_train(partial, mtiles, count, C, gamma, beta, running_mean, running_var, bn, red, (hipStream_t)stream, status);
+}
+int dic_debug_bn_finalize_eval(int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                               float* scale, float* shift, float* mean, float* invstd, void* stream) {
+  BnBuf bn;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_bn_finalize_eval"));
+  DIC_REQUIRE(gamma && beta && running_mean && running_var, "dic_debug_bn_finalize_eval: gamma / beta / running statistics NULL");
+  DIC_REQUIRE(C >= 1, "dic_debug_bn_finalize_eval: C=%d must be positive", C);
+  return bn_finalize_eval(C, gamma, beta, running_mean, running_var, bn, (hipStream_t)stream);
+}
+/* planes == NULL: bn_apply (y required, residual fp32 or none); otherwise bn_apply_planes */
+int dic_debug_bn_apply(const float* x, const float* residual, const uint16_t* const residual_planes[3], float* y, uint16_t* const planes[3],
+                       long long rows, int C, const float* scale, const float* shift, const float* mean, const float* invstd, int relu,
+                       const float* res_scale, const float* res_shift, const float* res_mean, const float* res_invstd, uint32_t* status,
+                       void* stream) {
+  BnBuf bn, rbn;
+  bool have_rbn;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_bn_apply"));
+  DIC_TRY(bn_buf_opt(res_scale, res_shift, res_mean, res_invstd, &rbn, &have_rbn, "dic_debug_bn_apply (residual)"));
+  DIC_TRY(plane_list(planes, "dic_debug_bn_apply"));
+  DIC_REQUIRE(x, "dic_debug_bn_apply: x is NULL");
+  DIC_REQUIRE(rows >= 1 && C >= 1, "dic_debug_bn_apply: rows=%lld C=%d must be positive", rows, C);
+  DIC_REQUIRE(!residual_planes || (residual_planes[0] && residual_planes[1] && residual_planes[2]), "dic_debug_bn_apply: a residual plane is NULL");
+  if (!planes) {
+    DIC_REQUIRE(y, "dic_debug_bn_apply: no output (y and planes NULL)");
+    DIC_REQUIRE(!residual_planes && !have_rbn, "dic_debug_bn_apply: a plane residual or a residual BatchNorm needs plane output");
+    DIC_REQUIRE(C % 4 == 0, "dic_debug_bn_apply: C=%d %% 4", C);
+    return bn_apply(x, residual, y, rows, C, bn, relu, (hipStream_t)stream);
+  }
+  DIC_REQUIRE(C % 32 == 0, "dic_debug_bn_apply: C=%d %% 32 (plane output)", C);
+  return bn_apply_planes(x, residual, residual_planes, y, planes, rows, C, bn, relu, (hipStream_t)stream, have_rbn ? &rbn : nullptr, status);
+}
+static int pool_geometry(const char* who, int B, int H, int W, int C, int k, int s, int p) {
+  DIC_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: B=%d H=%d W=%d C=%d must be positive", who, B, H, W, C);
+  DIC_REQUIRE(C % 4 == 0, "%s: C=%d %% 4", who, C);
+  DIC_REQUIRE(k >= 1 && k <= 15 && s >= 1 && p >= 0 && 2 * p <= k, "%s: k=%d (1..15) s=%d p=%d (at most k / 2)", who, k, s, p);
+  DIC_REQUIRE(H + 2 * p >= k && W + 2 * p >= k, "%s: the %dx%d window does not fit the padded %dx%d map", who, k, k, H + 2 * p, W + 2 * p);
+  return DIC_OK;
+}
+/* bn: all four NULL = no BatchNorm */
+int dic_debug_bn_relu_maxpool(const float* x, int B, int H, int W, int C, const float* scale, const float* shift, const float* mean,
+                              const float* invstd, int relu, int k, int s, int p, float* y, unsigned char* idx, uint16_t* const planes[3],
+                              uint32_t* status, float* xsel, void* stream) {
+  BnBuf bn;
+  bool have_bn;
+  DIC_TRY(bn_buf_opt(scale, shift, mean, invstd, &bn, &have_bn, "dic_debug_bn_relu_maxpool"));
+  DIC_TRY(plane_list(planes, "dic_debug_bn_relu_maxpool"));
+  DIC_TRY(pool_geometry("dic_debug_bn_relu_maxpool", B, H, W, C, k, s, p));
+  DIC_REQUIRE(x && (y || planes), "dic_debug_bn_relu_maxpool: x is NULL or there is no output");
+  DIC_REQUIRE(!planes || C % 32 == 0, "dic_debug_bn_relu_maxpool: C=%d %% 32 (plane output)", C);
+  return bn_relu_maxpool(x, B, H, W, C, have_bn ? &bn : nullptr, relu, k, s, p, y, idx, (hipStream_t)stream, planes, status, xsel);
+}
+int dic_debug_adaptive_avgpool(const float* x, int B, int H, int W, int C, const float* scale, const float* shift, const float* mean,
+                               const float* invstd, int relu, int out, float* y, void* stream) {
+  BnBuf bn;
+  bool have_bn;
+  DIC_TRY(bn_buf_opt(scale, shift, mean, invstd, &bn, &have_bn, "dic_debug_adaptive_avgpool"));
+  DIC_REQUIRE(x && y, "dic_debug_adaptive_avgpool: x / y is NULL");
+  DIC_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1 && out >= 1, "dic_debug_adaptive_avgpool: B=%d H=%d W=%d C=%d out=%d must be positive", B, H, W, C, out);
+  DIC_REQUIRE(C % 4 == 0, "dic_debug_adaptive_avgpool: C=%d %% 4", C);
+  return adaptive_avgpool(x, B, H, W, C, have_bn ? &bn : nullptr, relu, out, y, (hipStream_t)stream);
+}
+int dic_debug_adaptive_avgpool_bwd(const float* dy, int B, int H, int W, int C, int out, float* dx, void* stream) {
+  DIC_REQUIRE(dy && dx, "dic_debug_adaptive_avgpool_bwd: dy / dx is NULL");
+  DIC_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1 && out >= 1, "dic_debug_adaptive_avgpool_bwd: B=%d H=%d W=%d C=%d out=%d must be positive", B, H, W, C, out);
+  DIC_REQUIRE(C % 4 == 0, "dic_debug_adaptive_avgpool_bwd: C=%d %% 4", C);
+  return adaptive_avgpool_bwd(dy, B, H, W, C, out, dx, (hipStream_t)stream);
+}
+/* k == stride, no padding; idx as bn_relu_maxpool wrote it */
+int dic_debug_maxpool_relu_bwd(const float* dpool, const unsigned char* idx, const float* x, int B, int H, int W, int C, int k,
+                               const float* scale, const float* shift, const float* mean, const float* invstd, float* dy, void* stream) {
+  BnBuf bn;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_maxpool_relu_bwd"));
+  DIC_TRY(pool_geometry("dic_debug_maxpool_relu_bwd", B, H, W, C, k, k, 0));
+  DIC_REQUIRE(dpool && idx && x && dy, "dic_debug_maxpool_relu_bwd: dpool / idx / x / dy is NULL");
+  return maxpool_relu_bwd(dpool, idx, x, B, H, W, C, k, bn, dy, (hipStream_t)stream);
+}
+int dic_debug_relu_mask_bwd(float* dy, const float* x, long long rows, int C, const float* scale, const float* shift, const float* mean,
+                            const float* invstd, void* stream) {
+  BnBuf bn;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_relu_mask_bwd"));
+  DIC_REQUIRE(dy && x, "dic_debug_relu_mask_bwd: dy / x is NULL");
+  DIC_REQUIRE(rows >= 1 && C >= 1 && C % 4 == 0, "dic_debug_relu_mask_bwd: rows=%lld, C=%d %% 4", rows, C);
+  return relu_mask_bwd(dy, x, rows, C, bn, (hipStream_t)stream);
+}
+static int f16_scale(const uint16_t* const planes[3], uint32_t* bound, float* slot, F16Scale* out, const char* who) {
+  *out = F16Scale{bound, slot};
+  DIC_REQUIRE(!(planes && !planes[2]) || (bound && slot), "%s: f16x2 planes need the scale's bound word and slot", who);
+  return DIC_OK;
+}
+/* ws: dic_debug_bn_backward_ws_floats(C) floats */
+int dic_debug_bn_backward(float* dy_dx, const float* x, long long rows, int C, const float* gamma, const float* scale, const float* shift,
+                          const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ws, size_t ws_floats,
+                          uint16_t* const dx_planes[3], uint32_t* f16_bound, float* f16_slot, void* stream) {
+  BnBuf bn;
+  F16Scale fs;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_bn_backward"));
+  DIC_TRY(plane_list(dx_planes, "dic_debug_bn_backward"));
+  DIC_TRY(f16_scale(dx_planes, f16_bound, f16_slot, &fs, "dic_debug_bn_backward"));
+  DIC_REQUIRE(dy_dx && x && gamma && dgamma && dbeta && ws, "dic_debug_bn_backward: dy_dx / x / gamma / dgamma / dbeta / ws is NULL");
+  DIC_REQUIRE(rows >= 1 && C >= 1 && C % 64 == 0, "dic_debug_bn_backward: rows=%lld, C=%d %% 64", rows, C);
+  DIC_REQUIRE(ws_floats >= bn_backward_ws_floats(C), "dic_debug_bn_backward: ws holds %zu floats, %zu needed", ws_floats, bn_backward_ws_floats(C));
+  return bn_backward(dy_dx, x, rows, C, gamma, bn, dgamma, dbeta, ws, (hipStream_t)stream, dx_planes, &fs);
+}
+int dic_debug_bn_pool_backward(const float* dpool, const unsigned char* idx, const float* x, int B, int H, int W, int C, int k,
+                               const float* gamma, const float* scale, const float* shift, const float* mean, const float* invstd,
+                               float* dgamma, float* dbeta, float* ws, size_t ws_floats, float* dy, uint16_t* const dy_planes[3],
+                               uint32_t* f16_bound, float* f16_slot, void* stream) {
+  BnBuf bn;
+  F16Scale fs;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, "dic_debug_bn_pool_backward"));
+  DIC_TRY(plane_list(dy_planes, "dic_debug_bn_pool_backward"));
+  DIC_TRY(f16_scale(dy_planes, f16_bound, f16_slot, &fs, "dic_debug_bn_pool_backward"));
+  DIC_TRY(pool_geometry("dic_debug_bn_pool_backward", B, H, W, C, k, k, 0));
+  DIC_REQUIRE(dpool && idx && x && gamma && dgamma && dbeta && ws && dy, "dic_debug_bn_pool_backward: dpool / idx / x / gamma / dgamma / dbeta / ws / dy is NULL");
+  DIC_REQUIRE(C % 64 == 0 && 256 % (C / 4) == 0, "dic_debug_bn_pool_backward: C=%d %% 64, with C / 4 dividing 256", C);
+  DIC_REQUIRE(ws_floats >= bn_backward_ws_floats(C), "dic_debug_bn_pool_backward: ws holds %zu floats, %zu needed", ws_floats, bn_backward_ws_floats(C));
+  return bn_pool_backward(dpool, idx, x, B, H, W, C, k, gamma, bn, dgamma, dbeta, ws, dy, (hipStream_t)stream, dy_planes, &fs);
+}
+/* ws: 256 * C floats */
+int dic_debug_colsum_rows(const float* X, long long ld, long long rows, int C, float* out, float* ws, size_t ws_floats, void* stream) {
+  DIC_REQUIRE(X && out && ws, "dic_debug_colsum_rows: X / out / ws is NULL");
+  DIC_REQUIRE(rows >= 1 && C >= 1 && ld >= C, "dic_debug_colsum_rows: rows=%lld C=%d ld=%lld (at least C)", rows, C, ld);
+  DIC_REQUIRE(ws_floats >= (size_t)256 * C, "dic_debug_colsum_rows: ws holds %zu floats, %zu needed", ws_floats, (size_t)256 * C);
+  return colsum_rows(X, ld, rows, C, out, ws, (hipStream_t)stream);
+}
+int dic_debug_f16_scale_reset(uint32_t* bounds, int n, void* stream) {
+  DIC_REQUIRE(bounds && n >= 1 && n <= 64, "dic_debug_f16_scale_reset: bounds is NULL or n=%d is outside 1..64", n);
+  return f16_scale_reset(bounds, n, (hipStream_t)stream);
+}
+int dic_debug_f16_scale_from_absmax(const float* x, long long n, uint32_t* bound, float* slot, void* stream) {
+  DIC_REQUIRE(x && bound && slot, "dic_debug_f16_scale_from_absmax: x / bound / slot is NULL");
+  DIC_REQUIRE(n >= 4 && n % 4 == 0, "dic_debug_f16_scale_from_absmax: n=%lld %% 4", n);
+  return f16_scale_from_absmax(x, n, F16Scale{bound, slot}, (hipStream_t)stream);
+}
+int dic_debug_f16_scale_finish(uint32_t* bound, float* slot, void* stream) {
+  DIC_REQUIRE(bound && slot, "dic_debug_f16_scale_finish: bound / slot is NULL");
+  return f16_scale_finish(F16Scale{bound, slot}, (hipStream_t)stream);
 }
 int dic_profile_begin(void) { return gemm_profile_begin(); }
 int dic_profile_end(int max_entries, int* keys, double* total_ms, double* total_flops, long long* launches, int* n_out) {

@@ -826,6 +826,76 @@ int dic_gather_rows(const float* table, const int64_t* idx, int n, long long row
  * bf16x3 key of dic_profile_end: 2000 (f16x2 operand format: 3000) + 10*A_kind (6 = on-the-fly BatchNorm operand) + t, t = 2*(tile_m/64 - 1) + (tile_n/64 - 1) for the plain tiles,
  * 5 = persistent warp-specialised 128x128, 6 = LDS-halo 3x3 (experiments: 4 = deep-pipelined, 7 = 256x128, 8 = computing-wave DMA). */
 int dic_debug_force_staged_gemm(int on);
+/* The BatchNorm / pooling / element-wise kernels between the encoders' convolutions (csrc/nn_kernels.hip), one at a time, for
+ * tests/test_nn_kernels_gpu.py: the same host functions and launches the encoders use, nothing else.  Activations NHWC fp32.
+ *   A BatchNorm buffer travels as its four device arrays of C floats: scale, shift (y = x * scale + shift) and the saved mean,
+ *   invstd.  Where it is optional, all four NULL mean "no BatchNorm".
+ *   Plane output `planes`: NULL (none), {hi, mid, lo} (bf16x3: hi + mid + lo is the fp32 value, exactly) or {h1, h2, NULL} (f16x2:
+ *   the planes of dic_split_f16x2_paired; scale 4 for activations, the device-chosen scale for gradients), each in the row-pair
+ *   layout of dic_split_bf16x3_paired with ((rows + 1) & ~1) * C elements.  dic_debug_bn_apply zeroes the pad row of an odd row
+ *   count; the other kernels leave it alone.
+ *   A device-chosen f16x2 scale travels as f16_bound (one uint32 the caller has zeroed, dic_debug_f16_scale_reset: receives the bit
+ *   pattern of an upper bound of |value|) and f16_slot (two floats: s = 2^(13 - floor(log2 bound)), so that bound * s lies in
+ *   [2^13, 2^14), and 1 / s); both required with f16x2 planes.
+ *   status (nullable): the overflow guard word of dic_resnet_fwd - bit 1 / 2 a plane value beyond the fp16 range (bn_apply /
+ *   max-pool), bit 8 non-finite BatchNorm sums.
+ * Every entry point checks its arguments before the first launch and returns a negative code with dic_last_error() set: NULL
+ * pointers, non-positive sizes, C % 4 (the apply, pooling and mask kernels; the two finalize entry points and dic_debug_colsum_rows take
+ * any C), C % 32 (plane output), C % 64 (the two backward reductions), C / 4 dividing 256 (dic_debug_bn_pool_backward), a workspace below
+ * the stated size.  Not checked: that the contents agree with the sizes (count against mtiles * 64, idx below k * k). */
+/* train mode: partial [mtiles][2][C] = per-64-row sums and sums of squares of a convolution output of `count` rows -> scale, shift,
+ * mean, invstd (biased variance, eps 1e-5); running statistics (both or neither) updated in place with momentum 0.1 and the unbiased
+ * variance (count = 1: the biased one), exactly as a zeroed slot followed by dic_bn_ema_update; left untouched for a channel whose sums
+ * are not finite.  red (nullable: one launch whatever mtiles): red_doubles >= ceil(mtiles / 256) * 2 * C + 16 doubles of scratch for
+ * the two-launch form taken above 1024 rows of partials (dic_debug_force_staged_gemm(182): above 512). */
+int dic_debug_bn_finalize(const float* partial, int mtiles, long long count, int C, const float* gamma, const float* beta,
+                          float* running_mean, float* running_var, float* scale, float* shift, float* mean, float* invstd, double* red,
+                          size_t red_doubles, uint32_t* status, void* stream);
+/* eval mode: the same four arrays from the running statistics */
+int dic_debug_bn_finalize_eval(int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                               float* scale, float* shift, float* mean, float* invstd, void* stream);
+/* y = [relu](x * scale + shift [+ residual]), rows x C.  planes == NULL: fp32 only (y required; residual fp32 or NULL; C % 4).
+ * Otherwise planes (+ the fp32 copy y, nullable), C % 32, and the residual is one of: none, fp32 `residual`, bf16x3 `residual_planes`
+ * (bf16x3 output only), or a raw fp32 `residual` with its own BatchNorm res_* (added as residual * res_scale + res_shift). */
+int dic_debug_bn_apply(const float* x, const float* residual, const uint16_t* const residual_planes[3], float* y, uint16_t* const planes[3],
+                       long long rows, int C, const float* scale, const float* shift, const float* mean, const float* invstd, int relu,
+                       const float* res_scale, const float* res_shift, const float* res_mean, const float* res_invstd, uint32_t* status,
+                       void* stream);
+/* y [B,PH,PW,C] = max over k x k windows (stride s, padding p <= k / 2, padded positions never selected) of [relu](x * scale + shift);
+ * idx (nullable): kh * k + kw of the first maximum in scan order; xsel (nullable): the raw x there; planes as above (y nullable then). */
+int dic_debug_bn_relu_maxpool(const float* x, int B, int H, int W, int C, const float* scale, const float* shift, const float* mean,
+                              const float* invstd, int relu, int k, int s, int p, float* y, unsigned char* idx, uint16_t* const planes[3],
+                              uint32_t* status, float* xsel, void* stream);
+/* F.adaptive_avg_pool2d([relu](x * scale + shift), out) on [B,H,W,C] -> [B,out,out,C], and its backward dy -> dx (no BatchNorm) */
+int dic_debug_adaptive_avgpool(const float* x, int B, int H, int W, int C, const float* scale, const float* shift, const float* mean,
+                               const float* invstd, int relu, int out, float* y, void* stream);
+int dic_debug_adaptive_avgpool_bwd(const float* dy, int B, int H, int W, int C, int out, float* dx, void* stream);
+/* non-overlapping k x k windows (stride k, no padding): dy[b,h,w,c] = dpool of its window where idx names this position and
+ * x * scale + shift > 0, else 0 (rows / columns behind the last whole window: 0) */
+int dic_debug_maxpool_relu_bwd(const float* dpool, const unsigned char* idx, const float* x, int B, int H, int W, int C, int k,
+                               const float* scale, const float* shift, const float* mean, const float* invstd, float* dy, void* stream);
+/* dy *= (x * scale + shift > 0), in place */
+int dic_debug_relu_mask_bwd(float* dy, const float* x, long long rows, int C, const float* scale, const float* shift, const float* mean,
+                            const float* invstd, void* stream);
+/* floats of workspace the two BatchNorm backward entry points need for C channels (C % 64 == 0); negative on a bad C */
+int dic_debug_bn_backward_ws_floats(int C);
+/* train-mode BatchNorm backward over rows x C from the saved mean / invstd: dgamma = sum g * xhat, dbeta = sum g, and in place over
+ * dy_dx  dx = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat)); dx_planes (nullable) the same dx as planes */
+int dic_debug_bn_backward(float* dy_dx, const float* x, long long rows, int C, const float* gamma, const float* scale, const float* shift,
+                          const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ws, size_t ws_floats,
+                          uint16_t* const dx_planes[3], uint32_t* f16_bound, float* f16_slot, void* stream);
+/* dic_debug_maxpool_relu_bwd followed by dic_debug_bn_backward without the intermediate: dpool [B,H/k,W/k,C], x and dy [B,H,W,C] */
+int dic_debug_bn_pool_backward(const float* dpool, const unsigned char* idx, const float* x, int B, int H, int W, int C, int k,
+                               const float* gamma, const float* scale, const float* shift, const float* mean, const float* invstd,
+                               float* dgamma, float* dbeta, float* ws, size_t ws_floats, float* dy, uint16_t* const dy_planes[3],
+                               uint32_t* f16_bound, float* f16_slot, void* stream);
+/* out[c] = sum_r X[r * ld + c], c < C <= ld; ws: 256 * C floats */
+int dic_debug_colsum_rows(const float* X, long long ld, long long rows, int C, float* out, float* ws, size_t ws_floats, void* stream);
+/* the device-chosen f16x2 scale on its own: zero n <= 64 bound words; bound = max |x| over n % 4 == 0 floats (a NaN counts as inf)
+ * and the slot; the slot alone from a bound other kernels have raised */
+int dic_debug_f16_scale_reset(uint32_t* bounds, int n, void* stream);
+int dic_debug_f16_scale_from_absmax(const float* x, long long n, uint32_t* bound, float* slot, void* stream);
+int dic_debug_f16_scale_finish(uint32_t* bound, float* slot, void* stream);
 /* Tuning knob (process-global): the persistent split-bf16 convolution kernels (one workgroup per CU, each walking several output
  * tiles) launch at most `max_workgroups` workgroups.  Default 224.  A small value (e.g. 49: every ResNet-152 layer at batch
  * 64 has a multiple of 49 tiles) lets the convolutions of several forwards in flight on different streams occupy disjoint
