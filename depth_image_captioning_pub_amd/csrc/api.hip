@@ -332,6 +332,147 @@ int dic_debug_f16_scale_finish(uint32_t* bound, float* slot, void* stream) {
   DIC_REQUIRE(bound && slot, "dic_debug_f16_scale_finish: bound / slot is NULL");
   return f16_scale_finish(F16Scale{bound, slot}, (hipStream_t)stream);
 }
+/* ---- debug entry points of the depth encoder's convolution gradient kernels and their operand producers (conv.h; declared in
+ *      include/dic.h): the host functions dic_depth_encoder_bwd calls, one at a time, every argument checked before the first launch. */
+static int conv_geometry(const char* who, int B, int H, int W, int C, int CO, int k, int stride, int pad) {
+  DIC_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1 && CO >= 1, "%s: B=%d H=%d W=%d C=%d CO=%d must be positive", who, B, H, W, C, CO);
+  DIC_REQUIRE(k >= 1 && k <= 7 && stride >= 1 && pad >= 0 && pad < k, "%s: k=%d (1..7) stride=%d pad=%d (below k)", who, k, stride, pad);
+  DIC_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k, "%s: the %dx%d filter does not fit the padded %dx%d map", who, k, k, H + 2 * pad, W + 2 * pad);
+  const ConvDesc d{B, H, W, C, CO, k, k, stride, pad, 0};
+  DIC_REQUIRE((long long)B * d.OH() * d.OW() <= 0x7fffffffll - 32 && (long long)B * H * W <= 0x7fffffffll, "%s: more than 2^31 pixels", who);
+  return DIC_OK;
+}
+// plane lists of these entry points: three planes (bf16x3) or the first two (f16x2)
+static int plane_triple(const uint16_t* const planes[3], int fmt, const char* who, const char* what) {
+  DIC_REQUIRE(planes && planes[0] && planes[1] && (fmt || planes[2]), "%s: %s: a plane pointer is NULL", who, what);
+  return DIC_OK;
+}
+int dic_debug_conv_wgrad_sizes(int B, int H, int W, int C, int CO, int k, int stride, int pad, int splitk, size_t* dyT_elems, size_t* pT_elems,
+                               size_t* ws_floats) {
+  DIC_TRY(conv_geometry("dic_debug_conv_wgrad_sizes", B, H, W, C, CO, k, stride, pad));
+  DIC_REQUIRE(C % 32 == 0 && CO % 32 == 0, "dic_debug_conv_wgrad_sizes: C=%d and CO=%d %% 32", C, CO);
+  DIC_REQUIRE(splitk >= 1 && splitk <= 16, "dic_debug_conv_wgrad_sizes: splitk=%d is outside 1..16", splitk);
+  DIC_REQUIRE(dyT_elems && pT_elems && ws_floats, "dic_debug_conv_wgrad_sizes: an output pointer is NULL");
+  const ConvDesc d{B, H, W, C, CO, k, k, stride, pad, 0};
+  *dyT_elems = conv_wgrad_bf3_plane_elems(d, 0); *pT_elems = conv_wgrad_bf3_plane_elems(d, 1); *ws_floats = conv_wgrad_bf3_ws_floats(d, splitk);
+  return DIC_OK;
+}
+int dic_debug_conv_wgrad(const float* x, int B, int H, int W, int C, int CO, int k, int stride, int pad, const float* dy, float* dw_ohwi,
+                         int splitk, uint16_t* const dyT[3], size_t dyT_elems, uint16_t* const pT[3], size_t pT_elems, float* ws,
+                         size_t ws_floats, int fmt, const float* dy_slot, void* stream) {
+  const char* who = "dic_debug_conv_wgrad";
+  DIC_TRY(conv_geometry(who, B, H, W, C, CO, k, stride, pad));
+  DIC_REQUIRE(x && dy && dw_ohwi && ws, "%s: x / dy / dw_ohwi / ws is NULL", who);
+  DIC_REQUIRE(fmt == 0 || fmt == 1, "%s: fmt=%d is neither 0 (bf16x3) nor 1 (f16x2)", who, fmt);
+  DIC_REQUIRE(C % 32 == 0 && CO % 32 == 0, "%s: C=%d and CO=%d %% 32", who, C, CO);
+  DIC_REQUIRE(splitk >= 1 && splitk <= 16, "%s: splitk=%d is outside 1..16", who, splitk);
+  DIC_TRY(plane_triple(dyT, fmt, who, "dyT"));
+  DIC_TRY(plane_triple(pT, fmt, who, "pT"));
+  DIC_REQUIRE(fmt == 0 || dy_slot, "%s: the f16x2 format needs the gradient's scale slot", who);
+  const ConvDesc d{B, H, W, C, CO, k, k, stride, pad, 0};
+  DIC_REQUIRE(dyT_elems >= conv_wgrad_bf3_plane_elems(d, 0), "%s: dyT planes hold %zu elements, %zu needed", who, dyT_elems, conv_wgrad_bf3_plane_elems(d, 0));
+  DIC_REQUIRE(pT_elems >= conv_wgrad_bf3_plane_elems(d, 1), "%s: pT planes hold %zu elements, %zu needed", who, pT_elems, conv_wgrad_bf3_plane_elems(d, 1));
+  DIC_REQUIRE(ws_floats >= conv_wgrad_bf3_ws_floats(d, splitk), "%s: ws holds %zu floats, %zu needed", who, ws_floats, conv_wgrad_bf3_ws_floats(d, splitk));
+  return conv_wgrad_bf3(x, d, dy, dw_ohwi, splitk, dyT, pT, ws, (hipStream_t)stream, fmt, dy_slot);
+}
+/* (B, H, W, C, CO, k, pad describe the FORWARD convolution, stride 1; dy planes [B*OH*OW][CO], wflip planes [C][k*k*CO], dx [B,H,W,C]) */
+int dic_debug_conv_dgrad_s1(const uint16_t* const dy_planes[3], int B, int H, int W, int C, int CO, int k, int pad,
+                            const uint16_t* const wflip_planes[3], float* dx, float* tail_ws, int tail_ws_slabs, int fmt, const float* alpha_dev0,
+                            const float* alpha_dev1, void* stream) {
+  const char* who = "dic_debug_conv_dgrad_s1";
+  DIC_TRY(conv_geometry(who, B, H, W, C, CO, k, 1, pad));
+  DIC_REQUIRE(fmt == 0 || fmt == 1, "%s: fmt=%d is neither 0 (bf16x3) nor 1 (f16x2)", who, fmt);
+  DIC_REQUIRE(C % 32 == 0 && CO % 32 == 0, "%s: C=%d and CO=%d %% 32", who, C, CO);
+  DIC_REQUIRE(k * k <= 32, "%s: k=%d: at most 32 taps", who, k);
+  DIC_TRY(plane_triple(dy_planes, fmt, who, "dy_planes"));
+  DIC_TRY(plane_triple(wflip_planes, fmt, who, "wflip_planes"));
+  DIC_REQUIRE(dx, "%s: dx is NULL", who);
+  DIC_REQUIRE(!tail_ws == (tail_ws_slabs == 0) && tail_ws_slabs >= 0 && tail_ws_slabs <= 1024, "%s: tail_ws and tail_ws_slabs=%d (0..1024) go together", who, tail_ws_slabs);
+  DIC_REQUIRE(fmt == 1 || (!alpha_dev0 && !alpha_dev1), "%s: device-resident factors belong to the f16x2 format", who);
+  const ConvDesc d{B, H, W, C, CO, k, k, 1, pad, 0};
+  return conv_dgrad_s1_bf3(dy_planes, d, wflip_planes, dx, (hipStream_t)stream, tail_ws, tail_ws ? tail_ws_slabs : 256, fmt, alpha_dev0, alpha_dev1);
+}
+/* plane_elems: what every plane holds, at least 512 * 1152 (w2, w2f) resp. 2048 * 512 (w3, w3f) */
+int dic_debug_depth_prepare_weights(const float* w2_oihw, const float* w3_oihw, uint16_t* const w2_pl[3], uint16_t* const w2f_pl[3],
+                                    uint16_t* const w3_pl[3], uint16_t* const w3f_pl[3], size_t w2_plane_elems, size_t w3_plane_elems,
+                                    const float* slots, void* stream) {
+  const char* who = "dic_debug_depth_prepare_weights";
+  const int fmt = slots ? 1 : 0;
+  DIC_REQUIRE(w2_oihw && w3_oihw, "%s: w2 / w3 is NULL", who);
+  DIC_TRY(plane_triple(w2_pl, fmt, who, "w2_pl"));
+  DIC_TRY(plane_triple(w2f_pl, fmt, who, "w2f_pl"));
+  DIC_TRY(plane_triple(w3_pl, fmt, who, "w3_pl"));
+  DIC_TRY(plane_triple(w3f_pl, fmt, who, "w3f_pl"));
+  DIC_REQUIRE(w2_plane_elems >= (size_t)512 * 1152 && w3_plane_elems >= (size_t)2048 * 512, "%s: planes hold %zu / %zu elements, %zu / %zu needed", who,
+              w2_plane_elems, w3_plane_elems, (size_t)512 * 1152, (size_t)2048 * 512);
+  return depth_prepare_weights(w2_oihw, w3_oihw, w2_pl, w2f_pl, w3_pl, w3f_pl, slots, (hipStream_t)stream);
+}
+/* the fp32 weight gradient of the generic contraction kernel (conv_wgrad, conv.hip; layer 1 of the depth encoder for W > 640):
+ * x NHWC or (in_nchw = 1, as the encoder describes its one-channel map) NCHW, dw OHWI, ws: splitk * CO * k * k * C floats for splitk > 1 */
+int dic_debug_conv_wgrad_f32(const float* x, int B, int H, int W, int C, int in_nchw, int CO, int k, int stride, int pad, const float* dy, float* dw_ohwi,
+                             int splitk, float* ws, size_t ws_floats, void* stream) {
+  const char* who = "dic_debug_conv_wgrad_f32";
+  DIC_TRY(conv_geometry(who, B, H, W, C, CO, k, stride, pad));
+  DIC_REQUIRE(x && dy && dw_ohwi, "%s: x / dy / dw_ohwi is NULL", who);
+  DIC_REQUIRE(splitk >= 1 && splitk <= 1024, "%s: splitk=%d is outside 1..1024", who, splitk);
+  DIC_REQUIRE(in_nchw == 0 || in_nchw == 1, "%s: in_nchw=%d is neither 0 nor 1", who, in_nchw);
+  const size_t need = gemm_splitk_ws_bytes(CO, k * k * C, splitk) / sizeof(float);
+  DIC_REQUIRE(splitk == 1 || (ws && ws_floats >= need), "%s: ws holds %zu floats, %zu needed", who, ws ? ws_floats : (size_t)0, need);
+  const ConvDesc d{B, H, W, C, CO, k, k, stride, pad, in_nchw};
+  return conv_wgrad(x, d, dy, dw_ohwi, splitk, ws, (hipStream_t)stream);
+}
+static const ConvDesc layer1_desc(int B, int H, int W) { return ConvDesc{B, H, W, 1, 128, 7, 7, 3, 0, 0}; }
+/* floats of `ws` dic_debug_depth_layer1_bwd_sparse needs; negative on a bad shape */
+int dic_debug_depth_layer1_sparse_ws_floats(int B, int H, int W) {
+  DIC_REQUIRE(B >= 1 && H >= 7 && W >= 7 && (long long)B * H * W <= 0x7fffffffll, "dic_debug_depth_layer1_sparse_ws_floats: B=%d H=%d W=%d", B, H, W);
+  const size_t n = depth_layer1_sparse_ws_floats(layer1_desc(B, H, W));
+  DIC_REQUIRE(n < ((size_t)1 << 31), "dic_debug_depth_layer1_sparse_ws_floats: B=%d H=%d W=%d is out of range", B, H, W);
+  return (int)n;
+}
+constexpr size_t kLayer1ColsumFloats = (size_t)64 * 128 * 49;      // colsum_rows scratch for 128 * 49 columns (conv.h)
+/* returns 1 (nothing launched) where depth_layer1_sparse_supported is false */
+int dic_debug_depth_layer1_bwd_sparse(const float* depth, int B, int H, int W, const float* dpool, const unsigned char* idx, const float* xsel,
+                                      const float* conv_w, const float* conv_b, const float* gamma, const float* scale, const float* shift,
+                                      const float* mean, const float* invstd, float* dgamma, float* dbeta, float* dW, float* db, float* bn_ws,
+                                      size_t bn_ws_floats, float* ws, size_t ws_floats, float* cs_ws, size_t cs_ws_floats, void* stream) {
+  const char* who = "dic_debug_depth_layer1_bwd_sparse";
+  BnBuf bn;
+  DIC_TRY(bn_buf(scale, shift, mean, invstd, &bn, who));
+  DIC_REQUIRE(depth && dpool && idx && xsel && conv_w && conv_b && gamma, "%s: depth / dpool / idx / xsel / conv_w / conv_b / gamma is NULL", who);
+  DIC_REQUIRE(dgamma && dbeta && dW && db && bn_ws && ws && cs_ws, "%s: dgamma / dbeta / dW / db / bn_ws / ws / cs_ws is NULL", who);
+  DIC_REQUIRE(B >= 1 && H >= 7 && W >= 7 && (long long)B * H * W <= 0x7fffffffll, "%s: B=%d H=%d W=%d", who, B, H, W);
+  const ConvDesc d = layer1_desc(B, H, W);
+  if (!depth_layer1_sparse_supported(d)) return 1;
+  DIC_REQUIRE(bn_ws_floats >= bn_backward_ws_floats(128), "%s: bn_ws holds %zu floats, %zu needed", who, bn_ws_floats, bn_backward_ws_floats(128));
+  DIC_REQUIRE(ws_floats >= depth_layer1_sparse_ws_floats(d), "%s: ws holds %zu floats, %zu needed", who, ws_floats, depth_layer1_sparse_ws_floats(d));
+  DIC_REQUIRE(cs_ws_floats >= kLayer1ColsumFloats, "%s: cs_ws holds %zu floats, %zu needed", who, cs_ws_floats, kLayer1ColsumFloats);
+  return depth_layer1_backward_sparse(depth, d, dpool, idx, xsel, conv_w, conv_b, gamma, bn, dgamma, dbeta, dW, db, bn_ws, ws, cs_ws, (hipStream_t)stream);
+}
+/* dic_debug_conv1_fwd / dic_debug_conv1_wgrad with their arguments checked: the packed layer-1 kernels (conv1_depth.hip) take W <= 640 only
+ * (-> 1, nothing launched).  partial (nullable): partial_floats >= min(B * OH, 512) * 2 * 128; *partial_rows receives the rows written */
+int dic_debug_conv1_fwd_checked(const float* x, int B, int H, int W, const float* w, const float* bias, float* y, float* partial,
+                                size_t partial_floats, int* partial_rows, void* stream) {
+  const char* who = "dic_debug_conv1_fwd_checked";
+  DIC_REQUIRE(x && w && bias && y, "%s: x / w / bias / y is NULL", who);
+  DIC_REQUIRE(B >= 1 && H >= 7 && W >= 7 && (long long)B * H * W <= 0x7fffffffll, "%s: B=%d H=%d W=%d", who, B, H, W);
+  const ConvDesc d = layer1_desc(B, H, W);
+  if (!conv1_depth_supported(d)) return 1;
+  DIC_REQUIRE(!partial || partial_floats >= (size_t)conv1_depth_fwd_blocks(d) * 2 * 128, "%s: partial holds %zu floats, %zu needed", who, partial_floats,
+              (size_t)conv1_depth_fwd_blocks(d) * 2 * 128);
+  return conv1_depth_fwd(x, d, w, bias, y, partial, partial_rows, (hipStream_t)stream);
+}
+/* ws_floats >= min(B * OH, 1024) * (128 * 49 + 128); cs_ws_floats >= 64 * 128 * 49; dbias nullable */
+int dic_debug_conv1_wgrad_checked(const float* x, int B, int H, int W, const float* dy, float* dw, float* dbias, float* ws, size_t ws_floats,
+                                  float* cs_ws, size_t cs_ws_floats, void* stream) {
+  const char* who = "dic_debug_conv1_wgrad_checked";
+  DIC_REQUIRE(x && dy && dw && ws && cs_ws, "%s: x / dy / dw / ws / cs_ws is NULL", who);
+  DIC_REQUIRE(B >= 1 && H >= 7 && W >= 7 && (long long)B * H * W <= 0x7fffffffll, "%s: B=%d H=%d W=%d", who, B, H, W);
+  const ConvDesc d = layer1_desc(B, H, W);
+  if (!conv1_depth_supported(d)) return 1;
+  DIC_REQUIRE(ws_floats >= conv1_depth_wgrad_ws_floats(d), "%s: ws holds %zu floats, %zu needed", who, ws_floats, conv1_depth_wgrad_ws_floats(d));
+  DIC_REQUIRE(cs_ws_floats >= kLayer1ColsumFloats, "%s: cs_ws holds %zu floats, %zu needed", who, cs_ws_floats, kLayer1ColsumFloats);
+  return conv1_depth_wgrad(x, d, dy, dw, dbias, ws, cs_ws, (hipStream_t)stream);
+}
 int dic_profile_begin(void) { return gemm_profile_begin(); }
 int dic_profile_end(int max_entries, int* keys, double* total_ms, double* total_flops, long long* launches, int* n_out) {
   DIC_REQUIRE(keys && total_ms && total_flops && launches && n_out && max_entries > 0, "profile_end: bad arguments");

@@ -98,6 +98,13 @@ bool depth_layer1_sparse_supported(const ConvDesc& d);
 size_t depth_layer1_sparse_ws_floats(const ConvDesc& d);
 int conv1_depth_wgrad(const float* x, const ConvDesc& d, const float* dy, float* dw, float* dbias, float* ws, float* cs_ws,
                       hipStream_t st);
+int depth_layer1_backward_sparse(const float* depth, const ConvDesc& d, const float* dpool, const unsigned char* idx, const float* xsel,
+                                 const float* conv_w, const float* conv_b, const float* gamma, BnBuf bn, float* dgamma, float* dbeta,
+                                 float* dW, float* db, float* bn_ws, float* ws, float* cs_ws, hipStream_t st);
+// every weight operand of the depth encoder's conv2 (512x128x3x3 OIHW) / conv3 (2048x512) in one launch (encoders.hip): forward
+// planes and the flipped, channel-transposed data-gradient planes; slots != NULL: f16x2 planes with the scales slots[0] / slots[2]
+int depth_prepare_weights(const float* w2, const float* w3, unsigned short* const w2_pl[3], unsigned short* const w2f_pl[3],
+                          unsigned short* const w3_pl[3], unsigned short* const w3f_pl[3], const float* slots, hipStream_t st);
 // dW[CO][KH][KW][C] = sum_m dY[m,co] * patch(m)[kh,kw,c]   (split over M with workspace `ws`)
 int conv_wgrad(const float* x, const ConvDesc& d, const float* dy, float* dw_ohwi, int splitk, float* ws,
                hipStream_t st);

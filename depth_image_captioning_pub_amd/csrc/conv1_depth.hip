@@ -88,6 +88,10 @@ __global__ void __launch_bounds__(256, 2) conv1_fwd_kernel(const float* __restri
   bs.x = bias ? bias[j] : 0.f; bs.y = bias ? bias[j + 64] : 0.f;
   f2 s = {0.f, 0.f}, s2 = {0.f, 0.f};
   __syncthreads();                                                          // weights consumed: stages may be filled
+  // the 16 floats behind each of the three stages are never written by the copies, but the ragged last pixel group of a row reads
+  // them (W = 512: taps 3584..3591 of the seventh row) into accumulators that enter the statistics multiplied by 0: they must be
+  // finite.  Stage 0's lie where the weights were; the others may be LDS nobody wrote (a NaN there made the sums NaN)
+  if (tid < 3 * kTapPad) smem[(tid / kTapPad) * SL + SL - kTapPad + tid % kTapPad] = 0.f;
   const int G = gridDim.x;
   // Row pipeline (vmcnt retires in order, and a store only retires when it is acknowledged - microseconds under load):
   // the copy of row k+2 is issued at the END of row k, after that row's stores; the top of row k+1 then waits until

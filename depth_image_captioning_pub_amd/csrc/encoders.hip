@@ -39,9 +39,6 @@ static DepthGeom depth_geom(int B, int H, int W) {
 
 static int g_l1_sparse = 1;        // codes 180 / 181: backward of the depth encoder's first layer: dense passes over its 175-MB map / sparse (default)
 void depth_encoder_l1_sparse(int on) { g_l1_sparse = on; }
-int depth_layer1_backward_sparse(const float* depth, const ConvDesc& d, const float* dpool, const unsigned char* idx, const float* xsel,
-                                 const float* conv_w, const float* conv_b, const float* gamma, BnBuf bn, float* dgamma, float* dbeta,
-                                 float* dW, float* db, float* bn_ws, float* ws, float* cs_ws, hipStream_t st);      // depth_layer1.hip
 static int g_depth_f16x2 = 1;      // codes 116 / 117: conv2 / conv3 of the depth encoder in bf16x3 / f16x2 (default) arithmetic
 void depth_encoder_f16x2(int on) { g_depth_f16x2 = on; }
 constexpr int kWg1Split = 128;   // split-K of the conv1 weight gradient (K = B*73*73)
@@ -460,23 +457,6 @@ static int resnet_fwd_bf3(const dic_conv_bn_layer* layers, const int* blocks, co
   return DIC_OK;
 }
 
-}  // namespace dic
-
-using namespace dic;
-
-extern "C" {
-
-int dic_oihw_to_ohwi(const float* src, float* dst, int O, int I, int KH, int KW, void* stream) {
-  DIC_REQUIRE(src && dst && src != dst, "oihw_to_ohwi: bad pointers");
-  return oihw_to_ohwi(src, dst, O, I, KH, KW, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------------------------
-size_t dic_depth_encoder_workspace_bytes(int B, int H, int W) {
-  bool ov;
-  return depth_carve(nullptr, 0, depth_geom(B, H, W), &ov).bytes;
-}
-
 // All bf16x3 weight operands of the depth encoder in one launch, straight from the OIHW parameters (they are trained, so
 // this runs every step): conv2 / conv3 forward operands [CO][(kh,kw,c)] and the flipped data-gradient operands
 // [C][(KH-1-kh, KW-1-kw, co)], each as paired hi/mid/lo planes.  Replaces seven layout / flip / split launches.
@@ -531,6 +511,33 @@ __global__ void __launch_bounds__(256) depth_prepare_weights_kernel(const float*
   }
 }
 
+// (the launch; also behind dic_debug_depth_prepare_weights, api.hip)
+int depth_prepare_weights(const float* w2, const float* w3, unsigned short* const w2_pl[3], unsigned short* const w2f_pl[3],
+                          unsigned short* const w3_pl[3], unsigned short* const w3f_pl[3], const float* slots, hipStream_t st) {
+  DepthWeightPlanes pl;
+  for (int i = 0; i < 3; ++i) { pl.w2[i] = w2_pl[i]; pl.w2f[i] = w2f_pl[i]; pl.w3[i] = w3_pl[i]; pl.w3f[i] = w3f_pl[i]; }
+  hipLaunchKernelGGL(depth_prepare_weights_kernel, dim3(2048), dim3(256), 0, st, w2, w3, pl, slots);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
+
+}  // namespace dic
+
+using namespace dic;
+
+extern "C" {
+
+int dic_oihw_to_ohwi(const float* src, float* dst, int O, int I, int KH, int KW, void* stream) {
+  DIC_REQUIRE(src && dst && src != dst, "oihw_to_ohwi: bad pointers");
+  return oihw_to_ohwi(src, dst, O, I, KH, KW, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+size_t dic_depth_encoder_workspace_bytes(int B, int H, int W) {
+  bool ov;
+  return depth_carve(nullptr, 0, depth_geom(B, H, W), &ov).bytes;
+}
+
 static int depth_encoder_fwd_impl(const dic_depth_encoder_weights* w, const dic_depth_bn_state* s, const float* depth, int B,
                                   int H, int W, int train, float* features, void* workspace, size_t workspace_bytes,
                                   void* stream, int pool_out) {
@@ -556,12 +563,7 @@ static int depth_encoder_fwd_impl(const dic_depth_encoder_weights* w, const dic_
     DIC_TRY(f16_scale_from_absmax(w->conv2_w, 512ll * 128 * 9, s_w2, st));
     DIC_TRY(f16_scale_from_absmax(w->conv3_w, 2048ll * 512, s_w3, st));
   }
-  {
-    DepthWeightPlanes pl;
-    for (int i = 0; i < 3; ++i) { pl.w2[i] = ws.w2_pl[i]; pl.w2f[i] = ws.w2f_pl[i]; pl.w3[i] = ws.w3_pl[i]; pl.w3f[i] = ws.w3f_pl[i]; }
-    hipLaunchKernelGGL(depth_prepare_weights_kernel, dim3(2048), dim3(256), 0, st, w->conv2_w, w->conv3_w, pl, fmt ? (const float*)ws.slots : nullptr);
-    DIC_LAUNCH_CHECK();
-  }
+  DIC_TRY(depth_prepare_weights(w->conv2_w, w->conv3_w, ws.w2_pl, ws.w2f_pl, ws.w3_pl, ws.w3f_pl, fmt ? (const float*)ws.slots : nullptr, st));
   unsigned short* const y1p_out[3] = {ws.y1p_pl[0], ws.y1p_pl[1], fmt ? nullptr : ws.y1p_pl[2]};      // (third pointer NULL = f16x2 planes)
   unsigned short* const y2p_out[3] = {ws.y2p_pl[0], ws.y2p_pl[1], fmt ? nullptr : ws.y2p_pl[2]};
   // conv1 (1->128, k7 s3) + BN + ReLU + maxpool3          (depth_models.py:19-20,36-39)

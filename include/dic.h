@@ -896,6 +896,56 @@ int dic_debug_colsum_rows(const float* X, long long ld, long long rows, int C, f
 int dic_debug_f16_scale_reset(uint32_t* bounds, int n, void* stream);
 int dic_debug_f16_scale_from_absmax(const float* x, long long n, uint32_t* bound, float* slot, void* stream);
 int dic_debug_f16_scale_finish(uint32_t* bound, float* slot, void* stream);
+/* The convolution gradient kernels of the depth encoder's backward pass and their operand producers, one at a time, for
+ * tests/test_conv_grad_gpu.py: the host functions dic_depth_encoder_bwd calls, nothing else.  Activations NHWC fp32, plane lists
+ * {hi, mid, lo} (fmt 0, bf16x3) or {h1, h2, ignored} (fmt 1, f16x2) in the row-pair layout of dic_split_bf16x3_paired.  Every entry
+ * point checks its arguments before the first launch (NULL pointers, C / CO % 32, plane and workspace sizes) and returns a negative
+ * code with dic_last_error() set; 1 = the route does not take the shape, nothing launched.
+ * Weight gradient dw[CO][k][k][C] (OHWI) = sum over output pixels m of dy[m][CO] * patch(m)[k][k][C]: dyT / pT are scratch planes
+ * of the element counts dic_debug_conv_wgrad_sizes reports (dY^T and patch^T, the pixel count zero-padded to 32), ws its float
+ * count; splitk 1..16 is used where the shape does not take the persistent K-slice route (dic_debug_bf3_plan route 3).  f16x2: dy_slot = {s, 1 / s},
+ * the device-resident scale of the gradient (dic_debug_f16_scale_*); x is scaled by 4. */
+int dic_debug_conv_wgrad_sizes(int B, int H, int W, int C, int CO, int k, int stride, int pad, int splitk, size_t* dyT_elems, size_t* pT_elems,
+                               size_t* ws_floats);
+int dic_debug_conv_wgrad(const float* x, int B, int H, int W, int C, int CO, int k, int stride, int pad, const float* dy, float* dw_ohwi,
+                         int splitk, uint16_t* const dyT[3], size_t dyT_elems, uint16_t* const pT[3], size_t pT_elems, float* ws,
+                         size_t ws_floats, int fmt, const float* dy_slot, void* stream);
+/* Data gradient dx [B,H,W,C] of the stride-1 convolution (B, H, W, C, CO, k, pad: the FORWARD geometry) as the full correlation of
+ * dy [B,OH,OW,CO] (planes of [B*OH*OW][CO]) with the flipped kernel, padding k - 1 - pad: wflip planes of [C][(k-1-kh, k-1-kw, co)].
+ * tail_ws (nullable) with tail_ws_slabs [64][64]-float slabs (<= 1024) allows the K-split routes.  f16x2: dx = product *
+ * alpha_dev0[0] * alpha_dev1[0] (each nullable: factor 1), the inverse scales of the two plane sets, read on the device. */
+int dic_debug_conv_dgrad_s1(const uint16_t* const dy_planes[3], int B, int H, int W, int C, int CO, int k, int pad,
+                            const uint16_t* const wflip_planes[3], float* dx, float* tail_ws, int tail_ws_slabs, int fmt, const float* alpha_dev0,
+                            const float* alpha_dev1, void* stream);
+/* All weight operands of the depth encoder's conv2 (w2 OIHW [512][128][3][3]) and conv3 (w3 [2048][512]) in one launch: w2_pl
+ * [512][(kh,kw,c)], w2f_pl [128][(2-kh,2-kw,co)], w3_pl [2048][512], w3f_pl [512][2048] (w3 transposed).  slots == NULL: bf16x3
+ * planes; else f16x2 planes of slots[0] * w2 and slots[2] * w3 (the third plane of each list is not touched). */
+int dic_debug_depth_prepare_weights(const float* w2_oihw, const float* w3_oihw, uint16_t* const w2_pl[3], uint16_t* const w2f_pl[3],
+                                    uint16_t* const w3_pl[3], uint16_t* const w3f_pl[3], size_t w2_plane_elems, size_t w3_plane_elems,
+                                    const float* slots, void* stream);
+/* The fp32 weight gradient on the generic contraction kernel (the depth encoder's layer 1 for W > 640): x NHWC, or NCHW with
+ * in_nchw = 1 (how the encoder passes its one-channel map: the gather loaders' NCHW branch); ws of splitk * CO * k * k * C floats
+ * for splitk > 1.  Its forward is dic_conv2d_fwd. */
+int dic_debug_conv_wgrad_f32(const float* x, int B, int H, int W, int C, int in_nchw, int CO, int k, int stride, int pad, const float* dy, float* dw_ohwi,
+                             int splitk, float* ws, size_t ws_floats, void* stream);
+/* Backward of the depth encoder's first layer (conv 1 -> 128, k 7, stride 3 + BatchNorm + ReLU + max-pool 3) without its full-size
+ * gradient (csrc/depth_layer1.hip): depth [B,H,W]; dpool, idx, xsel [B,OH/3,OW/3,128] (gradient of the pooled map, kh * 3 + kw of
+ * the selected position, conv1's raw output there); conv_w [128][49], conv_b, gamma [128]; the layer's BatchNorm buffer; outputs
+ * dgamma, dbeta, db [128] (db = 0), dW [128][49].  bn_ws: dic_debug_bn_backward_ws_floats(128); ws:
+ * dic_debug_depth_layer1_sparse_ws_floats (negative on a bad shape); cs_ws: 64 * 128 * 49 floats.  1 where the route does not take
+ * the shape (W > 640, OH or OW < 3). */
+int dic_debug_depth_layer1_sparse_ws_floats(int B, int H, int W);
+int dic_debug_depth_layer1_bwd_sparse(const float* depth, int B, int H, int W, const float* dpool, const unsigned char* idx, const float* xsel,
+                                      const float* conv_w, const float* conv_b, const float* gamma, const float* scale, const float* shift,
+                                      const float* mean, const float* invstd, float* dgamma, float* dbeta, float* dW, float* db, float* bn_ws,
+                                      size_t bn_ws_floats, float* ws, size_t ws_floats, float* cs_ws, size_t cs_ws_floats, void* stream);
+/* The packed layer-1 kernels (csrc/conv1_depth.hip) alone: y [B,OH,OW,128] = conv(x [B,H,W], w [128][49]) + bias, with per-workgroup
+ * BatchNorm partial sums (partial nullable: min(B * OH, 512) * 2 * 128 floats, *partial_rows rows written), and dw [128][49], dbias
+ * [128] (nullable) from dy [B,OH,OW,128]; ws: min(B * OH, 1024) * (128 * 49 + 128) floats, cs_ws: 64 * 128 * 49.  1 for W > 640. */
+int dic_debug_conv1_fwd_checked(const float* x, int B, int H, int W, const float* w, const float* bias, float* y, float* partial,
+                                size_t partial_floats, int* partial_rows, void* stream);
+int dic_debug_conv1_wgrad_checked(const float* x, int B, int H, int W, const float* dy, float* dw, float* dbias, float* ws, size_t ws_floats,
+                                  float* cs_ws, size_t cs_ws_floats, void* stream);
 /* Tuning knob (process-global): the persistent split-bf16 convolution kernels (one workgroup per CU, each walking several output
  * tiles) launch at most `max_workgroups` workgroups.  Default 224.  A small value (e.g. 49: every ResNet-152 layer at batch
  * 64 has a multiple of 49 tiles) lets the convolutions of several forwards in flight on different streams occupy disjoint
