@@ -157,6 +157,23 @@ class NIC_RNNDecoder(nn.Module):
                     lengths.cpu().numpy().astype(np.int32))
         return ids[:, 0].cpu().numpy().astype(np.int64)
 
+    # ---- scoring given captions (no counterpart in the reference; semantics: include/dic.h) -------------------------
+    @torch.no_grad()
+    def score_captions(self, features, captions, word_to_id, return_all=False):
+        """Log-probability the model gives to GIVEN captions: np.float32 [B] for captions int64 [B,T], [B,S] for [B,S,T] (S <= 8
+        captions per image) - the sum over each caption's tokens up to and including its first '<end>'.  The captions are scored as
+        they are: NIC predicts '<start>' itself (the image is step 0), so collated ground-truth captions keep theirs.
+        return_all=True: (logprobs np.float32 [B,(S,)T] - one entry per token, 0 behind '<end>' -, scores, lengths np.int32)."""
+        caps = torch.as_tensor(captions)
+        if caps.dim() not in (2, 3):
+            raise DicError(f"score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        features = _contig(features)
+        logprobs, scores, lengths = native.nic_score(self._weights(), features, word_to_id["<end>"], caps.to(features.device))
+        if return_all:
+            return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return scores.cpu().numpy().astype(np.float32)
+
 
 class NicTrainer(CaptionTrainer):
     """Weights, optimiser state and workspaces of one NIC training run: the 11 decoder tensors and encoder.linear in one flat fp32
@@ -339,7 +356,21 @@ def evaluation_nic(useData: str = "synthetic", config=None, param_files: Optiona
     reference; beam_size > 1 with beam_sample - the best of `beam_size` hypotheses per image, ranked by
     score / length^length_penalty.  Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} and writes the hypotheses to
     {save_directory_nic}/{useData}_nic_hypotheses.json.  No metric scores (nic.py:444-455: pycocoevalcap, out of scope).
-    config.resnet_layers (optional, not in the reference) shrinks the backbone's block counts as in train_nic."""
+    config.resnet_layers (optional, not in the reference) shrinks the backbone's block counts as in train_nic.
+    evaluation_nic_scored is the same loop with the model's log-probability of every hypothesis beside it."""
+    return _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, False)
+
+
+@torch.no_grad()
+def evaluation_nic_scored(useData: str = "synthetic", config=None, param_files: Optional[Dict[str, List[str]]] = None,
+                          n_batches: int = 2, beam_size: int = 1, length_penalty: float = 0.0):
+    """evaluation_nic whose results also carry "scores" (np.float32 [N]) and "lengths" (np.int32 [N]): score_captions
+    (dic_nic_score) of the decoded ids - the log-probability the model gives each hypothesis up to and including its first
+    '<end>', and that token count.  Hypotheses, ids and the written file are those of evaluation_nic."""
+    return _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, True)
+
+
+def _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, score):
     from ...depth_evaluation import synthetic_vocabulary          # (that module imports this package)
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
@@ -361,15 +392,20 @@ def evaluation_nic(useData: str = "synthetic", config=None, param_files: Optiona
     for key, (f_enc, f_dec) in param_files.items():
         encoder.load_state_dict(torch.load(f"{save_directory}/{f_enc}", weights_only=True), strict=True)      # nic.py:412-415
         decoder.load_state_dict(torch.load(f"{save_directory}/{f_dec}", weights_only=True), strict=True)
-        hypos_id = []
+        hypos_id, scored = [], []
         for b in range(n_batches):
             feature = encoder(syn.rgb_images(config.batch_size, seed=5000 + b).to(dev))      # nic.py:426
             if int(beam_size) > 1:
                 hypos_id.append(decoder.beam_sample(feature, word_to_id, beam_size=int(beam_size), length_penalty=length_penalty))
             else:
                 hypos_id.append(np.asarray(decoder.batch_sample(feature), dtype=np.int64))   # nic.py:427
+            if score:
+                scored.append(decoder.score_captions(feature, hypos_id[-1], word_to_id, return_all=True)[1:])
         hypos_id = np.concatenate(hypos_id)
         results[key] = {"hypotheses": nic_ids_to_captions(hypos_id, id_to_word), "ids": hypos_id}
+        if score:
+            results[key]["scores"] = np.concatenate([s for s, _ in scored])
+            results[key]["lengths"] = np.concatenate([n for _, n in scored])
     with open(os.path.join(save_directory, f"{useData}_nic_hypotheses.json"), "w") as f:
         json.dump({k: v["hypotheses"] for k, v in results.items()}, f)
     return results

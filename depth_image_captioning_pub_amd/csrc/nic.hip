@@ -1,6 +1,6 @@
 // NIC / Show-and-Tell baseline (Base_caption_model/nic.py): encoder head, stacked two-layer LSTM over packed ragged sequences
-// (teacher-forced forward, BPTT backward), greedy and beam-search decode.  Semantics: include/dic.h; mapping and measurements:
-// DESIGN.md 5.7 (training, greedy) and 5.8 (beam search).
+// (teacher-forced forward, BPTT backward), greedy and beam-search decode, scoring of given captions.  Semantics: include/dic.h;
+// mapping and measurements: DESIGN.md 5.7 (training, greedy), 5.8 (beam search) and 5.20 (scoring).
 //
 // The time loop of forward and backward is ONE launch each (nic_lstm2_seq_fwd / nic_lstm2_seq_bwd): workgroup g owns kNicR
 // consecutive batch rows for all their steps, h and c stay in LDS / registers, and nothing is exchanged between workgroups (no
@@ -9,6 +9,7 @@
 // The arithmetic of a row does not depend on which rows share its workgroup: a row run alone gives the same recurrence bit for bit.
 #include "beam.h"
 #include "nn_kernels.h"
+#include "score.h"
 #include <algorithm>
 #include <vector>
 
@@ -376,6 +377,119 @@ __global__ void __launch_bounds__(kNicThreads) nic_step_kernel(const float* __re
   }
 }
 
+// Scoring given captions (dic_nic_score): ALL steps of both layers for rows [blockIdx.x * kNicR, +kNicR) of the R = B*S caption
+// rows (row r = b*S + s, captions [R][T]): the tapeless relative of nic_lstm2_seq_fwd whose step is nic_step_kernel's - layer 0's
+// input product stays in here (bsum0, then W_ih_l0 x, then W_hh_l0 h: the greedy step's fma chain per gate column), so no GEMM
+// whose plan could depend on the row count takes part and a row's bytes do not depend on its neighbours.
+// Prologue: length[r] = first id_end + 1 or T, found by the 128 threads of the row (an integer minimum in LDS); target[r*T + t] =
+// the clamped token, -1 from the length on; hidden rows from the length on are cleared (the fused projection reads every row of a
+// live tile).  Rows come in any order of length: the workgroup runs max(length) steps and a row behind its length makes no
+// state update and no store.  The token that feeds step t+1 is loaded at the top of step t (only for a row that is live at
+// t+1: nothing from id_end on is ever fed) and its embedding row goes to LDS while the cells of layer 0 are computed.
+// Thread tid owns gate column tid in the products, (row tid >> 7, unit tid & 127) in the cells and, for tid < 300, float4
+// (tid % 75) of input row tid / 75.
+struct NicScoreSeq {
+  const float *features, *embed, *Wih0p, *Whh0p, *Wih1p, *Whh1p, *bsum0, *bsum1;
+  const long long* cap;
+  long long id_end;
+  int V, R, S, T;
+  float* hidden;            // [R*T][H], row r*T + t
+  long long* target;        // [R*T]
+  int* length;              // [R]
+};
+__global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicScoreSeq a) {
+  constexpr int kX4 = kNicE / 4;
+  __shared__ __align__(16) float x_s[kNicR][kNicE];
+  __shared__ __align__(16) float h0_s[kNicR][kH];
+  __shared__ __align__(16) float h1_s[kNicR][kH];
+  __shared__ __align__(16) float g_s[kNicR][kG];
+  __shared__ int len_s[kNicR];
+  const int tid = threadIdx.x, r0 = blockIdx.x * kNicR;
+  const int rc = tid >> 7, u = tid & (kH - 1), rr = r0 + rc;
+  const int T = a.T;
+  const bool row = rr < a.R;
+  const __amdgpu_buffer_rsrc_t Wih0 = nic_rsrc(a.Wih0p, kG * kNicE), Whh0 = nic_rsrc(a.Whh0p, kG * kH), Wih1 = nic_rsrc(a.Wih1p, kG * kH),
+                               Whh1 = nic_rsrc(a.Whh1p, kG * kH);
+  const long long* mycap = a.cap + (long long)min(rr, a.R - 1) * T;
+  if (tid < kNicR) len_s[tid] = r0 + tid < a.R ? T : 0;
+  __syncthreads();
+  if (row)
+    for (int t = u; t < T; t += kH)
+      if (mycap[t] == a.id_end) atomicMin(&len_s[rc], t + 1);
+  __syncthreads();
+  const int mylen = len_s[rc];
+  int steps = 0;                            // rows arrive in any order: the longest of the workgroup, not its first row
+#pragma unroll
+  for (int r = 0; r < kNicR; ++r) steps = max(steps, len_s[r]);
+  if (row) {
+    if (u == 0) a.length[rr] = mylen;
+    for (int t = u; t < T; t += kH) a.target[(long long)rr * T + t] = t < mylen ? clamp_token(mycap[t], a.V) : -1;
+    for (int t = mylen; t < T; ++t) a.hidden[((long long)rr * T + t) * kH + u] = 0.f;
+  }
+  // the input row this thread stages: step 0 is the image
+  const bool stager = tid < kNicR * kX4;
+  const int xr = stager ? tid / kX4 : 0, xq = tid - xr * kX4;
+  const int xlen = stager ? len_s[xr] : 0;
+  const long long* xcap = a.cap + (long long)min(r0 + xr, a.R - 1) * T;
+  if (stager) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r0 + xr < a.R) v = *reinterpret_cast<const float4*>(a.features + (long long)((r0 + xr) / a.S) * kNicE + xq * 4);
+    *reinterpret_cast<float4*>(&x_s[xr][xq * 4]) = v;
+  }
+  const float bias0 = a.bsum0[tid], bias1 = a.bsum1[tid];
+  float c0 = 0.f, c1 = 0.f;
+  h0_s[rc][u] = 0.f;
+  h1_s[rc][u] = 0.f;
+  __syncthreads();
+  for (int t = 0; t < steps; ++t) {
+    const bool active = t < mylen;
+    const bool feed = t + 1 < xlen;                 // (false for every thread that stages nothing)
+    long long next_tok = 0;
+    if (feed) next_tok = xcap[t];
+    float acc[kNicR];
+#pragma unroll
+    for (int r = 0; r < kNicR; ++r) acc[r] = bias0;
+    nic_matvec<25>(Wih0, 0, kX4, kG, tid, &x_s[0][0], kNicE, 0, acc);
+    nic_matvec<kH / 4>(Whh0, 0, kH / 4, kG, tid, &h0_s[0][0], kH, 0, acc);
+#pragma unroll
+    for (int r = 0; r < kNicR; ++r) g_s[r][tid] = acc[r];
+    __syncthreads();
+    if (active) {
+      const NicCellOut q = nic_cell(g_s[rc], u, c0);
+      c0 = q.c;
+      h0_s[rc][u] = q.h;
+    }
+    // (x_s was last read in front of the barrier above; the next read is behind the barrier that ends the step)
+    if (feed)
+      *reinterpret_cast<float4*>(&x_s[xr][xq * 4]) =
+          *reinterpret_cast<const float4*>(a.embed + clamp_token(next_tok, a.V) * kNicE + xq * 4);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kNicR; ++r) acc[r] = bias1;
+    nic_matvec<kH / 4>(Wih1, 0, kH / 4, kG, tid, &h0_s[0][0], kH, 0, acc);
+    nic_matvec<kH / 4>(Whh1, 0, kH / 4, kG, tid, &h1_s[0][0], kH, 0, acc);
+#pragma unroll
+    for (int r = 0; r < kNicR; ++r) g_s[r][tid] = acc[r];
+    __syncthreads();
+    if (active) {
+      const NicCellOut q = nic_cell(g_s[rc], u, c1);
+      c1 = q.c;
+      h1_s[rc][u] = q.h;
+      a.hidden[((long long)rr * T + t) * kH + u] = q.h;
+    }
+    __syncthreads();
+  }
+}
+
+// out_scores[r] = the fp32 sum of out_logprobs[r, 0..T-1] in ascending t (the skipped positions hold exactly 0)
+__global__ void __launch_bounds__(256) nic_score_sum_kernel(const float* __restrict__ lp, int R, int T, float* __restrict__ out_scores) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  float sum = 0.f;
+  for (int t = 0; t < T; ++t) sum += lp[(long long)r * T + t];
+  out_scores[r] = sum;
+}
+
 // ids[b] = argmax_v logits[b, v] (first maximum on ties, like torch.argmax), also out[b * T + t]
 __global__ void __launch_bounds__(256) nic_argmax_kernel(const float* __restrict__ logits, int V, int t, int T,
                                                           long long* __restrict__ ids, long long* __restrict__ out) {
@@ -648,6 +762,38 @@ bool nic_beam_sizes_ok(int B, int K, int max_length, int V) {
   return B > 0 && K >= 1 && K <= kBeamMax && max_length >= 1 && V >= K;
 }
 
+// dic_nic_score: the packed step weights, h_top of every (row, step) - the A operand of the one fused projection - and its targets
+struct NicScoreWs : NicStepWs {
+  float* hidden;
+  long long* target;
+  void* lse_ws;
+  size_t bytes;
+};
+
+NicScoreWs nic_score_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* overflow) {
+  Carver c(p, bytes);
+  NicScoreWs w{};
+  const size_t M = (size_t)B * S * T;
+  nic_step_carve(c, w);
+  w.hidden = c.take<float>(M * kH);
+  w.target = c.take<long long>(M);
+  w.lse_ws = c.take<char>(token_logprobs_bytes((int)M, V));
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+
+// the scalar arguments of dic_nic_score and of its size query, checked before any pointer and before the first HIP call
+int nic_score_check(const char* who, int B, int S, int max_length, int V) {
+  DIC_REQUIRE(B > 0, "%s: bad batch size B=%d", who, B);
+  DIC_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", who, V);
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "%s: captions per image S=%d is outside 1..%d", who, S, kBeamMax);
+  DIC_REQUIRE(max_length >= 1, "%s: max_length=%d is < 1", who, max_length);
+  DIC_REQUIRE((long long)B * S * max_length <= kScoreMaxM, "%s: B*S*max_length=%lld exceeds %d token positions per call", who,
+              (long long)B * S * max_length, kScoreMaxM);
+  return DIC_OK;
+}
+
 int nic_upload_plan(const NicWs& ws, const int* lengths, int B, const StepPlan& pl, hipStream_t st) {
   // the caller's `lengths` and the plan are only read during this call: hipMemcpyAsync from pageable host memory returns after the
   // bytes have been staged
@@ -870,6 +1016,42 @@ int dic_nic_beam(const dic_nic_weights* w, int V, const float* features, int B, 
   DIC_LAUNCH_CHECK();
   return launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, nullptr, ws.path,
                                (long long*)out_ids, out_scores, out_lengths, nullptr, st);
+}
+
+int dic_nic_score_sizes(int B, int S, int max_length, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "dic_nic_score_sizes: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_TRY(nic_score_check("dic_nic_score_sizes", B, S, max_length, V));
+  bool ov;
+  *workspace_bytes = nic_score_carve(nullptr, 0, B, S, max_length, V, &ov).bytes;
+  return DIC_OK;
+}
+
+int dic_nic_score(const dic_nic_weights* w, int V, const float* features, int B, int S, long long id_end, int max_length,
+                  const int64_t* captions, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call, the scalars before the pointers
+  DIC_TRY(nic_score_check("dic_nic_score", B, S, max_length, V));
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "dic_nic_score: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(w && features && captions && out_logprobs && out_scores && out_lengths && workspace, "dic_nic_score: null pointer");
+  const int T = max_length, R = B * S, M = R * T;
+  bool ov = false;
+  NicScoreWs ws = nic_score_carve(workspace, workspace_bytes, B, S, T, V, &ov);
+  if (ov) {
+    set_last_error("dic_nic_score: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  DIC_TRY(nic_step_setup(w, ws, st));
+  const NicScoreSeq a{features, w->embed, ws.Wih0F, ws.Whh0F, ws.Wih1F, ws.Whh1F, ws.bsum0, ws.bsum1, (const long long*)captions,
+                      id_end, V, R, S, T, ws.hidden, ws.target, out_lengths};
+  hipLaunchKernelGGL(nic_score_seq_kernel, dim3(ceil_div(R, kNicR)), dim3(kNicThreads), 0, st, a);
+  DIC_LAUNCH_CHECK();
+  // rows r*T + t are the [B,S,T] layout itself: the fused projection writes out_logprobs, exact zeros for the -1 targets
+  DIC_TRY(launch_token_logprobs(ws.hidden, w->out_w, w->out_b, ws.target, M, V, out_logprobs, nullptr, ws.lse_ws, st));
+  hipLaunchKernelGGL(nic_score_sum_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, st, out_logprobs, R, T, out_scores);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
 }
 
 }  // extern "C"

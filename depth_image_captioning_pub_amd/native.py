@@ -1155,3 +1155,38 @@ def nic_beam(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: i
                           ptr(ids), ptr(scores), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_nic_beam")
     return ids, scores, lengths
+
+
+def _workspace_out(query, device, *sizes) -> torch.Tensor:
+    """_workspace for a query that returns int and hands the size back through a size_t* (0 for sizes its call refuses)."""
+    need = C.c_size_t(0)
+    query(*sizes, C.byref(need))
+    return torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=device)
+
+
+def nic_score(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, captions: torch.Tensor):
+    """dic_nic_score: the log-probability the NIC decoder gives every token of given captions, on the device (semantics:
+    include/dic.h).  captions: int64 [B,T] (one per image) or [B,S,T] (S <= 8 per image) - the ids nic_greedy / nic_beam return.
+    Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
+    lib = _load()
+    f, B = _nic_features(features)
+    wp, keep = nic_ptrs(weights)
+    vocab = int(weights["linear.weight"].shape[0])
+    cap = _dev(captions, "captions", torch.int64)
+    squeeze = cap.dim() == 2
+    if squeeze:
+        cap = cap.unsqueeze(1)
+    if cap.dim() != 3 or cap.shape[0] != B:
+        raise _lib.DicError(f"nic_score: captions must be [B,T] or [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+    S, T = int(cap.shape[1]), int(cap.shape[2])
+    ws = _workspace_out(lib.dic_nic_score_sizes, f.device, B, S, T, vocab)
+    ss, tt = max(S, 1), max(T, 1)
+    logprobs = torch.empty((B, ss, tt), dtype=torch.float32, device=f.device)
+    scores = torch.empty((B, ss), dtype=torch.float32, device=f.device)
+    lengths = torch.empty((B, ss), dtype=torch.int32, device=f.device)
+    rc = lib.dic_nic_score(C.byref(wp), vocab, ptr(f), B, S, int(id_end), T, ptr(cap), ptr(logprobs), ptr(scores), ptr(lengths),
+                           ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_score")
+    if squeeze:
+        return logprobs[:, 0], scores[:, 0], lengths[:, 0]
+    return logprobs, scores, lengths

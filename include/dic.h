@@ -491,6 +491,38 @@ int dic_nic_beam(const dic_nic_weights* w, int V, const float* features, int B, 
                  float length_penalty, int64_t* out_ids, float* out_scores, int* out_lengths, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* scoring of GIVEN captions by the NIC baseline: the log-probability the model gives every token of S captions per image.
+ *   Entirely on the device: every launch is enqueued on `stream`, nothing is copied to the host, nothing synchronises.  There is
+ *   no reference implementation; this comment is the specification.
+ *   Rows: row r = b*S + s is caption s of image b, 1 <= S <= 8.  features float [B,300], the output of the encoder head.
+ *     captions int64 [B,S,T] on the device, T = max_length: the ids dic_nic_greedy and dic_nic_beam return.  Rows may come in any
+ *     order of length.
+ *   Inputs of a row: NIC has no start token outside the caption.  Step 0 takes features[b] with h and c of both layers zero; step
+ *     t >= 1 takes embed[captions[r, t-1]], clamped into the vocabulary like every token input.  One step of a row is the body of
+ *     dic_nic_greedy up to h_top: both cells, gate order i, f, g, o, b_ih + b_hh, no dropout - the same products in the same
+ *     summation order, so the h_top of a row are bit for bit those of the greedy and the beam step for the same inputs.
+ *   length[r] = (index of the first id_end in captions[r, :]) + 1, or T when there is none; derived on the device (the ids are
+ *     compared as given).
+ *   t <  length: out_logprobs[r,t] = dic_token_logprobs of the step's h_top with linear.weight / linear.bias and target
+ *     captions[r,t] (clamped).
+ *   t >= length: out_logprobs[r,t] = 0 exactly; the tokens there are never read as a target and never fed.
+ *   out_scores[r] = the fp32 sum of out_logprobs[r, 0..T-1] in ascending t.
+ *   out_logprobs float [B,S,T], out_scores float [B,S], out_lengths int [B,S].
+ *   A null pointer, B <= 0, V <= 0, S outside 1..8, max_length < 1, B*S*max_length > 65535 * 128, id_end outside [0, V) or a short
+ *   workspace returns a negative code and a dic_last_error() text that starts with "dic_nic_score:", before the first HIP call
+ *   (the scalar arguments are checked before the pointers).  dic_nic_score_sizes hands the workspace size back through
+ *   *workspace_bytes; for sizes the call refuses it writes 0 and returns a negative code.
+ *   Properties: row (b,s) depends only on features[b] and caption (b,s) - it returns the same bytes whatever the other rows hold,
+ *   and the same bytes whether scored with S = 1 alone or inside a batch of another size (the layer-0 input product stays inside
+ *   the sequence kernel: no GEMM whose plan could depend on the row count takes part); tokens behind a row's id_end change
+ *   nothing; two calls return identical bytes; no float atomics.  The recurrence of all steps is ONE launch, the vocabulary
+ *   projection runs once over all B*S*T hidden states, and the workspace holds no array of M*V elements: its size depends on V
+ *   only through dic_token_logprobs's own scratch. */
+int dic_nic_score_sizes(int B, int S, int max_length, int V, size_t* workspace_bytes);
+int dic_nic_score(const dic_nic_weights* w, int V, const float* features, int B, int S, long long id_end, int max_length,
+                  const int64_t* captions, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* stand-alone attention module: Soft_Attention.forward (attention.py:81-95), Hard_Attention.forward (:132-148,
  *   mode 1, gumbel_u [B,196], temp) and Hard_Attention.Hard_sample (:150-167, mode 2): feats [B,196,2048],
  *   h [B,128] -> ctx [B,2048], alpha [B,196] (float; one-hot in mode 2). */
