@@ -22,7 +22,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ... import native, synthetic as syn
+from ... import losses, native, synthetic as syn
 from ..._lib import DicError
 from ...engine import CaptionTrainer, FlatParams
 from ..config import ConfigTrain
@@ -63,6 +63,30 @@ class _NicDecoderFn(torch.autograd.Function):
     def backward(ctx, d_logits):
         grads, dfeat = native.nic_backward(ctx.tape, _contig(d_logits))
         return (None, dfeat, None) + tuple(grads[k] for k in _DEC_KEYS)
+
+
+class _NicStatesFn(torch.autograd.Function):
+    """Hidden states of given captions (dic_nic_states_fwd) and their backward through time (dic_nic_states_bwd).  params: the 9
+    decoder parameters other than linear.*, which enter through losses.token_logprobs."""
+
+    @staticmethod
+    def forward(ctx, cfg, features, captions, *params):
+        ctx.set_materialize_grads(False)
+        weights = {k: p.detach() for k, p in zip(native.NIC_STATES_GRAD_KEYS, params)}
+        weights.update(cfg["linear"])
+        hidden, targets, lengths, tape = native.nic_states_forward(weights, _contig(features.detach()), cfg["id_end"], captions,
+                                                                   cfg.get("drop_mult"))
+        ctx.tape = tape
+        cfg["targets"], cfg["lengths"] = targets, lengths
+        return hidden
+
+    @staticmethod
+    def backward(ctx, d_hidden):
+        n = 3 + len(native.NIC_STATES_GRAD_KEYS)
+        if d_hidden is None:
+            return (None,) * n
+        grads, dfeat = native.nic_states_backward(ctx.tape, _contig(d_hidden), need_features=bool(ctx.needs_input_grad[1]))
+        return (None, dfeat, None) + tuple(grads[k] for k in native.NIC_STATES_GRAD_KEYS)
 
 
 class NIC_CNNEncoder(CNNEncoder_Atten):
@@ -174,6 +198,85 @@ class NIC_RNNDecoder(nn.Module):
                     lengths.cpu().numpy().astype(np.int32))
         return scores.cpu().numpy().astype(np.float32)
 
+    # ---- differentiable scoring (no counterpart in the reference; semantics: include/dic.h) -------------------------
+    def caption_logprobs(self, features, captions, word_to_id):
+        """Differentiable log-probabilities of GIVEN captions: (logprobs float32 [B,(S,)T] on the device - one entry per token, 0
+        from each caption's length on -, lengths int32 [B(,S)]) for captions int64 [B,T] or [B,S,T] (S <= 8 per image), scored as
+        they are, like score_captions.  backward() reaches all 11 decoder parameters and `features`, so the encoder head trains
+        through it: the recurrence is dic_nic_states_fwd / _bwd, the vocabulary projection losses.token_logprobs.  In train() mode
+        the hidden states that enter the projection are dropped as in forward(); eval() draws no multiplier and returns
+        score_captions' numbers bit for bit.  Frozen features skip the feature gradient."""
+        caps = torch.as_tensor(captions)
+        if caps.dim() not in (2, 3):
+            raise DicError(f"caption_logprobs: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        squeeze = caps.dim() == 2
+        if squeeze:
+            caps = caps.unsqueeze(1)
+        caps = _contig(caps.to(features.device))
+        B, S, T = (int(v) for v in caps.shape)
+        cfg = {"id_end": word_to_id["<end>"],
+               "linear": {"linear.weight": self.linear.weight.detach(), "linear.bias": self.linear.bias.detach()}}
+        p = float(self.dropout.p)
+        if self.training and p > 0.0:
+            cfg["drop_mult"] = native.dropout_mask((B * S, T, native.D_HID), p, self._rng_seed, self._rng_offset, features.device)
+            self._rng_offset += B * S * T * native.D_HID // 4 + 1
+        sd = dict(self.named_parameters())
+        hidden = _NicStatesFn.apply(cfg, features, caps, *[sd[k] for k in native.NIC_STATES_GRAD_KEYS])
+        logprobs, _ = losses.token_logprobs(hidden, self.linear.weight, self.linear.bias, cfg["targets"])
+        logprobs = logprobs.view(B, S, T)
+        if squeeze:
+            return logprobs[:, 0], cfg["lengths"][:, 0]
+        return logprobs, cfg["lengths"]
+
+
+NIC_STATES_MAX_CELLS = 393216      # B * S * T: DIC_NIC_STATES_MAX_M of include/dic.h
+
+
+def nic_scst_arguments(B: int, vocab: int, id_end, captions, n_candidates, max_length, length_penalty, baseline, reward_fn=None,
+                       drop_mult=None):
+    """The argument checks of NicTrainer.scst_step / scst_step_on_map, made before anything is launched (no device needed), in the
+    spirit of engine.scst_arguments.  Returns (baseline mode of dic_scst_loss: 0 none | 1 others | 2 per caption | 3 per image,
+    S, T) - S and T from `captions` [B,S,T] when given, else n_candidates and max_length."""
+    if reward_fn is not None and not callable(reward_fn):
+        raise DicError("scst_step: reward_fn must be callable: reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S]")
+    if not 0 <= int(id_end) < int(vocab):
+        raise DicError(f"scst_step: id_end={id_end} is outside the vocabulary [0, {vocab})")
+    if captions is not None:
+        if not torch.is_tensor(captions) or captions.dtype != torch.int64 or captions.dim() != 3 or captions.shape[0] != B:
+            raise DicError(f"scst_step: captions must be an int64 tensor [B,S,T] with B = {B}, got "
+                           f"{(captions.dtype, tuple(captions.shape)) if torch.is_tensor(captions) else type(captions).__name__}")
+        S, T = int(captions.shape[1]), int(captions.shape[2])
+    else:
+        S, T = int(n_candidates), int(max_length)
+        if not float(length_penalty) >= 0.0:
+            raise DicError(f"scst_step: length_penalty={length_penalty} must be >= 0")
+        if S > int(vocab):
+            raise DicError(f"scst_step: n_candidates={S} exceeds the vocabulary size {vocab}")
+    if not 1 <= S <= 8:
+        raise DicError(f"scst_step: {S} captions per image is outside 1 .. 8")
+    if T < 1:
+        raise DicError(f"scst_step: max_length={T} is < 1")
+    if B < 1 or B * S * T > NIC_STATES_MAX_CELLS:
+        raise DicError(f"scst_step: B*S*T = {B * S * T} is outside 1 .. {NIC_STATES_MAX_CELLS} (the states route's limit)")
+    if isinstance(baseline, str):
+        if baseline != "others":
+            raise DicError(f"scst_step: baseline must be 'others', a tensor [B,S] or [B], or None, got {baseline!r}")
+        if S < 2:
+            raise DicError("scst_step: the 'others' baseline is the mean reward of the image's other captions and needs at least 2 "
+                           f"captions per image, got {S}")
+        mode = 1
+    elif baseline is None:
+        mode = 0
+    elif torch.is_tensor(baseline) and tuple(baseline.shape) in ((B, S), (B,)):
+        mode = 3 if baseline.dim() == 1 else 2
+    else:
+        raise DicError(f"scst_step: baseline must be 'others', a tensor [{B},{S}] or [{B}], or None, got "
+                       f"{tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__}")
+    if drop_mult is not None and tuple(drop_mult.shape) != (B * S, T, native.D_HID):
+        raise DicError(f"scst_step: drop_mult must be [B*S, T, {native.D_HID}] = [{B * S}, {T}, {native.D_HID}], got "
+                       f"{tuple(drop_mult.shape)}")
+    return mode, S, T
+
 
 class NicTrainer(CaptionTrainer):
     """Weights, optimiser state and workspaces of one NIC training run: the 11 decoder tensors and encoder.linear in one flat fp32
@@ -200,6 +303,7 @@ class NicTrainer(CaptionTrainer):
         self.head_w, self.head_b = (self.flat.view(self.flat.data, "encoder.linear." + k) for k in ("weight", "bias"))
         self.head_gw, self.head_gb = (self.flat.view(self.flat.grad, "encoder.linear." + k) for k in ("weight", "bias"))
         self.dec_span = (0, self.flat.total)
+        self.states_ws: Optional[torch.Tensor] = None
 
     def step_on_map(self, fmap: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int],
                     drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False) -> torch.Tensor:
@@ -245,6 +349,88 @@ class NicTrainer(CaptionTrainer):
                     self.prefetch_features(nxt, compact=True)
         self._mark("resnet152_fwd")
         return self.step_on_map(fmap, captions, lengths, keep_guard=True)
+
+    # ---- self-critical step (no counterpart in the reference) ---------------------------------------------------------
+    def scst_step_on_map(self, fmap: torch.Tensor, reward_fn, id_end: int, captions: Optional[torch.Tensor] = None,
+                         n_candidates: int = 5, max_length: int = 30, length_penalty: float = 0.0, baseline="others",
+                         drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False):
+        """One self-critical step on a final feature map [B,cells,2048], on the flat buffers: head, candidate captions, rewards,
+        dic_nic_states_fwd + dic_token_logprobs, dic_scst_loss, back through dic_token_logprobs_bwd, dic_nic_states_bwd and
+        dic_nic_head_bwd, one guarded AdamW.  Everything is enqueued on the current stream; ids, lengths and rewards never visit
+        the host.  Returns (loss, mean reward) as 1-element device tensors.
+        captions: int64 [B,S,T] candidates from any source (a sampler's draws go in here).  None: the n_candidates hypotheses of
+          dic_nic_beam (max_length steps, ranked with length_penalty) - the model's K MOST LIKELY captions, not draws from it: with
+          them the step is a risk-minimising update over an n-best list, not REINFORCE.
+        reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S] on the device.
+        baseline: "others" | a tensor [B,S] or [B] | None.  drop_mult: float32 [B*S,T,128]; default: dic_dropout_mask at the
+          trainer's rate (none at rate 0 or with dropout=False), on the scored hidden states only.
+        Unless keep_guard, the map is taken as given (the overflow guard word is cleared).  Single GPU, like NicTrainer."""
+        B = int(fmap.shape[0])
+        mode, S, T = nic_scst_arguments(B, self.vocab, id_end, captions, n_candidates, max_length, length_penalty, baseline, reward_fn,
+                                        drop_mult)
+        if not keep_guard:
+            self._guard_take(None)
+        R = B * S
+        pooled, feats = native.nic_head_forward(self.head_w, self.head_b, fmap)
+        if captions is None:
+            ids, _, _ = native.nic_beam(self.dec_w, feats, int(id_end), S, T, float(length_penalty))
+        else:
+            ids = _contig(captions.to(self.device))
+        ended = ids == int(id_end)
+        lengths = torch.where(ended.any(-1), ended.int().argmax(-1) + 1, torch.full_like(ids[..., 0], T)).to(torch.int32)
+        self._mark("candidates")
+        rewards = reward_fn(ids, lengths)
+        if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
+            raise DicError(f"scst_step: reward_fn must return a tensor [B,S] = [{B}, {S}], got "
+                           f"{tuple(rewards.shape) if torch.is_tensor(rewards) else type(rewards).__name__}")
+        rewards = rewards.detach().to(self.device, torch.float32).contiguous()
+        base = baseline.detach().to(self.device, torch.float32).contiguous() if torch.is_tensor(baseline) else None
+        self._mark("reward")
+        if drop_mult is None and dropout and self.p_drop > 0:
+            drop_mult = native.dropout_mask((R, T, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset, self.device)
+            self.rng_offset += R * T * native.D_HID // 4 + 1
+        hidden, targets, lens, tape = native.nic_states_forward(self.dec_w, feats, int(id_end), ids, drop_mult,
+                                                                workspace=self.states_ws)
+        self.states_ws = tape.workspace
+        lw, lb = self.dec_w["linear.weight"], self.dec_w["linear.bias"]
+        logprobs, lse = native.token_logprobs(hidden, lw, lb, targets)                       # [R*T], row r*T + t
+        self._mark("states_fwd")
+        # dic_scst_loss is time-major: two small transposes of [R,T] values
+        loss, d_logprob, _ = native.scst_loss(logprobs.view(R, T).t().contiguous(), lens, rewards, base, mode)
+        self._mark("loss")
+        d_hidden = native.token_logprobs_bwd_into(self.dec_g, hidden, lw, lb, targets, lse, d_logprob.t().contiguous().view(-1))
+        _, dfeat = native.nic_states_backward(tape, d_hidden, True, grads=self.dec_g)
+        gw, gb = native.nic_head_backward(pooled, dfeat)
+        self.head_gw.copy_(gw)
+        self.head_gb.copy_(gb)
+        self._mark("states_bwd")
+        self.apply_update()                    # AdamW on the flat buffer, skipped on the device when the guard word is raised
+        self._mark("adamw")
+        self.last = {"ids": ids, "lengths": lens, "rewards": rewards, "logprobs": logprobs.view(B, S, T), "features": feats,
+                     "map": fmap}
+        return loss, rewards.mean().view(1)
+
+    def scst_step(self, imgs: torch.Tensor, reward_fn, id_end: int, captions: Optional[torch.Tensor] = None,
+                  n_candidates: int = 5, max_length: int = 30, length_penalty: float = 0.0, baseline="others", next_imgs=None):
+        """scst_step_on_map behind the frozen ResNet-152 forward of `imgs` (train-mode BatchNorm, quirk Q1; prefetching and the
+        overflow guard as in train_step).  Replaces CaptionTrainer.scst_step, which is built for the attention decoder."""
+        nic_scst_arguments(int(imgs.shape[0]), self.vocab, id_end, captions, n_candidates, max_length, length_penalty, baseline,
+                           reward_fn, None)
+        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
+        self.marks = []
+        self._mark("start")
+        fmap = self._take_prefetched(imgs)
+        if fmap is None:
+            fmap = self._resnet_eager(imgs, True, True)
+            self._guard_take(self.resnet)
+        if next_imgs is not None:
+            upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
+            for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
+                if k >= len(self.queue):
+                    self.prefetch_features(nxt, compact=True)
+        self._mark("resnet152_fwd")
+        return self.scst_step_on_map(fmap, reward_fn, id_end, captions, n_candidates, max_length, length_penalty, baseline,
+                                     keep_guard=True)
 
     @torch.no_grad()
     def eval_loss(self, imgs: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:

@@ -12,11 +12,15 @@ metric of non-zero weight), e.g. CIDEr-D + 0.5 BLEU-4, as a device tensor as wel
 
 The same step on the engine's flat parameter buffers - one AdamW launch, the depth encoder trained through it, the data-parallel
 gradient exchange with a global token count - is engine.CaptionTrainer.scst_step; this module stays the route
-for nn.Module decoders and torch optimisers.  Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
+for nn.Module decoders and torch optimisers.  nic_scst_step is the step for the NIC baseline's decoder (dic_nic_states_fwd / _bwd,
+DESIGN.md 5.21; its engine form is NicTrainer.scst_step); it has no sampler of its own and takes its candidates as an argument or
+from the beam search.  Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
 reward_fn is the seam for any other reward."""
 from __future__ import annotations
 
-from .. import losses
+import torch
+
+from .. import losses, native
 from .Depth_caption_model.depth_models import _CaptionDecoderBase
 
 
@@ -34,6 +38,39 @@ def scst_step(decoder, optimizer, features, depth_features, word_to_id, reward_f
     optimizer.zero_grad(set_to_none=True)
     logprobs, lens = _CaptionDecoderBase.caption_logprobs(decoder, features, depth_features, ids, word_to_id)
     loss = losses.self_critical_loss(logprobs, lens, rewards, baseline)
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), rewards.detach().float().mean()
+
+
+def nic_scst_step(decoder, optimizer, features, word_to_id, reward_fn, captions=None, n_candidates=5, max_length=30,
+                  length_penalty=0.0, baseline="others"):
+    """One self-critical step of a NIC_RNNDecoder (Base_caption_model/nic.py) on candidate captions of `features` [B,300], the
+    encoder head's output.
+    captions: int64 [B,S,T] candidates from any source, S <= 8 per image - a sampler's draws go in here.  None: the n_candidates
+    hypotheses of dic_nic_beam (max_length steps, ranked with length_penalty), taken under no_grad.  Beam hypotheses are the
+    model's K MOST LIKELY captions, not draws from its distribution: with them the step is a risk-minimising update over an n-best
+    list (it moves probability from the worse of the likely captions to the better ones), not REINFORCE - the gradient is not an
+    unbiased estimate of the expected reward's.
+    reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S], device tensors in and out: one reward per caption.
+    features may require grad: its .grad is filled, so the encoder head trains through the step when its parameters are in
+    `optimizer` (pass the head's output itself).  The log-probabilities are NIC_RNNDecoder.caption_logprobs (dic_nic_states_fwd /
+    _bwd), the loss losses.self_critical_loss.
+    Returns (loss, mean reward) as 0-dim device tensors: reading them is the only synchronisation."""
+    id_end = word_to_id["<end>"]
+    if captions is None:
+        with torch.no_grad():
+            feats = features.detach()
+            ids, _, _ = native.nic_beam(decoder._weights(), feats if feats.is_contiguous() else feats.contiguous(), id_end,
+                                        n_candidates, max_length, float(length_penalty))
+    else:
+        ids = torch.as_tensor(captions).to(features.device)
+    ended = ids == id_end
+    lengths = torch.where(ended.any(-1), ended.int().argmax(-1) + 1, torch.full_like(ids[..., 0], ids.shape[-1])).to(torch.int32)
+    rewards = reward_fn(ids, lengths)
+    optimizer.zero_grad(set_to_none=True)
+    logprobs, lengths = decoder.caption_logprobs(features, ids, word_to_id)
+    loss = losses.self_critical_loss(logprobs, lengths, rewards, baseline)
     loss.backward()
     optimizer.step()
     return loss.detach(), rewards.detach().float().mean()

@@ -1,6 +1,7 @@
 // NIC / Show-and-Tell baseline (Base_caption_model/nic.py): encoder head, stacked two-layer LSTM over packed ragged sequences
-// (teacher-forced forward, BPTT backward), greedy and beam-search decode, scoring of given captions.  Semantics: include/dic.h;
-// mapping and measurements: DESIGN.md 5.7 (training, greedy), 5.8 (beam search) and 5.20 (scoring).
+// (teacher-forced forward, BPTT backward), greedy and beam-search decode, scoring of given captions and its differentiable form
+// (hidden states with a tape, backward through time over fixed-stride rows).  Semantics: include/dic.h; mapping and measurements:
+// DESIGN.md 5.7 (training, greedy), 5.8 (beam search), 5.20 (scoring) and 5.21 (training through the scores).
 //
 // The time loop of forward and backward is ONE launch each (nic_lstm2_seq_fwd / nic_lstm2_seq_bwd): workgroup g owns kNicR
 // consecutive batch rows for all their steps, h and c stay in LDS / registers, and nothing is exchanged between workgroups (no
@@ -397,7 +398,20 @@ struct NicScoreSeq {
   long long* target;        // [R*T]
   int* length;              // [R]
 };
-__global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicScoreSeq a) {
+// TAPE (dic_nic_states_fwd): the same steps, and every (row, step) leaves what nic_states_seq_bwd and the weight-gradient GEMMs
+// read at tape row m = r*T + t (NicStatesTape below); drop [R][T][H] (or nullptr) multiplies the h_top that is stored, never
+// the carried one.  Nothing the cells compute changes: the TAPE = false instantiation is the kernel dic_nic_score has always
+// launched, and with drop == nullptr the two store the same hidden bytes.
+struct NicStatesTape {      // rows m = r*T + t, fixed stride: no packing, no host plan
+  float *G0, *G1;           // [M][4H] activated gates i, f, g, o
+  float *C0, *C1, *H0, *H0p, *H1p;      // [M][H]: cell states, layer 0's output, the h both layers started the step with
+  float* X;                 // [M][E] the step's input row
+  int* tok;                 // [M] the token that fed the step; -1 for the image step and from the row's length on
+  int* len;                 // [R]
+  const float* drop;
+};
+template <bool TAPE>
+__global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicScoreSeq a, const NicStatesTape tp) {
   constexpr int kX4 = kNicE / 4;
   __shared__ __align__(16) float x_s[kNicR][kNicE];
   __shared__ __align__(16) float h0_s[kNicR][kH];
@@ -425,6 +439,19 @@ __global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicSco
     if (u == 0) a.length[rr] = mylen;
     for (int t = u; t < T; t += kH) a.target[(long long)rr * T + t] = t < mylen ? clamp_token(mycap[t], a.V) : -1;
     for (int t = mylen; t < T; ++t) a.hidden[((long long)rr * T + t) * kH + u] = 0.f;
+    if constexpr (TAPE) {
+      // the weight-gradient GEMMs run over all M rows of an uninitialised workspace: every row they read for a dead (row, step)
+      // is cleared here (its dG0 / dG1 rows are exact zeros, and 0 * NaN is not)
+      if (u == 0) tp.len[rr] = mylen;
+      for (int t = u; t < T; t += kH) tp.tok[(long long)rr * T + t] = t >= 1 && t < mylen ? (int)clamp_token(mycap[t - 1], a.V) : -1;
+      for (int t = mylen; t < T; ++t) {
+        const long long m = (long long)rr * T + t;
+        tp.H0[m * kH + u] = 0.f;
+        tp.H0p[m * kH + u] = 0.f;
+        tp.H1p[m * kH + u] = 0.f;
+        for (int e = u; e < kNicE; e += kH) tp.X[m * kNicE + e] = 0.f;
+      }
+    }
   }
   // the input row this thread stages: step 0 is the image
   const bool stager = tid < kNicR * kX4;
@@ -446,6 +473,10 @@ __global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicSco
     const bool feed = t + 1 < xlen;                 // (false for every thread that stages nothing)
     long long next_tok = 0;
     if (feed) next_tok = xcap[t];
+    if constexpr (TAPE) {                           // (this thread staged these four floats itself)
+      if (t < xlen)
+        *reinterpret_cast<float4*>(tp.X + ((long long)(r0 + xr) * T + t) * kNicE + xq * 4) = *reinterpret_cast<const float4*>(&x_s[xr][xq * 4]);
+    }
     float acc[kNicR];
 #pragma unroll
     for (int r = 0; r < kNicR; ++r) acc[r] = bias0;
@@ -456,6 +487,13 @@ __global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicSco
     __syncthreads();
     if (active) {
       const NicCellOut q = nic_cell(g_s[rc], u, c0);
+      if constexpr (TAPE) {
+        const long long m = (long long)rr * T + t;
+        tp.H0p[m * kH + u] = h0_s[rc][u];
+        tp.G0[m * kG + u] = q.i; tp.G0[m * kG + kH + u] = q.f; tp.G0[m * kG + 2 * kH + u] = q.g; tp.G0[m * kG + 3 * kH + u] = q.o;
+        tp.C0[m * kH + u] = q.c;
+        tp.H0[m * kH + u] = q.h;
+      }
       c0 = q.c;
       h0_s[rc][u] = q.h;
     }
@@ -473,9 +511,15 @@ __global__ void __launch_bounds__(kNicThreads) nic_score_seq_kernel(const NicSco
     __syncthreads();
     if (active) {
       const NicCellOut q = nic_cell(g_s[rc], u, c1);
+      const long long m = (long long)rr * T + t;
+      if constexpr (TAPE) {
+        tp.H1p[m * kH + u] = h1_s[rc][u];
+        tp.G1[m * kG + u] = q.i; tp.G1[m * kG + kH + u] = q.f; tp.G1[m * kG + 2 * kH + u] = q.g; tp.G1[m * kG + 3 * kH + u] = q.o;
+        tp.C1[m * kH + u] = q.c;
+      }
       c1 = q.c;
       h1_s[rc][u] = q.h;
-      a.hidden[((long long)rr * T + t) * kH + u] = q.h;
+      a.hidden[m * kH + u] = TAPE && tp.drop ? q.h * tp.drop[m * kH + u] : q.h;
     }
     __syncthreads();
   }
@@ -488,6 +532,92 @@ __global__ void __launch_bounds__(256) nic_score_sum_kernel(const float* __restr
   float sum = 0.f;
   for (int t = 0; t < T; ++t) sum += lp[(long long)r * T + t];
   out_scores[r] = sum;
+}
+
+// Backward through time of the TAPE form of nic_score_seq_kernel (dic_nic_states_bwd): nic_lstm2_seq_bwd over tape rows
+// m = r*T + t for rows [blockIdx.x * kNicR, +kNicR) of the R caption rows.  Rows come in any order of length: the workgroup runs
+// max of its four device lengths and a row is inactive until t < length; the previous step's row is m - 1.  dHd [M][H] is the
+// gradient of the stored (dropped) h_top: rows at or behind the length are never read.  dG0 / dG1 [M][4H] are written for every
+// row of the M: exact zeros from the length on (prologue), since the weight-gradient GEMMs run over all of them.
+__global__ void __launch_bounds__(kNicThreads) nic_states_seq_bwd(const float* __restrict__ dHd, const float* __restrict__ Wih1Bp,
+                                                                   const float* __restrict__ Whh1Bp, const float* __restrict__ Whh0Bp,
+                                                                   int R, int T, NicStatesTape tp, float* __restrict__ dG0,
+                                                                   float* __restrict__ dG1) {
+  __shared__ __align__(16) float dg_s[kNicR][kG];
+  __shared__ float part_s[2][4][kNicR][kH];
+  const int tid = threadIdx.x, r0 = blockIdx.x * kNicR;
+  const int rc = tid >> 7, u = tid & (kH - 1), rr = r0 + rc;      // (also quarter rc / output u of the products)
+  const __amdgpu_buffer_rsrc_t Wih1B = nic_rsrc(Wih1Bp, kG * kH), Whh1B = nic_rsrc(Whh1Bp, kG * kH), Whh0B = nic_rsrc(Whh0Bp, kG * kH);
+  const int mylen = rr < R ? tp.len[rr] : 0;
+  int steps = 0;
+#pragma unroll
+  for (int r = 0; r < kNicR; ++r) steps = max(steps, r0 + r < R ? tp.len[r0 + r] : 0);
+  if (rr < R)
+    for (int t = mylen; t < T; ++t) {
+      const long long m = (long long)rr * T + t;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { dG0[m * kG + k * kH + u] = 0.f; dG1[m * kG + k * kH + u] = 0.f; }
+    }
+  float dh0c = 0.f, dc0c = 0.f, dh1c = 0.f, dc1c = 0.f;
+  for (int t = steps - 1; t >= 0; --t) {
+    const long long n = (long long)rr * T + t, np = n - 1;
+    const bool active = t < mylen;
+    float d[4] = {0.f, 0.f, 0.f, 0.f};
+    if (active) {
+      const float dm = tp.drop ? tp.drop[n * kH + u] : 1.f;
+      const float dh = dHd[n * kH + u] * dm + dh1c;
+      dc1c = nic_cell_bwd(tp.G1, tp.C1, n, np, t > 0, u, dh, dc1c, d);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dG1[n * kG + k * kH + u] = d[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dg_s[rc][k * kH + u] = d[k];
+    __syncthreads();
+    {
+      float a_ih[kNicR], a_hh[kNicR];
+#pragma unroll
+      for (int r = 0; r < kNicR; ++r) { a_ih[r] = 0.f; a_hh[r] = 0.f; }
+      nic_matvec<kH / 4>(Wih1B, rc * (kH / 4), kH / 4, kH, u, &dg_s[0][0], kG, rc * kH, a_ih);
+      nic_matvec<kH / 4>(Whh1B, rc * (kH / 4), kH / 4, kH, u, &dg_s[0][0], kG, rc * kH, a_hh);
+#pragma unroll
+      for (int r = 0; r < kNicR; ++r) { part_s[0][rc][r][u] = a_ih[r]; part_s[1][rc][r][u] = a_hh[r]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = 0.f;
+    if (active) {
+      const float dh0 = ((part_s[0][0][rc][u] + part_s[0][1][rc][u]) + (part_s[0][2][rc][u] + part_s[0][3][rc][u])) + dh0c;
+      dh1c = (part_s[1][0][rc][u] + part_s[1][1][rc][u]) + (part_s[1][2][rc][u] + part_s[1][3][rc][u]);
+      dc0c = nic_cell_bwd(tp.G0, tp.C0, n, np, t > 0, u, dh0, dc0c, d);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dG0[n * kG + k * kH + u] = d[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dg_s[rc][k * kH + u] = d[k];
+    __syncthreads();
+    {
+      float a[kNicR];
+#pragma unroll
+      for (int r = 0; r < kNicR; ++r) a[r] = 0.f;
+      nic_matvec<kH / 4>(Whh0B, rc * (kH / 4), kH / 4, kH, u, &dg_s[0][0], kG, rc * kH, a);
+#pragma unroll
+      for (int r = 0; r < kNicR; ++r) part_s[0][rc][r][u] = a[r];
+    }
+    __syncthreads();
+    if (active) dh0c = (part_s[0][0][rc][u] + part_s[0][1][rc][u]) + (part_s[0][2][rc][u] + part_s[0][3][rc][u]);
+    // (part_s[0] is next written behind the barrier that follows the next step's cell-1 part)
+  }
+}
+
+// d_features[b] = the sum over s, ascending, of dX[(b*S + s) * T]: the image is step 0 of each of its S rows
+__global__ void __launch_bounds__(256) nic_states_dfeat_kernel(const float* __restrict__ dX, int B, int S, int T,
+                                                                float* __restrict__ d_features) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * kNicE) return;
+  const int b = i / kNicE, e = i - b * kNicE;
+  float sum = 0.f;
+  for (int s = 0; s < S; ++s) sum += dX[(long long)(b * S + s) * T * kNicE + e];
+  d_features[i] = sum;
 }
 
 // ids[b] = argmax_v logits[b, v] (first maximum on ties, like torch.argmax), also out[b * T + t]
@@ -794,7 +924,50 @@ int nic_score_check(const char* who, int B, int S, int max_length, int V) {
   return DIC_OK;
 }
 
-int nic_upload_plan(const NicWs& ws, const int* lengths, int B, const StepPlan& pl, hipStream_t st) {
+// dic_nic_states_fwd / _bwd: the packed step weights, the tape at fixed-stride rows, and the backward's own arrays.  Nothing here
+// has a V dimension.
+constexpr int kNicStatesMaxM = (48 * 1024 / (4 * (int)sizeof(unsigned long long))) * 256;      // nic_embed_grad_kernel: one ballot bit per row in 48 KiB of LDS
+static_assert(kNicStatesMaxM == DIC_NIC_STATES_MAX_M && kNicStatesMaxM <= kScoreMaxM, "nic states: the limit include/dic.h states");
+
+struct NicStatesWs : NicStepWs {
+  NicStatesTape tp;
+  float *Wih1B, *Whh1B, *Whh0B, *dG0, *dG1, *dX, *cs_ws;
+  size_t bytes;
+};
+
+NicStatesWs nic_states_carve(void* p, size_t bytes, int B, int S, int T, bool* overflow) {
+  Carver c(p, bytes);
+  NicStatesWs w{};
+  const size_t M = (size_t)B * S * T;
+  nic_step_carve(c, w);
+  w.tp.len = c.take<int>((size_t)B * S);
+  w.tp.tok = c.take<int>(M);
+  w.tp.G0 = c.take<float>(M * kG);
+  w.tp.G1 = c.take<float>(M * kG);
+  for (float** m : {&w.tp.C0, &w.tp.C1, &w.tp.H0, &w.tp.H0p, &w.tp.H1p}) *m = c.take<float>(M * kH);
+  w.tp.X = c.take<float>(M * kNicE);
+  for (float** m : {&w.Wih1B, &w.Whh1B, &w.Whh0B}) *m = c.take<float>((size_t)kG * kH);
+  w.dG0 = c.take<float>(M * kG);
+  w.dG1 = c.take<float>(M * kG);
+  w.dX = c.take<float>(M * kNicE);
+  w.cs_ws = c.take<float>((size_t)256 * kG);
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+
+// the scalar arguments of dic_nic_states_fwd / _bwd and of their size query, checked before any pointer and before the first HIP call
+int nic_states_check(const char* who, int B, int S, int T, int V) {
+  DIC_REQUIRE(B > 0, "%s: bad batch size B=%d", who, B);
+  DIC_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", who, V);
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "%s: captions per image S=%d is outside 1..%d", who, S, kBeamMax);
+  DIC_REQUIRE(T >= 1, "%s: T=%d is < 1", who, T);
+  DIC_REQUIRE((long long)B * S * T <= kNicStatesMaxM, "%s: B*S*T=%lld exceeds %d token positions per call", who, (long long)B * S * T,
+              kNicStatesMaxM);
+  return DIC_OK;
+}
+
+int nic_upload_plan(const NicWs& ws,const int* lengths, int B, const StepPlan& pl, hipStream_t st) {
   // the caller's `lengths` and the plan are only read during this call: hipMemcpyAsync from pageable host memory returns after the
   // bytes have been staged
   DIC_CHECK_HIP(hipMemcpyAsync(ws.dlen, lengths, sizeof(int) * B, hipMemcpyHostToDevice, st));
@@ -1045,12 +1218,93 @@ int dic_nic_score(const dic_nic_weights* w, int V, const float* features, int B,
   DIC_TRY(nic_step_setup(w, ws, st));
   const NicScoreSeq a{features, w->embed, ws.Wih0F, ws.Whh0F, ws.Wih1F, ws.Whh1F, ws.bsum0, ws.bsum1, (const long long*)captions,
                       id_end, V, R, S, T, ws.hidden, ws.target, out_lengths};
-  hipLaunchKernelGGL(nic_score_seq_kernel, dim3(ceil_div(R, kNicR)), dim3(kNicThreads), 0, st, a);
+  hipLaunchKernelGGL(nic_score_seq_kernel<false>, dim3(ceil_div(R, kNicR)), dim3(kNicThreads), 0, st, a, NicStatesTape{});
   DIC_LAUNCH_CHECK();
   // rows r*T + t are the [B,S,T] layout itself: the fused projection writes out_logprobs, exact zeros for the -1 targets
   DIC_TRY(launch_token_logprobs(ws.hidden, w->out_w, w->out_b, ws.target, M, V, out_logprobs, nullptr, ws.lse_ws, st));
   hipLaunchKernelGGL(nic_score_sum_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, st, out_logprobs, R, T, out_scores);
   DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
+
+int dic_nic_states_sizes(int B, int S, int T, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "dic_nic_states_sizes: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_TRY(nic_states_check("dic_nic_states_sizes", B, S, T, V));
+  bool ov;
+  *workspace_bytes = nic_states_carve(nullptr, 0, B, S, T, &ov).bytes;
+  return DIC_OK;
+}
+
+int dic_nic_states_fwd(const dic_nic_weights* w, int V, const float* features, int B, int S, long long id_end, int T,
+                       const int64_t* captions, const float* drop_mult, float* out_hidden, int64_t* out_targets, int* out_lengths,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call, the scalars before the pointers
+  DIC_TRY(nic_states_check("dic_nic_states_fwd", B, S, T, V));
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "dic_nic_states_fwd: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(w && features && captions && out_hidden && out_targets && out_lengths && workspace, "dic_nic_states_fwd: null pointer");
+  const int R = B * S;
+  bool ov = false;
+  NicStatesWs ws = nic_states_carve(workspace, workspace_bytes, B, S, T, &ov);
+  if (ov) {
+    set_last_error("dic_nic_states_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  DIC_TRY(nic_step_setup(w, ws, st));
+  const NicScoreSeq a{features, w->embed, ws.Wih0F, ws.Whh0F, ws.Wih1F, ws.Whh1F, ws.bsum0, ws.bsum1, (const long long*)captions,
+                      id_end, V, R, S, T, out_hidden, (long long*)out_targets, out_lengths};
+  ws.tp.drop = drop_mult;
+  hipLaunchKernelGGL(nic_score_seq_kernel<true>, dim3(ceil_div(R, kNicR)), dim3(kNicThreads), 0, st, a, ws.tp);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
+
+int dic_nic_states_bwd(const dic_nic_weights* w, int V, int B, int S, long long id_end, int T, const int64_t* captions,
+                       const float* drop_mult, const float* d_hidden, const dic_nic_grads* g, float* d_features, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  DIC_TRY(nic_states_check("dic_nic_states_bwd", B, S, T, V));
+  DIC_REQUIRE(id_end >= 0 && id_end < V, "dic_nic_states_bwd: id_end=%lld is outside the vocabulary [0, %d)", id_end, V);
+  DIC_REQUIRE(w && captions && d_hidden && g && workspace, "dic_nic_states_bwd: null pointer");
+  DIC_REQUIRE(g->embed && g->w_ih_l0 && g->w_hh_l0 && g->b_ih_l0 && g->b_hh_l0 && g->w_ih_l1 && g->w_hh_l1 && g->b_ih_l1 && g->b_hh_l1,
+              "dic_nic_states_bwd: null pointer (gradient table)");
+  const int R = B * S, M = R * T;
+  bool ov = false;
+  NicStatesWs ws = nic_states_carve(workspace, workspace_bytes, B, S, T, &ov);
+  if (ov) {
+    set_last_error("dic_nic_states_bwd: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    return DIC_ERR_WORKSPACE;
+  }
+  ws.tp.drop = drop_mult;
+  // the reverse loop (lengths, tokens and every activation come from the tape: the captions are not read again)
+  DIC_TRY(nic_pack4(w->w_ih_l1, kH, kG, 1, kH, ws.Wih1B, st));
+  DIC_TRY(nic_pack4(w->w_hh_l1, kH, kG, 1, kH, ws.Whh1B, st));
+  DIC_TRY(nic_pack4(w->w_hh_l0, kH, kG, 1, kH, ws.Whh0B, st));
+  hipLaunchKernelGGL(nic_states_seq_bwd, dim3(ceil_div(R, kNicR)), dim3(kNicThreads), 0, st, d_hidden, ws.Wih1B, ws.Whh1B, ws.Whh0B,
+                     R, T, ws.tp, ws.dG0, ws.dG1);
+  DIC_LAUNCH_CHECK();
+  // weight gradients over all M rows (dead rows: dG = 0 against cleared tape rows)
+  DIC_TRY(gemm(kG, kH, M, op_colk(ws.dG1, kG), op_colk(ws.tp.H0, kH), ep_store(g->w_ih_l1, kH), st));
+  DIC_TRY(gemm(kG, kH, M, op_colk(ws.dG1, kG), op_colk(ws.tp.H1p, kH), ep_store(g->w_hh_l1, kH), st));
+  DIC_TRY(gemm(kG, kH, M, op_colk(ws.dG0, kG), op_colk(ws.tp.H0p, kH), ep_store(g->w_hh_l0, kH), st));
+  DIC_TRY(gemm(kG, kNicE, M, op_colk(ws.dG0, kG), op_colk(ws.tp.X, kNicE), ep_store(g->w_ih_l0, kNicE), st));
+  DIC_TRY(colsum_rows(ws.dG0, kG, M, kG, g->b_ih_l0, ws.cs_ws, st));
+  DIC_TRY(colsum_rows(ws.dG1, kG, M, kG, g->b_ih_l1, ws.cs_ws, st));
+  DIC_CHECK_HIP(hipMemcpyAsync(g->b_hh_l0, g->b_ih_l0, sizeof(float) * kG, hipMemcpyDeviceToDevice, st));
+  DIC_CHECK_HIP(hipMemcpyAsync(g->b_hh_l1, g->b_ih_l1, sizeof(float) * kG, hipMemcpyDeviceToDevice, st));
+  // input rows: dX = dG0 W_ih_l0; row r*T is the image step of caption r, the others go to the embedding table in a fixed order
+  DIC_TRY(gemm(M, kNicE, kG, op_rowk(ws.dG0, kG), op_colk(w->w_ih_l0, kNicE), ep_store(ws.dX, kNicE), st));
+  if (d_features) {
+    hipLaunchKernelGGL(nic_states_dfeat_kernel, dim3(ceil_div((long long)B * kNicE, 256)), dim3(256), 0, st, ws.dX, B, S, T, d_features);
+    DIC_LAUNCH_CHECK();
+  }
+  DIC_CHECK_HIP(hipMemsetAsync(g->embed, 0, sizeof(float) * (size_t)V * kNicE, st));
+  if (T > 1) {
+    const size_t bal_bytes = (size_t)ceil_div(M, 256) * 4 * sizeof(unsigned long long);      // <= 48 KiB: nic_states_check
+    hipLaunchKernelGGL(nic_embed_grad_kernel, dim3(M), dim3(256), bal_bytes, st, ws.dX, ws.tp.tok, M, g->embed);
+    DIC_LAUNCH_CHECK();
+  }
   return DIC_OK;
 }
 

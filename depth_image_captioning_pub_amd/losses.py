@@ -72,7 +72,11 @@ def self_critical_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: t
         -(sum over tokens of (rewards - baseline)[..., None] * logprobs) / lengths.sum()
     rewards: float [B,S] (or [B]), one per caption.  baseline: "others" - per caption the mean reward of the image's other S - 1
     captions (needs S >= 2); a tensor broadcastable to the rewards, for example the reward of the greedy caption; or None.
-    Plain torch reductions over [B,S,T] values; no gradient flows into rewards or baseline."""
+    Plain torch reductions over [B,S,T] values; no gradient flows into rewards or baseline.
+    Evaluated as sum(w[..., None] * logprobs) with the per-caption weight w = -(adv / N), the rewards of an image added in
+    ascending s: the fp32 operations of dic_scst_loss (include/dic.h) in its order, so the gradient autograd hands to the
+    log-probabilities inside a caption's length is that call's d_logprob bit for bit, and a step through the modules and a step
+    on the engine's flat buffers start from the same gradients."""
     r = rewards.detach().to(logprobs.dtype)
     if tuple(r.shape) != tuple(logprobs.shape[:-1]):
         raise _lib.DicError(f"self_critical_loss: rewards must be {tuple(logprobs.shape[:-1])}, one per caption, got {tuple(r.shape)}")
@@ -82,9 +86,13 @@ def self_critical_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: t
         if r.dim() != 2 or r.shape[1] < 2:
             raise _lib.DicError("self_critical_loss: the 'others' baseline is the mean reward of the image's other captions and "
                                 f"needs rewards [B,S] with S >= 2, got {tuple(r.shape)}")
-        adv = r - (r.sum(1, keepdim=True) - r) / (r.shape[1] - 1)
+        total = r[:, :1]
+        for s in range(1, r.shape[1]):                 # ascending s, like the kernel: torch.sum may associate otherwise
+            total = total + r[:, s:s + 1]
+        adv = r - (total - r) / (r.shape[1] - 1)
     elif baseline is None:
         adv = r
     else:
         adv = r - torch.as_tensor(baseline, device=r.device).detach().to(r.dtype)
-    return -(adv.unsqueeze(-1) * logprobs).sum() / lengths.sum().to(logprobs.dtype)
+    w = -(adv / lengths.sum().to(logprobs.dtype))
+    return (w.unsqueeze(-1) * logprobs).sum()

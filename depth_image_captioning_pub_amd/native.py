@@ -1190,3 +1190,86 @@ def nic_score(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: 
     if squeeze:
         return logprobs[:, 0], scores[:, 0], lengths[:, 0]
     return logprobs, scores, lengths
+
+
+# the 9 NIC decoder gradients dic_nic_states_bwd writes (linear.* come from token_logprobs_bwd)
+NIC_STATES_GRAD_KEYS = tuple(k for k, _ in NIC_FIELDS if not k.startswith("linear."))
+
+
+@dataclass
+class NicStatesTape:
+    """Everything dic_nic_states_bwd needs from the matching forward call."""
+    workspace: torch.Tensor
+    weights: Dict[str, torch.Tensor]
+    vocab: int
+    B: int
+    S: int
+    T: int
+    id_end: int
+    captions: torch.Tensor
+    drop_mult: Optional[torch.Tensor]
+
+
+def nic_states_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, captions: torch.Tensor,
+                       drop_mult: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """dic_nic_states_fwd: the hidden states of given captions, with a tape for nic_states_backward (semantics: include/dic.h).
+    captions int64 [B,S,T], S <= 8 per image; drop_mult float32 [B*S,T,128] or None (eval); workspace: a uint8 GPU tensor to use
+    when it is large enough (its contents do not matter).
+    Returns (hidden float32 [B*S*T,128], row r*T + t, 0 from each row's length on; targets int64 [B*S*T], -1 there; lengths int32
+    [B,S]; tape): token_logprobs(hidden, linear.weight, linear.bias, targets) is the [B,S,T] log-probabilities."""
+    lib = _load()
+    f, B = _nic_features(features)
+    wp, keep = nic_ptrs(weights)
+    vocab = int(weights["linear.weight"].shape[0])
+    cap = _dev(captions, "captions", torch.int64)
+    if cap.dim() != 3 or cap.shape[0] != B:
+        raise _lib.DicError(f"nic_states: captions must be [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+    S, T = int(cap.shape[1]), int(cap.shape[2])
+    R = B * S
+    dm = None
+    if drop_mult is not None:
+        dm = _dev(drop_mult, "drop_mult")
+        if tuple(dm.shape) != (R, T, D_HID):
+            raise _lib.DicError(f"nic_states: drop_mult must be [B*S,T,{D_HID}] = [{R},{T},{D_HID}], got {tuple(dm.shape)}")
+    need = C.c_size_t(0)
+    lib.dic_nic_states_sizes(B, S, T, vocab, C.byref(need))
+    if workspace is not None and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= max(int(need.value), 256):
+        ws = workspace
+    else:
+        ws = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=f.device)
+    m = max(R * T, 1)
+    hidden = torch.empty((m, D_HID), dtype=torch.float32, device=f.device)
+    targets = torch.empty((m,), dtype=torch.int64, device=f.device)
+    lengths = torch.empty((B, max(S, 1)), dtype=torch.int32, device=f.device)
+    rc = lib.dic_nic_states_fwd(C.byref(wp), vocab, ptr(f), B, S, int(id_end), T, ptr(cap), ptr(dm), ptr(hidden), ptr(targets),
+                                ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_states_fwd")
+    tape = NicStatesTape(ws, {k: t for (k, _), t in zip(NIC_FIELDS, keep)}, vocab, B, S, T, int(id_end), cap, dm)
+    return hidden, targets, lengths, tape
+
+
+def nic_states_backward(tape: NicStatesTape, d_hidden: torch.Tensor, need_features: bool = True,
+                        grads: Optional[Dict[str, torch.Tensor]] = None):
+    """dic_nic_states_bwd: backward through time of nic_states_forward.  d_hidden float32 [B*S*T,128] (rows behind a caption's
+    length are ignored).  grads: write (not accumulate) into the caller's contiguous float32 GPU tensors grads[k], k in
+    NIC_STATES_GRAD_KEYS - the engine's views of its flat gradient buffer; further keys are left alone.
+    Returns (grads: dict over the 9 keys NIC_STATES_GRAD_KEYS, d_features [B,300] or None)."""
+    lib = _load()
+    dh = _dev(d_hidden, "d_hidden")
+    M = tape.B * tape.S * tape.T
+    if tuple(dh.shape) != (M, D_HID):
+        raise _lib.DicError(f"nic_states: d_hidden must be [B*S*T,{D_HID}] = [{M},{D_HID}], got {tuple(dh.shape)}")
+    wp, keep = nic_ptrs(tape.weights)
+    if grads is None:
+        out = {k: torch.empty_like(tape.weights[k]) for k in NIC_STATES_GRAD_KEYS}
+    else:
+        out = {k: _grad_out(grads, k, tape.weights[k].shape, "nic_states") for k in NIC_STATES_GRAD_KEYS}
+    gp = NicPtrs()
+    for key, field in NIC_FIELDS:
+        setattr(gp, field, out[key].data_ptr() if key in out else None)
+    d_features = torch.empty((tape.B, NIC_EMB), dtype=torch.float32, device=dh.device) if need_features else None
+    rc = lib.dic_nic_states_bwd(C.byref(wp), tape.vocab, tape.B, tape.S, tape.id_end, tape.T, ptr(tape.captions),
+                                ptr(tape.drop_mult), ptr(dh), C.byref(gp), ptr(d_features), ptr(tape.workspace),
+                                tape.workspace.numel(), stream_ptr())
+    check(rc, "dic_nic_states_bwd")
+    return out, d_features

@@ -523,6 +523,45 @@ int dic_nic_score(const dic_nic_weights* w, int V, const float* features, int B,
                   const int64_t* captions, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* the differentiable form of dic_nic_score: the hidden states of GIVEN captions with a tape, and their backward through time - the
+ *   NIC counterpart of dic_decoder_states_fwd / _bwd.  There is no reference implementation; this comment is the specification
+ *   (DESIGN.md 5.21).  Entirely on the device: every launch is enqueued on `stream`, nothing is copied to the host, nothing
+ *   synchronises, no float atomics; two calls return identical bytes, forward and backward.
+ *   Rows, inputs and lengths are those of dic_nic_score, word for word: row r = b*S + s, 1 <= S <= 8; features float [B,300];
+ *     captions int64 [B,S,T] on the device, no start token; step 0 takes features[b] with h and c of both layers zero, step t >= 1
+ *     takes embed[captions[r,t-1]] clamped into the vocabulary; length[r] = (index of the first id_end) + 1, or T, found on the
+ *     device; rows may come in any order of length.  A forward row depends only on its own image and caption.
+ *   Forward outputs, in the row order of dic_nic_score (row r*T + t), so that dic_token_logprobs over them writes [B,S,T] directly:
+ *     out_hidden float [B*S*T,128]: h_top of (r,t), times drop_mult[r,t,:] when drop_mult (float [B*S,T,128], 0 or 1/(1-p)) is
+ *       given; NULL = eval.  The carried h is never dropped, as in dic_nic_fwd.  Exactly 0 from the row's length on.
+ *     out_targets int64 [B*S*T]: the clamped token, -1 from the length on.  out_lengths int [B,S].
+ *     With drop_mult == NULL out_hidden holds, bit for bit, the hidden states dic_nic_score projects for the same inputs (one
+ *     sequence kernel, compiled with and without the tape stores; layer 0's input product stays inside it), so dic_token_logprobs
+ *     of (out_hidden, out_targets) returns dic_nic_score's out_logprobs bit for bit.
+ *   The forward leaves the tape in the workspace at fixed-stride rows r*T + t - no packing, no host plan; the workspace may
+ *     arrive uninitialised: every tape row the backward's GEMMs read for a dead (row, step) is cleared by the forward.
+ *   Backward: consumes the workspace the forward left, with the same w, captions and drop_mult.  d_hidden float [B*S*T,128], the
+ *     gradient of out_hidden; rows at or behind the length are ignored (selected to 0, never multiplied: any bytes there, NaN
+ *     included, change nothing).  Writes (not accumulates) the 9 gradients of embed and the two LSTM layers; g->out_w / g->out_b
+ *     are not read and may be NULL (dic_token_logprobs_bwd gives them).  b_hh is a copy of b_ih.  Embedding rows of tokens never
+ *     fed are 0 - every token at or behind a row's id_end included; the first occurrence of a token sums its rows in row order.
+ *     d_features float [B,300] (nullable: not written when NULL): d_features[b] = the sum over s, ascending, of the gradient of
+ *     row b*S + s's step-0 input.
+ *   B <= 0, V <= 0, S outside 1..8, T < 1, B*S*T > DIC_NIC_STATES_MAX_M = 393216 (the embedding-gradient kernel keeps one bit per
+ *   row in 48 KiB of LDS), id_end outside [0, V), a null pointer other than drop_mult, d_features, g->out_w and g->out_b, or a
+ *   short workspace returns a negative code and a dic_last_error() text that starts with the entry point's name, before the first
+ *   HIP call (the scalar arguments are checked before the pointers).  dic_nic_states_sizes hands the workspace size back through
+ *   *workspace_bytes; for sizes the calls refuse it writes 0 and returns a negative code.  The workspace holds no array with a V
+ *   dimension: its size does not depend on V. */
+#define DIC_NIC_STATES_MAX_M 393216
+int dic_nic_states_sizes(int B, int S, int T, int V, size_t* workspace_bytes);
+int dic_nic_states_fwd(const dic_nic_weights* w, int V, const float* features, int B, int S, long long id_end, int T,
+                       const int64_t* captions, const float* drop_mult, float* out_hidden, int64_t* out_targets,
+                       int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+int dic_nic_states_bwd(const dic_nic_weights* w, int V, int B, int S, long long id_end, int T, const int64_t* captions,
+                       const float* drop_mult, const float* d_hidden, const dic_nic_grads* g, float* d_features,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* stand-alone attention module: Soft_Attention.forward (attention.py:81-95), Hard_Attention.forward (:132-148,
  *   mode 1, gumbel_u [B,196], temp) and Hard_Attention.Hard_sample (:150-167, mode 2): feats [B,196,2048],
  *   h [B,128] -> ctx [B,2048], alpha [B,196] (float; one-hot in mode 2). */
