@@ -1,5 +1,5 @@
 // Beam-search selection shared by the two decode routes that keep K hypotheses per image: dic_decoder_beam (decoder_decode.hip,
-// soft attention) and dic_nic_beam (nic.hip).  One candidate rule (include/dic.h), one copy of each piece:
+// soft attention) and dic_nic_beam (nic_decode.hip).  One candidate rule (include/dic.h), one copy of each piece:
 //   launch_beam_topk       beam_topk_kernel<K>: log-softmax of a row + its K best candidates          (beam.hip)
 //   beam_select_rank<K>    the K best of an image's K x K candidates become the new beams              (device, this header)
 //   launch_beam_backtrack  beam_backtrack_kernel: final ranking and the token histories                (beam.hip)
