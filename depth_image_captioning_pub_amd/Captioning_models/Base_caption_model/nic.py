@@ -24,7 +24,7 @@ from torch import nn
 
 from ... import losses, native, synthetic as syn
 from ..._lib import DicError
-from ...engine import CaptionTrainer, FlatParams
+from ...engine import BackboneTrainer, FlatParams, baseline_mode, look_ahead, reward_tensor
 from ..config import ConfigTrain
 from .base_caption_models import _LAYERS, CNNEncoder_Atten
 
@@ -148,8 +148,8 @@ class NIC_RNNDecoder(nn.Module):
         p = float(self.dropout.p)
         if self.training and p > 0.0:
             B, tmax = features.shape[0], max(cfg["lengths"])
-            cfg["drop_mult"] = native.dropout_mask((B, tmax, native.D_HID), p, self._rng_seed, self._rng_offset, features.device)
-            self._rng_offset += B * tmax * native.D_HID // 4 + 1
+            cfg["drop_mult"], self._rng_offset = native.dropout_draw((B, tmax, native.D_HID), p, self._rng_seed, self._rng_offset,
+                                                                     features.device)
         return _NicDecoderFn.apply(cfg, features, captions, *self._params())
 
     def _greedy(self, features, states, max_length):
@@ -218,8 +218,8 @@ class NIC_RNNDecoder(nn.Module):
                "linear": {"linear.weight": self.linear.weight.detach(), "linear.bias": self.linear.bias.detach()}}
         p = float(self.dropout.p)
         if self.training and p > 0.0:
-            cfg["drop_mult"] = native.dropout_mask((B * S, T, native.D_HID), p, self._rng_seed, self._rng_offset, features.device)
-            self._rng_offset += B * S * T * native.D_HID // 4 + 1
+            cfg["drop_mult"], self._rng_offset = native.dropout_draw((B * S, T, native.D_HID), p, self._rng_seed, self._rng_offset,
+                                                                     features.device)
         sd = dict(self.named_parameters())
         hidden = _NicStatesFn.apply(cfg, features, caps, *[sd[k] for k in native.NIC_STATES_GRAD_KEYS])
         logprobs, _ = losses.token_logprobs(hidden, self.linear.weight, self.linear.bias, cfg["targets"])
@@ -258,39 +258,24 @@ def nic_scst_arguments(B: int, vocab: int, id_end, captions, n_candidates, max_l
         raise DicError(f"scst_step: max_length={T} is < 1")
     if B < 1 or B * S * T > NIC_STATES_MAX_CELLS:
         raise DicError(f"scst_step: B*S*T = {B * S * T} is outside 1 .. {NIC_STATES_MAX_CELLS} (the states route's limit)")
-    if isinstance(baseline, str):
-        if baseline != "others":
-            raise DicError(f"scst_step: baseline must be 'others', a tensor [B,S] or [B], or None, got {baseline!r}")
-        if S < 2:
-            raise DicError("scst_step: the 'others' baseline is the mean reward of the image's other captions and needs at least 2 "
-                           f"captions per image, got {S}")
-        mode = 1
-    elif baseline is None:
-        mode = 0
-    elif torch.is_tensor(baseline) and tuple(baseline.shape) in ((B, S), (B,)):
-        mode = 3 if baseline.dim() == 1 else 2
-    else:
-        raise DicError(f"scst_step: baseline must be 'others', a tensor [{B},{S}] or [{B}], or None, got "
-                       f"{tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__}")
+    mode = baseline_mode(baseline, B, S, ("others",), "at least 2 captions per image")
     if drop_mult is not None and tuple(drop_mult.shape) != (B * S, T, native.D_HID):
         raise DicError(f"scst_step: drop_mult must be [B*S, T, {native.D_HID}] = [{B * S}, {T}, {native.D_HID}], got "
                        f"{tuple(drop_mult.shape)}")
     return mode, S, T
 
 
-class NicTrainer(CaptionTrainer):
+class NicTrainer(BackboneTrainer):
     """Weights, optimiser state and workspaces of one NIC training run: the 11 decoder tensors and encoder.linear in one flat fp32
-    buffer (one AdamW launch per step, nic.py:243-245).  The frozen ResNet-152 side is CaptionTrainer's as it stands - forwards of
-    the next batches running ahead on side streams (captured graphs), BatchNorm running statistics applied in batch order, the
-    f16x2 overflow guard as AdamW's skip word - with the depth branch and the attention decoder switched off.  Single GPU."""
+    buffer (one AdamW launch per step, nic.py:243-245).  The frozen ResNet-152 side is engine.BackboneTrainer, the base it shares
+    with CaptionTrainer: forwards of the next batches running ahead on side streams (captured graphs), BatchNorm running
+    statistics applied in batch order, the f16x2 overflow guard as AdamW's skip word.  Single GPU."""
 
     def __init__(self, vocab: int, device: str = "cuda:0", seed: int = 123, lr: float = 1e-3, dropout: float = 0.5,
                  resnet_layers: Sequence[int] = _LAYERS, conv_mode: Optional[str] = None,
                  decoder_init: Optional[Dict[str, torch.Tensor]] = None, head_init: Optional[Dict[str, torch.Tensor]] = None,
                  resnet_init: Optional[Dict[str, torch.Tensor]] = None):
-        placeholder = {k: torch.zeros(1) for k, _ in native.DECODER_FIELDS}       # (the attention decoder's slots stay empty)
-        super().__init__(vocab, device=device, seed=seed, lr=lr, hard=False, resnet_layers=resnet_layers, dropout=dropout,
-                         decoder_init=placeholder, resnet_init=resnet_init, conv_mode=conv_mode, use_depth=False)
+        super().__init__(vocab, device, seed, lr, dropout, resnet_layers, resnet_init, conv_mode)
         dec, head = syn.nic_weights(vocab, seed=seed)
         dec = decoder_init if decoder_init is not None else dec
         head = head_init if head_init is not None else head
@@ -303,7 +288,14 @@ class NicTrainer(CaptionTrainer):
         self.head_w, self.head_b = (self.flat.view(self.flat.data, "encoder.linear." + k) for k in ("weight", "bias"))
         self.head_gw, self.head_gb = (self.flat.view(self.flat.grad, "encoder.linear." + k) for k in ("weight", "bias"))
         self.dec_span = (0, self.flat.total)
+        self.dec_ws: Optional[torch.Tensor] = None
         self.states_ws: Optional[torch.Tensor] = None
+
+    def _head_backward(self, pooled: torch.Tensor, dfeat: torch.Tensor) -> None:
+        """dic_nic_head_bwd into encoder.linear's views of the flat gradient buffer."""
+        gw, gb = native.nic_head_backward(pooled, dfeat)
+        self.head_gw.copy_(gw)
+        self.head_gb.copy_(gb)
 
     def step_on_map(self, fmap: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int],
                     drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False) -> torch.Tensor:
@@ -313,9 +305,8 @@ class NicTrainer(CaptionTrainer):
             self._guard_take(None)
         B, tmax = fmap.shape[0], max(lengths)
         pooled, feats = native.nic_head_forward(self.head_w, self.head_b, fmap)
-        if drop_mult is None and dropout and self.p_drop > 0:
-            drop_mult = native.dropout_mask((B, tmax, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset, self.device)
-            self.rng_offset += B * tmax * native.D_HID // 4 + 1
+        if drop_mult is None and dropout:
+            drop_mult = self._draw_dropout(B, tmax)
         logits, tape = native.nic_forward(self.dec_w, feats, captions, lengths, drop_mult, workspace=self.dec_ws)
         self.dec_ws = tape.workspace
         self._mark("nic_fwd")
@@ -323,9 +314,7 @@ class NicTrainer(CaptionTrainer):
                                                in_place=not self.keep_outputs)
         self._mark("loss")
         _, dfeat = native.nic_backward(tape, dlogits, grads=self.dec_g)
-        gw, gb = native.nic_head_backward(pooled, dfeat)
-        self.head_gw.copy_(gw)
-        self.head_gb.copy_(gb)
+        self._head_backward(pooled, dfeat)
         self._mark("nic_bwd")
         self.apply_update()                    # AdamW on the flat buffer, skipped on the device when the guard word is raised
         self._mark("adamw")
@@ -335,19 +324,7 @@ class NicTrainer(CaptionTrainer):
     def train_step(self, imgs: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int], next_imgs=None) -> torch.Tensor:
         """One iteration of nic.py:270-290; returns the loss as a 1-element device tensor (no host sync).  next_imgs: the images
         of the following batches in order (CaptionTrainer.train_step's convention): their ResNet forwards run ahead."""
-        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
-        self.marks = []
-        self._mark("start")
-        fmap = self._take_prefetched(imgs)
-        if fmap is None:
-            fmap = self._resnet_eager(imgs, True, True)                       # train-mode BatchNorm in the frozen net (Q1)
-            self._guard_take(self.resnet)
-        if next_imgs is not None:
-            upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
-            for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
-                if k >= len(self.queue):
-                    self.prefetch_features(nxt, compact=True)
-        self._mark("resnet152_fwd")
+        fmap = self._open_step(imgs, next_imgs, lambda x: True)      # train-mode BatchNorm in the frozen net (Q1); the 7x7 map
         return self.step_on_map(fmap, captions, lengths, keep_guard=True)
 
     # ---- self-critical step (no counterpart in the reference; DESIGN.md 5.21) ---------------------------------------------------------
@@ -376,19 +353,13 @@ class NicTrainer(CaptionTrainer):
             ids, _, _ = native.nic_beam(self.dec_w, feats, int(id_end), S, T, float(length_penalty))
         else:
             ids = _contig(captions.to(self.device))
-        ended = ids == int(id_end)
-        lengths = torch.where(ended.any(-1), ended.int().argmax(-1) + 1, torch.full_like(ids[..., 0], T)).to(torch.int32)
+        lengths = native.caption_lengths(ids, id_end)
         self._mark("candidates")
-        rewards = reward_fn(ids, lengths)
-        if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
-            raise DicError(f"scst_step: reward_fn must return a tensor [B,S] = [{B}, {S}], got "
-                           f"{tuple(rewards.shape) if torch.is_tensor(rewards) else type(rewards).__name__}")
-        rewards = rewards.detach().to(self.device, torch.float32).contiguous()
+        rewards = reward_tensor(reward_fn(ids, lengths), B, S, self.device)
         base = baseline.detach().to(self.device, torch.float32).contiguous() if torch.is_tensor(baseline) else None
         self._mark("reward")
-        if drop_mult is None and dropout and self.p_drop > 0:
-            drop_mult = native.dropout_mask((R, T, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset, self.device)
-            self.rng_offset += R * T * native.D_HID // 4 + 1
+        if drop_mult is None and dropout:
+            drop_mult = self._draw_dropout(R, T)
         hidden, targets, lens, tape = native.nic_states_forward(self.dec_w, feats, int(id_end), ids, drop_mult,
                                                                 workspace=self.states_ws)
         self.states_ws = tape.workspace
@@ -400,9 +371,7 @@ class NicTrainer(CaptionTrainer):
         self._mark("loss")
         d_hidden = native.token_logprobs_bwd_into(self.dec_g, hidden, lw, lb, targets, lse, d_logprob.t().contiguous().view(-1))
         _, dfeat = native.nic_states_backward(tape, d_hidden, True, grads=self.dec_g)
-        gw, gb = native.nic_head_backward(pooled, dfeat)
-        self.head_gw.copy_(gw)
-        self.head_gb.copy_(gb)
+        self._head_backward(pooled, dfeat)
         self._mark("states_bwd")
         self.apply_update()                    # AdamW on the flat buffer, skipped on the device when the guard word is raised
         self._mark("adamw")
@@ -413,22 +382,10 @@ class NicTrainer(CaptionTrainer):
     def scst_step(self, imgs: torch.Tensor, reward_fn, id_end: int, captions: Optional[torch.Tensor] = None,
                   n_candidates: int = 5, max_length: int = 30, length_penalty: float = 0.0, baseline="others", next_imgs=None):
         """scst_step_on_map behind the frozen ResNet-152 forward of `imgs` (train-mode BatchNorm, quirk Q1; prefetching and the
-        overflow guard as in train_step).  Replaces CaptionTrainer.scst_step, which is built for the attention decoder."""
+        overflow guard as in train_step)."""
         nic_scst_arguments(int(imgs.shape[0]), self.vocab, id_end, captions, n_candidates, max_length, length_penalty, baseline,
                            reward_fn, None)
-        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
-        self.marks = []
-        self._mark("start")
-        fmap = self._take_prefetched(imgs)
-        if fmap is None:
-            fmap = self._resnet_eager(imgs, True, True)
-            self._guard_take(self.resnet)
-        if next_imgs is not None:
-            upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
-            for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
-                if k >= len(self.queue):
-                    self.prefetch_features(nxt, compact=True)
-        self._mark("resnet152_fwd")
+        fmap = self._open_step(imgs, next_imgs, lambda x: True)
         return self.scst_step_on_map(fmap, reward_fn, id_end, captions, n_candidates, max_length, length_penalty, baseline,
                                      keep_guard=True)
 
@@ -483,20 +440,11 @@ def train_nic(ext, useData: str = "synthetic", config=None, stats=None):
     history = []
     for epoch in range(config.num_epochs):
         losses = []
-        # two batches of look-ahead: the frozen ResNet runs ahead of the step on side streams (as depth_train._train)
+        # the frozen ResNet runs ahead of the step on side streams (as in depth_train._train)
         stream_it = ((imgs.to(dev), caps.to(dev), lens) for imgs, caps, lens in
                      _synthetic_batches(config, config.iters_per_epoch, 1000 * epoch))
-        ahead = []
-        for nxt in stream_it:
-            ahead.append(nxt)
-            if len(ahead) > 2:
-                break
-        while ahead:
-            imgs, caps, lens = ahead.pop(0)
-            nxt = next(stream_it, None)
-            if nxt is not None:
-                ahead.append(nxt)
-            losses.append(trainer.train_step(imgs, caps, lens, next_imgs=[a[0] for a in ahead[:2]]))      # no per-iteration host sync
+        for (imgs, caps, lens), following in look_ahead(stream_it):
+            losses.append(trainer.train_step(imgs, caps, lens, next_imgs=[f[0] for f in following]))      # no per-iteration host sync
         trainer.check_status()          # f16x2 overflow guard: raises DicError if a step of this epoch tripped it
         train_loss = float(torch.stack(losses).mean().item())
         with open(train_loss_file, "a") as f:

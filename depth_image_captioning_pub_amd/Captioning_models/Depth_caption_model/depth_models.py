@@ -185,8 +185,7 @@ class _CaptionDecoderBase(nn.Module):
         p = float(self.dropout.p)
         if not self.training or p <= 0.0:
             return None
-        m = native.dropout_mask((B, tmax, native.D_HID), p, self._rng_seed, self._rng_offset, device)
-        self._rng_offset += B * tmax * native.D_HID // 4 + 1
+        m, self._rng_offset = native.dropout_draw((B, tmax, native.D_HID), p, self._rng_seed, self._rng_offset, device)
         return m
 
     def _draw_uniforms(self, batch_sizes: Sequence[int], device) -> torch.Tensor:

@@ -19,7 +19,7 @@ import torch
 from ... import metrics, native, synthetic as syn
 from ...cider import CiderD
 from ..._lib import DicError
-from ...engine import CaptionTrainer
+from ...engine import CaptionTrainer, look_ahead
 from ..config import ConfigTrain
 
 lam = 0.7             # depth_train.py:25
@@ -96,19 +96,10 @@ def _scst_epochs(trainer, config, rank: int, first_epoch: int, n_epochs: int, re
                 reward = metrics.reward_fn(ref_ids, ref_counts, id_end=id_end, vocab=config.vocab_size, cider=scorer,
                                            weights=config.scst_reward_weights)
                 yield imgs.to(dev), (depth.to(dev) if depth_branch else None), reward
-        ahead, stream_it = [], on_device()
-        for nxt in stream_it:
-            ahead.append(nxt)
-            if len(ahead) > 2:
-                break
         rewards = []
-        while ahead:
-            imgs, depth, reward = ahead.pop(0)
-            nxt = next(stream_it, None)
-            if nxt is not None:
-                ahead.append(nxt)
+        for (imgs, depth, reward), following in look_ahead(on_device()):
             _, mean = trainer.scst_step(imgs, depth, reward, id_start=id_start, id_end=id_end, n_samples=config.scst_samples,
-                                        max_length=config.seq_len, next_imgs=[a[0] for a in ahead[:2]])
+                                        max_length=config.seq_len, next_imgs=[f[0] for f in following])
             rewards.append(mean)                                        # device tensors: no per-iteration host sync
         trainer.check_status()
         means.append(float(torch.cat(rewards).mean().item()))
@@ -173,22 +164,13 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
                 if use_dpt:
                     imgs, depth = front.depth_maps(epoch, [f"{it}:{i}" for i in range(len(lens))], imgs.to(dev))
                 yield it, imgs.to(dev), (depth.to(dev) if depth_branch else None), caps.to(dev), lens
-        # two batches of look-ahead: the frozen RGB encoder runs ahead of the step on side streams (engine.prefetch_features)
-        ahead, stream_it = [], on_device()
-        for nxt in stream_it:
-            ahead.append(nxt)
-            if len(ahead) > 2:
-                break
-        while ahead:
-            it, imgs, depth, caps, lens = ahead.pop(0)
-            nxt = next(stream_it, None)
-            if nxt is not None:
-                ahead.append(nxt)
+        # the frozen RGB encoder runs ahead of the step on side streams (engine.look_ahead, engine.prefetch_features)
+        for (it, imgs, depth, caps, lens), following in look_ahead(on_device()):
             # the reference draws a fresh torch.rand(bs, 196) per decode step of every iteration (attention.py:17); here
             # the T draws of one iteration come as one [T,B,196] tensor from a stream keyed by (epoch, iteration, rank)
             u = _gumbel_draws(max(lens) - 1, len(lens), epoch, it, rank, int(ext)).to(dev) if hard else None
             loss = trainer.train_step(imgs, depth, caps, lens, gumbel_u=u, temp=float(temp),
-                                      next_imgs=[a[1] for a in ahead[:2]])
+                                      next_imgs=[f[1] for f in following])
             losses.append(loss)                                         # device tensors: no per-iteration host sync
             window.append(loss)
             if len(window) > config.moving_avg:

@@ -65,9 +65,7 @@ def nic_scst_step(decoder, optimizer, features, word_to_id, reward_fn, captions=
                                         n_candidates, max_length, float(length_penalty))
     else:
         ids = torch.as_tensor(captions).to(features.device)
-    ended = ids == id_end
-    lengths = torch.where(ended.any(-1), ended.int().argmax(-1) + 1, torch.full_like(ids[..., 0], ids.shape[-1])).to(torch.int32)
-    rewards = reward_fn(ids, lengths)
+    rewards = reward_fn(ids, native.caption_lengths(ids, id_end))
     optimizer.zero_grad(set_to_none=True)
     logprobs, lengths = decoder.caption_logprobs(features, ids, word_to_id)
     loss = losses.self_critical_loss(logprobs, lengths, rewards, baseline)

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
 
+import itertools
 import os
 
 import torch
@@ -106,6 +107,46 @@ def exchange_gradients(flat_grad: torch.Tensor, spans, group, between=None) -> N
         w.wait()
 
 
+def look_ahead(batches, depth: int = 2):
+    """Yields (batch, following) over `batches`, `following` being the list of at most `depth` batches behind it: what a step takes
+    and what it announces as next_imgs.  depth + 1 batches are pulled before the first one is handed out and one more before each
+    is, so whatever device work the iterator enqueues per batch (uploads, the DPT front-end) stays that far ahead of the steps.
+    (`depth` is where the look-ahead would be made to follow the trainer's prefetch_depth.)"""
+    it = iter(batches)
+    ahead = list(itertools.islice(it, depth + 1))
+    while ahead:
+        batch = ahead.pop(0)
+        ahead.extend(itertools.islice(it, 1))
+        yield batch, ahead[:depth]
+
+
+def baseline_mode(baseline, B: int, S: int, named: Sequence[str], two_captions: str) -> int:
+    """Baseline mode of dic_scst_loss: 0 none | 1 others | 2 per caption (a tensor [B,S]) | 3 per image (a tensor [B], or a name
+    other than "others").  named: the names the caller takes; two_captions: its wording of what "others" needs."""
+    choice = ", ".join(repr(n) for n in named)
+    if isinstance(baseline, str):
+        if baseline not in named:
+            raise DicError(f"scst_step: baseline must be {choice}, a tensor [B,S] or [B], or None, got {baseline!r}")
+        if baseline == "others" and S < 2:
+            raise DicError("scst_step: the 'others' baseline is the mean reward of the image's other captions and needs "
+                           f"{two_captions}, got {S}")
+        return 1 if baseline == "others" else 3
+    if baseline is None:
+        return 0
+    if torch.is_tensor(baseline) and tuple(baseline.shape) in ((B, S), (B,)):
+        return 3 if baseline.dim() == 1 else 2
+    raise DicError(f"scst_step: baseline must be {choice}, a tensor [{B},{S}] or [{B}], or None, got "
+                   f"{tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__}")
+
+
+def reward_tensor(rewards, B: int, S: int, device) -> torch.Tensor:
+    """What a step's reward_fn returned, checked to be [B,S] and made a contiguous fp32 device tensor outside autograd."""
+    if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
+        raise DicError(f"scst_step: reward_fn must return a tensor [B,S] = [{B}, {S}], got "
+                       f"{tuple(rewards.shape) if torch.is_tensor(rewards) else type(rewards).__name__}")
+    return rewards.detach().to(device, torch.float32).contiguous()
+
+
 SCST_MAX_CELLS = 491520      # B * S * T: the limit of dic_decoder_states_fwd / _bwd and dic_scst_loss (include/dic.h)
 
 
@@ -126,20 +167,7 @@ def scst_arguments(hard: bool, B: int, n_samples: int, max_length: int, baseline
         raise DicError(f"scst_step: max_length={T} is outside 1 .. 64")
     if B < 1 or B * S * T > SCST_MAX_CELLS:
         raise DicError(f"scst_step: B*n_samples*max_length = {B * S * T} is outside 1 .. {SCST_MAX_CELLS} (the states route's limit)")
-    if isinstance(baseline, str):
-        if baseline not in ("others", "greedy"):
-            raise DicError(f"scst_step: baseline must be 'others', 'greedy', a tensor [B,S] or [B], or None, got {baseline!r}")
-        if baseline == "others" and S < 2:
-            raise DicError("scst_step: the 'others' baseline is the mean reward of the image's other captions and needs "
-                           f"n_samples >= 2, got {S}")
-        mode = 1 if baseline == "others" else 3
-    elif baseline is None:
-        mode = 0
-    elif torch.is_tensor(baseline) and tuple(baseline.shape) in ((B, S), (B,)):
-        mode = 3 if baseline.dim() == 1 else 2
-    else:
-        raise DicError(f"scst_step: baseline must be 'others', 'greedy', a tensor [{B},{S}] or [{B}], or None, got "
-                       f"{tuple(baseline.shape) if torch.is_tensor(baseline) else type(baseline).__name__}")
+    mode = baseline_mode(baseline, B, S, ("others", "greedy"), "n_samples >= 2")
     if uniform_u is not None and tuple(uniform_u.shape) != (T, B * S):
         raise DicError(f"scst_step: uniform_u must be [max_length, B*n_samples] = [{T}, {B * S}], got {tuple(uniform_u.shape)}")
     if drop_mult is not None and tuple(drop_mult.shape) != (B * S, T, native.D_HID):
@@ -158,7 +186,7 @@ class _PrefetchSlot:
     """One frozen-ResNet forward in flight: own HIP stream, own runner (shared weights, own workspace, BatchNorm
     running-statistic pointers redirected to `delta`), own feature buffer, static input buffer and captured graphs."""
 
-    def __init__(self, tr: "CaptionTrainer"):
+    def __init__(self, tr: "BackboneTrainer"):
         self.tr = tr
         self.stream = torch.cuda.Stream(device=tr.device)
         self.delta = torch.zeros_like(tr.rn_stats)            # momentum * batch statistic of the forward in flight
@@ -221,42 +249,22 @@ class _PrefetchSlot:
         return done
 
 
-class CaptionTrainer:
-    """Owns weights, optimiser state and workspaces of one rank and runs fused train steps."""
+class BackboneTrainer:
+    """What every trainer of one rank has around its decoder: the frozen ResNet-152 feature pipeline (forwards of the next batches
+    on side streams, captured graphs, BatchNorm running statistics applied in batch order, the f16x2 overflow guard), the dropout
+    generator's state, stage timing, and the guarded AdamW on `self.flat` - the FlatParams of whatever the subclass trains, which
+    the subclass builds once the base is set up."""
 
-    def __init__(self, vocab: int, device: str = "cuda:0", seed: int = 123, lr: float = 1e-3, hard: bool = False,
-                 resnet_layers: Sequence[int] = (3, 8, 36, 3), dropout: float = 0.5, lam: float = 0.7,
-                 decoder_init: Optional[Dict[str, torch.Tensor]] = None,
-                 depth_init: Optional[Dict[str, torch.Tensor]] = None,
-                 depth_state: Optional[Dict[str, torch.Tensor]] = None,
-                 resnet_init: Optional[Dict[str, torch.Tensor]] = None,
-                 process_group=None, conv_mode: Optional[str] = None, use_depth: bool = True):
-        """conv_mode: arithmetic of the frozen ResNet-152's convolutions - None = native.DEFAULT_CONV_MODE ("f16x2", the mode
-        bench.py measures); "bf16x3" / "fp32" are the exact-operand alternatives (no range limit, ~1.4x / ~2.3x the step time)."""
+    def __init__(self, vocab: int, device: str, seed: int, lr: float, dropout: float, resnet_layers: Sequence[int],
+                 resnet_init: Optional[Dict[str, torch.Tensor]], conv_mode: Optional[str], process_group=None):
         if not torch.cuda.is_available():
             raise DicError("CaptionTrainer needs a GPU: the product path has no CPU fallback")
         self.device = torch.device(device)
-        self.vocab, self.lr, self.hard, self.p_drop, self.lam = vocab, lr, hard, dropout, lam
+        self.vocab, self.lr, self.p_drop = vocab, lr, dropout
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
-        self.use_depth = use_depth     # False: base-soft / base-hard (base_train.py): no depth encoder, decoder-only optimiser
-        dec = decoder_init if decoder_init is not None else syn.decoder_weights(vocab, seed=seed)
-        if use_depth and depth_init is None:
-            depth_init, depth_state = syn.depth_encoder_weights(seed=seed + 1)
         rn = resnet_init if resnet_init is not None else syn.resnet152_weights(seed=seed + 2, layers=resnet_layers)
-        self.dec_names = [k for k, _ in native.DECODER_FIELDS]
-        self.enc_names = [k for k, _ in native.DEPTH_FIELDS] if use_depth else []
-        merged = {("decoder." + k): dec[k] for k in self.dec_names}
-        merged.update({("depth_encoder." + k): depth_init[k] for k in self.enc_names})
-        self.flat = FlatParams(merged, self.device)
-        self.dec_w = {k: self.flat.view(self.flat.data, "decoder." + k) for k in self.dec_names}
-        self.enc_w = {k: self.flat.view(self.flat.data, "depth_encoder." + k) for k in self.enc_names}
-        self.dec_g = {k: self.flat.view(self.flat.grad, "decoder." + k) for k in self.dec_names}
-        self.enc_g = {k: self.flat.view(self.flat.grad, "depth_encoder." + k) for k in self.enc_names}
-        self.dec_span = self.flat.span(["decoder." + k for k in self.dec_names])
-        self.enc_span = self.flat.span(["depth_encoder." + k for k in self.enc_names]) if use_depth else None
-        self.enc_state = {k: v.to(self.device).contiguous() for k, v in depth_state.items()} if use_depth else {}
         self.rn_w = {k: v.to(self.device).contiguous() for k, v in rn.items()}
         # every BatchNorm running statistic of the frozen ResNet lives in ONE flat buffer (the dict holds views), so that
         # the update of a whole batch is one dic_bn_ema_update launch (see _PrefetchSlot)
@@ -279,16 +287,11 @@ class CaptionTrainer:
         self._guard_pending: List[tuple] = []      # (ring slot, event, step number) of copies in flight
         self._guard_slot = 0
         self.step_count = 0
-        self.depth_fwd_count = 0       # train-mode depth-encoder forwards (= BatchNorm num_batches_tracked)
         self.rng_offset = 0
         self.seed = seed
-        self.sample_count = 0          # scst_step calls that drew their own uniforms: part of the sampling generator's key
-        self._expand_idx = {}          # B -> int64 [B*196] row indices of the 49 -> 196 cell replication (scst_step)
         # every rank draws its own dropout masks: the rank is mixed into the Philox key (same key on all ranks would
         # apply one mask pattern to every shard of the global batch)
         self.drop_seed = (seed + 0x9E3779B97F4A7C15 * self.rank) & 0xFFFFFFFFFFFFFFFF
-        self.dec_ws: Optional[torch.Tensor] = None
-        self.enc_ws: Optional[torch.Tensor] = None
         self.last = {}
         # Software pipelining of the frozen RGB encoder: the features of the NEXT batches are computed on side streams while
         # the rest of the current step runs (prefetch_features).  Up to `prefetch_depth` forwards are in flight, each on its own
@@ -304,10 +307,6 @@ class CaptionTrainer:
         # each forward is ~620 launches (9 ms of host enqueue); it is captured once per (batch shape, slot) into a hipGraph
         # and replayed (0.2 ms).  DIC_RESNET_GRAPH=0 keeps eager launches.
         self.use_graph = os.environ.get("DIC_RESNET_GRAPH", "1") != "0"
-        # compact 49-cell layout (quirk Q3): at 224x224 both encoders end in a 7x7 map that AdaptiveAvgPool2d(14) only
-        # replicates 2x2, so the soft-attention decoder runs on the 49 distinct cells (same logits / alphas / gradients,
-        # 4x less feature traffic).  DIC_COMPACT_CELLS=0 keeps the reference's 196-cell evaluation everywhere.
-        self.compact_ok = os.environ.get("DIC_COMPACT_CELLS", "1") != "0"
         self.keep_outputs = False      # True: keep logits intact (loss gradient not written in place)
         self.timing = False            # True: record stage-boundary events on the current stream
         self.marks = []
@@ -378,7 +377,7 @@ class CaptionTrainer:
             self.prefetch_dropped += pos
             import warnings
             warnings.warn(f"CaptionTrainer: {pos} prefetched ResNet forward(s) discarded - train_step received a batch that "
-                          "was not the next announced one (next_imgs)", RuntimeWarning, stacklevel=3)
+                          "was not the next announced one (next_imgs)", RuntimeWarning, stacklevel=4)      # (the caller of the step)
             self.queue = self.queue[pos:]
             if not self.queue:
                 return None
@@ -452,7 +451,98 @@ class CaptionTrainer:
         torch.cuda.current_stream().synchronize()
         self._guard_poll(block=True)
 
-    # ---- pieces -----------------------------------------------------------------------------
+    # ---- pieces of a step ---------------------------------------------------------------------
+    def _begin_step(self) -> None:
+        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
+        self.marks = []
+        self._mark("start")
+
+    def _open_step(self, imgs: torch.Tensor, next_imgs, compact_of) -> torch.Tensor:
+        """The opening of every step that runs the frozen ResNet: the feature map of `imgs` - the prefetched one if its forward is
+        the oldest in flight, else an eager train-mode forward (depth_train.py:179) - with its guard word taken, and the forwards
+        of `next_imgs` launched.  compact_of(imgs) -> bool is the step's cell layout rule for a batch; a prefetched map comes in
+        the layout it was launched with.
+        next_imgs: one upcoming batch, or the list of the next `prefetch_depth` batches in order."""
+        self._begin_step()
+        feats = self._take_prefetched(imgs)
+        if feats is None:
+            feats = self._resnet_eager(imgs, True, compact_of(imgs))
+            self._guard_take(self.resnet)
+        if next_imgs is not None:
+            upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
+            for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
+                if k >= len(self.queue):        # (entry k of the queue is batch i+1+k when the caller keeps this order)
+                    self.prefetch_features(nxt, compact=compact_of(nxt))
+        self._mark("resnet152_fwd")
+        return feats
+
+    def _draw_dropout(self, rows: int, T: int) -> Optional[torch.Tensor]:
+        """Dropout multipliers [rows, T, 128] of the decoder's hidden states at the trainer's rate (None at rate 0)."""
+        if not self.p_drop > 0:
+            return None
+        mask, self.rng_offset = native.dropout_draw((rows, T, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset,
+                                                    self.device)
+        return mask
+
+    def apply_update(self) -> None:
+        """AdamW on the flat buffer with whatever self.flat.grad holds (depth_train.py:221)."""
+        self.step_count += 1
+        native.adamw_step(self.flat.data, self.flat.grad, self.flat.exp_avg, self.flat.exp_avg_sq, self.step_count,
+                          lr=self.lr, skip_if_raised=self.guard)
+        self._guard_publish()
+
+    def state_dicts(self):
+        """{"encoder": the frozen ResNet's state_dict contents}; BatchNorm layers carry `num_batches_tracked` = train-mode
+        forwards (quirk Q1)."""
+        rgb = {k: v.detach().clone() for k, v in self.rn_w.items()}
+        for k in list(rgb):
+            if k.endswith("running_mean"):
+                rgb[k[:-len("running_mean")] + "num_batches_tracked"] = torch.tensor(self.resnet.train_forwards,
+                                                                                   dtype=torch.int64, device=self.device)
+        return {"encoder": rgb}
+
+
+class CaptionTrainer(BackboneTrainer):
+    """Owns weights, optimiser state and workspaces of one rank and runs fused train steps."""
+
+    def __init__(self, vocab: int, device: str = "cuda:0", seed: int = 123, lr: float = 1e-3, hard: bool = False,
+                 resnet_layers: Sequence[int] = (3, 8, 36, 3), dropout: float = 0.5, lam: float = 0.7,
+                 decoder_init: Optional[Dict[str, torch.Tensor]] = None,
+                 depth_init: Optional[Dict[str, torch.Tensor]] = None,
+                 depth_state: Optional[Dict[str, torch.Tensor]] = None,
+                 resnet_init: Optional[Dict[str, torch.Tensor]] = None,
+                 process_group=None, conv_mode: Optional[str] = None, use_depth: bool = True):
+        """conv_mode: arithmetic of the frozen ResNet-152's convolutions - None = native.DEFAULT_CONV_MODE ("f16x2", the mode
+        bench.py measures); "bf16x3" / "fp32" are the exact-operand alternatives (no range limit, ~1.4x / ~2.3x the step time)."""
+        # (synthetic weights are drawn in the order decoder, depth encoder, ResNet: the base draws the last)
+        dec = decoder_init if decoder_init is not None else syn.decoder_weights(vocab, seed=seed)
+        if use_depth and depth_init is None:
+            depth_init, depth_state = syn.depth_encoder_weights(seed=seed + 1)
+        super().__init__(vocab, device, seed, lr, dropout, resnet_layers, resnet_init, conv_mode, process_group)
+        self.hard, self.lam = hard, lam
+        self.use_depth = use_depth     # False: base-soft / base-hard (base_train.py): no depth encoder, decoder-only optimiser
+        self.dec_names = [k for k, _ in native.DECODER_FIELDS]
+        self.enc_names = [k for k, _ in native.DEPTH_FIELDS] if use_depth else []
+        merged = {("decoder." + k): dec[k] for k in self.dec_names}
+        merged.update({("depth_encoder." + k): depth_init[k] for k in self.enc_names})
+        self.flat = FlatParams(merged, self.device)
+        self.dec_w = {k: self.flat.view(self.flat.data, "decoder." + k) for k in self.dec_names}
+        self.enc_w = {k: self.flat.view(self.flat.data, "depth_encoder." + k) for k in self.enc_names}
+        self.dec_g = {k: self.flat.view(self.flat.grad, "decoder." + k) for k in self.dec_names}
+        self.enc_g = {k: self.flat.view(self.flat.grad, "depth_encoder." + k) for k in self.enc_names}
+        self.dec_span = self.flat.span(["decoder." + k for k in self.dec_names])
+        self.enc_span = self.flat.span(["depth_encoder." + k for k in self.enc_names]) if use_depth else None
+        self.enc_state = {k: v.to(self.device).contiguous() for k, v in depth_state.items()} if use_depth else {}
+        self.depth_fwd_count = 0       # train-mode depth-encoder forwards (= BatchNorm num_batches_tracked)
+        self.sample_count = 0          # scst_step calls that drew their own uniforms: part of the sampling generator's key
+        self._expand_idx = {}          # B -> int64 [B*196] row indices of the 49 -> 196 cell replication (scst_step)
+        self.dec_ws: Optional[torch.Tensor] = None
+        self.enc_ws: Optional[torch.Tensor] = None
+        # compact 49-cell layout (quirk Q3): at 224x224 both encoders end in a 7x7 map that AdaptiveAvgPool2d(14) only
+        # replicates 2x2, so the soft-attention decoder runs on the 49 distinct cells (same logits / alphas / gradients,
+        # 4x less feature traffic).  DIC_COMPACT_CELLS=0 keeps the reference's 196-cell evaluation everywhere.
+        self.compact_ok = os.environ.get("DIC_COMPACT_CELLS", "1") != "0"
+
     def _compact(self, imgs, depth_map) -> bool:
         """Use the 49-cell layout for this batch? (soft attention, 224x224 RGB and depth inputs)"""
         if self.use_depth and (depth_map is None or tuple(depth_map.shape[-2:]) != (224, 224)):
@@ -469,6 +559,40 @@ class CaptionTrainer:
         self.enc_ws = dtape.workspace
         self.depth_fwd_count += int(train)
         return feats, fdep, dtape
+
+    def _open_step_on(self, precomputed_features: torch.Tensor) -> torch.Tensor:
+        """The opening of a decoder/depth-encoder-only step (tests): the map is taken as given, the guard word cleared."""
+        self._begin_step()
+        self._guard_take(None)
+        return precomputed_features
+
+    def _depth_forward(self, depth_map: Optional[torch.Tensor], compact: bool):
+        """Train-mode depth-encoder forward of a step (depth_train.py:204-206): (depth features, tape), (None, None) without the
+        depth branch."""
+        fdep = dtape = None
+        if self.use_depth:
+            fdep, dtape = native.depth_encoder_forward(self.enc_w, self.enc_state, depth_map.detach(), True,
+                                                       workspace=self.enc_ws, compact=compact)
+            self.enc_ws = dtape.workspace
+            self.depth_fwd_count += 1
+            self.guard.bitwise_or_(native.depth_status_word(dtape))      # the depth encoder's own guard word joins the step's (one 4-byte op)
+        self._mark("depth_encoder_fwd")
+        return fdep, dtape
+
+    def _finish_step(self, dtape, dfeat, apply_update: bool) -> None:
+        """Behind the decoder's backward: the gradient exchange with the depth-encoder backward inside it, then AdamW."""
+        if not self.use_depth:       # base-soft / base-hard: the decoder bucket is everything there is (base_train.py:115)
+            if self.world > 1:
+                exchange_gradients(self.flat.grad, [self.dec_span], self.pg)
+        elif self.world > 1:   # decoder bucket goes out while the depth-encoder backward still runs
+            exchange_gradients(self.flat.grad, [self.dec_span, self.enc_span], self.pg,
+                               between=lambda: native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g))
+        else:
+            native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g)
+        self._mark("depth_encoder_bwd+allreduce")
+        if apply_update:
+            self.apply_update()
+        self._mark("adamw")
 
     def train_step(self, imgs: torch.Tensor, depth_map: Optional[torch.Tensor], captions: torch.Tensor, lengths: Sequence[int],
                    drop_mult: Optional[torch.Tensor] = None, gumbel_u: Optional[torch.Tensor] = None,
@@ -488,39 +612,11 @@ class CaptionTrainer:
           reproduce an N-rank step shard by shard (tests)."""
         B = imgs.shape[0] if imgs is not None else precomputed_features.shape[0]
         tmax = max(lengths) - 1
-        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
-        self.marks = []
-        self._mark("start")
-        if precomputed_features is None:
-            compact = self._compact(imgs, depth_map)
-            feats = self._take_prefetched(imgs)
-            if feats is not None:
-                compact = feats.shape[1] == native.L_COMPACT
-            else:
-                feats = self._resnet_eager(imgs, True, compact)                             # depth_train.py:179
-                self._guard_take(self.resnet)
-            if next_imgs is not None:       # one upcoming batch, or the list of the next `prefetch_depth` batches in order
-                upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
-                for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
-                    if k >= len(self.queue):        # (entry k of the queue is batch i+1+k when the caller keeps this order)
-                        self.prefetch_features(nxt, compact=self._compact(nxt, depth_map))
-            self._mark("resnet152_fwd")
-        else:                                       # decoder/depth-encoder-only step (tests)
-            feats = precomputed_features
-            self._guard_take(None)
-            compact = feats.shape[1] == native.L_COMPACT
-        fdep = dtape = None
-        if self.use_depth:
-            fdep, dtape = native.depth_encoder_forward(self.enc_w, self.enc_state, depth_map.detach(), True,
-                                                       workspace=self.enc_ws, compact=compact)   # :204-206
-            self.enc_ws = dtape.workspace
-            self.depth_fwd_count += 1
-            self.guard.bitwise_or_(native.depth_status_word(dtape))      # the depth encoder's own guard word joins the step's (one 4-byte op)
-        self._mark("depth_encoder_fwd")
-        if drop_mult is None and self.p_drop > 0:
-            drop_mult = native.dropout_mask((B, tmax, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset,
-                                            self.device)
-            self.rng_offset += B * tmax * native.D_HID // 4 + 1
+        feats = (self._open_step(imgs, next_imgs, lambda x: self._compact(x, depth_map)) if precomputed_features is None
+                 else self._open_step_on(precomputed_features))
+        fdep, dtape = self._depth_forward(depth_map, compact=feats.shape[1] == native.L_COMPACT)
+        if drop_mult is None:
+            drop_mult = self._draw_dropout(B, tmax)
         mode = 1 if self.hard else 0
         logits, alphas, tape = native.decoder_forward(self.dec_w, feats, fdep, captions, lengths, drop_mult, mode=mode,
                                                       gumbel_u=gumbel_u, temp=temp, workspace=self.dec_ws)
@@ -535,18 +631,7 @@ class CaptionTrainer:
         self._mark("loss")
         _, dfeat = native.decoder_backward(tape, dlogits, dalphas, grads=self.dec_g)         # :219
         self._mark("decoder_bwd")
-        if not self.use_depth:       # base-soft / base-hard: the decoder bucket is everything there is (base_train.py:115)
-            if self.world > 1:
-                exchange_gradients(self.flat.grad, [self.dec_span], self.pg)
-        elif self.world > 1:   # decoder bucket goes out while the depth-encoder backward still runs
-            exchange_gradients(self.flat.grad, [self.dec_span, self.enc_span], self.pg,
-                               between=lambda: native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g))
-        else:
-            native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g)
-        self._mark("depth_encoder_bwd+allreduce")
-        if apply_update:
-            self.apply_update()
-        self._mark("adamw")
+        self._finish_step(dtape, dfeat, apply_update)
         self.last = {"logits": logits, "alphas": alphas, "features": feats, "depth_features": fdep}
         if self.keep_outputs:
             self.last["decoder_tape"] = tape           # parity tests: native.decoder_attention_relu_mask(tape)
@@ -595,33 +680,11 @@ class CaptionTrainer:
             raise DicError("scst_step: this trainer has a depth encoder: depth_map is required")
         S, T = int(n_samples), int(max_length)
         R = B * S
-        self._guard_poll()              # (non-blocking) an earlier step tripped the f16x2 overflow guard -> DicError
-        self.marks = []
-        self._mark("start")
-        if precomputed_features is None:
-            feats = self._take_prefetched(imgs)
-            if feats is None:
-                feats = self._resnet_eager(imgs, True, False)
-                self._guard_take(self.resnet)
-            if next_imgs is not None:
-                upcoming = list(next_imgs) if isinstance(next_imgs, (list, tuple)) else [next_imgs]
-                for k, nxt in enumerate(upcoming[:self.prefetch_depth]):
-                    if k >= len(self.queue):
-                        self.prefetch_features(nxt, compact=False)
-            self._mark("resnet152_fwd")
-        else:
-            feats = precomputed_features
-            self._guard_take(None)
+        feats = (self._open_step(imgs, next_imgs, lambda x: False) if precomputed_features is None
+                 else self._open_step_on(precomputed_features))
         if feats.shape[1] == native.L_COMPACT:
             feats = self._expand_cells(feats)
-        fdep = dtape = None
-        if self.use_depth:
-            fdep, dtape = native.depth_encoder_forward(self.enc_w, self.enc_state, depth_map.detach(), True,
-                                                       workspace=self.enc_ws, compact=False)
-            self.enc_ws = dtape.workspace
-            self.depth_fwd_count += 1
-            self.guard.bitwise_or_(native.depth_status_word(dtape))
-        self._mark("depth_encoder_fwd")
+        fdep, dtape = self._depth_forward(depth_map, compact=False)
         if uniform_u is None:
             gen = torch.Generator(self.device)
             gen.manual_seed((((self.seed * 1000003 + self.sample_count) * 64 + self.rank) ^ 0x5C57) & 0x7FFFFFFFFFFFFFFF)
@@ -641,22 +704,16 @@ class CaptionTrainer:
         base = None
         if isinstance(baseline, str) and baseline == "greedy":
             g_ids, _ = native.decoder_greedy(self.dec_w, feats, fdep, id_start, T)
-            ended = g_ids == int(id_end)
-            g_len = torch.where(ended.any(1), ended.int().argmax(1) + 1, torch.full_like(g_ids[:, 0], T)).to(torch.int32)
-            base = reward_fn(g_ids.unsqueeze(1), g_len.unsqueeze(1))
+            base = reward_fn(g_ids.unsqueeze(1), native.caption_lengths(g_ids, id_end).unsqueeze(1))
             if tuple(base.shape) != (B, 1):
                 raise DicError(f"scst_step: reward_fn must return [B,S] = [{B}, 1] for the greedy captions, got {tuple(base.shape)}")
             base = base.detach().float().reshape(B).contiguous()
         elif torch.is_tensor(baseline):
             base = baseline.detach().to(self.device, torch.float32).contiguous()
-        if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
-            raise DicError(f"scst_step: reward_fn must return a tensor [B,S] = [{B}, {S}], got "
-                           f"{tuple(rewards.shape) if torch.is_tensor(rewards) else type(rewards).__name__}")
-        rewards = rewards.detach().to(self.device, torch.float32).contiguous()
+        rewards = reward_tensor(rewards, B, S, self.device)
         self._mark("reward")
-        if drop_mult is None and self.p_drop > 0:
-            drop_mult = native.dropout_mask((R, T, native.D_HID), self.p_drop, self.drop_seed, self.rng_offset, self.device)
-            self.rng_offset += R * T * native.D_HID // 4 + 1
+        if drop_mult is None:
+            drop_mult = self._draw_dropout(R, T)
         hidden, targets, lens, tape = native.decoder_states_forward(self.dec_w, feats, fdep, id_start, id_end, ids, drop_mult)
         logprobs, lse = native.token_logprobs(hidden.view(T * R, native.D_HID), self.dec_w["linear.weight"],
                                               self.dec_w["linear.bias"], targets.view(-1))
@@ -670,28 +727,10 @@ class CaptionTrainer:
         dfeat = native.decoder_states_backward_into(self.dec_g, tape, d_hidden.view(T, R, native.D_HID),
                                                     need_features=self.use_depth)
         self._mark("states_bwd")
-        if not self.use_depth:
-            if self.world > 1:
-                exchange_gradients(self.flat.grad, [self.dec_span], self.pg)
-        elif self.world > 1:   # decoder bucket goes out while the depth-encoder backward still runs
-            exchange_gradients(self.flat.grad, [self.dec_span, self.enc_span], self.pg,
-                               between=lambda: native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g))
-        else:
-            native.depth_encoder_backward(dtape, dfeat, grads=self.enc_g)
-        self._mark("depth_encoder_bwd+allreduce")
-        if apply_update:
-            self.apply_update()
-        self._mark("adamw")
+        self._finish_step(dtape, dfeat, apply_update)
         self.last = {"ids": ids, "lengths": lengths, "rewards": rewards, "logprobs": logprobs.view(T, B, S).permute(1, 2, 0),
                      "features": feats, "depth_features": fdep}
         return loss, rewards.mean().view(1)
-
-    def apply_update(self) -> None:
-        """AdamW on the flat buffer with whatever self.flat.grad holds (depth_train.py:221)."""
-        self.step_count += 1
-        native.adamw_step(self.flat.data, self.flat.grad, self.flat.exp_avg, self.flat.exp_avg_sq, self.step_count,
-                          lr=self.lr, skip_if_raised=self.guard)
-        self._guard_publish()
 
     @torch.no_grad()
     def eval_loss(self, imgs, depth_map, captions, lengths, gumbel_u: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -719,18 +758,13 @@ class CaptionTrainer:
         tests/golden/state_dict_keys.json): Depth_CNN_endoder registers every layer twice (`conv1.*` and
         `features.0.*`, depth_models.py:19-34 - 42 keys), BatchNorm layers carry `num_batches_tracked` (one increment per
         train-mode forward: the depth encoder's = optimiser steps taken, the frozen ResNet's = train-mode forwards, Q1)."""
-        dev = self.device
         dec = {k: v.detach().clone() for k, v in self.dec_w.items()}
-        rgb = {k: v.detach().clone() for k, v in self.rn_w.items()}
-        for k in list(rgb):
-            if k.endswith("running_mean"):
-                rgb[k[:-len("running_mean")] + "num_batches_tracked"] = torch.tensor(self.resnet.train_forwards,
-                                                                                   dtype=torch.int64, device=dev)
+        rgb = super().state_dicts()["encoder"]
         if not self.use_depth:
             return {"decoder": dec, "encoder": rgb}
         enc = {k: v.detach().clone() for k, v in self.enc_w.items()}
         enc.update({k: v.detach().clone() for k, v in self.enc_state.items()})
-        nbt = torch.tensor(self.depth_fwd_count, dtype=torch.int64, device=dev)
+        nbt = torch.tensor(self.depth_fwd_count, dtype=torch.int64, device=self.device)
         for i, (conv_idx, bn_idx) in zip((1, 2, 3), ((0, 1), (4, 5), (8, 9))):
             enc[f"bn{i}.num_batches_tracked"] = nbt.clone()
             for kind in ("weight", "bias"):

@@ -288,6 +288,22 @@ def dropout_mask(shape, p: float, seed: int, offset: int, device) -> torch.Tenso
     return out
 
 
+def dropout_advance(numel: int) -> int:
+    """Generator offsets that dic_dropout_mask consumes for `numel` multipliers (four per counter, one counter to spare)."""
+    return numel // 4 + 1
+
+
+def dropout_draw(shape, p: float, seed: int, offset: int, device):
+    """(dropout_mask of `shape` drawn at `offset`, the offset of the next draw)."""
+    return dropout_mask(shape, p, seed, offset, device), offset + dropout_advance(math.prod(shape))
+
+
+def caption_lengths(ids: torch.Tensor, id_end: int) -> torch.Tensor:
+    """int32 ids.shape[:-1]: tokens of each caption up to and including its first `id_end`, the whole row where there is none."""
+    ended = ids == int(id_end)
+    return torch.where(ended.any(-1), ended.int().argmax(-1) + 1, torch.full_like(ids[..., 0], ids.shape[-1])).to(torch.int32)
+
+
 # ---------------------------------------------------------------------------------------------
 # depth encoder (dic_depth_encoder_fwd / _bwd)
 # ---------------------------------------------------------------------------------------------

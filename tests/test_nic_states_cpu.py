@@ -49,7 +49,8 @@ def test_entry_points_are_declared_exported_and_bound(lib):
     assert [sig[k].default for k in list(sig)[4:9]] == [None, 5, 30, 0.0, "others"]
     sig = inspect.signature(nic.NicTrainer.scst_step).parameters
     assert list(sig)[:4] == ["self", "imgs", "reward_fn", "id_end"]
-    assert nic.NicTrainer.scst_step is not nic.CaptionTrainer.scst_step
+    from depth_image_captioning_pub_amd.engine import CaptionTrainer
+    assert nic.NicTrainer.scst_step is not CaptionTrainer.scst_step
     assert "not draws" in scst.nic_scst_step.__doc__ and "REINFORCE" in scst.nic_scst_step.__doc__
     assert native.NIC_STATES_GRAD_KEYS == tuple(k for k in nc.NIC_KEYS if not k.startswith("linear."))
 

@@ -1,6 +1,7 @@
 """CPU: dic_scst_loss's fp64 restatement (tests/scst_engine_common.py) against losses.self_critical_loss + autograd, every refusal
 of the entry point before a launch, the preconditions of CaptionTrainer.scst_step, and the harness / CLI plumbing of
-`--scst-epochs`.  Nothing here needs a GPU."""
+`--scst-epochs`, and the pieces the steps and the harnesses share (look-ahead, caption lengths, dropout offset, baseline mode).
+Nothing here needs a GPU."""
 import ctypes
 import inspect
 import types
@@ -191,3 +192,124 @@ def test_config_and_harness_defaults():
         depth_train.train_Cdepth_hard(0, "synthetic", config=cfg)
     with pytest.raises(_lib.DicError, match="must be >= 0"):
         depth_train.train_Cdepth_soft(0, "synthetic", config=cfg, scst_epochs=-2)
+
+
+# ---- 5. the pieces the steps and the harnesses share ----------------------------------------------------------------------------------
+def _recorded(n, events):
+    for k in range(n):
+        events.append(("pulled", k))
+        yield k
+
+
+def _written_out_loop(n):
+    """The loop the three harnesses wrote out before engine.look_window: its events and the (item, following) pairs its steps saw."""
+    events, pairs = [], []
+    stream_it = _recorded(n, events)
+    window = []
+    for nxt in stream_it:
+        window.append(nxt)
+        if len(window) > 2:
+            break
+    while window:
+        item = window.pop(0)
+        nxt = next(stream_it, None)
+        if nxt is not None:
+            window.append(nxt)
+        events.append(("yielded", item))
+        pairs.append((item, list(window[:2])))
+    return events, pairs
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 5])
+def test_look_ahead_pairs_and_pull_points(n):
+    events, pairs = [], []
+    for item, following in engine.look_ahead(_recorded(n, events)):         # depth 2, the harnesses' call
+        events.append(("yielded", item))
+        pairs.append((item, following))
+    assert pairs == [(k, list(range(k + 1, min(k + 3, n)))) for k in range(n)]
+    assert all(len(f) <= 2 for _, f in pairs) and (n == 0 or pairs[-1][1] == [])
+    # the pull points: three items fill the window, then one more is pulled after each item is taken and before it is handed out
+    # (so a fourth precedes the first yield when there is one), one pull between consecutive yields while items last, none after
+    pulls_before = [sum(1 for e in events[:events.index(("yielded", k))] if e[0] == "pulled") for k in range(n)]
+    assert pulls_before == [min(k + 4, n) for k in range(n)]
+    assert [e for e in events if e[0] == "pulled"] == [("pulled", k) for k in range(n)]
+    assert (events, pairs) == _written_out_loop(n)                          # the schedule of the loops it replaced
+    if n == 5:
+        assert events == [("pulled", 0), ("pulled", 1), ("pulled", 2), ("pulled", 3), ("yielded", 0), ("pulled", 4), ("yielded", 1),
+                          ("yielded", 2), ("yielded", 3), ("yielded", 4)]
+
+
+def test_look_ahead_other_depths_and_fresh_lists():
+    assert [(i, f) for i, f in engine.look_ahead(iter("abcd"), depth=1)] == [("a", ["b"]), ("b", ["c"]), ("c", ["d"]), ("d", [])]
+    assert [f for _, f in engine.look_ahead(range(4), depth=3)] == [[1, 2, 3], [2, 3], [3], []]
+    seen = []
+    for item, following in engine.look_ahead(range(4)):
+        following.append("scribble")                                        # the caller's list: the generator's window is its own
+        seen.append(item)
+    assert seen == [0, 1, 2, 3]
+
+
+def _lengths_by_loop(ids, id_end):
+    rows = ids.reshape(-1, ids.shape[-1]).tolist()
+    out = []
+    for row in rows:
+        n = len(row)
+        for t, tok in enumerate(row):
+            if tok == id_end:
+                n = t + 1
+                break
+        out.append(n)
+    return torch.tensor(out, dtype=torch.int32).view(ids.shape[:-1])
+
+
+def test_caption_lengths_against_a_row_loop():
+    END = 7
+    ids = torch.randint(0, 7, (3, 4, 6), generator=torch.Generator().manual_seed(3), dtype=torch.int64)      # (no END yet)
+    ids[0, 1, 0] = END                                   # at position 0
+    ids[1, 0, 2], ids[1, 0, 4] = END, END                # twice: the first counts
+    ids[2, 3, 5] = END                                   # only at the last position
+    ids[2, 0, :] = END                                   # all of them
+    got = native.caption_lengths(ids, END)
+    assert got.dtype == torch.int32 and tuple(got.shape) == (3, 4)
+    assert torch.equal(got, _lengths_by_loop(ids, END))
+    assert (int(got[0, 0]), int(got[0, 1]), int(got[1, 0]), int(got[2, 3]), int(got[2, 0])) == (6, 1, 3, 6, 1)
+    flat = ids.view(12, 6)                               # [B,T], the greedy baseline's form
+    got2 = native.caption_lengths(flat, END)
+    assert got2.dtype == torch.int32 and tuple(got2.shape) == (12,) and torch.equal(got2, got.view(-1))
+    assert torch.equal(native.caption_lengths(ids[..., :1], END), torch.ones((3, 4), dtype=torch.int32))      # T = 1
+
+
+@pytest.mark.parametrize("shape", [(0, 5, 128), (1, 1, 1), (1, 2), (3, 1, 1), (2, 3, 128), (5, 7, 128), (1, 1, 129), (3, 43)])
+def test_dropout_offset_advance(shape, monkeypatch):
+    """What a draw moves the generator's offset by: numel // 4 + 1, for element counts 0, 1, 2 and 3 mod 4 (0, 1, 2, 3, 768, 4480,
+    129, 129 elements).  The launch is stubbed out: the arithmetic around it is what is under test."""
+    n = 1
+    for s in shape:
+        n *= s
+    assert native.dropout_advance(n) == n // 4 + 1
+    calls = []
+    monkeypatch.setattr(native, "dropout_mask", lambda *a: calls.append(a) or "mask")
+    assert native.dropout_draw(shape, 0.5, 11, 1000, "cpu") == ("mask", 1000 + n // 4 + 1)
+    assert calls == [(shape, 0.5, 11, 1000, "cpu")]                        # drawn at the offset it was given
+
+
+def test_baseline_mode_is_shared_and_keeps_both_wordings():
+    from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.nic import nic_scst_arguments as chk
+    for baseline, mode in ((None, 0), ("others", 1), (torch.zeros(4, 2), 2), (torch.zeros(4), 3)):
+        assert engine.baseline_mode(baseline, 4, 2, ("others",), "x") == mode
+        assert engine.scst_arguments(False, 4, 2, 5, baseline) == mode
+        assert chk(4, 200, 197, None, 2, 5, 0.0, baseline)[0] == mode
+    with pytest.raises(_lib.DicError, match="needs n_samples >= 2, got 1"):
+        engine.scst_arguments(False, 4, 1, 5, "others")
+    with pytest.raises(_lib.DicError, match="needs at least 2 captions per image, got 1"):
+        chk(4, 200, 197, None, 1, 5, 0.0, "others")
+    with pytest.raises(_lib.DicError, match=r"baseline must be 'others', 'greedy', a tensor \[B,S\] or \[B\], or None, got 'mean'"):
+        engine.scst_arguments(False, 4, 2, 5, "mean")
+    with pytest.raises(_lib.DicError, match=r"baseline must be 'others', a tensor \[B,S\] or \[B\], or None, got 'greedy'"):
+        chk(4, 200, 197, None, 2, 5, 0.0, "greedy")
+    with pytest.raises(_lib.DicError, match=r"baseline must be 'others', a tensor \[4,2\] or \[4\], or None, got \(5,\)"):
+        chk(4, 200, 197, None, 2, 5, 0.0, torch.zeros(5))
+    with pytest.raises(_lib.DicError, match=r"must return a tensor \[B,S\] = \[4, 2\], got \(4, 3\)"):
+        engine.reward_tensor(torch.zeros(4, 3), 4, 2, "cpu")
+    r = engine.reward_tensor(torch.ones(4, 2, dtype=torch.float64, requires_grad=True).t().t(), 4, 2, "cpu")
+    assert r.dtype == torch.float32 and r.is_contiguous() and not r.requires_grad
