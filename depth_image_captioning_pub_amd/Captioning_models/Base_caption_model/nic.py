@@ -181,6 +181,36 @@ class NIC_RNNDecoder(nn.Module):
                     lengths.cpu().numpy().astype(np.int32))
         return ids[:, 0].cpu().numpy().astype(np.int64)
 
+    # ---- stochastic decoding (no counterpart in the reference; semantics: include/dic.h).  `sample` stays greedy ----
+    @torch.no_grad()
+    def stochastic_sample(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                          return_all=False):
+        """Captions drawn from the model's distribution (temperature, top-k, nucleus): np.int64 [B,max_length] for n_samples == 1,
+        [B,n_samples,max_length] otherwise; positions behind the first '<end>' hold '<end>'.  The draws are
+        torch.rand((max_length, B*n_samples)) of a generator on the features' device seeded with `seed`: one seed, one set of
+        captions.  return_all=True: (ids, logprobs np.float32 - the log-probability of every drawn token under the filtered
+        distribution, 0 behind '<end>' -, lengths np.int32)."""
+        S = int(n_samples)
+        ids, logprobs, lengths = self.stochastic_sample_tensors(features, word_to_id, S, max_length, temperature, top_k, top_p, seed)
+        if S == 1:
+            ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
+        if return_all:
+            return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return ids.cpu().numpy().astype(np.int64)
+
+    @torch.no_grad()
+    def stochastic_sample_tensors(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0,
+                                  seed=0):
+        """What stochastic_sample draws, left on the device: (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length],
+        lengths int32 [B,S]) - for callers that feed the captions to another device call (scst.nic_scst_sample_step)."""
+        features = _contig(features.detach())
+        S = int(n_samples)
+        gen = torch.Generator(features.device).manual_seed(int(seed))
+        u = torch.rand((max_length, features.shape[0] * max(S, 1)), generator=gen, device=features.device)
+        return native.nic_sample(self._weights(), features, word_to_id["<end>"], S, u, max_length, float(temperature), int(top_k),
+                                 float(top_p))
+
     # ---- scoring given captions (no counterpart in the reference; semantics: include/dic.h, DESIGN.md 5.20) -------------------------
     @torch.no_grad()
     def score_captions(self, features, captions, word_to_id, return_all=False):
@@ -233,15 +263,32 @@ NIC_STATES_MAX_CELLS = 393216      # B * S * T: DIC_NIC_STATES_MAX_M of include/
 
 
 def nic_scst_arguments(B: int, vocab: int, id_end, captions, n_candidates, max_length, length_penalty, baseline, reward_fn=None,
-                       drop_mult=None):
+                       drop_mult=None, *, sample: bool = False, temperature=1.0, top_k=0, top_p=1.0, uniform_u=None):
     """The argument checks of NicTrainer.scst_step / scst_step_on_map, made before anything is launched (no device needed), in the
     spirit of engine.scst_arguments.  Returns (baseline mode of dic_scst_loss: 0 none | 1 others | 2 per caption | 3 per image,
-    S, T) - S and T from `captions` [B,S,T] when given, else n_candidates and max_length."""
+    S, T) - S and T from `captions` [B,S,T] when given, else n_candidates and max_length.  sample=True: the candidates are
+    n_candidates draws of dic_nic_sample with (temperature, top_k, top_p) and the draws uniform_u [max_length, B*n_candidates]."""
     if reward_fn is not None and not callable(reward_fn):
         raise DicError("scst_step: reward_fn must be callable: reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S]")
     if not 0 <= int(id_end) < int(vocab):
         raise DicError(f"scst_step: id_end={id_end} is outside the vocabulary [0, {vocab})")
-    if captions is not None:
+    if sample and captions is not None:
+        raise DicError("scst_step: sample=True draws the candidates itself: pass captions or sample=True, not both")
+    if uniform_u is not None and not sample:
+        raise DicError("scst_step: uniform_u is the draws of sample=True; it has no meaning for given or beam-search candidates")
+    if sample:
+        S, T = int(n_candidates), int(max_length)
+        t = float(temperature)
+        if not (t > 0.0 and t != float("inf")):
+            raise DicError(f"scst_step: temperature={temperature} must be finite and > 0")
+        if not 0 <= int(top_k) <= int(vocab):
+            raise DicError(f"scst_step: top_k={top_k} is outside 0..V={vocab} (0: no limit)")
+        if not 0.0 < float(top_p) <= 1.0:
+            raise DicError(f"scst_step: top_p={top_p} is outside (0, 1] (1: off)")
+        if uniform_u is not None and (not torch.is_tensor(uniform_u) or tuple(uniform_u.shape) != (T, B * S)):
+            raise DicError(f"scst_step: uniform_u must be a tensor [max_length, B*n_candidates] = [{T}, {B * S}], got "
+                           f"{tuple(uniform_u.shape) if torch.is_tensor(uniform_u) else type(uniform_u).__name__}")
+    elif captions is not None:
         if not torch.is_tensor(captions) or captions.dtype != torch.int64 or captions.dim() != 3 or captions.shape[0] != B:
             raise DicError(f"scst_step: captions must be an int64 tensor [B,S,T] with B = {B}, got "
                            f"{(captions.dtype, tuple(captions.shape)) if torch.is_tensor(captions) else type(captions).__name__}")
@@ -290,6 +337,7 @@ class NicTrainer(BackboneTrainer):
         self.dec_span = (0, self.flat.total)
         self.dec_ws: Optional[torch.Tensor] = None
         self.states_ws: Optional[torch.Tensor] = None
+        self.sample_count = 0          # scst steps that drew their own uniforms: part of the sampling generator's key
 
     def _head_backward(self, pooled: torch.Tensor, dfeat: torch.Tensor) -> None:
         """dic_nic_head_bwd into encoder.linear's views of the flat gradient buffer."""
@@ -330,26 +378,41 @@ class NicTrainer(BackboneTrainer):
     # ---- self-critical step (no counterpart in the reference) ---------------------------------------------------------
     def scst_step_on_map(self, fmap: torch.Tensor, reward_fn, id_end: int, captions: Optional[torch.Tensor] = None,
                          n_candidates: int = 5, max_length: int = 30, length_penalty: float = 0.0, baseline="others",
-                         drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False):
+                         drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False, *,
+                         sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                         uniform_u: Optional[torch.Tensor] = None):
         """One self-critical step on a final feature map [B,cells,2048], on the flat buffers: head, candidate captions, rewards,
         dic_nic_states_fwd + dic_token_logprobs, dic_scst_loss, back through dic_token_logprobs_bwd, dic_nic_states_bwd and
         dic_nic_head_bwd, one guarded AdamW.  Everything is enqueued on the current stream; ids, lengths and rewards never visit
         the host.  Returns (loss, mean reward) as 1-element device tensors.
-        captions: int64 [B,S,T] candidates from any source (a sampler's draws go in here).  None: the n_candidates hypotheses of
-          dic_nic_beam (max_length steps, ranked with length_penalty) - the model's K MOST LIKELY captions, not draws from it: with
-          them the step is a risk-minimising update over an n-best list, not REINFORCE.
+        captions: int64 [B,S,T] candidates from any source.  None with sample=False: the n_candidates hypotheses of dic_nic_beam
+          (max_length steps, ranked with length_penalty) - the model's K MOST LIKELY captions, not draws from it: with them the
+          step is a risk-minimising update over an n-best list, not REINFORCE.
+        sample=True (captions must be None): the candidates are n_candidates DRAWS of dic_nic_sample (max_length steps,
+          temperature / top_k / top_p) - with them, at temperature 1 and no filter, the step is REINFORCE with the chosen baseline.
+          uniform_u: float32 [max_length, B*n_candidates] draws in [0,1); default: a device generator keyed by (seed, the number
+          of earlier calls that drew their own).
         reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S] on the device.
         baseline: "others" | a tensor [B,S] or [B] | None.  drop_mult: float32 [B*S,T,128]; default: dic_dropout_mask at the
           trainer's rate (none at rate 0 or with dropout=False), on the scored hidden states only.
         Unless keep_guard, the map is taken as given (the overflow guard word is cleared).  Single GPU, like NicTrainer."""
         B = int(fmap.shape[0])
         mode, S, T = nic_scst_arguments(B, self.vocab, id_end, captions, n_candidates, max_length, length_penalty, baseline, reward_fn,
-                                        drop_mult)
+                                        drop_mult, sample=sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                        uniform_u=uniform_u)
         if not keep_guard:
             self._guard_take(None)
         R = B * S
         pooled, feats = native.nic_head_forward(self.head_w, self.head_b, fmap)
-        if captions is None:
+        if sample:
+            if uniform_u is None:
+                gen = torch.Generator(self.device)
+                gen.manual_seed(((self.seed * 1000003 + self.sample_count) ^ 0x5C57) & 0x7FFFFFFFFFFFFFFF)
+                self.sample_count += 1
+                uniform_u = torch.rand((T, R), generator=gen, device=self.device)
+            ids, _, _ = native.nic_sample(self.dec_w, feats, int(id_end), S, uniform_u.to(self.device, torch.float32), T,
+                                          float(temperature), int(top_k), float(top_p))
+        elif captions is None:
             ids, _, _ = native.nic_beam(self.dec_w, feats, int(id_end), S, T, float(length_penalty))
         else:
             ids = _contig(captions.to(self.device))
@@ -380,14 +443,17 @@ class NicTrainer(BackboneTrainer):
         return loss, rewards.mean().view(1)
 
     def scst_step(self, imgs: torch.Tensor, reward_fn, id_end: int, captions: Optional[torch.Tensor] = None,
-                  n_candidates: int = 5, max_length: int = 30, length_penalty: float = 0.0, baseline="others", next_imgs=None):
+                  n_candidates: int = 5, max_length: int = 30, length_penalty: float = 0.0, baseline="others", next_imgs=None, *,
+                  sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  uniform_u: Optional[torch.Tensor] = None):
         """scst_step_on_map behind the frozen ResNet-152 forward of `imgs` (train-mode BatchNorm, quirk Q1; prefetching and the
-        overflow guard as in train_step)."""
+        overflow guard as in train_step).  sample=True draws the candidates with dic_nic_sample instead of taking the beam's."""
         nic_scst_arguments(int(imgs.shape[0]), self.vocab, id_end, captions, n_candidates, max_length, length_penalty, baseline,
-                           reward_fn, None)
+                           reward_fn, None, sample=sample, temperature=temperature, top_k=top_k, top_p=top_p, uniform_u=uniform_u)
         fmap = self._open_step(imgs, next_imgs, lambda x: True)
         return self.scst_step_on_map(fmap, reward_fn, id_end, captions, n_candidates, max_length, length_penalty, baseline,
-                                     keep_guard=True)
+                                     keep_guard=True, sample=sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                     uniform_u=uniform_u)
 
     @torch.no_grad()
     def eval_loss(self, imgs: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int]) -> torch.Tensor:
@@ -491,7 +557,8 @@ def evaluation_nic(useData: str = "synthetic", config=None, param_files: Optiona
     score / length^length_penalty.  Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} and writes the hypotheses to
     {save_directory_nic}/{useData}_nic_hypotheses.json.  No metric scores (nic.py:444-455: pycocoevalcap, out of scope).
     config.resnet_layers (optional, not in the reference) shrinks the backbone's block counts as in train_nic.
-    evaluation_nic_scored is the same loop with the model's log-probability of every hypothesis beside it."""
+    evaluation_nic_scored is the same loop with the model's log-probability of every hypothesis beside it, evaluation_nic_sampled
+    the one that also draws captions from the model."""
     return _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, False)
 
 
@@ -504,7 +571,23 @@ def evaluation_nic_scored(useData: str = "synthetic", config=None, param_files: 
     return _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, True)
 
 
-def _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, score):
+@torch.no_grad()
+def evaluation_nic_sampled(useData: str = "synthetic", config=None, param_files: Optional[Dict[str, List[str]]] = None,
+                           n_batches: int = 2, beam_size: int = 1, length_penalty: float = 0.0, n_samples: int = 1,
+                           temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, score: bool = False):
+    """evaluation_nic (score=True: evaluation_nic_scored) whose results also carry "samples", a list of `n_samples` caption strings
+    per image DRAWN with NIC_RNNDecoder.stochastic_sample(temperature, top_k, top_p) (dic_nic_sample), and "sample_ids" np.int64
+    [N,n_samples,30], as depth_evaluation's n_samples does; batch b is seeded with seed + b.  Hypotheses, ids and the written
+    file are those of evaluation_nic: they do not depend on the draws.  n_samples = 0 adds nothing.  (evaluation_nic's own
+    parameter list is that of the reference loop plus the beam's and stays as it is.)"""
+    if int(n_samples) < 0:
+        raise DicError(f"n_samples={n_samples!r} must be at least 0")
+    return _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, bool(score), int(n_samples),
+                           temperature, top_k, top_p, seed)
+
+
+def _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_penalty, score, n_samples=0, temperature=1.0, top_k=0,
+                    top_p=1.0, seed=0):
     from ...depth_evaluation import synthetic_vocabulary          # (that module imports this package)
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
@@ -526,7 +609,7 @@ def _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_p
     for key, (f_enc, f_dec) in param_files.items():
         encoder.load_state_dict(torch.load(f"{save_directory}/{f_enc}", weights_only=True), strict=True)      # nic.py:412-415
         decoder.load_state_dict(torch.load(f"{save_directory}/{f_dec}", weights_only=True), strict=True)
-        hypos_id, scored = [], []
+        hypos_id, scored, sample_ids = [], [], []
         for b in range(n_batches):
             feature = encoder(syn.rgb_images(config.batch_size, seed=5000 + b).to(dev))      # nic.py:426
             if int(beam_size) > 1:
@@ -535,11 +618,19 @@ def _evaluation_nic(useData, config, param_files, n_batches, beam_size, length_p
                 hypos_id.append(np.asarray(decoder.batch_sample(feature), dtype=np.int64))   # nic.py:427
             if score:
                 scored.append(decoder.score_captions(feature, hypos_id[-1], word_to_id, return_all=True)[1:])
+            if n_samples > 0:
+                drawn = decoder.stochastic_sample(feature, word_to_id, n_samples=n_samples, temperature=temperature, top_k=top_k,
+                                                  top_p=top_p, seed=int(seed) + b)
+                sample_ids.append(drawn.reshape(drawn.shape[0], n_samples, -1))
         hypos_id = np.concatenate(hypos_id)
         results[key] = {"hypotheses": nic_ids_to_captions(hypos_id, id_to_word), "ids": hypos_id}
         if score:
             results[key]["scores"] = np.concatenate([s for s, _ in scored])
             results[key]["lengths"] = np.concatenate([n for _, n in scored])
+        if n_samples > 0:
+            sample_ids = np.concatenate(sample_ids)
+            results[key]["samples"] = [nic_ids_to_captions(rows, id_to_word) for rows in sample_ids]
+            results[key]["sample_ids"] = sample_ids
     with open(os.path.join(save_directory, f"{useData}_nic_hypotheses.json"), "w") as f:
         json.dump({k: v["hypotheses"] for k, v in results.items()}, f)
     return results

@@ -13,8 +13,9 @@ metric of non-zero weight), e.g. CIDEr-D + 0.5 BLEU-4, as a device tensor as wel
 The same step on the engine's flat parameter buffers - one AdamW launch, the depth encoder trained through it, the data-parallel
 gradient exchange with a global token count - is engine.CaptionTrainer.scst_step; this module stays the route
 for nn.Module decoders and torch optimisers.  nic_scst_step is the step for the NIC baseline's decoder (dic_nic_states_fwd / _bwd,
-DESIGN.md 5.21; its engine form is NicTrainer.scst_step); it has no sampler of its own and takes its candidates as an argument or
-from the beam search.  Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
+DESIGN.md 5.21; its engine form is NicTrainer.scst_step); it takes its candidates as an argument or from the beam search, and
+nic_scst_sample_step is the same step on captions drawn with dic_nic_sample (NicTrainer.scst_step(sample=True)).
+Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
 reward_fn is the seam for any other reward."""
 from __future__ import annotations
 
@@ -47,8 +48,8 @@ def nic_scst_step(decoder, optimizer, features, word_to_id, reward_fn, captions=
                   length_penalty=0.0, baseline="others"):
     """One self-critical step of a NIC_RNNDecoder (Base_caption_model/nic.py) on candidate captions of `features` [B,300], the
     encoder head's output.
-    captions: int64 [B,S,T] candidates from any source, S <= 8 per image - a sampler's draws go in here.  None: the n_candidates
-    hypotheses of dic_nic_beam (max_length steps, ranked with length_penalty), taken under no_grad.  Beam hypotheses are the
+    captions: int64 [B,S,T] candidates from any source, S <= 8 per image - nic_scst_sample_step passes the draws of
+    dic_nic_sample in here.  None: the n_candidates hypotheses of dic_nic_beam (max_length steps, ranked with length_penalty), taken under no_grad.  Beam hypotheses are the
     model's K MOST LIKELY captions, not draws from its distribution: with them the step is a risk-minimising update over an n-best
     list (it moves probability from the worse of the likely captions to the better ones), not REINFORCE - the gradient is not an
     unbiased estimate of the expected reward's.
@@ -72,3 +73,26 @@ def nic_scst_step(decoder, optimizer, features, word_to_id, reward_fn, captions=
     loss.backward()
     optimizer.step()
     return loss.detach(), rewards.detach().float().mean()
+
+
+def nic_scst_sample_step(decoder, optimizer, features, word_to_id, reward_fn, n_candidates=5, max_length=30, baseline="others", *,
+                         temperature=1.0, top_k=0, top_p=1.0, seed=0, uniform_u=None):
+    """nic_scst_step on n_candidates captions per image DRAWN from the model (dic_nic_sample, taken under no_grad): at temperature 1
+    without top-k / top-p the step is REINFORCE with the chosen baseline - the gradient is an unbiased estimate of the expected
+    reward's - where nic_scst_step's beam hypotheses give a risk-minimising update over an n-best list.  (A function of its own:
+    nic_scst_step's parameter list stays as it is.)
+    The draws are uniform_u, float32 [max_length, B*n_candidates] in [0,1), or else those of
+    NIC_RNNDecoder.stochastic_sample(seed=seed): pass a new seed every step.
+    Returns (loss, mean reward) as 0-dim device tensors, like nic_scst_step."""
+    from .Base_caption_model.nic import nic_scst_arguments
+    nic_scst_arguments(int(features.shape[0]), int(decoder.vocab_size), word_to_id["<end>"], None, n_candidates, max_length, 0.0,
+                       baseline, reward_fn, None, sample=True, temperature=temperature, top_k=top_k, top_p=top_p, uniform_u=uniform_u)
+    if uniform_u is None:
+        ids, _, _ = decoder.stochastic_sample_tensors(features, word_to_id, n_candidates, max_length, temperature, top_k, top_p, seed)
+    else:
+        with torch.no_grad():
+            feats = features.detach()
+            ids, _, _ = native.nic_sample(decoder._weights(), feats if feats.is_contiguous() else feats.contiguous(),
+                                          word_to_id["<end>"], int(n_candidates), uniform_u.to(features.device, torch.float32),
+                                          int(max_length), float(temperature), int(top_k), float(top_p))
+    return nic_scst_step(decoder, optimizer, features, word_to_id, reward_fn, captions=ids, baseline=baseline)

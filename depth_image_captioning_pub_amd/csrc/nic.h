@@ -1,7 +1,8 @@
 // NIC / Show-and-Tell baseline (Base_caption_model/nic.py): encoder head, stacked two-layer LSTM over packed ragged sequences
-// (teacher-forced forward, BPTT backward), greedy and beam-search decode, scoring of given captions and its differentiable form.
-// Semantics: include/dic.h; mapping and measurements: DESIGN.md 5.7 (training, greedy), 5.8 (beam search), 5.20 (scoring) and 5.21
-// (training through the scores).
+// (teacher-forced forward, BPTT backward), greedy, beam-search and stochastic decode, scoring of given captions and its
+// differentiable form.
+// Semantics: include/dic.h; mapping and measurements: DESIGN.md 5.7 (training, greedy), 5.8 (beam search), 5.20 (scoring), 5.21
+// (training through the scores) and 5.22 (sampling).
 // One translation unit per route, each with its kernels, carves and C ABI entry points; this header holds only what more than one
 // of them uses:
 //   nic.hip         what the routes share: weight packing and bias sums (nic_step_setup, nic_bwd_setup), the tail of both
@@ -9,6 +10,8 @@
 //   nic_train.hip   the packed teacher-forced route: nic_lstm2_seq_fwd / nic_lstm2_seq_bwd, one launch each for the whole time
 //                   loop; dic_nic_workspace_bytes, dic_nic_fwd, dic_nic_bwd, dic_nic_pack_targets
 //   nic_decode.hip  greedy and beam-search decode, one step kernel per token (the selection kernels: beam.h / beam.hip)
+//   nic_sample.hip  stochastic decode (dic_nic_sample): the greedy step over rows b*S + s that skips finished rows, one step kernel
+//                   per token (the draw: sample.h / sample.hip)
 //   nic_states.hip  scoring of given captions (dic_nic_score) and training through the scores (dic_nic_states_fwd / _bwd) over
 //                   fixed-stride rows r*T + t (the fused projection + log-sum-exp: score.h / score.hip)
 #pragma once

@@ -1208,6 +1208,30 @@ def nic_score(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: 
     return logprobs, scores, lengths
 
 
+def nic_sample(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, n_samples: int, uniform_u: torch.Tensor,
+               max_length: int = 30, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    """dic_nic_sample: `n_samples` captions per image drawn from the NIC decoder's distribution, on the device (semantics:
+    include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1) - the draws are an input.
+    Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S])."""
+    lib = _load()
+    f, B = _nic_features(features)
+    wp, keep = nic_ptrs(weights)
+    vocab = int(weights["linear.weight"].shape[0])
+    S, T = int(n_samples), int(max_length)
+    ss, tt = max(S, 1), max(T, 1)
+    u = _dev(uniform_u, "uniform_u")
+    if tuple(u.shape) != (T, B * ss):
+        raise _lib.DicError(f"nic_sample: uniform_u must be [max_length, B*n_samples] = [{T}, {B * ss}], got {tuple(u.shape)}")
+    ws = _workspace_out(lib.dic_nic_sample_sizes, f.device, B, S, T, vocab)
+    ids = torch.empty((B, ss, tt), dtype=torch.int64, device=f.device)
+    logprobs = torch.empty((B, ss, tt), dtype=torch.float32, device=f.device)
+    lengths = torch.empty((B, ss), dtype=torch.int32, device=f.device)
+    rc = lib.dic_nic_sample(C.byref(wp), vocab, ptr(f), B, S, int(id_end), T, float(temperature), int(top_k), float(top_p), ptr(u),
+                            ptr(ids), ptr(logprobs), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_sample")
+    return ids, logprobs, lengths
+
+
 # the 9 NIC decoder gradients dic_nic_states_bwd writes (linear.* come from token_logprobs_bwd)
 NIC_STATES_GRAD_KEYS = tuple(k for k, _ in NIC_FIELDS if not k.startswith("linear."))
 

@@ -562,6 +562,38 @@ int dic_nic_states_bwd(const dic_nic_weights* w, int V, int B, int S, long long 
                        const float* drop_mult, const float* d_hidden, const dic_nic_grads* g, float* d_features,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* stochastic decoding for the NIC baseline: S captions per image DRAWN from the model's distribution, with temperature, top-k and
+ *   nucleus (top-p) filtering and the log-probability of every drawn token - the NIC counterpart of dic_decoder_sample.  There is
+ *   no reference implementation; this comment is the specification.
+ *   Rows and start: row r = b*S + s is draw s of image b, 1 <= S <= 8.  features float [B,300], the output of the encoder head.
+ *     There is no start token (NIC has none, so there is no id_start): the step-0 input of all S rows of image b is features[b]; h
+ *     and c of both layers start at zero; exactly max_length = T steps.
+ *   One step of a live row is the body of dic_nic_greedy up to logits = linear(h_top) - both cells, gate order i, f, g, o,
+ *     b_ih + b_hh, no dropout, the products summed in the greedy step's order - and then the draw of dic_decoder_sample, word for
+ *     word ("One step of a live row, in fp32" in its comment above: z = logits / temperature, top-k and nucleus thresholds that
+ *     keep ties, inverse CDF in vocabulary index order against u * Z, the last kept token when rounding leaves none or u >= 1,
+ *     out_logprobs[r,t] = z_v - max z - log Z).  The next input is embed[token], clamped into the vocabulary like every token input.
+ *   Draws are an input (quirk Q6): uniform_u float [T, B*S] on the device; row r consumes u[t, r] while it is live; the library
+ *     generates no randomness, so the call is a pure function of its arguments.
+ *   Finished rows: after a row draws id_end at step t its length is t + 1 (otherwise T); later positions hold id_end with
+ *     log-probability exactly 0 and the row's logits are no longer read.
+ *   out_ids int64 [B,S,T], out_logprobs float [B,S,T], out_lengths int [B,S].
+ *   B <= 0, V <= 0, S outside 1..8, max_length < 1, B*S*max_length > 65535 * 128, id_end outside [0, V), a temperature that is not
+ *   finite or not > 0, top_k outside [0, V], top_p outside (0, 1] (NaN refused), a null pointer or a short workspace returns a
+ *   negative code and a dic_last_error() text that starts with "dic_nic_sample:", before the first HIP call (the scalar arguments
+ *   are checked before the pointers).  dic_nic_sample_sizes hands the workspace size back through *workspace_bytes; for sizes the
+ *   call refuses it writes 0 and returns a negative code.
+ *   Properties: every launch is enqueued on `stream`, nothing is copied to the host, nothing synchronises; no float atomics, two
+ *   calls return identical bytes; the workspace may arrive uninitialised (the finished flags, lengths, previous tokens and the
+ *   state are set by the call); row (b,s) depends only on features[b] and column b*S+s of uniform_u; top_k = 1 returns the ids of
+ *   dic_nic_greedy up to and including the first id_end (id_end behind it) with all log-probabilities 0 whenever each step's
+ *   maximum is unique.  A step is three launches - cells, vocabulary GEMM, draw - and a workgroup of the cell kernel whose rows have
+ *   all finished returns before it reads a weight. */
+int dic_nic_sample_sizes(int B, int S, int max_length, int V, size_t* workspace_bytes);
+int dic_nic_sample(const dic_nic_weights* w, int V, const float* features, int B, int S, long long id_end, int max_length,
+                   float temperature, int top_k, float top_p, const float* uniform_u, int64_t* out_ids, float* out_logprobs,
+                   int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+
 /* stand-alone attention module: Soft_Attention.forward (attention.py:81-95), Hard_Attention.forward (:132-148,
  *   mode 1, gumbel_u [B,196], temp) and Hard_Attention.Hard_sample (:150-167, mode 2): feats [B,196,2048],
  *   h [B,128] -> ctx [B,2048], alpha [B,196] (float; one-hot in mode 2). */
