@@ -17,7 +17,7 @@ from torch import nn
 
 from ... import native
 from ..._lib import DicError
-from ..Depth_caption_model.depth_models import _CaptionDecoderBase
+from ..Depth_caption_model.depth_models import _CaptionDecoderBase, _HardDecodeRoutes
 
 _LAYERS = (3, 8, 36, 3)
 
@@ -131,7 +131,7 @@ class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
         return super().caption_logprobs(features, None, captions, word_to_id, skip_start)
 
 
-class RNNDecoderWithHardAttention(_CaptionDecoderBase):
+class RNNDecoderWithHardAttention(_HardDecodeRoutes, _CaptionDecoderBase):
     """base-hard decoder (base_caption_models.py:257-508)."""
     hard = True
 
@@ -169,3 +169,18 @@ class RNNDecoderWithHardAttention(_CaptionDecoderBase):
 
     def caption_logprobs(self, features, captions, word_to_id, skip_start=False):
         return super().caption_logprobs(features, None, captions, word_to_id, skip_start)
+
+    # conditional on the attention noise (depth_models._HardDecodeRoutes)
+    def hard_beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, attention_seed=0,
+                         shared_noise=True, return_all=False, return_cells=False):
+        return super().hard_beam_sample(features, None, word_to_id, beam_size, max_length, length_penalty, attention_seed,
+                                        shared_noise, return_all, return_cells)
+
+    def hard_stochastic_sample(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                               attention_seed=0, shared_noise=False, return_all=False):
+        return super().hard_stochastic_sample(features, None, word_to_id, n_samples, max_length, temperature, top_k, top_p, seed,
+                                              attention_seed, shared_noise, return_all)
+
+    def hard_score_captions(self, features, captions, word_to_id, attention_seed=0, shared_noise=True, skip_start=False,
+                            return_all=False):
+        return super().hard_score_captions(features, None, captions, word_to_id, attention_seed, shared_noise, skip_start, return_all)

@@ -242,7 +242,8 @@ class _CaptionDecoderBase(nn.Module):
         [B,K,max_length], scores np.float32 [B,K] (sums of log-probabilities), lengths np.int32 [B,K]), best first."""
         if self.hard:
             raise DicError("beam_sample: beam search is built for the soft-attention decoders only (a Gumbel-max beam would need "
-                           "one noise draw per hypothesis and step); use batch_sample for hard attention")
+                           "one noise draw per hypothesis and step); use batch_sample for hard attention, or hard_beam_sample, "
+                           "which searches conditional on attention noise drawn from a seed")
         ids, scores, lengths = native.decoder_beam(self._weights(), _contig(features), _contig(depth_features),
                                                    word_to_id["<start>"], word_to_id["<end>"], beam_size, max_length,
                                                    float(length_penalty))
@@ -262,7 +263,8 @@ class _CaptionDecoderBase(nn.Module):
         distribution, 0 behind '<end>' -, lengths np.int32)."""
         if self.hard:
             raise DicError("stochastic_sample: sampling is built for the soft-attention decoders only (a Gumbel-max decode draws "
-                           "its attention already); use batch_sample for hard attention")
+                           "its attention already); use batch_sample for hard attention, or hard_stochastic_sample, which draws "
+                           "tokens conditional on attention noise drawn from a seed")
         S = int(n_samples)
         ids, logprobs, lengths = self.stochastic_sample_tensors(features, depth_features, word_to_id, S, max_length, temperature,
                                                                 top_k, top_p, seed)
@@ -298,7 +300,8 @@ class _CaptionDecoderBase(nn.Module):
         np.float32 [B,(S,)T] - one entry per token, 0 behind '<end>' -, scores, lengths np.int32)."""
         if self.hard:
             raise DicError("score_captions: scoring is built for the soft-attention decoders only (the likelihood of a Gumbel-max "
-                           "decode is an expectation over its attention draws); there is no hard-attention counterpart")
+                           "decode is an expectation over its attention draws); there is no hard-attention counterpart of that "
+                           "marginal - hard_score_captions scores conditional on attention noise drawn from a seed")
         caps = torch.as_tensor(captions)
         if caps.dim() not in (2, 3):
             raise DicError(f"score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
@@ -346,6 +349,88 @@ class _CaptionDecoderBase(nn.Module):
         return logprobs, cfg["lengths"]
 
 
+class _HardDecodeRoutes:
+    """Beam search, sampling and scoring of the hard-attention (Gumbel-max) decoders, CONDITIONAL on their attention noise (no
+    counterpart in the reference; semantics: include/dic.h).  The noise is torch.rand((max_length, rows, 196)) of a
+    generator on the features' device seeded with `attention_seed`, clamped to [1e-6, 1 - 1e-6] (as synthetic.gumbel_uniforms):
+    rows = B when the rows of an image share it, B*S otherwise; one seed, one result.  Every score and log-probability is
+    log p(token | history, noise) - not the marginal over the noise.  Mixed into the two hard classes only."""
+
+    @staticmethod
+    def attention_noise(max_length, rows, attention_seed, device):
+        gen = torch.Generator(device).manual_seed(int(attention_seed))
+        u = torch.rand((int(max_length), int(rows), native.L_CELLS), generator=gen, device=device)
+        return u.clamp_(1e-6, 1.0 - 1e-6)
+
+    @torch.no_grad()
+    def hard_beam_sample(self, features, depth_features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0,
+                         attention_seed=0, shared_noise=True, return_all=False, return_cells=False):
+        """Beam-search captions of a batch conditional on the attention noise: np.int64 [B,max_length], the best of `beam_size`
+        hypotheses per image; return_all=True: (ids np.int64 [B,K,max_length], scores np.float32 [B,K], lengths np.int32 [B,K]),
+        best first.  return_cells=True appends cells np.int32 [B(,K),max_length]: the attended cell of every step, -1 behind the
+        hypothesis' length.  shared_noise (default): the hypotheses of an image see the same noise, so their scores are comparable
+        and hard_score_captions reproduces them."""
+        features = _contig(features)
+        K = int(beam_size)
+        u = self.attention_noise(max_length, features.shape[0] * (1 if shared_noise else max(K, 1)), attention_seed, features.device)
+        ids, scores, lengths, cells = native.decoder_beam_hard(self._weights(), features, _contig(depth_features),
+                                                               word_to_id["<start>"], word_to_id["<end>"], K, u, max_length,
+                                                               float(length_penalty), bool(shared_noise), return_cells=True)
+        cells = cells.cpu().numpy().astype(np.int32)
+        if return_all:
+            out = (ids.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32),
+                   lengths.cpu().numpy().astype(np.int32))
+            return out + (cells,) if return_cells else out
+        best = ids[:, 0].cpu().numpy().astype(np.int64)
+        return (best, cells[:, 0]) if return_cells else best
+
+    @torch.no_grad()
+    def hard_stochastic_sample(self, features, depth_features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0,
+                               top_p=1.0, seed=0, attention_seed=0, shared_noise=False, return_all=False):
+        """Captions drawn from the hard model conditional on the attention noise: np.int64 [B,max_length] for n_samples == 1,
+        [B,n_samples,max_length] otherwise.  Token draws as in stochastic_sample (`seed`).  Per-row noise (default) makes the rows
+        independent draws from the model's own caption distribution.  return_all=True: (ids, logprobs np.float32, lengths np.int32)."""
+        features = _contig(features.detach())
+        depth_features = _contig(depth_features.detach()) if depth_features is not None else None
+        S = int(n_samples)
+        rows = features.shape[0] * max(S, 1)
+        gen = torch.Generator(features.device).manual_seed(int(seed))
+        u = torch.rand((max_length, rows), generator=gen, device=features.device)
+        gu = self.attention_noise(max_length, features.shape[0] if shared_noise else rows, attention_seed, features.device)
+        ids, logprobs, lengths = native.decoder_sample_hard(self._weights(), features, depth_features, word_to_id["<start>"],
+                                                            word_to_id["<end>"], S, u, gu, max_length, float(temperature),
+                                                            int(top_k), float(top_p), bool(shared_noise))
+        if S == 1:
+            ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
+        if return_all:
+            return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return ids.cpu().numpy().astype(np.int64)
+
+    @torch.no_grad()
+    def hard_score_captions(self, features, depth_features, captions, word_to_id, attention_seed=0, shared_noise=True,
+                            skip_start=False, return_all=False):
+        """Log-probability the hard model gives to GIVEN captions conditional on the attention noise: np.float32 [B] for captions
+        int64 [B,T], [B,S] for [B,S,T].  Conventions of score_captions; with the attention_seed and noise layout of
+        hard_beam_sample / hard_stochastic_sample it reproduces their scores."""
+        caps = torch.as_tensor(captions)
+        if caps.dim() not in (2, 3):
+            raise DicError(f"hard_score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        if skip_start:
+            caps = caps[..., 1:]
+        features = _contig(features)
+        S = int(caps.shape[1]) if caps.dim() == 3 else 1
+        u = self.attention_noise(caps.shape[-1], features.shape[0] * (1 if shared_noise else max(S, 1)), attention_seed,
+                                 features.device)
+        logprobs, scores, lengths = native.decoder_score_hard(self._weights(), features, _contig(depth_features),
+                                                              word_to_id["<start>"], word_to_id["<end>"], caps.to(features.device), u,
+                                                              bool(shared_noise))
+        if return_all:
+            return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
+                    lengths.cpu().numpy().astype(np.int32))
+        return scores.cpu().numpy().astype(np.float32)
+
+
 class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):
     def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,
                  dropout: float = 0.5):
@@ -357,7 +442,7 @@ class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):
         return self._run(features, depth_features, captions, lengths, mode=0)
 
 
-class CD_RNNDecoderWithHardAttention(_CaptionDecoderBase):
+class CD_RNNDecoderWithHardAttention(_HardDecodeRoutes, _CaptionDecoderBase):
     hard = True
 
     def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,

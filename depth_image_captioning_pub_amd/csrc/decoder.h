@@ -10,6 +10,8 @@
 //                       one step head (launch_row_step).  The selection kernels shared with the NIC beam search: beam.h / beam.hip;
 //                       the kernel that draws a token from a row of logits: sample.h / sample.hip; the fused projection +
 //                       log-sum-exp of the scoring route: score.h / score.hip
+//   decoder_hard.hip    the hard (Gumbel-max) attention step of those three routes' hard counterparts (hard_row_attn_kernel) and
+//                       the kernel that lays out the selected cells
 //   decoder_states.hip  hidden states of given captions with a tape and their backward through time, S captions per image that
 //                       share the image's F, P and mean (the tail of its backward is decoder_bwd.hip's)
 #pragma once
@@ -113,6 +115,19 @@ struct AttnStepArgs {
   int do_gate; FusedLstm fl; int nrows;
 };
 int launch_attn_step(const AttnStepArgs& a, int cells, hipStream_t st);
+
+// Hard (Gumbel-max) attention step over the S rows of each of B images (hard_row_attn_kernel<S>, decoder_hard.hip): the
+// arguments of beam_attn_kernel with the step's noise u_t ([B][196] when noise_shared, else [B*S][196]) in place of the attention
+// weights, and cell_t (nullable) int [B*S]: the selected cell of every row.
+struct HardAttnArgs {
+  const float *F, *P, *Hst; const long long* tok; const float* embed; int V;
+  const float *WhT, *b_h, *w_full, *b_full, *WbT, *b_beta;
+  const float* u_t; int noise_shared; int* cell_t; float* X; int B;
+};
+int launch_hard_row_attn(int S, const HardAttnArgs& a, hipStream_t st);
+// hist int [T][R] (cell_t of every step) -> out int [R][T], -1 from length[r] on.  slot (nullable) int [R][T]: the row of its
+// image (0..S-1) whose step-t cell belongs to returned row r - the back-pointer path of a beam search; null: the row itself.
+int launch_hard_cells(const int* hist, const int* slot, const int* length, int S, int R, int T, int* out, hipStream_t st);
 
 // Grid of the attention step kernels and its decoding.  Workgroup (chunk, b) owns channels [chunk*256, +256) of row b.  The
 // eight chunk workgroups of a row share its P rows and LSTM slabs (each recomputes scores and cell): they are mapped to

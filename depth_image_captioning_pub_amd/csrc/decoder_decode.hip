@@ -1,5 +1,7 @@
 // Decoding on the device: greedy (dic_decoder_greedy), beam search (dic_decoder_beam), sampling (dic_decoder_sample) and the
-// scoring of given captions (dic_decoder_score).  The last three keep S rows per image that share the image's F, P and mean:
+// scoring of given captions (dic_decoder_score), and the hard-attention counterparts of the last three (dic_decoder_*_hard: the
+// same route bodies with the attention noise as an argument and hard_row_attn_kernel, decoder_hard.hip, as the attention step).
+// The three routes keep S rows per image that share the image's F, P and mean:
 // their workspaces begin with one RowWs (row_carve), their start kernels call broadcast_state (and parse_caption) of decoder.h,
 // and every step begins with launch_row_step; what follows the LSTM cell - vocabulary GEMM, selection, hand-over - is the route's.
 #include "beam.h"
@@ -463,13 +465,23 @@ void row_carve(Carver& c, RowWs& w, int B, size_t R) {
 // Head of a step over the R = B*S rows: beam_attn_kernel<S> (input token of row r: tok[r]; attention weights to alpha_t when
 // not null) -> gate GEMM slabs -> lstm_fwd_kernel.  The state arrays are lstm_fwd_kernel's Hall / Call at T = 1, t = 0: c from
 // slot 0, h' / c' into slot 1; h' also goes to packed row packed_off + r of h_out (its "dropped" output, no dropout).
+// The hard routes pass the step's attention noise: hard_row_attn_kernel<S> (decoder_hard.hip) takes the kernel's place and the
+// selected cells go to hard->cell_t (nullable); alpha_t is not used then.
+struct HardStep { const float* u_t; int noise_shared; int* cell_t; };
+
 int launch_row_step(const RowWs& ws, const dic_decoder_weights* w, int V, int B, int S, const long long* tok, float* alpha_t,
-                    float* h_out, int packed_off, hipStream_t st) {
+                    float* h_out, int packed_off, hipStream_t st, const HardStep* hard = nullptr) {
   const int R = B * S;
-  DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P, ws.Hst, tok,
-                                        w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b, ws.WbT, w->fbeta_b,
-                                        alpha_t, ws.X, B);)
-  DIC_LAUNCH_CHECK();
+  if (hard) {
+    DIC_TRY(launch_hard_row_attn(S, HardAttnArgs{ws.F, ws.P, ws.Hst, tok, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w,
+                                                 w->full_att_b, ws.WbT, w->fbeta_b, hard->u_t, hard->noise_shared, hard->cell_t,
+                                                 ws.X, B}, st));
+  } else {
+    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(beam_attn_kernel<KB_>, attn_step_grid(B), dim3(512), 0, st, ws.F, ws.P, ws.Hst, tok,
+                                          w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b, ws.WbT, w->fbeta_b,
+                                          alpha_t, ws.X, B);)
+    DIC_LAUNCH_CHECK();
+  }
   DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.X, kXK), op_rowk(ws.Wcat, kXK), ws.slab, kS_LSTM, st));
   return launch_lstm_fwd(LstmCell{ws.slab, ws.bcat, nullptr, ws.Hst, ws.Cst, ws.Gact, h_out, kS_LSTM, R, packed_off}, 0, 1, st);
 }
@@ -479,7 +491,8 @@ int launch_row_step(const RowWs& ws, const dic_decoder_weights* w, int V, int B,
 namespace {
 struct BeamWs : RowWs {
   float *Hdrop, *logits, *cand_val, *score;
-  float* alpha_hist;
+  float* alpha_hist;          // soft: attention weights of every step [T][BK][196]
+  int* cell_hist;             // hard: selected cell of every step [T][BK], in the same memory (one workspace size for both)
   int *cand_tok, *fin, *length, *tok_hist, *bp_hist, *path;
   long long* prev;
   size_t bytes;
@@ -502,6 +515,7 @@ BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overf
   w.bp_hist = c.take<int>(BK * T);
   w.path = c.take<int>(BK * T);
   w.alpha_hist = c.take<float>(BK * T * kL);
+  w.cell_hist = reinterpret_cast<int*>(w.alpha_hist);
   w.bytes = c.off;
   if (overflow) *overflow = c.overflow;
   return w;
@@ -518,44 +532,74 @@ size_t dic_decoder_beam_workspace_bytes(int B, int K, int max_length, int V) {
   return beam_carve(nullptr, 0, B, K, max_length, V, &ov).bytes;
 }
 
-int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
-                     long long id_start, long long id_end, int max_length, float length_penalty, int64_t* out_ids,
-                     float* out_scores, int* out_lengths, float* alphas_out, void* workspace, size_t workspace_bytes,
-                     void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// dic_decoder_beam (noise null) and dic_decoder_beam_hard: one body.  `route` is the prefix of the refusals.
+namespace {
+int beam_route(const char* route, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+               long long id_start, long long id_end, int max_length, float length_penalty, bool hard, const float* gumbel_u,
+               int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths, float* alphas_out, int* out_cells,
+               void* workspace, size_t workspace_bytes, hipStream_t st) {
   // every argument check comes before the first HIP call
-  DIC_REQUIRE(K >= 1 && K <= kBeamMax, "decoder_beam: beam width K=%d is outside 1..%d", K, kBeamMax);
-  DIC_TRY(check_row_sizes("decoder_beam", B, V, max_length));
-  DIC_REQUIRE(V >= K, "decoder_beam: vocabulary V=%d is smaller than the beam width K=%d", V, K);
-  DIC_TRY(check_token_ids("decoder_beam", V, id_start, id_end));
-  DIC_REQUIRE(length_penalty >= 0.f, "decoder_beam: length_penalty=%g must be >= 0 (NaN is refused too)", (double)length_penalty);
-  DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace, "decoder_beam: null pointer");
+  DIC_REQUIRE(K >= 1 && K <= kBeamMax, "%s: beam width K=%d is outside 1..%d", route, K, kBeamMax);
+  DIC_TRY(check_row_sizes(route, B, V, max_length));
+  DIC_REQUIRE(V >= K, "%s: vocabulary V=%d is smaller than the beam width K=%d", route, V, K);
+  DIC_TRY(check_token_ids(route, V, id_start, id_end));
+  DIC_REQUIRE(length_penalty >= 0.f, "%s: length_penalty=%g must be >= 0 (NaN is refused too)", route, (double)length_penalty);
+  if (hard) DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
+  DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace && (!hard || gumbel_u), "%s: null pointer", route);
   const int T = max_length, BK = B * K;
   bool ov = false;
   BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov);
-  if (ov) return workspace_too_small("decoder_beam", workspace_bytes, ws.bytes);
+  if (ov) return workspace_too_small(route, workspace_bytes, ws.bytes);
   // per image, never per beam.  [h0 | c0] -> slot 1 of beam 0, then copied to the KB beams
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)K * 2 * kH, false}, st));
   hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
                      ws.Cst);
   DIC_LAUNCH_CHECK();
+  const size_t noise_rows = noise_shared ? (size_t)B : (size_t)BK;
   for (int t = 0; t < T; ++t) {
-    float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * BK * kL : nullptr;
-    DIC_TRY(launch_row_step(ws, w, V, B, K, ws.prev, alpha_t, ws.Hdrop, 0, st));
+    if (hard) {     // slot k of image b consumes u[t, b*K + k] (or u[t, b]) whichever hypothesis the selection of step t-1 put there
+      const HardStep hs{gumbel_u + (size_t)t * noise_rows * kL, noise_shared, out_cells ? ws.cell_hist + (size_t)t * BK : nullptr};
+      DIC_TRY(launch_row_step(ws, w, V, B, K, ws.prev, nullptr, ws.Hdrop, 0, st, &hs));
+    } else {
+      float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * BK * kL : nullptr;
+      DIC_TRY(launch_row_step(ws, w, V, B, K, ws.prev, alpha_t, ws.Hdrop, 0, st));
+    }
     DIC_TRY(gemm(BK, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
     DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st));
     DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
                                           BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
     DIC_LAUNCH_CHECK();
   }
-  return launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, ws.alpha_hist, ws.path,
-                               (long long*)out_ids, out_scores, out_lengths, alphas_out, st);
+  DIC_TRY(launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, hard ? nullptr : ws.alpha_hist, ws.path,
+                                (long long*)out_ids, out_scores, out_lengths, alphas_out, st));
+  // the cell of step t along returned hypothesis r: that of the slot the back-pointer path passes at step t
+  if (hard && out_cells) DIC_TRY(launch_hard_cells(ws.cell_hist, ws.path, out_lengths, K, BK, T, out_cells, st));
+  return DIC_OK;
+}
+}  // namespace
+
+int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                     long long id_start, long long id_end, int max_length, float length_penalty, int64_t* out_ids,
+                     float* out_scores, int* out_lengths, float* alphas_out, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  return beam_route("decoder_beam", w, V, feat_rgb, feat_depth, B, K, id_start, id_end, max_length, length_penalty, false, nullptr,
+                    1, out_ids, out_scores, out_lengths, alphas_out, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int dic_decoder_beam_hard(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                          long long id_start, long long id_end, int max_length, float length_penalty, const float* gumbel_u,
+                          int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths, int* out_cells, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  return beam_route("decoder_beam_hard", w, V, feat_rgb, feat_depth, B, K, id_start, id_end, max_length, length_penalty, true,
+                    gumbel_u, noise_shared, out_ids, out_scores, out_lengths, nullptr, out_cells, workspace, workspace_bytes,
+                    (hipStream_t)stream);
 }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------
 namespace {
 struct SampleWs : RowWs {      // (BeamWs without the candidate, back-pointer and path arrays)
   float *Hdrop, *logits, *alpha_hist;
+  int* cell_hist;                // hard: selected cell of every step [T][R], in the memory of alpha_hist
   int* fin;
   long long* prev;
   size_t bytes;
@@ -571,6 +615,7 @@ SampleWs sample_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* o
   w.fin = c.take<int>(R);
   w.prev = c.take<long long>(R);
   w.alpha_hist = c.take<float>(R * T * kL);
+  w.cell_hist = reinterpret_cast<int*>(w.alpha_hist);
   w.bytes = c.off;
   if (overflow) *overflow = c.overflow;
   return w;
@@ -587,31 +632,40 @@ size_t dic_decoder_sample_workspace_bytes(int B, int S, int max_length, int V) {
   return sample_carve(nullptr, 0, B, S, max_length, V, &ov).bytes;
 }
 
-int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
-                       long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
-                       const float* uniform_u, int64_t* out_ids, float* out_logprobs, int* out_lengths, float* alphas_out,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// dic_decoder_sample (noise null) and dic_decoder_sample_hard: one body.  `route` is the prefix of the refusals.
+namespace {
+int sample_route(const char* route, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                 long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                 const float* uniform_u, bool hard, const float* gumbel_u, int noise_shared, int64_t* out_ids, float* out_logprobs,
+                 int* out_lengths, float* alphas_out, int* out_cells, void* workspace, size_t workspace_bytes, hipStream_t st) {
   // every argument check comes before the first HIP call
-  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_sample: samples per image S=%d is outside 1..%d", S, kBeamMax);
-  DIC_TRY(check_row_sizes("decoder_sample", B, V, max_length));
-  DIC_TRY(check_token_ids("decoder_sample", V, id_start, id_end));
-  DIC_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "decoder_sample: temperature=%g must be finite and > 0",
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "%s: samples per image S=%d is outside 1..%d", route, S, kBeamMax);
+  DIC_TRY(check_row_sizes(route, B, V, max_length));
+  DIC_TRY(check_token_ids(route, V, id_start, id_end));
+  DIC_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "%s: temperature=%g must be finite and > 0", route,
               (double)temperature);
-  DIC_REQUIRE(top_k >= 0 && top_k <= V, "decoder_sample: top_k=%d is outside 0..V=%d (0: no limit)", top_k, V);
-  DIC_REQUIRE(top_p > 0.f && top_p <= 1.f, "decoder_sample: top_p=%g is outside (0, 1] (1: off; NaN is refused too)", (double)top_p);
-  DIC_REQUIRE(w && feat_rgb && uniform_u && out_ids && out_logprobs && out_lengths && workspace, "decoder_sample: null pointer");
+  DIC_REQUIRE(top_k >= 0 && top_k <= V, "%s: top_k=%d is outside 0..V=%d (0: no limit)", route, top_k, V);
+  DIC_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p=%g is outside (0, 1] (1: off; NaN is refused too)", route, (double)top_p);
+  if (hard) DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
+  DIC_REQUIRE(w && feat_rgb && uniform_u && out_ids && out_logprobs && out_lengths && workspace && (!hard || gumbel_u),
+              "%s: null pointer", route);
   const int T = max_length, R = B * S;
   bool ov = false;
   SampleWs ws = sample_carve(workspace, workspace_bytes, B, S, T, V, &ov);
-  if (ov) return workspace_too_small("decoder_sample", workspace_bytes, ws.bytes);
+  if (ov) return workspace_too_small(route, workspace_bytes, ws.bytes);
   // per image, never per sample.  [h0 | c0] -> slot 1 of sample 0, then copied to the S rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
   hipLaunchKernelGGL(sample_init_kernel, dim3(B), dim3(kH), 0, st, S, id_start, ws.fin, out_lengths, ws.prev, ws.Hst, ws.Cst);
   DIC_LAUNCH_CHECK();
+  const size_t noise_rows = noise_shared ? (size_t)B : (size_t)R;
   for (int t = 0; t < T; ++t) {
-    float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * R * kL : nullptr;
-    DIC_TRY(launch_row_step(ws, w, V, B, S, ws.prev, alpha_t, ws.Hdrop, 0, st));
+    if (hard) {
+      const HardStep hs{gumbel_u + (size_t)t * noise_rows * kL, noise_shared, out_cells ? ws.cell_hist + (size_t)t * R : nullptr};
+      DIC_TRY(launch_row_step(ws, w, V, B, S, ws.prev, nullptr, ws.Hdrop, 0, st, &hs));
+    } else {
+      float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * R * kL : nullptr;
+      DIC_TRY(launch_row_step(ws, w, V, B, S, ws.prev, alpha_t, ws.Hdrop, 0, st));
+    }
     DIC_TRY(gemm(R, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
     DIC_TRY(launch_sample_token(SampleStep{ws.logits, R, V, temperature, top_k, top_p, uniform_u + (size_t)t * R, id_end, t, T,
                                            ws.fin, out_lengths, ws.prev, (long long*)out_ids, out_logprobs, ws.Hst, ws.Cst, kH},
@@ -622,7 +676,27 @@ int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rg
                        T, alphas_out);
     DIC_LAUNCH_CHECK();
   }
+  if (hard && out_cells) DIC_TRY(launch_hard_cells(ws.cell_hist, nullptr, out_lengths, S, R, T, out_cells, st));
   return DIC_OK;
+}
+}  // namespace
+
+int dic_decoder_sample(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                       long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                       const float* uniform_u, int64_t* out_ids, float* out_logprobs, int* out_lengths, float* alphas_out,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  return sample_route("decoder_sample", w, V, feat_rgb, feat_depth, B, S, id_start, id_end, max_length, temperature, top_k, top_p,
+                      uniform_u, false, nullptr, 1, out_ids, out_logprobs, out_lengths, alphas_out, nullptr, workspace,
+                      workspace_bytes, (hipStream_t)stream);
+}
+
+int dic_decoder_sample_hard(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                            long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                            const float* uniform_u, const float* gumbel_u, int noise_shared, int64_t* out_ids, float* out_logprobs,
+                            int* out_lengths, int* out_cells, void* workspace, size_t workspace_bytes, void* stream) {
+  return sample_route("decoder_sample_hard", w, V, feat_rgb, feat_depth, B, S, id_start, id_end, max_length, temperature, top_k,
+                      top_p, uniform_u, true, gumbel_u, noise_shared, out_ids, out_logprobs, out_lengths, nullptr, out_cells,
+                      workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------------
@@ -660,29 +734,35 @@ size_t dic_decoder_score_workspace_bytes(int B, int S, int max_length, int V) {
   return score_carve(nullptr, 0, B, S, max_length, V, &ov).bytes;
 }
 
-int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
-                      long long id_start, long long id_end, int max_length, const int64_t* captions, float* out_logprobs,
-                      float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// dic_decoder_score (noise null) and dic_decoder_score_hard: one body.  `route` is the prefix of the refusals.
+namespace {
+int score_route(const char* route, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                long long id_start, long long id_end, int max_length, const int64_t* captions, bool hard, const float* gumbel_u,
+                int noise_shared, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes,
+                hipStream_t st) {
   // every argument check comes before the first HIP call
-  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_score: captions per image S=%d is outside 1..%d", S, kBeamMax);
-  DIC_TRY(check_row_sizes("decoder_score", B, V, max_length));
-  DIC_REQUIRE((long long)B * S * max_length <= kScoreMaxM, "decoder_score: B*S*max_length=%lld exceeds %d token positions per call",
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "%s: captions per image S=%d is outside 1..%d", route, S, kBeamMax);
+  DIC_TRY(check_row_sizes(route, B, V, max_length));
+  DIC_REQUIRE((long long)B * S * max_length <= kScoreMaxM, "%s: B*S*max_length=%lld exceeds %d token positions per call", route,
               (long long)B * S * max_length, kScoreMaxM);
-  DIC_TRY(check_token_ids("decoder_score", V, id_start, id_end));
-  DIC_REQUIRE(w && feat_rgb && captions && out_logprobs && out_scores && out_lengths && workspace, "decoder_score: null pointer");
+  DIC_TRY(check_token_ids(route, V, id_start, id_end));
+  if (hard) DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
+  DIC_REQUIRE(w && feat_rgb && captions && out_logprobs && out_scores && out_lengths && workspace && (!hard || gumbel_u),
+              "%s: null pointer", route);
   const int T = max_length, R = B * S;
   bool ov = false;
   ScoreWs ws = score_carve(workspace, workspace_bytes, B, S, T, V, &ov);
-  if (ov) return workspace_too_small("decoder_score", workspace_bytes, ws.bytes);
+  if (ov) return workspace_too_small(route, workspace_bytes, ws.bytes);
   // per image, never per caption.  [h0 | c0] -> slot 1 of row 0 of the image, then copied to its S rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
   hipLaunchKernelGGL(score_init_kernel, dim3(B), dim3(kH), 0, st, S, T, V, id_start, id_end, (const long long*)captions, ws.tok_in,
                      ws.target, out_lengths, ws.Hst, ws.Cst);
   DIC_LAUNCH_CHECK();
+  const size_t noise_rows = noise_shared ? (size_t)B : (size_t)R;
   for (int t = 0; t < T; ++t) {
     // the cell writes h' / c' into slot 1 and appends h' to the history (packed row t*R + r)
-    DIC_TRY(launch_row_step(ws, w, V, B, S, ws.tok_in + (size_t)t * R, nullptr, ws.hist, t * R, st));
+    const HardStep hs{hard ? gumbel_u + (size_t)t * noise_rows * kL : nullptr, noise_shared, nullptr};
+    DIC_TRY(launch_row_step(ws, w, V, B, S, ws.tok_in + (size_t)t * R, nullptr, ws.hist, t * R, st, hard ? &hs : nullptr));
     if (t + 1 < T) {
       hipLaunchKernelGGL(score_handover_kernel, dim3(R), dim3(kH), 0, st, ws.Hst, ws.Cst);
       DIC_LAUNCH_CHECK();
@@ -692,6 +772,22 @@ int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb
   hipLaunchKernelGGL(score_finish_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, st, ws.lp, R, T, out_logprobs, out_scores);
   DIC_LAUNCH_CHECK();
   return DIC_OK;
+}
+}  // namespace
+
+int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                      long long id_start, long long id_end, int max_length, const int64_t* captions, float* out_logprobs,
+                      float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  return score_route("decoder_score", w, V, feat_rgb, feat_depth, B, S, id_start, id_end, max_length, captions, false, nullptr, 1,
+                     out_logprobs, out_scores, out_lengths, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int dic_decoder_score_hard(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                           long long id_start, long long id_end, int max_length, const int64_t* captions, const float* gumbel_u,
+                           int noise_shared, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return score_route("decoder_score_hard", w, V, feat_rgb, feat_depth, B, S, id_start, id_end, max_length, captions, true, gumbel_u,
+                     noise_shared, out_logprobs, out_scores, out_lengths, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

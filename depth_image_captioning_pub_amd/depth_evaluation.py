@@ -56,7 +56,8 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
                       length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False):
+                      top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False,
+                      attention_seed: Optional[int] = None):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
@@ -65,6 +66,10 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     n_samples > 0 (soft attention only) ADDS to each result "samples", a list of `n_samples` caption strings per image drawn with
     decoder.stochastic_sample(temperature, top_k, top_p), and "sample_ids" np.int64 [N,n_samples,30]; batch b is seeded with
     seed + b.  The hypotheses, the ids and the written file do not depend on it.
+    attention_seed (atten="hard" only): with it a hard model decodes CONDITIONAL on attention noise drawn from a seed - beam_size > 1
+    with decoder.hard_beam_sample (noise shared by an image's hypotheses), n_samples > 0 with decoder.hard_stochastic_sample
+    (noise per row); batch b is seeded attention_seed + b.  None (default): both refuse for a hard model as before; the greedy
+    path of a hard model never uses it.
     cider=True ADDS "CIDEr": the mean CIDEr-D (evaluate_metrix.py:31; x10 as pycocoevalcap reports it) of the hypotheses against
     synthetic.reference_captions(batch_size, vocab_size, seed=5000 + b) of batch b, five per image, scored on the device as decoded
     strings are (count_end=False); the idf table is that of all the evaluated images' references.  Nothing else depends on it.
@@ -76,12 +81,16 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
         raise DicError("atten must be 'soft' or 'hard'")
     if int(beam_size) < 1:
         raise DicError(f"beam_size={beam_size!r} must be at least 1")
-    if int(beam_size) > 1 and atten != "soft":
-        raise DicError("beam_size > 1 needs atten='soft': beam search is built for the soft-attention decoder only")
+    if attention_seed is not None and atten != "hard":
+        raise DicError("attention_seed seeds the attention noise of the hard-attention decoder: it needs atten='hard'")
+    if int(beam_size) > 1 and atten != "soft" and attention_seed is None:
+        raise DicError("beam_size > 1 needs atten='soft': beam search is built for the soft-attention decoder only (a hard model "
+                       "searches conditional on its attention noise when attention_seed is given)")
     if int(n_samples) < 0:
         raise DicError(f"n_samples={n_samples!r} must be at least 0")
-    if int(n_samples) > 0 and atten != "soft":
-        raise DicError("n_samples > 0 needs atten='soft': sampling is built for the soft-attention decoder only")
+    if int(n_samples) > 0 and atten != "soft" and attention_seed is None:
+        raise DicError("n_samples > 0 needs atten='soft': sampling is built for the soft-attention decoder only (a hard model "
+                       "samples conditional on its attention noise when attention_seed is given)")
     config = config or ConfigTrain()
     dev = config.device
     tag = f"depth_{atten}"
@@ -117,12 +126,20 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             feature = encoder(imgs)                                                         # :164
             if cider or metrics:
                 references += syn.reference_captions(config.batch_size, config.vocab_size, seed=5000 + b)
-            if int(beam_size) > 1:
+            if int(beam_size) > 1 and atten == "hard":
+                hypos_id.append(decoder.hard_beam_sample(feature, depth_features, word_to_id, beam_size=int(beam_size),
+                                                         length_penalty=length_penalty, attention_seed=int(attention_seed) + b))
+            elif int(beam_size) > 1:
                 hypos_id.append(decoder.beam_sample(feature, depth_features, word_to_id, beam_size=int(beam_size),
                                                     length_penalty=length_penalty))
             else:
                 hypos_id.append(decoder.batch_sample(feature, depth_features, word_to_id))     # :165
-            if int(n_samples) > 0:
+            if int(n_samples) > 0 and atten == "hard":
+                drawn = decoder.hard_stochastic_sample(feature, depth_features, word_to_id, n_samples=int(n_samples),
+                                                       temperature=temperature, top_k=top_k, top_p=top_p, seed=int(seed) + b,
+                                                       attention_seed=int(attention_seed) + b)
+                sample_ids.append(drawn.reshape(drawn.shape[0], int(n_samples), -1))
+            elif int(n_samples) > 0:
                 drawn = decoder.stochastic_sample(feature, depth_features, word_to_id, n_samples=int(n_samples),
                                                   temperature=temperature, top_k=top_k, top_p=top_p, seed=int(seed) + b)
                 sample_ids.append(drawn.reshape(drawn.shape[0], int(n_samples), -1))

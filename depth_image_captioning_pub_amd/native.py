@@ -733,6 +733,97 @@ def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat
     return logprobs, scores, lengths
 
 
+def _hard_noise(what: str, gumbel_u: torch.Tensor, max_length: int, B: int, S: int, noise_shared: bool) -> torch.Tensor:
+    """The attention noise of a hard route: float32 [max_length, B, 196] when shared by the rows of an image, else
+    [max_length, B*S, 196]."""
+    u = _dev(gumbel_u, "gumbel_u")
+    rows = B if noise_shared else B * S
+    if tuple(u.shape) != (max_length, rows, L_CELLS):
+        raise _lib.DicError(f"{what}: gumbel_u must be [max_length, {'B' if noise_shared else 'B*S'}, {L_CELLS}] = "
+                            f"[{max_length}, {rows}, {L_CELLS}] with noise_shared={bool(noise_shared)}, got {tuple(u.shape)}")
+    return u
+
+
+def decoder_beam_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                      id_end: int, beam_size: int, gumbel_u: torch.Tensor, max_length: int = 30, length_penalty: float = 0.0,
+                      noise_shared: bool = True, return_cells: bool = False):
+    """dic_decoder_beam_hard: fixed-width beam search of the hard-attention (Gumbel-max) decoder conditional on the attention noise
+    gumbel_u - float32 [max_length, B, 196] (noise_shared) or [max_length, B*beam_size, 196], values in (0,1) - on the device
+    (semantics: include/dic.h).  Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K][, cells int32
+    [B,K,max_length]: the selected cell along each hypothesis, -1 from its length on]), best first."""
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    K = int(beam_size)
+    kk = max(K, 1)
+    u = _hard_noise("decoder_beam_hard", gumbel_u, max_length, B, kk, noise_shared)
+    ws = _workspace(lib.dic_decoder_beam_workspace_bytes, f_rgb.device, B, K, max_length, vocab)
+    ids = torch.empty((B, kk, max_length), dtype=torch.int64, device=f_rgb.device)
+    scores = torch.empty((B, kk), dtype=torch.float32, device=f_rgb.device)
+    lengths = torch.empty((B, kk), dtype=torch.int32, device=f_rgb.device)
+    cells = torch.empty((B, kk, max_length), dtype=torch.int32, device=f_rgb.device) if return_cells else None
+    rc = lib.dic_decoder_beam_hard(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, int(id_start), int(id_end), max_length,
+                                   length_penalty, ptr(u), int(bool(noise_shared)), ptr(ids), ptr(scores), ptr(lengths), ptr(cells),
+                                   ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_decoder_beam_hard")
+    return (ids, scores, lengths, cells) if return_cells else (ids, scores, lengths)
+
+
+def decoder_sample_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                        id_end: int, n_samples: int, uniform_u: torch.Tensor, gumbel_u: torch.Tensor, max_length: int = 30,
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, noise_shared: bool = False,
+                        return_cells: bool = False):
+    """dic_decoder_sample_hard: `n_samples` captions per image drawn from the hard-attention decoder conditional on the attention
+    noise, on the device (semantics: include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1), the token draws;
+    gumbel_u: float32 [max_length, B*n_samples, 196] or, with noise_shared, [max_length, B, 196], in (0,1).
+    Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S][, cells int32 [B,S,max_length]])."""
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    S = int(n_samples)
+    ss = max(S, 1)
+    u = _dev(uniform_u, "uniform_u")
+    if tuple(u.shape) != (max_length, B * ss):
+        raise _lib.DicError(f"decoder_sample_hard: uniform_u must be [max_length, B*n_samples] = [{max_length}, {B * ss}], got "
+                            f"{tuple(u.shape)}")
+    gu = _hard_noise("decoder_sample_hard", gumbel_u, max_length, B, ss, noise_shared)
+    ws = _workspace(lib.dic_decoder_sample_workspace_bytes, f_rgb.device, B, S, max_length, vocab)
+    ids = torch.empty((B, ss, max_length), dtype=torch.int64, device=f_rgb.device)
+    logprobs = torch.empty((B, ss, max_length), dtype=torch.float32, device=f_rgb.device)
+    lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
+    cells = torch.empty((B, ss, max_length), dtype=torch.int32, device=f_rgb.device) if return_cells else None
+    rc = lib.dic_decoder_sample_hard(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), max_length,
+                                     temperature, int(top_k), top_p, ptr(u), ptr(gu), int(bool(noise_shared)), ptr(ids),
+                                     ptr(logprobs), ptr(lengths), ptr(cells), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_decoder_sample_hard")
+    return (ids, logprobs, lengths, cells) if return_cells else (ids, logprobs, lengths)
+
+
+def decoder_score_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                       id_end: int, captions: torch.Tensor, gumbel_u: torch.Tensor, noise_shared: bool = True):
+    """dic_decoder_score_hard: the log-probability the hard-attention decoder gives every token of given captions, conditional on
+    the attention noise, on the device (semantics: include/dic.h).  captions: int64 [B,T] or [B,S,T] (S <= 8), without '<start>';
+    gumbel_u: float32 [T, B, 196] (noise_shared) or [T, B*S, 196], in (0,1).
+    Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    cap = _dev(captions, "captions", torch.int64)
+    squeeze = cap.dim() == 2
+    if squeeze:
+        cap = cap.unsqueeze(1)
+    if cap.dim() != 3 or cap.shape[0] != B:
+        raise _lib.DicError(f"decoder_score_hard: captions must be [B,T] or [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+    S, T = int(cap.shape[1]), int(cap.shape[2])
+    ss, tt = max(S, 1), max(T, 1)
+    u = _hard_noise("decoder_score_hard", gumbel_u, tt, B, ss, noise_shared)
+    ws = _workspace(lib.dic_decoder_score_workspace_bytes, f_rgb.device, B, S, T, vocab)
+    logprobs = torch.empty((B, ss, tt), dtype=torch.float32, device=f_rgb.device)
+    scores = torch.empty((B, ss), dtype=torch.float32, device=f_rgb.device)
+    lengths = torch.empty((B, ss), dtype=torch.int32, device=f_rgb.device)
+    rc = lib.dic_decoder_score_hard(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), T, ptr(cap),
+                                    ptr(u), int(bool(noise_shared)), ptr(logprobs), ptr(scores), ptr(lengths), ptr(ws), ws.numel(),
+                                    stream_ptr())
+    check(rc, "dic_decoder_score_hard")
+    if squeeze:
+        return logprobs[:, 0], scores[:, 0], lengths[:, 0]
+    return logprobs, scores, lengths
+
+
 # the 15 decoder gradients dic_decoder_states_bwd writes (linear.* come from token_logprobs_bwd)
 STATES_GRAD_KEYS = tuple(k for k, _ in DECODER_FIELDS if not k.startswith("linear."))
 

@@ -265,6 +265,65 @@ int dic_decoder_score(const dic_decoder_weights* w, int V, const float* feat_rgb
                       long long id_start, long long id_end, int max_length, const int64_t* captions, float* out_logprobs,
                       float* out_scores, int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Beam search, sampling and scoring for the HARD-attention (Gumbel-max) decoder (depth-hard, or base-hard with feat_depth = NULL).
+ *   There is no reference implementation (the reference decodes a hard model greedily); these comments are the specification.
+ *   What the three calls share.  The attention noise is an input (quirk Q6, as gumbel_u of dic_decoder_fwd / dic_decoder_greedy):
+ *     gumbel_u float [T, B, 196] when noise_shared = 1 (the S rows of an image see the same noise), [T, B*S, 196] when
+ *     noise_shared = 0, on the device, T = max_length, values in (0,1); the values are not validated, the library generates no
+ *     randomness.  CONDITIONAL ON THE NOISE the hard decoder is a deterministic function of its tokens, and everything below is
+ *     that conditional quantity: scores and log-probabilities are log p(token | history, u), never the marginal over u.
+ *   One step of row r = b*S + s at step t is the decode-step body of dic_decoder_greedy with mode 2:
+ *       q = W_h h_r + b_h,  e[l] = w_full . relu(P[b,l,:] + q) + b_full  (fp32, l = 0..195),
+ *       z[l] = e[l] + (-logf(-logf(u[t, n, l]))),   n = b when noise_shared, else the row whose noise the step consumes (below),
+ *       l* = the FIRST index attaining max_l z[l],  ctx = F[b, l*, :],  gate = sigmoid(f_beta h_r),
+ *       LSTMCell([embed(prev) ; gate * ctx]), logits = linear(h'), no dropout.
+ *     q and e take the thread roles and summation orders of the greedy step, so for one row per image and the same u the step
+ *     selects the cell dic_decoder_greedy(mode 2) selects, on every image.  Of F a step reads only the selected rows
+ *     (DESIGN.md 5.24); there is no [.., 196] array of attention weights, they are one-hot: out_cells holds l*.
+ *   Everything is enqueued on `stream`; nothing is copied to the host, nothing synchronises; two calls return identical bytes.
+ *   Refusals: those of the soft call of the same name, in its order, with the text prefix given below; then noise_shared outside
+ *   {0, 1}; then a null pointer (gumbel_u included; feat_depth and out_cells may be null) - all before any HIP call, with a
+ *   dic_last_error() text; then a short workspace.
+ *   Workspace: that of the soft call of the same name and sizes - dic_decoder_beam_workspace_bytes(B, K, max_length, V),
+ *   dic_decoder_sample_workspace_bytes, dic_decoder_score_workspace_bytes (the cell history lies where the soft call keeps its
+ *   attention weights); the queries return 0 for sizes the calls refuse.
+ *
+ * dic_decoder_beam_hard ("decoder_beam_hard:"): dic_decoder_beam, word for word - start state, candidate rule, ties, finished
+ *   hypotheses, lengths, ranking by score / length^length_penalty - over the step above.  Noise index: the hypothesis that occupies
+ *   slot k of image b when step t begins (after the selection of step t-1) consumes u[t, b*K + k, :] (u[t, b, :] when shared).
+ *   out_ids int64 [B,K,T], out_scores float [B,K] (raw sums of log p(token | history, u)), out_lengths int [B,K], out_cells
+ *   (nullable) int [B,K,T]: the selected cell along each returned hypothesis; positions at or behind `length` hold -1.
+ *   Properties: K = 1 with shared noise decodes what dic_decoder_greedy(mode 2, the same u) decodes up to the first id_end.  With
+ *   per-row noise a hypothesis collects the noise of the slots it passed through: its score is then not re-scorable from its
+ *   tokens and one noise row (no property is claimed there).
+ *
+ * dic_decoder_sample_hard ("decoder_sample_hard:"): dic_decoder_sample, word for word - draws uniform_u float [T, B*S], temperature,
+ *   top-k, top-p, the inverse-CDF draw, finished rows - over the step above.  Row r consumes u[t, r, :] (u[t, b, :] when shared) at
+ *   step t.  out_ids int64 [B,S,T], out_logprobs float [B,S,T] (log p(token | history, u) under the filtered distribution),
+ *   out_lengths int [B,S], out_cells (nullable) int [B,S,T]: the selected cell of each row's own steps, -1 at or behind `length`.
+ *   Properties: row (b,s) depends only on image b, its noise row and column b*S+s of uniform_u; top_k = 1, S = 1 with shared noise
+ *   decodes what dic_decoder_greedy(mode 2, the same u) decodes up to the first id_end whenever each step's maximum is unique.
+ *
+ * dic_decoder_score_hard ("decoder_score_hard:"): dic_decoder_score, word for word - captions int64 [B,S,T] without <start>,
+ *   input tokens, lengths, out_logprobs exactly 0 from each length on, out_scores the fp32 sum in ascending t - over the step
+ *   above.  Row r consumes u[t, r, :] (u[t, b, :] when shared) at step t.  out_logprobs float [B,S,T], out_scores float [B,S],
+ *   out_lengths int [B,S].
+ *   Properties: with the same noise (and layout) the result agrees, up to fp32 rounding, with dic_decoder_sample_hard's
+ *   out_logprobs for the ids it drew at temperature 1 with the filters off; with noise_shared = 1 also with
+ *   dic_decoder_beam_hard's out_scores for the hypotheses it returned. */
+int dic_decoder_beam_hard(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                          long long id_start, long long id_end, int max_length, float length_penalty, const float* gumbel_u,
+                          int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths, int* out_cells, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int dic_decoder_sample_hard(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                            long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                            const float* uniform_u, const float* gumbel_u, int noise_shared, int64_t* out_ids, float* out_logprobs,
+                            int* out_lengths, int* out_cells, void* workspace, size_t workspace_bytes, void* stream);
+int dic_decoder_score_hard(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                           long long id_start, long long id_end, int max_length, const int64_t* captions, const float* gumbel_u,
+                           int noise_shared, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* hidden states of GIVEN captions with a tape, and the backward through time: the differentiable form of dic_decoder_score's
  *   recurrence (soft attention, 196 cells), S captions per image that SHARE the image's F, P = W_z F + b_z and mean.  Composed with
  *   dic_token_logprobs / dic_token_logprobs_bwd it makes the log-probabilities of dic_decoder_score trainable (self-critical
