@@ -99,16 +99,9 @@ class CNNEncoder_Atten(nn.Module):
         return out
 
 
-class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
-    """base-soft decoder: identical to the CD_ variant without the depth features (base_caption_models.py:49-250)."""
-
-    def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,
-                 dropout: float = 0.5):
-        super().__init__()
-        self._build(dim_attention, dim_embedding, dim_encoder, dim_decoder, vocab_size, dropout)
-
-    def forward(self, features: torch.Tensor, captions: torch.Tensor, lengths: list):
-        return self._run(features, None, captions, lengths, mode=0)
+class _NoDepthRoutes:
+    """The decode routes of _CaptionDecoderBase with the base models' signatures: no depth features.  First base of the two classes
+    below, so super() here is _CaptionDecoderBase (whose refusals of the soft-only routes still fire on the hard class)."""
 
     def sample(self, features, word_to_id, max_length=30):
         return super().sample(features, None, word_to_id, max_length)
@@ -131,7 +124,19 @@ class RNNDecoderWithSoftAttention(_CaptionDecoderBase):
         return super().caption_logprobs(features, None, captions, word_to_id, skip_start)
 
 
-class RNNDecoderWithHardAttention(_HardDecodeRoutes, _CaptionDecoderBase):
+class RNNDecoderWithSoftAttention(_NoDepthRoutes, _CaptionDecoderBase):
+    """base-soft decoder: identical to the CD_ variant without the depth features (base_caption_models.py:49-250)."""
+
+    def __init__(self, dim_attention: int, dim_embedding: int, dim_encoder: int, dim_decoder: int, vocab_size: int,
+                 dropout: float = 0.5):
+        super().__init__()
+        self._build(dim_attention, dim_embedding, dim_encoder, dim_decoder, vocab_size, dropout)
+
+    def forward(self, features: torch.Tensor, captions: torch.Tensor, lengths: list):
+        return self._run(features, None, captions, lengths, mode=0)
+
+
+class RNNDecoderWithHardAttention(_NoDepthRoutes, _HardDecodeRoutes, _CaptionDecoderBase):
     """base-hard decoder (base_caption_models.py:257-508)."""
     hard = True
 
@@ -149,26 +154,6 @@ class RNNDecoderWithHardAttention(_HardDecodeRoutes, _CaptionDecoderBase):
     def eval_forward(self, features, captions, lengths):
         packed, _ = self._run(features, None, captions, lengths, mode=2)
         return packed
-
-    def sample(self, features, word_to_id, max_length=30):
-        return super().sample(features, None, word_to_id, max_length)
-
-    def batch_sample(self, features, word_to_id, max_length=30):
-        return super().batch_sample(features, None, word_to_id, max_length)
-
-    def beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, return_all=False):
-        return super().beam_sample(features, None, word_to_id, beam_size, max_length, length_penalty, return_all)
-
-    def stochastic_sample(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                          return_all=False):
-        return super().stochastic_sample(features, None, word_to_id, n_samples, max_length, temperature, top_k, top_p, seed,
-                                         return_all)
-
-    def score_captions(self, features, captions, word_to_id, skip_start=False, return_all=False):
-        return super().score_captions(features, None, captions, word_to_id, skip_start, return_all)
-
-    def caption_logprobs(self, features, captions, word_to_id, skip_start=False):
-        return super().caption_logprobs(features, None, captions, word_to_id, skip_start)
 
     # conditional on the attention noise (depth_models._HardDecodeRoutes)
     def hard_beam_sample(self, features, word_to_id, beam_size=3, max_length=30, length_penalty=0.0, attention_seed=0,

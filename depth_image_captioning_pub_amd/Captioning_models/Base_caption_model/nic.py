@@ -26,6 +26,7 @@ from ... import losses, native, synthetic as syn
 from ..._lib import DicError
 from ...engine import BackboneTrainer, FlatParams, baseline_mode, look_ahead, reward_tensor
 from ..config import ConfigTrain
+from ..util import given_captions, host, host_all, token_uniforms
 from .base_caption_models import _LAYERS, CNNEncoder_Atten
 
 tqdm_disable = True   # nic.py:20
@@ -176,10 +177,7 @@ class NIC_RNNDecoder(nn.Module):
         beam_size=1 gives batch_sample's tokens up to the first '<end>'."""
         ids, scores, lengths = native.nic_beam(self._weights(), _contig(features), word_to_id["<end>"], beam_size, max_length,
                                                float(length_penalty))
-        if return_all:
-            return (ids.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return ids[:, 0].cpu().numpy().astype(np.int64)
+        return host_all(ids, scores, lengths) if return_all else host(ids[:, 0])
 
     # ---- stochastic decoding (no counterpart in the reference; semantics: include/dic.h, DESIGN.md 5.22).  `sample` stays greedy ----
     @torch.no_grad()
@@ -194,10 +192,7 @@ class NIC_RNNDecoder(nn.Module):
         ids, logprobs, lengths = self.stochastic_sample_tensors(features, word_to_id, S, max_length, temperature, top_k, top_p, seed)
         if S == 1:
             ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
-        if return_all:
-            return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return ids.cpu().numpy().astype(np.int64)
+        return host_all(ids, logprobs, lengths) if return_all else host(ids)
 
     @torch.no_grad()
     def stochastic_sample_tensors(self, features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0, top_p=1.0,
@@ -206,8 +201,7 @@ class NIC_RNNDecoder(nn.Module):
         lengths int32 [B,S]) - for callers that feed the captions to another device call (scst.nic_scst_sample_step)."""
         features = _contig(features.detach())
         S = int(n_samples)
-        gen = torch.Generator(features.device).manual_seed(int(seed))
-        u = torch.rand((max_length, features.shape[0] * max(S, 1)), generator=gen, device=features.device)
+        u = token_uniforms(max_length, features.shape[0] * max(S, 1), seed, features.device)
         return native.nic_sample(self._weights(), features, word_to_id["<end>"], S, u, max_length, float(temperature), int(top_k),
                                  float(top_p))
 
@@ -218,15 +212,10 @@ class NIC_RNNDecoder(nn.Module):
         captions per image) - the sum over each caption's tokens up to and including its first '<end>'.  The captions are scored as
         they are: NIC predicts '<start>' itself (the image is step 0), so collated ground-truth captions keep theirs.
         return_all=True: (logprobs np.float32 [B,(S,)T] - one entry per token, 0 behind '<end>' -, scores, lengths np.int32)."""
-        caps = torch.as_tensor(captions)
-        if caps.dim() not in (2, 3):
-            raise DicError(f"score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        caps = given_captions("score_captions", captions)
         features = _contig(features)
         logprobs, scores, lengths = native.nic_score(self._weights(), features, word_to_id["<end>"], caps.to(features.device))
-        if return_all:
-            return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return scores.cpu().numpy().astype(np.float32)
+        return host_all(logprobs, scores, lengths) if return_all else host(scores)
 
     # ---- differentiable scoring (no counterpart in the reference; semantics: include/dic.h, DESIGN.md 5.21) -------------------------
     def caption_logprobs(self, features, captions, word_to_id):
@@ -236,9 +225,7 @@ class NIC_RNNDecoder(nn.Module):
         through it: the recurrence is dic_nic_states_fwd / _bwd, the vocabulary projection losses.token_logprobs.  In train() mode
         the hidden states that enter the projection are dropped as in forward(); eval() draws no multiplier and returns
         score_captions' numbers bit for bit.  Frozen features skip the feature gradient."""
-        caps = torch.as_tensor(captions)
-        if caps.dim() not in (2, 3):
-            raise DicError(f"caption_logprobs: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+        caps = given_captions("caption_logprobs", captions)
         squeeze = caps.dim() == 2
         if squeeze:
             caps = caps.unsqueeze(1)

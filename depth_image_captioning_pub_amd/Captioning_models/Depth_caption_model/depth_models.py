@@ -11,7 +11,6 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
-import numpy as np
 import torch
 from torch import nn
 from torch.nn.utils.rnn import PackedSequence
@@ -19,6 +18,7 @@ from torch.nn.utils.rnn import PackedSequence
 from ... import losses, native
 from ..._lib import DicError
 from ..attention import Hard_Attention, Soft_Attention
+from ..util import given_captions, host, host_all, token_uniforms
 
 _DEC_KEYS = [k for k, _ in native.DECODER_FIELDS]
 _ENC_KEYS = [k for k, _ in native.DEPTH_FIELDS]
@@ -231,7 +231,7 @@ class _CaptionDecoderBase(nn.Module):
     def batch_sample(self, features, depth_features, word_to_id, max_length=30):
         """Greedy captions of a batch: np.int64 [B,max_length]  (depth_models.py:259-305)."""
         ids, _ = self._greedy(features, depth_features, word_to_id, max_length)
-        return ids.cpu().numpy().astype(np.int64)
+        return host(ids)
 
     # ---- beam-search decoding (no counterpart in the reference, whose evaluation is greedy; semantics: include/dic.h) -------
     @torch.no_grad()
@@ -247,10 +247,7 @@ class _CaptionDecoderBase(nn.Module):
         ids, scores, lengths = native.decoder_beam(self._weights(), _contig(features), _contig(depth_features),
                                                    word_to_id["<start>"], word_to_id["<end>"], beam_size, max_length,
                                                    float(length_penalty))
-        if return_all:
-            return (ids.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return ids[:, 0].cpu().numpy().astype(np.int64)
+        return host_all(ids, scores, lengths) if return_all else host(ids[:, 0])
 
     # ---- stochastic decoding (no counterpart in the reference; semantics: include/dic.h).  `sample` stays the greedy one-image call
     @torch.no_grad()
@@ -270,10 +267,7 @@ class _CaptionDecoderBase(nn.Module):
                                                                 top_k, top_p, seed)
         if S == 1:
             ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
-        if return_all:
-            return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return ids.cpu().numpy().astype(np.int64)
+        return host_all(ids, logprobs, lengths) if return_all else host(ids)
 
     @torch.no_grad()
     def stochastic_sample_tensors(self, features, depth_features, word_to_id, n_samples=1, max_length=30, temperature=1.0,
@@ -286,8 +280,7 @@ class _CaptionDecoderBase(nn.Module):
         features = _contig(features.detach())
         depth_features = _contig(depth_features.detach()) if depth_features is not None else None
         S = int(n_samples)
-        gen = torch.Generator(features.device).manual_seed(int(seed))
-        u = torch.rand((max_length, features.shape[0] * max(S, 1)), generator=gen, device=features.device)
+        u = token_uniforms(max_length, features.shape[0] * max(S, 1), seed, features.device)
         return native.decoder_sample(self._weights(), features, depth_features, word_to_id["<start>"], word_to_id["<end>"], S, u,
                                      max_length, float(temperature), int(top_k), float(top_p))
 
@@ -302,18 +295,11 @@ class _CaptionDecoderBase(nn.Module):
             raise DicError("score_captions: scoring is built for the soft-attention decoders only (the likelihood of a Gumbel-max "
                            "decode is an expectation over its attention draws); there is no hard-attention counterpart of that "
                            "marginal - hard_score_captions scores conditional on attention noise drawn from a seed")
-        caps = torch.as_tensor(captions)
-        if caps.dim() not in (2, 3):
-            raise DicError(f"score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
-        if skip_start:
-            caps = caps[..., 1:]
+        caps = given_captions("score_captions", captions, skip_start)
         features = _contig(features)
         logprobs, scores, lengths = native.decoder_score(self._weights(), features, _contig(depth_features), word_to_id["<start>"],
                                                          word_to_id["<end>"], caps.to(features.device))
-        if return_all:
-            return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return scores.cpu().numpy().astype(np.float32)
+        return host_all(logprobs, scores, lengths) if return_all else host(scores)
 
     # ---- the same log-probabilities, differentiable (no counterpart in the reference; semantics: include/dic.h) ---
     def caption_logprobs(self, features, depth_features, captions, word_to_id, skip_start=False):
@@ -326,11 +312,7 @@ class _CaptionDecoderBase(nn.Module):
         if self.hard:
             raise DicError("caption_logprobs: scoring is built for the soft-attention decoders only (the likelihood of a Gumbel-max "
                            "decode is an expectation over its attention draws); there is no hard-attention counterpart")
-        caps = torch.as_tensor(captions)
-        if caps.dim() not in (2, 3):
-            raise DicError(f"caption_logprobs: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
-        if skip_start:
-            caps = caps[..., 1:]
+        caps = given_captions("caption_logprobs", captions, skip_start)
         squeeze = caps.dim() == 2
         if squeeze:
             caps = caps.unsqueeze(1)
@@ -376,13 +358,11 @@ class _HardDecodeRoutes:
         ids, scores, lengths, cells = native.decoder_beam_hard(self._weights(), features, _contig(depth_features),
                                                                word_to_id["<start>"], word_to_id["<end>"], K, u, max_length,
                                                                float(length_penalty), bool(shared_noise), return_cells=True)
-        cells = cells.cpu().numpy().astype(np.int32)
+        cells = host(cells)
         if return_all:
-            out = (ids.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32),
-                   lengths.cpu().numpy().astype(np.int32))
+            out = host_all(ids, scores, lengths)
             return out + (cells,) if return_cells else out
-        best = ids[:, 0].cpu().numpy().astype(np.int64)
-        return (best, cells[:, 0]) if return_cells else best
+        return (host(ids[:, 0]), cells[:, 0]) if return_cells else host(ids[:, 0])
 
     @torch.no_grad()
     def hard_stochastic_sample(self, features, depth_features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0,
@@ -394,18 +374,14 @@ class _HardDecodeRoutes:
         depth_features = _contig(depth_features.detach()) if depth_features is not None else None
         S = int(n_samples)
         rows = features.shape[0] * max(S, 1)
-        gen = torch.Generator(features.device).manual_seed(int(seed))
-        u = torch.rand((max_length, rows), generator=gen, device=features.device)
+        u = token_uniforms(max_length, rows, seed, features.device)
         gu = self.attention_noise(max_length, features.shape[0] if shared_noise else rows, attention_seed, features.device)
         ids, logprobs, lengths = native.decoder_sample_hard(self._weights(), features, depth_features, word_to_id["<start>"],
                                                             word_to_id["<end>"], S, u, gu, max_length, float(temperature),
                                                             int(top_k), float(top_p), bool(shared_noise))
         if S == 1:
             ids, logprobs, lengths = ids[:, 0], logprobs[:, 0], lengths[:, 0]
-        if return_all:
-            return (ids.cpu().numpy().astype(np.int64), logprobs.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return ids.cpu().numpy().astype(np.int64)
+        return host_all(ids, logprobs, lengths) if return_all else host(ids)
 
     @torch.no_grad()
     def hard_score_captions(self, features, depth_features, captions, word_to_id, attention_seed=0, shared_noise=True,
@@ -413,11 +389,7 @@ class _HardDecodeRoutes:
         """Log-probability the hard model gives to GIVEN captions conditional on the attention noise: np.float32 [B] for captions
         int64 [B,T], [B,S] for [B,S,T].  Conventions of score_captions; with the attention_seed and noise layout of
         hard_beam_sample / hard_stochastic_sample it reproduces their scores."""
-        caps = torch.as_tensor(captions)
-        if caps.dim() not in (2, 3):
-            raise DicError(f"hard_score_captions: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
-        if skip_start:
-            caps = caps[..., 1:]
+        caps = given_captions("hard_score_captions", captions, skip_start)
         features = _contig(features)
         S = int(caps.shape[1]) if caps.dim() == 3 else 1
         u = self.attention_noise(caps.shape[-1], features.shape[0] * (1 if shared_noise else max(S, 1)), attention_seed,
@@ -425,10 +397,7 @@ class _HardDecodeRoutes:
         logprobs, scores, lengths = native.decoder_score_hard(self._weights(), features, _contig(depth_features),
                                                               word_to_id["<start>"], word_to_id["<end>"], caps.to(features.device), u,
                                                               bool(shared_noise))
-        if return_all:
-            return (logprobs.cpu().numpy().astype(np.float32), scores.cpu().numpy().astype(np.float32),
-                    lengths.cpu().numpy().astype(np.int32))
-        return scores.cpu().numpy().astype(np.float32)
+        return host_all(logprobs, scores, lengths) if return_all else host(scores)
 
 
 class CD_RNNDecoderWithSoftAttention(_CaptionDecoderBase):

@@ -154,3 +154,28 @@ class DepthCache:
         row = self.table[0].numel()
         check(_lib.load().dic_gather_rows(ptr(self.table), ptr(idx), len(keys), row, ptr(out), stream_ptr()), "dic_gather_rows")
         return out
+
+
+# ---- what the decode routes of the model classes share (depth_models, nic) ------------------------------------------------------------
+def host(t: torch.Tensor):
+    """A device output as a numpy array of its own type (ids int64, scores / log-probabilities float32, lengths / cells int32)."""
+    return t.cpu().numpy()
+
+
+def host_all(*tensors: torch.Tensor):
+    return tuple(host(t) for t in tensors)
+
+
+def token_uniforms(max_length: int, rows: int, seed: int, device) -> torch.Tensor:
+    """The token draws of a sampling route: torch.rand((max_length, rows)) of a generator on `device` seeded with `seed` - one
+    seed, one set of captions."""
+    gen = torch.Generator(device).manual_seed(int(seed))
+    return torch.rand((max_length, rows), generator=gen, device=device)
+
+
+def given_captions(what: str, captions, skip_start: bool = False) -> torch.Tensor:
+    """Captions to score as a tensor [B,T] or [B,S,T]; skip_start drops column 0 (collated captions begin with '<start>')."""
+    caps = torch.as_tensor(captions)
+    if caps.dim() not in (2, 3):
+        raise _lib.DicError(f"{what}: captions must be [B,T] or [B,S,T], got {tuple(caps.shape)}")
+    return caps[..., 1:] if skip_start else caps

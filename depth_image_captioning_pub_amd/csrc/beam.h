@@ -1,5 +1,6 @@
-// Beam-search selection shared by the two decode routes that keep K hypotheses per image: dic_decoder_beam (decoder_decode.hip,
-// soft attention) and dic_nic_beam (nic_decode.hip).  One candidate rule (include/dic.h), one copy of each piece:
+// Token selection shared by the decode routes of both decoders (decoder_decode.hip, nic_decode.hip): the greedy arg-max, and the
+// beam search of the routes that keep K hypotheses per image.  One candidate rule (include/dic.h), one copy of each piece:
+//   launch_argmax          argmax_kernel: the first maximum of a row of logits, the greedy token     (beam.hip)
 //   launch_beam_topk       beam_topk_kernel<K>: log-softmax of a row + its K best candidates          (beam.hip)
 //   beam_select_rank<K>    the K best of an image's K x K candidates become the new beams              (device, this header)
 //   launch_beam_backtrack  beam_backtrack_kernel: final ranking and the token histories                (beam.hip)
@@ -22,6 +23,9 @@ constexpr int kBeamMax = 8;
     case 7: { constexpr int KB_ = 7; STMT } break;     \
     default: { constexpr int KB_ = 8; STMT } break;    \
   }
+
+// Rows [0, B) of logits [B][V]: ids[b] = out[b*T + t] = the first maximum of row b; 0 for a row without one (all NaN or -inf).
+int launch_argmax(const float* logits, int B, int V, int t, int T, long long* ids, long long* out, hipStream_t st);
 
 // Rows [0, BK) of logits [BK][V]: lsm = logits - max - log sum exp(logits - max) (fp32), then the K best of score + lsm[v] (ties:
 // lower v), best first, into cand_val / cand_tok [row][K].  A finished beam has the single candidate (score, id_end).

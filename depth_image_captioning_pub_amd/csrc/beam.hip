@@ -1,7 +1,44 @@
-// The selection kernels both beam-search routes launch (beam.h): per-row top-K of the candidates and the final backtrack.
+// The selection kernels both decoders launch (beam.h): the greedy arg-max, per-row top-K of the candidates and the final backtrack.
 #include "beam.h"
 
 namespace dic {
+
+// ids[b] = argmax_v logits[b,v] (first maximum on ties, like torch.argmax); also out[b*T + t].  A row in which no element
+// compares greater than -inf (all NaN, or all -inf) gives token 0: the next step's embedding read stays inside the vocabulary.
+__global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ logits, int V, int t, int T,
+                                                      long long* __restrict__ ids, long long* __restrict__ out) {
+  __shared__ float bv[4];
+  __shared__ int bi[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* x = logits + (long long)b * V;
+  float best = -INFINITY;
+  int idx = 0x7fffffff;
+  for (int v = tid; v < V; v += 256) {
+    const float f = x[v];
+    if (f > best) { best = f; idx = v; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+  }
+  if (lane == 0) { bv[w] = best; bi[w] = idx; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < 4; ++i)
+      if (bv[i] > best || (bv[i] == best && bi[i] < idx)) { best = bv[i]; idx = bi[i]; }
+    if (idx == 0x7fffffff) idx = 0;
+    ids[b] = idx;
+    out[(long long)b * T + t] = idx;
+  }
+}
+
+int launch_argmax(const float* logits, int B, int V, int t, int T, long long* ids, long long* out, hipStream_t st) {
+  hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, V, t, T, ids, out);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
 
 // Row b*KB+k: lsm = logits - max - log sum exp(logits - max) (fp32), then the KB best of score + lsm[v] (ties: lower v), best
 // first, into cand_val / cand_tok [row][KB].  A finished beam has the single candidate (score, id_end); unused slots get

@@ -27,35 +27,6 @@ __global__ void __launch_bounds__(kE) embed_step_kernel(const float* __restrict_
   Xall[((long long)b * T + t) * kXK + threadIdx.x] = embed[id * kE + threadIdx.x];
 }
 
-// ids[b] = argmax_v logits[b,v] (first maximum on ties, like torch.argmax); also out[b*T + t]
-__global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ logits, int V, int t, int T,
-                                                      long long* __restrict__ ids, long long* __restrict__ out) {
-  __shared__ float bv[4];
-  __shared__ int bi[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float* x = logits + (long long)b * V;
-  float best = -INFINITY;
-  int idx = 0x7fffffff;
-  for (int v = tid; v < V; v += 256) {
-    const float f = x[v];
-    if (f > best) { best = f; idx = v; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
-  }
-  if (lane == 0) { bv[w] = best; bi[w] = idx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < 4; ++i)
-      if (bv[i] > best || (bv[i] == best && bi[i] < idx)) { best = bv[i]; idx = bi[i]; }
-    ids[b] = idx;
-    out[(long long)b * T + t] = idx;
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // beam search (dic_decoder_beam; semantics in include/dic.h, layout in DESIGN.md 5.6): KB hypotheses per image, rows b*KB + k.
 // Per step: beam_attn_kernel -> gate GEMM slabs -> lstm_fwd_kernel -> vocabulary GEMM -> beam_topk_kernel -> beam_select_kernel.
@@ -432,8 +403,7 @@ int dic_decoder_greedy(const dic_decoder_weights* w, int V, const float* feat_rg
     // pred = linear(h) (no dropout, depth_models.py:295); softmax is monotone -> argmax of the logits
     DIC_TRY(gemm(B, V, kH, op_rowk(ws.Hdrop + (long long)t * B * kH, kH), op_rowk(w->out_w, kH),
                  ep_store(ws.logits_step, V, w->out_b), st, 1, nullptr, 64));
-    hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, ws.logits_step, V, t, T, ws.ids, (long long*)out_ids);
-    DIC_LAUNCH_CHECK();
+    DIC_TRY(launch_argmax(ws.logits_step, B, V, t, T, ws.ids, (long long*)out_ids, st));
   }
   return DIC_OK;
 }
@@ -468,6 +438,19 @@ void row_carve(Carver& c, RowWs& w, int B, size_t R) {
 // The hard routes pass the step's attention noise: hard_row_attn_kernel<S> (decoder_hard.hip) takes the kernel's place and the
 // selected cells go to hard->cell_t (nullable); alpha_t is not used then.
 struct HardStep { const float* u_t; int noise_shared; int* cell_t; };
+
+// step t of a hard route over R = B*S rows: its noise is gumbel_u[t], B rows when the rows of an image share theirs, else R
+HardStep hard_step(const float* gumbel_u, int t, int noise_shared, int B, int R, int* cell_t) {
+  return HardStep{gumbel_u + (size_t)t * (size_t)(noise_shared ? B : R) * kL, noise_shared, cell_t};
+}
+
+// what a hard route requires of its noise arguments: behind the soft route's scalar checks, in front of its pointer check
+int check_hard_noise(const char* route, bool hard, int noise_shared, const float* gumbel_u) {
+  if (!hard) return DIC_OK;
+  DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
+  DIC_REQUIRE(gumbel_u != nullptr, "%s: null pointer", route);
+  return DIC_OK;
+}
 
 int launch_row_step(const RowWs& ws, const dic_decoder_weights* w, int V, int B, int S, const long long* tok, float* alpha_t,
                     float* h_out, int packed_off, hipStream_t st, const HardStep* hard = nullptr) {
@@ -544,8 +527,8 @@ int beam_route(const char* route, const dic_decoder_weights* w, int V, const flo
   DIC_REQUIRE(V >= K, "%s: vocabulary V=%d is smaller than the beam width K=%d", route, V, K);
   DIC_TRY(check_token_ids(route, V, id_start, id_end));
   DIC_REQUIRE(length_penalty >= 0.f, "%s: length_penalty=%g must be >= 0 (NaN is refused too)", route, (double)length_penalty);
-  if (hard) DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
-  DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace && (!hard || gumbel_u), "%s: null pointer", route);
+  DIC_TRY(check_hard_noise(route, hard, noise_shared, gumbel_u));
+  DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace, "%s: null pointer", route);
   const int T = max_length, BK = B * K;
   bool ov = false;
   BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov);
@@ -555,10 +538,9 @@ int beam_route(const char* route, const dic_decoder_weights* w, int V, const flo
   hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
                      ws.Cst);
   DIC_LAUNCH_CHECK();
-  const size_t noise_rows = noise_shared ? (size_t)B : (size_t)BK;
   for (int t = 0; t < T; ++t) {
     if (hard) {     // slot k of image b consumes u[t, b*K + k] (or u[t, b]) whichever hypothesis the selection of step t-1 put there
-      const HardStep hs{gumbel_u + (size_t)t * noise_rows * kL, noise_shared, out_cells ? ws.cell_hist + (size_t)t * BK : nullptr};
+      const HardStep hs = hard_step(gumbel_u, t, noise_shared, B, BK, out_cells ? ws.cell_hist + (size_t)t * BK : nullptr);
       DIC_TRY(launch_row_step(ws, w, V, B, K, ws.prev, nullptr, ws.Hdrop, 0, st, &hs));
     } else {
       float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * BK * kL : nullptr;
@@ -646,9 +628,8 @@ int sample_route(const char* route, const dic_decoder_weights* w, int V, const f
               (double)temperature);
   DIC_REQUIRE(top_k >= 0 && top_k <= V, "%s: top_k=%d is outside 0..V=%d (0: no limit)", route, top_k, V);
   DIC_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p=%g is outside (0, 1] (1: off; NaN is refused too)", route, (double)top_p);
-  if (hard) DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
-  DIC_REQUIRE(w && feat_rgb && uniform_u && out_ids && out_logprobs && out_lengths && workspace && (!hard || gumbel_u),
-              "%s: null pointer", route);
+  DIC_TRY(check_hard_noise(route, hard, noise_shared, gumbel_u));
+  DIC_REQUIRE(w && feat_rgb && uniform_u && out_ids && out_logprobs && out_lengths && workspace, "%s: null pointer", route);
   const int T = max_length, R = B * S;
   bool ov = false;
   SampleWs ws = sample_carve(workspace, workspace_bytes, B, S, T, V, &ov);
@@ -657,10 +638,9 @@ int sample_route(const char* route, const dic_decoder_weights* w, int V, const f
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
   hipLaunchKernelGGL(sample_init_kernel, dim3(B), dim3(kH), 0, st, S, id_start, ws.fin, out_lengths, ws.prev, ws.Hst, ws.Cst);
   DIC_LAUNCH_CHECK();
-  const size_t noise_rows = noise_shared ? (size_t)B : (size_t)R;
   for (int t = 0; t < T; ++t) {
     if (hard) {
-      const HardStep hs{gumbel_u + (size_t)t * noise_rows * kL, noise_shared, out_cells ? ws.cell_hist + (size_t)t * R : nullptr};
+      const HardStep hs = hard_step(gumbel_u, t, noise_shared, B, R, out_cells ? ws.cell_hist + (size_t)t * R : nullptr);
       DIC_TRY(launch_row_step(ws, w, V, B, S, ws.prev, nullptr, ws.Hdrop, 0, st, &hs));
     } else {
       float* alpha_t = alphas_out ? ws.alpha_hist + (size_t)t * R * kL : nullptr;
@@ -746,9 +726,8 @@ int score_route(const char* route, const dic_decoder_weights* w, int V, const fl
   DIC_REQUIRE((long long)B * S * max_length <= kScoreMaxM, "%s: B*S*max_length=%lld exceeds %d token positions per call", route,
               (long long)B * S * max_length, kScoreMaxM);
   DIC_TRY(check_token_ids(route, V, id_start, id_end));
-  if (hard) DIC_REQUIRE(noise_shared == 0 || noise_shared == 1, "%s: noise_shared=%d must be 0 (per row) or 1 (per image)", route, noise_shared);
-  DIC_REQUIRE(w && feat_rgb && captions && out_logprobs && out_scores && out_lengths && workspace && (!hard || gumbel_u),
-              "%s: null pointer", route);
+  DIC_TRY(check_hard_noise(route, hard, noise_shared, gumbel_u));
+  DIC_REQUIRE(w && feat_rgb && captions && out_logprobs && out_scores && out_lengths && workspace, "%s: null pointer", route);
   const int T = max_length, R = B * S;
   bool ov = false;
   ScoreWs ws = score_carve(workspace, workspace_bytes, B, S, T, V, &ov);
@@ -758,10 +737,9 @@ int score_route(const char* route, const dic_decoder_weights* w, int V, const fl
   hipLaunchKernelGGL(score_init_kernel, dim3(B), dim3(kH), 0, st, S, T, V, id_start, id_end, (const long long*)captions, ws.tok_in,
                      ws.target, out_lengths, ws.Hst, ws.Cst);
   DIC_LAUNCH_CHECK();
-  const size_t noise_rows = noise_shared ? (size_t)B : (size_t)R;
   for (int t = 0; t < T; ++t) {
     // the cell writes h' / c' into slot 1 and appends h' to the history (packed row t*R + r)
-    const HardStep hs{hard ? gumbel_u + (size_t)t * noise_rows * kL : nullptr, noise_shared, nullptr};
+    const HardStep hs = hard ? hard_step(gumbel_u, t, noise_shared, B, R, nullptr) : HardStep{};
     DIC_TRY(launch_row_step(ws, w, V, B, S, ws.tok_in + (size_t)t * R, nullptr, ws.hist, t * R, st, hard ? &hs : nullptr));
     if (t + 1 < T) {
       hipLaunchKernelGGL(score_handover_kernel, dim3(R), dim3(kH), 0, st, ws.Hst, ws.Cst);

@@ -48,36 +48,6 @@ __global__ void __launch_bounds__(kNicThreads) nic_step_kernel(const float* __re
   }
 }
 
-// ids[b] = argmax_v logits[b, v] (first maximum on ties, like torch.argmax), also out[b * T + t]
-__global__ void __launch_bounds__(256) nic_argmax_kernel(const float* __restrict__ logits, int V, int t, int T,
-                                                          long long* __restrict__ ids, long long* __restrict__ out) {
-  __shared__ float bv[4];
-  __shared__ int bi[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float* x = logits + (long long)b * V;
-  float best = -INFINITY;
-  int idx = 0x7fffffff;
-  for (int v = tid; v < V; v += 256) {
-    const float f = x[v];
-    if (f > best) { best = f; idx = v; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    if (ob > best || (ob == best && oi < idx)) { best = ob; idx = oi; }
-  }
-  if (lane == 0) { bv[w] = best; bi[w] = idx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < 4; ++i)
-      if (bv[i] > best || (bv[i] == best && bi[i] < idx)) { best = bv[i]; idx = bi[i]; }
-    if (idx == 0x7fffffff) idx = 0;            // a row of NaN: stay inside the vocabulary
-    ids[b] = idx;
-    out[(long long)b * T + t] = idx;
-  }
-}
-
 // One beam-search step for the KB hypotheses (rows b*KB + k) of image b = blockIdx.x: nic_step_kernel with the selection and
 // the state hand-over in front.  At t > 0 the workgroup first turns the image's KB x KB candidates of step t-1 into the new beams
 // (beam_select_rank), then loads h0, c0, h1, c1 of each survivor's PARENT row - h into LDS, c into registers - and only behind
@@ -276,8 +246,7 @@ int dic_nic_greedy(const dic_nic_weights* w, int V, const float* features, int B
     DIC_LAUNCH_CHECK();
     // softmax is monotone: argmax of the logits (nic.py:164-166)
     DIC_TRY(gemm(B, V, kH, op_rowk(ws.Hout, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
-    hipLaunchKernelGGL(nic_argmax_kernel, dim3(B), dim3(256), 0, st, ws.logits, V, t, max_length, ws.ids, (long long*)out_ids);
-    DIC_LAUNCH_CHECK();
+    DIC_TRY(launch_argmax(ws.logits, B, V, t, max_length, ws.ids, (long long*)out_ids, st));
   }
   return DIC_OK;
 }

@@ -1,0 +1,247 @@
+"""Greedy, beam, sample and score of both decoders (dic_decoder_* soft and hard, dic_nic_*; semantics: include/dic.h).  One body per
+route: what the routes share exists once, a soft / hard pair is ONE private body that takes the attention noise or None under two
+thin public signatures, and the NIC functions keep their own dic_nic_* call lines (other argument lists).  DESIGN.md 5.25."""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+from typing import Dict, Optional
+
+import torch
+
+from .. import _lib
+from .._lib import check, ptr, stream_ptr
+from ._core import L_CELLS, _dev, _workspace
+from .decoder import _decoder_prologue
+from .nic import _nic_prologue
+
+
+def _outputs(first, per_token: bool, B: int, S: int, T: int, device):
+    """The output triple of a route, no extent below 1 (the call refuses such sizes itself): ([B,S,T] of dtype `first`, float32
+    [B,S,T] if per_token else [B,S], lengths int32 [B,S])."""
+    ss, tt = max(S, 1), max(T, 1)
+    return (torch.empty((B, ss, tt), dtype=first, device=device),
+            torch.empty((B, ss, tt) if per_token else (B, ss), dtype=torch.float32, device=device),
+            torch.empty((B, ss), dtype=torch.int32, device=device))
+
+
+_beam_outputs = functools.partial(_outputs, torch.int64, False)        # ids [B,K,T], scores [B,K], lengths [B,K]
+_sample_outputs = functools.partial(_outputs, torch.int64, True)       # ids [B,S,T], logprobs [B,S,T], lengths [B,S]
+_score_outputs = functools.partial(_outputs, torch.float32, False)     # logprobs [B,S,T], scores [B,S], lengths [B,S]
+
+
+def _step_record(want: bool, hard: bool, B: int, S: int, T: int, device) -> Optional[torch.Tensor]:
+    """The optional per-step output of a beam / sample route: alphas float32 [B,S,T,196] (soft) or cells int32 [B,S,T] (hard)."""
+    if not want:
+        return None
+    shape, dtype = ((B, max(S, 1), T), torch.int32) if hard else ((B, max(S, 1), T, L_CELLS), torch.float32)
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _captions(what: str, captions: torch.Tensor, B: int):
+    """(captions int64 [B,S,T] on the device, whether they came as [B,T], S, T)."""
+    cap = _dev(captions, "captions", torch.int64)
+    squeeze = cap.dim() == 2
+    if squeeze:
+        cap = cap.unsqueeze(1)
+    if cap.dim() != 3 or cap.shape[0] != B:
+        raise _lib.DicError(f"{what}: captions must be [B,T] or [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+    return cap, squeeze, int(cap.shape[1]), int(cap.shape[2])
+
+
+def _as_given(squeeze: bool, outputs):
+    """[B,S,..] outputs as the captions came: [B,..] for captions [B,T]."""
+    return tuple(o[:, 0] for o in outputs) if squeeze else outputs
+
+
+def _uniforms(what: str, uniform_u: torch.Tensor, max_length, rows: int) -> torch.Tensor:
+    u = _dev(uniform_u, "uniform_u")
+    if tuple(u.shape) != (max_length, rows):
+        raise _lib.DicError(f"{what}: uniform_u must be [max_length, B*n_samples] = [{max_length}, {rows}], got {tuple(u.shape)}")
+    return u
+
+
+def _hard_noise(what: str, gumbel_u: torch.Tensor, max_length: int, B: int, S: int, noise_shared: bool) -> torch.Tensor:
+    """The attention noise of a hard route: float32 [max_length, B if the rows of an image share it else B*S, 196]."""
+    u = _dev(gumbel_u, "gumbel_u")
+    rows = B if noise_shared else B * S
+    if tuple(u.shape) != (max_length, rows, L_CELLS):
+        raise _lib.DicError(f"{what}: gumbel_u must be [max_length, {'B' if noise_shared else 'B*S'}, {L_CELLS}] = "
+                            f"[{max_length}, {rows}, {L_CELLS}] with noise_shared={bool(noise_shared)}, got {tuple(u.shape)}")
+    return u
+
+
+def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
+                   id_start: int, max_length: int = 30, mode: int = 0, gumbel_u: Optional[torch.Tensor] = None):
+    """dic_decoder_greedy. Returns (ids int64 [B,max_length] on device, alphas [B,max_length,196])."""
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    ws = _workspace(lib.dic_decoder_greedy_workspace_bytes, f_rgb.device, B, max_length, vocab)
+    ids = torch.empty((B, max_length), dtype=torch.int64, device=f_rgb.device)
+    alphas = torch.empty((B, max_length, L_CELLS), dtype=torch.float32, device=f_rgb.device)
+    gu = _dev(gumbel_u, "gumbel_u") if gumbel_u is not None else None
+    rc = lib.dic_decoder_greedy(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, int(id_start), max_length, mode, ptr(gu), ptr(ids),
+                                ptr(alphas), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_decoder_greedy")
+    return ids, alphas
+
+
+# ---- attention decoder: beam / sample / score.  noise: None (soft) or (gumbel_u, noise_shared) (hard, conditional on that noise) -------
+def _decoder_beam(what, weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length, length_penalty, record, noise):
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    K, dev = int(beam_size), f_rgb.device
+    u = _hard_noise(what, noise[0], max_length, B, max(K, 1), noise[1]) if noise else None
+    ws = _workspace(lib.dic_decoder_beam_workspace_bytes, dev, B, K, max_length, vocab)
+    ids, scores, lengths = _beam_outputs(B, K, max_length, dev)
+    rec = _step_record(record, noise is not None, B, K, max_length, dev)
+    head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, int(id_start), int(id_end), max_length, length_penalty)
+    tail = (ptr(ids), ptr(scores), ptr(lengths), ptr(rec), ptr(ws), ws.numel(), stream_ptr())
+    rc = (lib.dic_decoder_beam(*head, *tail) if noise is None else
+          lib.dic_decoder_beam_hard(*head, ptr(u), int(bool(noise[1])), *tail))
+    check(rc, "dic_" + what)
+    return (ids, scores, lengths, rec) if record else (ids, scores, lengths)
+
+
+def _decoder_sample(what, weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u, max_length, temperature, top_k,
+                    top_p, record, noise):
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    S, dev = int(n_samples), f_rgb.device
+    u = _uniforms(what, uniform_u, max_length, B * max(S, 1))
+    gu = _hard_noise(what, noise[0], max_length, B, max(S, 1), noise[1]) if noise else None
+    ws = _workspace(lib.dic_decoder_sample_workspace_bytes, dev, B, S, max_length, vocab)
+    ids, logprobs, lengths = _sample_outputs(B, S, max_length, dev)
+    rec = _step_record(record, noise is not None, B, S, max_length, dev)
+    head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), max_length, temperature, int(top_k),
+            top_p, ptr(u))
+    tail = (ptr(ids), ptr(logprobs), ptr(lengths), ptr(rec), ptr(ws), ws.numel(), stream_ptr())
+    rc = (lib.dic_decoder_sample(*head, *tail) if noise is None else
+          lib.dic_decoder_sample_hard(*head, ptr(gu), int(bool(noise[1])), *tail))
+    check(rc, "dic_" + what)
+    return (ids, logprobs, lengths, rec) if record else (ids, logprobs, lengths)
+
+
+def _decoder_score(what, weights, feat_rgb, feat_depth, id_start, id_end, captions, noise):
+    lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
+    cap, squeeze, S, T = _captions(what, captions, B)
+    u = _hard_noise(what, noise[0], max(T, 1), B, max(S, 1), noise[1]) if noise else None
+    ws = _workspace(lib.dic_decoder_score_workspace_bytes, f_rgb.device, B, S, T, vocab)
+    logprobs, scores, lengths = _score_outputs(B, S, T, f_rgb.device)
+    head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), T, ptr(cap))
+    tail = (ptr(logprobs), ptr(scores), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
+    rc = (lib.dic_decoder_score(*head, *tail) if noise is None else
+          lib.dic_decoder_score_hard(*head, ptr(u), int(bool(noise[1])), *tail))
+    check(rc, "dic_" + what)
+    return _as_given(squeeze, (logprobs, scores, lengths))
+
+
+def decoder_beam(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                 id_end: int, beam_size: int, max_length: int = 30, length_penalty: float = 0.0,
+                 return_alphas: bool = False):
+    """dic_decoder_beam: fixed-width beam search of the soft-attention decoder, on the device (semantics: include/dic.h).
+    Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K][, alphas [B,K,max_length,196]]), best first."""
+    return _decoder_beam("decoder_beam", weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length, length_penalty,
+                         return_alphas, None)
+
+
+def decoder_beam_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                      id_end: int, beam_size: int, gumbel_u: torch.Tensor, max_length: int = 30, length_penalty: float = 0.0,
+                      noise_shared: bool = True, return_cells: bool = False):
+    """dic_decoder_beam_hard: fixed-width beam search of the hard-attention (Gumbel-max) decoder conditional on the attention noise
+    gumbel_u - float32 [max_length, B, 196] (noise_shared) or [max_length, B*beam_size, 196], values in (0,1) - on the device
+    (semantics: include/dic.h).  Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K][, cells int32
+    [B,K,max_length]: the selected cell along each hypothesis, -1 from its length on]), best first."""
+    return _decoder_beam("decoder_beam_hard", weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length, length_penalty,
+                         return_cells, (gumbel_u, noise_shared))
+
+
+def decoder_sample(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                   id_end: int, n_samples: int, uniform_u: torch.Tensor, max_length: int = 30, temperature: float = 1.0,
+                   top_k: int = 0, top_p: float = 1.0, return_alphas: bool = False):
+    """dic_decoder_sample: `n_samples` captions per image drawn from the soft-attention decoder's distribution, on the device
+    (semantics: include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1) - the draws are an input.
+    Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S][, alphas [B,S,max_length,196]])."""
+    return _decoder_sample("decoder_sample", weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u, max_length,
+                           temperature, top_k, top_p, return_alphas, None)
+
+
+def decoder_sample_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                        id_end: int, n_samples: int, uniform_u: torch.Tensor, gumbel_u: torch.Tensor, max_length: int = 30,
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, noise_shared: bool = False,
+                        return_cells: bool = False):
+    """dic_decoder_sample_hard: `n_samples` captions per image drawn from the hard-attention decoder conditional on the attention
+    noise, on the device (semantics: include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1), the token draws;
+    gumbel_u: float32 [max_length, B*n_samples, 196] or, with noise_shared, [max_length, B, 196], in (0,1).
+    Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S][, cells int32 [B,S,max_length]])."""
+    return _decoder_sample("decoder_sample_hard", weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u, max_length,
+                           temperature, top_k, top_p, return_cells, (gumbel_u, noise_shared))
+
+
+def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                  id_end: int, captions: torch.Tensor):
+    """dic_decoder_score: the log-probability the soft-attention decoder gives every token of given captions, on the device
+    (semantics: include/dic.h).  captions: int64 [B,T] (one per image) or [B,S,T] (S <= 8 per image), without '<start>'.
+    Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
+    return _decoder_score("decoder_score", weights, feat_rgb, feat_depth, id_start, id_end, captions, None)
+
+
+def decoder_score_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                       id_end: int, captions: torch.Tensor, gumbel_u: torch.Tensor, noise_shared: bool = True):
+    """dic_decoder_score_hard: the log-probability the hard-attention decoder gives every token of given captions, conditional on
+    the attention noise, on the device (semantics: include/dic.h).  captions: int64 [B,T] or [B,S,T] (S <= 8), without '<start>';
+    gumbel_u: float32 [T, B, 196] (noise_shared) or [T, B*S, 196], in (0,1).
+    Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
+    return _decoder_score("decoder_score_hard", weights, feat_rgb, feat_depth, id_start, id_end, captions, (gumbel_u, noise_shared))
+
+
+# ---- NIC decoder: the same helpers, its own call lines (no id_start, no depth features) ----------------------------------------------
+def nic_greedy(weights: Dict[str, torch.Tensor], features: torch.Tensor, max_length: int = 30) -> torch.Tensor:
+    """dic_nic_greedy.  Returns ids int64 [B,max_length] on the device."""
+    lib, f, B, vocab, wp, keep = _nic_prologue(weights, features)
+    ws = _workspace(lib.dic_nic_greedy_workspace_bytes, f.device, B, int(max_length), vocab)
+    ids = torch.empty((B, max(int(max_length), 1)), dtype=torch.int64, device=f.device)
+    rc = lib.dic_nic_greedy(C.byref(wp), vocab, ptr(f), B, int(max_length), ptr(ids), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_greedy")
+    return ids
+
+
+def nic_beam(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, beam_size: int, max_length: int = 30,
+             length_penalty: float = 0.0):
+    """dic_nic_beam: fixed-width beam search of the NIC decoder, on the device (semantics: include/dic.h).
+    Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K]), best first."""
+    lib, f, B, vocab, wp, keep = _nic_prologue(weights, features)
+    K, T = int(beam_size), int(max_length)
+    ws = _workspace(lib.dic_nic_beam_workspace_bytes, f.device, B, K, T, vocab)
+    ids, scores, lengths = _beam_outputs(B, K, T, f.device)
+    rc = lib.dic_nic_beam(C.byref(wp), vocab, ptr(f), B, K, int(id_end), T, length_penalty,
+                          ptr(ids), ptr(scores), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_beam")
+    return ids, scores, lengths
+
+
+def nic_score(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, captions: torch.Tensor):
+    """dic_nic_score: the log-probability the NIC decoder gives every token of given captions, on the device (semantics:
+    include/dic.h).  captions: int64 [B,T] (one per image) or [B,S,T] (S <= 8 per image) - the ids nic_greedy / nic_beam return.
+    Returns (logprobs float32, scores float32, lengths int32) of shapes [B,T], [B], [B] or [B,S,T], [B,S], [B,S]."""
+    lib, f, B, vocab, wp, keep = _nic_prologue(weights, features)
+    cap, squeeze, S, T = _captions("nic_score", captions, B)
+    ws = _workspace(lib.dic_nic_score_sizes, f.device, B, S, T, vocab)
+    logprobs, scores, lengths = _score_outputs(B, S, T, f.device)
+    rc = lib.dic_nic_score(C.byref(wp), vocab, ptr(f), B, S, int(id_end), T, ptr(cap), ptr(logprobs), ptr(scores), ptr(lengths),
+                           ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_score")
+    return _as_given(squeeze, (logprobs, scores, lengths))
+
+
+def nic_sample(weights: Dict[str, torch.Tensor], features: torch.Tensor, id_end: int, n_samples: int, uniform_u: torch.Tensor,
+               max_length: int = 30, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    """dic_nic_sample: `n_samples` captions per image drawn from the NIC decoder's distribution, on the device (semantics:
+    include/dic.h).  uniform_u: float32 [max_length, B*n_samples] in [0,1) - the draws are an input.
+    Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S])."""
+    lib, f, B, vocab, wp, keep = _nic_prologue(weights, features)
+    S, T = int(n_samples), int(max_length)
+    u = _uniforms("nic_sample", uniform_u, T, B * max(S, 1))
+    ws = _workspace(lib.dic_nic_sample_sizes, f.device, B, S, T, vocab)
+    ids, logprobs, lengths = _sample_outputs(B, S, T, f.device)
+    rc = lib.dic_nic_sample(C.byref(wp), vocab, ptr(f), B, S, int(id_end), T, float(temperature), int(top_k), float(top_p), ptr(u),
+                            ptr(ids), ptr(logprobs), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
+    check(rc, "dic_nic_sample")
+    return ids, logprobs, lengths

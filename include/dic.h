@@ -121,7 +121,8 @@ int dic_decoder_bwd_cells(const dic_decoder_weights* w, int V, int cells, const 
 
 /* greedy decoding: batch_sample / sample (depth_models.py:216-305 soft, 698-789 hard with Gumbel-max).
  *   Starts from id_start (<start>), max_length steps, dropout off, token = argmax(linear(h)); the previous
- *   token stays on the device (the reference copies it to the host every step, :298-299).
+ *   token stays on the device (the reference copies it to the host every step, :298-299).  argmax is the first maximum; a row
+ *   of logits without one (all NaN or all -inf) gives token 0, inside the vocabulary.
  *   out_ids: int64 [B,max_length]; alphas_out (nullable when max_length <= 8): [B,max_length,196];
  *   mode 0 soft | 2 hard (gumbel_u [max_length,B,196]). */
 size_t dic_decoder_greedy_workspace_bytes(int B, int max_length, int V);
@@ -494,7 +495,8 @@ int dic_scst_loss(const float* logprobs, const int* lengths, const float* reward
  *     give bit-identical gradients.
  *   Greedy decode (batch_sample / sample, nic.py:126-175): step 0 input is features[b], states zero, exactly max_length steps,
  *     token = argmax(linear(h_top)) (softmax is monotone; first maximum on ties), next input embed(token); there is NO start token
- *     and no early stop.  Tokens stay on the device.  out_ids int64 [B,max_length].
+ *     and no early stop.  Tokens stay on the device.  out_ids int64 [B,max_length].  A row of logits without a maximum (all NaN or
+ *     all -inf) gives token 0, inside the vocabulary.
  *   Every argument violation - a null pointer, B <= 0, V <= 0, cells < 1, lengths not descending, a length < 1 or > cap_stride, a
  *     short workspace, max_length < 1 - returns a negative code with a dic_last_error() text that starts with the entry point's
  *     name, before anything is launched.  The workspace queries return 0 for sizes the calls refuse. */

@@ -8,7 +8,7 @@ ones (the method of scripts/bench_beam.py).
 usage: python scripts/bench_nic_beam.py [--batch 64] [--beams 5] [--steps 30] [--vocab 10000] [--iters 30] [--warmup 3]
                                         [--only all|beam|replicated|greedy] [--kernel-stats <kernel_stats.csv>] [--out <json>]
 --kernel-stats: the per-kernel table of a separate `rocprofv3 --kernel-trace --stats --output-format csv -- python
-scripts/bench_nic_beam.py --iters 5 --warmup 2` run; the average times of beam_topk_kernel<K> and nic_argmax_kernel from it give
+scripts/bench_nic_beam.py --iters 5 --warmup 2` run; the average times of beam_topk_kernel<K> and argmax_kernel from it give
 the allowance  T * (top-K - argmax) + 10 % of (b)  that (a) - (b) is compared with.  Prints one line per route and a final JSON line."""
 import argparse
 import csv
@@ -79,12 +79,12 @@ if "beam_ms" in out and "replicated_ms" in out:
     if a.kernel_stats:
         avg = kernel_avg_us(a.kernel_stats)
         topk = next(v for k, v in avg.items() if "beam_topk_kernel" in k and f"<{K}>" in k)
-        argmax = next(v for k, v in avg.items() if "nic_argmax_kernel" in k)
+        argmax = next(v for k, v in avg.items() if "argmax_kernel" in k)
         out["topk_us"], out["argmax_us"] = topk, argmax
         out["allowance_ms"] = T * (topk - argmax) / 1e3 + 0.10 * out["replicated_ms"]
         out["within_allowance"] = out["beam_minus_replicated_ms"] <= out["allowance_ms"]
         out["kernels_us"] = {k: round(v, 2) for k, v in avg.items() if any(s in k for s in ("nic_", "beam_", "gemm"))}
-        print(f"beam_topk_kernel<{K}> {topk:.1f} us, nic_argmax_kernel {argmax:.1f} us: allowance {out['allowance_ms']:.3f} ms -> "
+        print(f"beam_topk_kernel<{K}> {topk:.1f} us, argmax_kernel {argmax:.1f} us: allowance {out['allowance_ms']:.3f} ms -> "
               f"{'within' if out['within_allowance'] else 'MISSED'}")
 print(json.dumps(out))
 if a.out:

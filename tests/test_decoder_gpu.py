@@ -179,6 +179,30 @@ def test_decoder_no_depth_features_is_base_model(lib):
     _assert_close("alphas", alphas, al_ref, 1e-4)
 
 
+def _argmax_bias(case, vocab=300):
+    """linear.bias of the two arg-max cases (linear.weight is zeroed: the logits are exactly this row)."""
+    if case == "nan":
+        return torch.full((vocab,), float("nan"))
+    bias = torch.zeros(vocab)
+    bias[[70, 263]] = 1.0          # the same maximum in wave 1 / lane 6 / first stride and in wave 0 / lane 7 / second stride
+    return bias
+
+
+@pytest.mark.parametrize("case,want", [("tie", 70), ("nan", 0)])
+def test_greedy_argmax_takes_the_first_maximum_and_stays_in_the_vocabulary(lib, case, want):
+    """The arg-max of dic_decoder_greedy (launch_argmax, shared with dic_nic_greedy) at V = 300, no multiple of its 256 threads:
+    a maximum that occurs twice, in different waves and stride iterations, goes to the lower token; a row of NaN gives token 0."""
+    B, T, V = 2, 3, 300
+    w = syn.decoder_weights(V, seed=31)
+    w["linear.weight"] = torch.zeros_like(w["linear.weight"])
+    w["linear.bias"] = _argmax_bias(case, V)
+    ids, _ = native.decoder_greedy(_to_dev(w), syn.features(B, 32).to(DEV), syn.features(B, 33, scale=0.5).to(DEV),
+                                   syn.special_token_ids(V)["<start>"], T)
+    print(f"{case}: ids {ids.cpu().tolist()}")
+    assert ids.dtype == torch.int64 and tuple(ids.shape) == (B, T)
+    assert torch.equal(ids.cpu(), torch.full((B, T), want, dtype=torch.int64))
+
+
 def test_decoder_rejects_unsorted_lengths(lib):
     w, f_rgb, f_dep, caps, lens = _inputs([5, 4, 2], 40, 5)
     with pytest.raises(Exception, match="descending"):

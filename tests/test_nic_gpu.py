@@ -167,6 +167,23 @@ def test_greedy_full_size_matches_the_fp64_restatement(lib):
     assert bool(same[ok].all()), f"rows {torch.nonzero(ok & ~same).flatten().tolist()} differ"
 
 
+@pytest.mark.parametrize("case,want", [("tie", 70), ("nan", 0)])
+def test_greedy_argmax_takes_the_first_maximum_and_stays_in_the_vocabulary(lib, case, want):
+    """The arg-max of dic_nic_greedy (launch_argmax, shared with dic_decoder_greedy) at V = 300, no multiple of its 256 threads,
+    on logits that are exactly linear.bias (linear.weight zeroed): a maximum that occurs twice - v = 70: wave 1, lane 6, first
+    stride; v = 263: wave 0, lane 7, second stride - goes to the lower token; a row of NaN gives token 0."""
+    B, T, V = 2, 3, 300
+    w, hw = syn.nic_weights(V, seed=31)
+    w["linear.weight"] = torch.zeros_like(w["linear.weight"])
+    w["linear.bias"] = torch.full((V,), float("nan")) if case == "nan" else torch.zeros(V).index_fill_(0, torch.tensor([70, 263]), 1.0)
+    hg = _to_dev(hw)
+    _, feats = native.nic_head_forward(hg["linear.weight"], hg["linear.bias"], syn.nic_map(B, 49, 32).to(DEV))
+    ids = native.nic_greedy(_to_dev(w), feats, T)
+    print(f"{case}: ids {ids.cpu().tolist()}")
+    assert ids.dtype == torch.int64 and tuple(ids.shape) == (B, T)
+    assert torch.equal(ids.cpu(), torch.full((B, T), want, dtype=torch.int64))
+
+
 def test_shim_sample_is_row_zero_of_batch_sample(lib):
     from depth_image_captioning_pub_amd.Captioning_models.Base_caption_model.nic import NIC_RNNDecoder
     w, hw, fmap = nc.greedy_inputs("golden")
