@@ -146,6 +146,38 @@ class _CaptionStatesFn(torch.autograd.Function):
             grads[k] for k in native.STATES_GRAD_KEYS)
 
 
+class _HardCaptionStatesFn(torch.autograd.Function):
+    """_CaptionStatesFn along given attention cells (dic_decoder_states_hard_fwd / _bwd): returns the hidden states and the
+    log-probabilities of the cells, [T,R] as losses.token_logprobs lays out its own."""
+
+    @staticmethod
+    def forward(ctx, cfg, features, depth_features, captions, cells, *params):
+        ctx.set_materialize_grads(False)
+        weights = {k: p.detach() for k, p in zip(native.STATES_GRAD_KEYS, params)}
+        weights.update(cfg["linear"])
+        hidden, targets, cell_lp, lengths, tape = native.decoder_states_hard_forward(
+            weights, _contig(features.detach()), _contig(depth_features.detach()) if depth_features is not None else None,
+            cfg["id_start"], cfg["id_end"], captions, cells, cfg.get("drop_mult"))
+        ctx.tape = tape
+        ctx.has_depth = depth_features is not None
+        cfg["targets"], cfg["lengths"] = targets, lengths
+        return hidden, cell_lp
+
+    @staticmethod
+    def backward(ctx, d_hidden, d_cell_lp):
+        n = 5 + len(native.STATES_GRAD_KEYS)
+        if d_hidden is None and d_cell_lp is None:
+            return (None,) * n
+        if d_hidden is None:
+            d_hidden = torch.zeros((ctx.tape.T, ctx.tape.B * ctx.tape.S, native.D_HID), dtype=torch.float32, device=d_cell_lp.device)
+        need_rgb, need_depth = ctx.needs_input_grad[1], ctx.has_depth and ctx.needs_input_grad[2]
+        grads, dfeat = native.decoder_states_hard_backward(ctx.tape, _contig(d_hidden),
+                                                           _contig(d_cell_lp) if d_cell_lp is not None else None,
+                                                           need_features=need_rgb or need_depth)
+        return (None, dfeat if need_rgb else None, dfeat if need_depth else None, None, None) + tuple(
+            grads[k] for k in native.STATES_GRAD_KEYS)
+
+
 class _CaptionDecoderBase(nn.Module):
     """Shared plumbing of the soft / hard decoders (parameters live in standard torch sub-modules)."""
 
@@ -311,7 +343,8 @@ class _CaptionDecoderBase(nn.Module):
         projection are dropped as in forward(); eval() has no dropout.  Frozen features or a frozen `linear` skip their kernels."""
         if self.hard:
             raise DicError("caption_logprobs: scoring is built for the soft-attention decoders only (the likelihood of a Gumbel-max "
-                           "decode is an expectation over its attention draws); there is no hard-attention counterpart")
+                           "decode is an expectation over its attention draws); there is no hard-attention counterpart of that "
+                           "marginal - scst.hard_caption_logprobs gives the joint log-probability of captions and attended cells")
         caps = given_captions("caption_logprobs", captions, skip_start)
         squeeze = caps.dim() == 2
         if squeeze:

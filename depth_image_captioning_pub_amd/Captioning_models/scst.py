@@ -15,6 +15,9 @@ gradient exchange with a global token count - is engine.CaptionTrainer.scst_step
 for nn.Module decoders and torch optimisers.  nic_scst_step is the step for the NIC baseline's decoder (dic_nic_states_fwd / _bwd,
 DESIGN.md 5.21; its engine form is NicTrainer.scst_step); it takes its candidates as an argument or from the beam search, and
 nic_scst_sample_step is the same step on captions drawn with dic_nic_sample (NicTrainer.scst_step(sample=True)).
+The hard-attention decoders train through their drawn attention cells instead: hard_sample_tensors draws joint
+samples (tokens, cells), hard_caption_logprobs gives their joint log-probability with a tape (dic_decoder_states_hard_fwd / _bwd),
+hard_reinforce_step is the step; its engine form is CaptionTrainer.reinforce_step.
 Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
 reward_fn is the seam for any other reward."""
 from __future__ import annotations
@@ -22,7 +25,8 @@ from __future__ import annotations
 import torch
 
 from .. import losses, native
-from .Depth_caption_model.depth_models import _CaptionDecoderBase
+from .Depth_caption_model.depth_models import _CaptionDecoderBase, _HardCaptionStatesFn, _contig, _param
+from .util import given_captions, token_uniforms
 
 
 def scst_step(decoder, optimizer, features, depth_features, word_to_id, reward_fn, n_samples=5, max_length=30, temperature=1.0,
@@ -39,6 +43,93 @@ def scst_step(decoder, optimizer, features, depth_features, word_to_id, reward_f
     optimizer.zero_grad(set_to_none=True)
     logprobs, lens = _CaptionDecoderBase.caption_logprobs(decoder, features, depth_features, ids, word_to_id)
     loss = losses.self_critical_loss(logprobs, lens, rewards, baseline)
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), rewards.detach().float().mean()
+
+
+def _hard_decoder(what, decoder):
+    from .Depth_caption_model.depth_models import _HardDecodeRoutes
+    if not isinstance(decoder, _HardDecodeRoutes):
+        raise native._lib.DicError(f"{what}: built for the hard-attention decoders only; the soft-attention decoders have "
+                                   "caption_logprobs and scst_step")
+    return decoder
+
+
+@torch.no_grad()
+def hard_sample_tensors(decoder, features, depth_features, word_to_id, n_samples=1, max_length=30, temperature=1.0, top_k=0,
+                        top_p=1.0, seed=0, attention_seed=0):
+    """What decoder.hard_stochastic_sample draws with per-row noise, left on the device and with the attended cells: (ids int64
+    [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S], cells int32 [B,S,max_length], -1 from each length
+    on).  decoder: a hard-attention decoder shim (depth_features None for the base-hard model).  With per-row noise a row is a
+    joint sample (tokens, cells) of the hard model: argmax(e + Gumbel noise) is a draw from softmax(e)."""
+    _hard_decoder("hard_sample_tensors", decoder)
+    features = _contig(features.detach())
+    depth_features = _contig(depth_features.detach()) if depth_features is not None else None
+    S = int(n_samples)
+    rows = features.shape[0] * max(S, 1)
+    u = token_uniforms(max_length, rows, seed, features.device)
+    gu = decoder.attention_noise(max_length, rows, attention_seed, features.device)
+    return native.decoder_sample_hard(decoder._weights(), features, depth_features, word_to_id["<start>"], word_to_id["<end>"], S, u,
+                                      gu, max_length, float(temperature), int(top_k), float(top_p), False, return_cells=True)
+
+
+def hard_caption_logprobs(decoder, features, depth_features, captions, cells, word_to_id, skip_start=False):
+    """Differentiable joint log-probability of GIVEN captions and GIVEN attended cells under a hard-attention decoder shim
+    (depth_features None for the base-hard model): (token_logprobs float32 [B,(S,)T] - log p(token | history, cells so far) -,
+    cell_logprobs float32 [B,(S,)T] - log softmax(e_t)[cell_t] -, lengths int32 [B(,S)]), on the device, both 0 from each
+    caption's length on.  captions int64 [B,T] or [B,S,T] as for caption_logprobs; cells int32 of the captions' shape (after
+    skip_start), what hard_sample_tensors / decoder.hard_beam_sample(return_cells=True) return - entries from a caption's length on
+    are not read.  backward() reaches every decoder parameter and the features: the recurrence is dic_decoder_states_hard_fwd /
+    _bwd, the vocabulary projection losses.token_logprobs.  In train() mode the hidden states that enter the projection are
+    dropped as in caption_logprobs; eval() has no dropout.
+    A function, not a method of the hard classes: caption_logprobs on them keeps refusing and points here."""
+    _hard_decoder("hard_caption_logprobs", decoder)
+    caps = given_captions("hard_caption_logprobs", captions, skip_start)
+    squeeze = caps.dim() == 2
+    if squeeze:
+        caps = caps.unsqueeze(1)
+    caps = _contig(caps.to(features.device))
+    B, S, T = (int(v) for v in caps.shape)
+    cells = torch.as_tensor(cells)
+    if squeeze and cells.dim() == 2:
+        cells = cells.unsqueeze(1)
+    if tuple(cells.shape) != (B, S, T) or cells.dtype != torch.int32:
+        raise native._lib.DicError(f"hard_caption_logprobs: cells must be int32 of the captions' shape [{B},{S},{T}], got "
+                                   f"{cells.dtype} {tuple(cells.shape)}")
+    cells = _contig(cells.to(features.device))
+    cfg = {"id_start": word_to_id["<start>"], "id_end": word_to_id["<end>"],
+           "drop_mult": decoder._dropout_mult(B * S, T, features.device),
+           "linear": {"linear.weight": decoder.linear.weight.detach(), "linear.bias": decoder.linear.bias.detach()}}
+    params = [_param(decoder, k) for k in native.STATES_GRAD_KEYS]
+    hidden, cell_lp = _HardCaptionStatesFn.apply(cfg, features, depth_features, caps, cells, *params)
+    logprobs, _ = losses.token_logprobs(hidden.view(T * B * S, native.D_HID), decoder.linear.weight, decoder.linear.bias,
+                                        cfg["targets"].view(-1))
+    logprobs = logprobs.view(T, B, S).permute(1, 2, 0)
+    cell_lp = cell_lp.view(T, B, S).permute(1, 2, 0)
+    if squeeze:
+        return logprobs[:, 0], cell_lp[:, 0], cfg["lengths"][:, 0]
+    return logprobs, cell_lp, cfg["lengths"]
+
+
+def hard_reinforce_step(decoder, optimizer, features, depth_features, word_to_id, reward_fn, n_samples=5, max_length=30,
+                        temperature=1.0, top_k=0, top_p=1.0, baseline="others", cell_weight=1.0, seed=0, attention_seed=0):
+    """One REINFORCE step of a hard-attention decoder shim through its drawn attention cells (Show, Attend and Tell 4.2;
+    depth_features None for the base-hard model).  n_samples rows per image are drawn with per-row attention noise
+    (dic_decoder_sample_hard): each is a joint sample (tokens, cells) of the model.  The loss is losses.self_critical_loss of
+    token_logprobs + cell_weight * cell_logprobs (hard_caption_logprobs: dic_decoder_states_hard_fwd / _bwd); at
+    temperature 1 with the filters off and cell_weight 1 its gradient is an unbiased estimate of the expected reward's.
+    reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S] as for scst_step; a reward that looks at the attention reads
+    `decoder.last_cells` (int32 [B,S,T], -1 from each length on), set before reward_fn is called.
+    Pass a new seed and attention_seed every step.  Returns (loss, mean reward) as 0-dim device tensors."""
+    _hard_decoder("hard_reinforce_step", decoder)
+    ids, _, lengths, cells = hard_sample_tensors(decoder, features, depth_features, word_to_id, n_samples, max_length, temperature,
+                                                 top_k, top_p, seed, attention_seed)
+    decoder.last_cells = cells
+    rewards = reward_fn(ids, lengths)
+    optimizer.zero_grad(set_to_none=True)
+    token_lp, cell_lp, lens = hard_caption_logprobs(decoder, features, depth_features, ids, cells, word_to_id)
+    loss = losses.self_critical_loss(token_lp + float(cell_weight) * cell_lp, lens, rewards, baseline)
     loss.backward()
     optimizer.step()
     return loss.detach(), rewards.detach().float().mean()

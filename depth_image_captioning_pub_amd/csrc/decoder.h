@@ -13,7 +13,10 @@
 //   decoder_hard.hip    the hard (Gumbel-max) attention step of those three routes' hard counterparts (hard_row_attn_kernel) and
 //                       the kernel that lays out the selected cells
 //   decoder_states.hip  hidden states of given captions with a tape and their backward through time, S captions per image that
-//                       share the image's F, P and mean (the tail of its backward is decoder_bwd.hip's)
+//                       share the image's F, P and mean (the tail of its backward is decoder_bwd.hip's); the same two bodies
+//                       with given attention cells (dic_decoder_states_hard_*)
+//   decoder_states_hard.hip  what the backward of that hard route has of its own: gate gradients of a gathered context, and the
+//                       ordered scatter of the context gradients into d_features
 #pragma once
 #include "dic.h"
 #include "gemm.h"
@@ -128,6 +131,17 @@ int launch_hard_row_attn(int S, const HardAttnArgs& a, hipStream_t st);
 // hist int [T][R] (cell_t of every step) -> out int [R][T], -1 from length[r] on.  slot (nullable) int [R][T]: the row of its
 // image (0..S-1) whose step-t cell belongs to returned row r - the back-pointer path of a beam search; null: the row itself.
 int launch_hard_cells(const int* hist, const int* slot, const int* length, int S, int R, int T, int* out, hipStream_t st);
+
+// Backward of the hard states route (dic_decoder_states_hard_bwd; decoder_states_hard.hip), step t of the S rows of each image:
+// the gate gradients of the gathered context (hard_states_gate_bwd_kernel<S>), and after the loop the scatter of the context
+// gradients into d_features (hard_states_dF_kernel).  cells int [R][T], len int [R]; tapes [R][T][...] as in decoder_states.hip.
+struct HardStatesBwdArgs {
+  const float *F, *slab_dx; const int *cells, *len; const float *gate_all, *W_beta;
+  float *dctx_all, *dgpre_all, *pbeta, *dXe; int B, t, T;
+};
+int launch_hard_states_gate_bwd(int S, const HardStatesBwdArgs& a, hipStream_t st);
+int launch_hard_states_dF(const float* dctx_all, const float* dmean, const int* cells, const int* len, int B, int S, int T,
+                          float* d_features, hipStream_t st);
 
 // Grid of the attention step kernels and its decoding.  Workgroup (chunk, b) owns channels [chunk*256, +256) of row b.  The
 // eight chunk workgroups of a row share its P rows and LSTM slabs (each recomputes scores and cell): they are mapped to

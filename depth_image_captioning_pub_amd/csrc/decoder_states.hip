@@ -8,6 +8,10 @@
 //   sums, grouped weight-gradient GEMMs), dF (states_dF_kernel, then launch_dP_Wz).
 // Tape layouts are those of the teacher-forced route with its batch row replaced by r ([R][T][...], Hall / Call [R][T+1][H]), so
 // the LSTM cell kernels, embed_grad_kernel and the weight-gradient GEMMs are that route's; F, P and mean stay [B][...].
+// The hard route (dic_decoder_states_hard_fwd / _bwd: given attention cells, the context a gather of one F row, the log-probability
+// of every cell returned and differentiated) runs the same two bodies: the HARD instances of states_attn_kernel
+// and states_attn_bwd_b_kernel here, and in the place of states_attn_bwd_a_kernel / states_dF_kernel the two kernels of
+// decoder_states_hard.hip.
 #include "beam.h"
 #include "decoder.h"
 #include <algorithm>
@@ -26,7 +30,8 @@ struct StatesWs : SetupBufs {
   size_t bytes;
 };
 
-StatesWs states_carve(void* p, size_t bytes, int B, int S, int T, bool* overflow) {
+// hard: the tape of the hard route (dic_decoder_states_hard_*): no context tape - the gather is recomputed - and no d alpha partials
+StatesWs states_carve(void* p, size_t bytes, int B, int S, int T, bool* overflow, bool hard = false) {
   Carver c(p, bytes);
   StatesWs w{};
   const size_t R = (size_t)B * S, RT = R * T, BL = (size_t)B * kL;
@@ -56,7 +61,7 @@ StatesWs states_carve(void* p, size_t bytes, int B, int S, int T, bool* overflow
   w.Call = c.take<float>(R * (T + 1) * kH);
   w.Gact = c.take<float>(RT * kG);
   w.Qall = c.take<float>(RT * kA);
-  w.ctx = c.take<float>(RT * kD);
+  if (!hard) w.ctx = c.take<float>(RT * kD);
   w.gate = c.take<float>(RT * kD);
   w.alpha = c.take<float>(RT * kL);
   w.slab_g = c.take<float>((size_t)kS_LSTM * R * kG);
@@ -69,7 +74,7 @@ StatesWs states_carve(void* p, size_t bytes, int B, int S, int T, bool* overflow
   w.dctx = c.take<float>(RT * kD);
   w.dgpre = c.take<float>(RT * kD);
   w.dq = c.take<float>(RT * kA);
-  w.dalp = c.take<float>((size_t)kNCH * R * kL);
+  if (!hard) w.dalp = c.take<float>((size_t)kNCH * R * kL);
   w.pbeta = c.take<float>((size_t)kNCH * R * kH);
   w.dqp = c.take<float>((size_t)kLCH * R * kA);
   w.dwf_acc = c.take<float>((size_t)kLCH * R * kA);
@@ -117,14 +122,19 @@ __global__ void __launch_bounds__(kH) states_init_kernel(int S, int T, int V, lo
 //   q_s = W_h h_s + b_h (k ascending) -> e_s[l] = w . relu(P[b,l] + q_s) + b (a half-wave per cell) -> alpha_s = softmax_l ->
 //   ctx_s[d] = sum_l alpha_s[l] F[b,l,d] (l ascending, thread = channel) -> gate_s[d] = sigmoid(W_beta h_s + b)[d] (k ascending)
 // Writes alpha / Q / ctx / gate of (r, t) and the LSTM input row X[r,t] = [embed[token] | gate * ctx | h].
+// HARD (dic_decoder_states_hard_fwd): the cell of (r, t) is an input, cells int [R][T].  q, the scores and the softmax are the
+// ones above; the pass over F becomes the gather ctx_s[d] = F[b, cell, d], and chunk 0 stores the cell's log-probability
+// e[cell] - max - log(sum) at cell_lp[t*R + r].  A step at or behind the row's length (its cell is not read) or a cell outside
+// 0..L-1 has ctx = 0 and log-probability 0.  No context tape: the backward gathers again.
 // ------------------------------------------------------------------------------------------
-template <int S>
+template <int S, bool HARD>
 __global__ void __launch_bounds__(256) states_attn_kernel(
     const float* __restrict__ F, const float* __restrict__ P, const float* __restrict__ Hall, const long long* __restrict__ tok,
     const float* __restrict__ embed, int V, const float* __restrict__ WhT, const float* __restrict__ b_h,
     const float* __restrict__ w_full, const float* __restrict__ b_full, const float* __restrict__ WbT,
     const float* __restrict__ b_beta, int t, int T, float* __restrict__ alpha_all, float* __restrict__ Qall,
-    float* __restrict__ ctx_all, float* __restrict__ gate_all, float* __restrict__ Xall) {
+    float* __restrict__ ctx_all, float* __restrict__ gate_all, float* __restrict__ Xall, const int* __restrict__ cells,
+    const int* __restrict__ len, float* __restrict__ cell_lp) {
   constexpr int L = kL;
   constexpr int NPS = (L + 7) / 8;                   // score passes: 8 cells (half-waves) per pass
   __shared__ float h_s[S][kH];
@@ -174,10 +184,17 @@ __global__ void __launch_bounds__(256) states_attn_kernel(
     }
   }
   __syncthreads();
+  [[maybe_unused]] int cell[S];       // HARD: the row's cell of this step, -1 = none (uniform)
   {  // softmax over the L cells of every row: thread = cell
     float ex[S];
+    [[maybe_unused]] float e_cell[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
+      if constexpr (HARD) {
+        const int c = t < len[row0 + s] ? cells[(row0 + s) * T + t] : -1;
+        cell[s] = (c >= 0 && c < L) ? c : -1;
+        e_cell[s] = e_s[s][max(cell[s], 0)];
+      }
       ex[s] = tid < L ? e_s[s][tid] : -INFINITY;
       const float m = wave_max(ex[s]);
       if (lane == 0) red_s[0][s][wv] = m;
@@ -193,10 +210,17 @@ __global__ void __launch_bounds__(256) states_attn_kernel(
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < S; ++s) {
+      const float sum = (red_s[1][s][0] + red_s[1][s][1]) + (red_s[1][s][2] + red_s[1][s][3]);
       if (tid < L) {
-        const float al = ex[s] / ((red_s[1][s][0] + red_s[1][s][1]) + (red_s[1][s][2] + red_s[1][s][3]));
+        const float al = ex[s] / sum;
         e_s[s][tid] = al;
         if (chunk == 0) alpha_all[((row0 + s) * T + t) * L + tid] = al;
+      }
+      if constexpr (HARD) {
+        if (chunk == 0 && tid == 0) {
+          const float m = fmaxf(fmaxf(red_s[0][s][0], red_s[0][s][1]), fmaxf(red_s[0][s][2], red_s[0][s][3]));
+          cell_lp[(long long)t * gridDim.y * S + row0 + s] = cell[s] >= 0 ? (e_cell[s] - m) - logf(sum) : 0.f;
+        }
       }
     }
   }
@@ -206,11 +230,16 @@ __global__ void __launch_bounds__(256) states_attn_kernel(
 #pragma unroll
   for (int s = 0; s < S; ++s) { acc[s] = 0.f; gs[s] = 0.f; }
   const float* Fu = F + (long long)b * L * kD + d;
-#pragma unroll 4
-  for (int l = 0; l < L; ++l) {        // ONE pass over the image's F rows feeds the S accumulators
-    const float f = Fu[(long long)l * kD];
+  if constexpr (HARD) {                // one F row per row of the image
 #pragma unroll
-    for (int s = 0; s < S; ++s) acc[s] += e_s[s][l] * f;
+    for (int s = 0; s < S; ++s) acc[s] = cell[s] >= 0 ? Fu[(long long)cell[s] * kD] : 0.f;
+  } else {
+#pragma unroll 4
+    for (int l = 0; l < L; ++l) {      // ONE pass over the image's F rows feeds the S accumulators
+      const float f = Fu[(long long)l * kD];
+#pragma unroll
+      for (int s = 0; s < S; ++s) acc[s] += e_s[s][l] * f;
+    }
   }
 #pragma unroll 4
   for (int k = 0; k < kH; ++k) {
@@ -223,7 +252,7 @@ __global__ void __launch_bounds__(256) states_attn_kernel(
   for (int s = 0; s < S; ++s) {
     const long long rt = (row0 + s) * T + t;
     const float g = sigmoidf_(bb + gs[s]);
-    ctx_all[rt * kD + d] = acc[s];
+    if constexpr (!HARD) ctx_all[rt * kD + d] = acc[s];
     gate_all[rt * kD + d] = g;
     Xall[rt * kXK + kE + d] = g * acc[s];
   }
@@ -371,12 +400,15 @@ __global__ void __launch_bounds__(512, 2) states_attn_bwd_a_kernel(
 // summation orders with P read from the row's IMAGE and the step plan replaced by the row's own length:
 //   a row whose length is <= t returns - its accumulators are never touched at a dead step;
 //   dPacc [R][L][A], dwf_acc, dbf_acc are initialised at t = length - 1, the row's own last step, and accumulated below it.
+// HARD (dic_decoder_states_hard_bwd): the score gradient does not come through the context but from the log-probability of the
+// row's cell: d_e = d_lp[t*R + r] * (onehot(cell) - alpha), d_lp null = 0; a cell outside 0..L-1 gives d_e = 0.  dalp is not read.
 // ------------------------------------------------------------------------------------------
+template <bool HARD>
 __global__ void __launch_bounds__(256) states_attn_bwd_b_kernel(
     const float* __restrict__ P, const float* __restrict__ Qall, const float* __restrict__ alphas,
     const float* __restrict__ dalp, const float* __restrict__ w_full, int R, int S, int t, int T,
     const int* __restrict__ len, float* __restrict__ dPacc, float* __restrict__ dqp, float* __restrict__ dwf_acc,
-    float* __restrict__ dbf_acc) {
+    float* __restrict__ dbf_acc, const int* __restrict__ cells, const float* __restrict__ d_lp) {
   constexpr int L = kL;
   __shared__ float de_s[L];
   __shared__ float red_s[4];
@@ -389,17 +421,23 @@ __global__ void __launch_bounds__(256) states_attn_bwd_b_kernel(
   const int img = r / S;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const long long rt = (long long)r * T + t;
-  float al = 0.f, da = 0.f;
-  if (tid < L) {
-    al = alphas[rt * L + tid];
+  if constexpr (HARD) {
+    const int cell = cells[rt];
+    const float dl = d_lp ? d_lp[(long long)t * R + r] : 0.f;
+    if (tid < L) de_s[tid] = (cell >= 0 && cell < L) ? dl * ((tid == cell ? 1.f : 0.f) - alphas[rt * L + tid]) : 0.f;
+  } else {
+    float al = 0.f, da = 0.f;
+    if (tid < L) {
+      al = alphas[rt * L + tid];
 #pragma unroll
-    for (int c = 0; c < kNCH; ++c) da += dalp[((long long)c * R + r) * L + tid];
+      for (int c = 0; c < kNCH; ++c) da += dalp[((long long)c * R + r) * L + tid];
+    }
+    const float part = wave_sum(al * da);
+    if (lane == 0) red_s[w] = part;
+    __syncthreads();
+    const float dot = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+    if (tid < L) de_s[tid] = al * (da - dot);
   }
-  const float part = wave_sum(al * da);
-  if (lane == 0) red_s[w] = part;
-  __syncthreads();
-  const float dot = red_s[0] + red_s[1] + red_s[2] + red_s[3];
-  if (tid < L) de_s[tid] = al * (da - dot);
   __syncthreads();
   const int l32 = lane & 31, sub = lane >> 5, hw = w * 2 + sub;      // 8 half-waves
   const float4 q4 = *reinterpret_cast<const float4*>(Qall + rt * kA + l32 * 4);
@@ -512,75 +550,81 @@ __global__ void __launch_bounds__(256) states_dF_kernel(const float* __restrict_
   }
 }
 
-}  // namespace
-}  // namespace dic
+// What the hard route (dic_decoder_states_hard_*) adds to the arguments of the soft one; `route` is the prefix of the refusals.
+struct StatesRoute {
+  const char* route;
+  bool hard;
+  const int* cells;               // [R][T]
+  float* out_cell_logprobs;       // forward, [T][R]
+  const float* d_cell_logprobs;   // backward, [T][R] or null
+};
 
-using namespace dic;
-
-extern "C" {
-
-size_t dic_decoder_states_workspace_bytes(int B, int S, int T, int V) {
-  if (!states_sizes_ok(B, S, T, V)) return 0;
-  bool ov;
-  return states_carve(nullptr, 0, B, S, T, &ov).bytes;
-}
-
-// the argument checks the two calls share; every one comes before the first HIP call
-static int states_check(int V, int B, int S, long long id_start, long long id_end, int T) {
-  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "decoder_states: captions per image S=%d is outside 1..%d", S, kBeamMax);
-  DIC_REQUIRE(V > 0 && B > 0, "decoder_states: bad sizes (B=%d, V=%d)", B, V);
-  DIC_REQUIRE(T >= 1 && T <= 64, "decoder_states: T=%d is outside 1..64 decode steps", T);
+// the argument checks the calls share; every one comes before the first HIP call
+int states_check(const char* route, int V, int B, int S, long long id_start, long long id_end, int T) {
+  DIC_REQUIRE(S >= 1 && S <= kBeamMax, "%s: captions per image S=%d is outside 1..%d", route, S, kBeamMax);
+  DIC_REQUIRE(V > 0 && B > 0, "%s: bad sizes (B=%d, V=%d)", route, B, V);
+  DIC_REQUIRE(T >= 1 && T <= 64, "%s: T=%d is outside 1..64 decode steps", route, T);
   DIC_REQUIRE(embed_grad_rows_ok((long long)B * S * T),
-              "decoder_states: B*S*T=%lld exceeds the %d (row, step) pairs of the embedding-gradient kernel", (long long)B * S * T,
+              "%s: B*S*T=%lld exceeds the %d (row, step) pairs of the embedding-gradient kernel", route, (long long)B * S * T,
               60 * 1024 / 16 * kE);
-  return check_token_ids("decoder_states", V, id_start, id_end);
+  return check_token_ids(route, V, id_start, id_end);
 }
 
-int dic_decoder_states_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
-                           long long id_start, long long id_end, int T, const int64_t* captions, const float* drop_mult,
-                           float* out_hidden, int64_t* out_targets, int* out_lengths, void* workspace, size_t workspace_bytes,
-                           void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DIC_TRY(states_check(V, B, S, id_start, id_end, T));
-  DIC_REQUIRE(w && feat_rgb && captions && out_hidden && out_targets && out_lengths && workspace, "decoder_states: null pointer");
+// dic_decoder_states_fwd and dic_decoder_states_hard_fwd: one body
+int states_fwd_route(const StatesRoute& rt, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B,
+                     int S, long long id_start, long long id_end, int T, const int64_t* captions, const float* drop_mult,
+                     float* out_hidden, int64_t* out_targets, int* out_lengths, void* workspace, size_t workspace_bytes,
+                     hipStream_t st) {
+  DIC_TRY(states_check(rt.route, V, B, S, id_start, id_end, T));
+  DIC_REQUIRE(w && feat_rgb && captions && out_hidden && out_targets && out_lengths && workspace &&
+                  (!rt.hard || (rt.cells && rt.out_cell_logprobs)),
+              "%s: null pointer", rt.route);
   const int R = B * S;
   bool ov = false;
-  StatesWs ws = states_carve(workspace, workspace_bytes, B, S, T, &ov);
-  if (ov) return workspace_too_small("decoder_states", workspace_bytes, ws.bytes);
+  StatesWs ws = states_carve(workspace, workspace_bytes, B, S, T, &ov, rt.hard);
+  if (ov) return workspace_too_small(rt.route, workspace_bytes, ws.bytes);
   // per image, never per caption.  [h0 | c0] -> slot 0 of row 0 of the image, then copied to its other rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hall, ws.Call, (long long)S * (T + 1) * kH, true}, st));
   hipLaunchKernelGGL(states_init_kernel, dim3(B), dim3(kH), 0, st, S, T, V, id_start, id_end, (const long long*)captions, ws.tok,
                      (long long*)out_targets, ws.len, out_lengths, ws.Hall, ws.Call);
   DIC_LAUNCH_CHECK();
+#define DIC_STATES_ATTN(HARD_)                                                                                                    \
+  DIC_BEAM_SWITCH(S, hipLaunchKernelGGL((states_attn_kernel<KB_, HARD_>), dim3(kNCH, B), dim3(256), 0, st, ws.F, ws.P, ws.Hall,   \
+                                        ws.tok, w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b, ws.WbT,          \
+                                        w->fbeta_b, t, T, ws.alpha, ws.Qall, ws.ctx, ws.gate, ws.Xall, rt.cells, ws.len,          \
+                                        rt.out_cell_logprobs);)
   for (int t = 0; t < T; ++t) {
-    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(states_attn_kernel<KB_>, dim3(kNCH, B), dim3(256), 0, st, ws.F, ws.P, ws.Hall, ws.tok,
-                                          w->embed, V, ws.WhT, w->dec_att_b, w->full_att_w, w->full_att_b, ws.WbT, w->fbeta_b, t,
-                                          T, ws.alpha, ws.Qall, ws.ctx, ws.gate, ws.Xall);)
+    if (rt.hard) {
+      DIC_STATES_ATTN(true)
+    } else {
+      DIC_STATES_ATTN(false)
+    }
     DIC_LAUNCH_CHECK();
     DIC_TRY(gemm_slabs(R, kG, kXK, op_rowk(ws.Xall + (long long)t * kXK, (long long)T * kXK), op_rowk(ws.Wcat, kXK), ws.slab_g,
                        kS_LSTM, st));
     // the cell writes slot t+1 of Hall / Call and h x drop_mult at packed row t*R + r of out_hidden
     DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab_g, ws.bcat, drop_mult, ws.Hall, ws.Call, ws.Gact, out_hidden, kS_LSTM, R, t * R}, t, T, st));
   }
+#undef DIC_STATES_ATTN
   const long long n = (long long)T * R * kH;
   hipLaunchKernelGGL(states_mask_hidden_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, out_hidden, ws.len, R, n);
   DIC_LAUNCH_CHECK();
   return DIC_OK;
 }
 
-int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, long long id_start, long long id_end, int T,
-                           const int64_t* captions, const float* drop_mult, const float* d_hidden, const dic_decoder_grads* g,
-                           float* d_features, void* workspace, size_t workspace_bytes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DIC_TRY(states_check(V, B, S, id_start, id_end, T));
-  DIC_REQUIRE(w && captions && d_hidden && g && workspace, "decoder_states: null pointer");
+// dic_decoder_states_bwd and dic_decoder_states_hard_bwd: one body
+int states_bwd_route(const StatesRoute& rt, const dic_decoder_weights* w, int V, int B, int S, long long id_start, long long id_end,
+                     int T, const int64_t* captions, const float* drop_mult, const float* d_hidden, const dic_decoder_grads* g,
+                     float* d_features, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  DIC_TRY(states_check(rt.route, V, B, S, id_start, id_end, T));
+  DIC_REQUIRE(w && captions && d_hidden && g && workspace && (!rt.hard || rt.cells), "%s: null pointer", rt.route);
   DIC_REQUIRE(g->enc_att_w && g->enc_att_b && g->dec_att_w && g->dec_att_b && g->full_att_w && g->full_att_b && g->embed && g->w_ih &&
                   g->w_hh && g->b_ih && g->b_hh && g->init_w && g->init_b && g->fbeta_w && g->fbeta_b,
-              "decoder_states: null pointer among the 15 gradients");
+              "%s: null pointer among the 15 gradients", rt.route);
   const int R = B * S;
   bool ov = false;
-  StatesWs ws = states_carve(workspace, workspace_bytes, B, S, T, &ov);
-  if (ov) return workspace_too_small("decoder_states", workspace_bytes, ws.bytes);
+  StatesWs ws = states_carve(workspace, workspace_bytes, B, S, T, &ov, rt.hard);
+  if (ov) return workspace_too_small(rt.route, workspace_bytes, ws.bytes);
   const size_t RT = (size_t)R * T;
   // (row, step) pairs behind the row's length keep zero gradients: dG, dctx, dgpre, dq are carved back to back
   DIC_CHECK_HIP(hipMemsetAsync(ws.dG, 0, (size_t)((char*)(ws.dq + RT * kA) - (char*)ws.dG), st));
@@ -603,11 +647,18 @@ int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, lo
   for (int t = T - 1; t >= 0; --t) {
     DIC_TRY(gemm_slabs(R, kXK, kG, op_rowk(ws.dG + (long long)t * kG, (long long)T * kG), op_rowk(ws.WcatT, kG), ws.slab_dx, kS_DX,
                        st));
-    DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(states_attn_bwd_a_kernel<KB_>, dim3(kNCH, B), dim3(512), 0, st, ws.F, ws.slab_dx, R, t, T,
-                                          ws.len, ws.ctx, ws.gate, w->fbeta_w, ws.dctx, ws.dgpre, ws.dalp, ws.pbeta, ws.dXe);)
-    DIC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(states_attn_bwd_b_kernel, dim3(kLCH, R), dim3(256), 0, st, ws.P, ws.Qall, ws.alpha, ws.dalp, w->full_att_w, R,
-                       S, t, T, ws.len, ws.dPacc, ws.dqp, ws.dwf_acc, ws.dbf_acc);
+    if (rt.hard) {
+      DIC_TRY(launch_hard_states_gate_bwd(S, HardStatesBwdArgs{ws.F, ws.slab_dx, rt.cells, ws.len, ws.gate, w->fbeta_w, ws.dctx,
+                                                               ws.dgpre, ws.pbeta, ws.dXe, B, t, T}, st));
+      hipLaunchKernelGGL(states_attn_bwd_b_kernel<true>, dim3(kLCH, R), dim3(256), 0, st, ws.P, ws.Qall, ws.alpha, nullptr,
+                         w->full_att_w, R, S, t, T, ws.len, ws.dPacc, ws.dqp, ws.dwf_acc, ws.dbf_acc, rt.cells, rt.d_cell_logprobs);
+    } else {
+      DIC_BEAM_SWITCH(S, hipLaunchKernelGGL(states_attn_bwd_a_kernel<KB_>, dim3(kNCH, B), dim3(512), 0, st, ws.F, ws.slab_dx, R, t, T,
+                                            ws.len, ws.ctx, ws.gate, w->fbeta_w, ws.dctx, ws.dgpre, ws.dalp, ws.pbeta, ws.dXe);)
+      DIC_LAUNCH_CHECK();
+      hipLaunchKernelGGL(states_attn_bwd_b_kernel<false>, dim3(kLCH, R), dim3(256), 0, st, ws.P, ws.Qall, ws.alpha, ws.dalp,
+                         w->full_att_w, R, S, t, T, ws.len, ws.dPacc, ws.dqp, ws.dwf_acc, ws.dbf_acc, nullptr, nullptr);
+    }
     DIC_LAUNCH_CHECK();
     launch_lstm(t - 1);
     DIC_LAUNCH_CHECK();
@@ -623,11 +674,72 @@ int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, lo
                                     ws.Xall, ws.F, ws.mean, ws.colsum_ws, ws.gemm_ws}, g, st));
   if (d_features) {
     DIC_TRY(gemm(B, kD, 2 * kH, op_rowk(ws.dinit_img, 2 * kH), op_colk(w->init_w, kD), ep_store(ws.dmean, kD), st, 8, ws.gemm_ws, 64));
-    hipLaunchKernelGGL(states_dF_kernel, dim3(kNCH, B), dim3(256), 0, st, ws.alpha, ws.dctx, ws.dmean, S, T, ws.len, d_features);
-    DIC_LAUNCH_CHECK();
+    if (rt.hard) {
+      DIC_TRY(launch_hard_states_dF(ws.dctx, ws.dmean, rt.cells, ws.len, B, S, T, d_features, st));
+    } else {
+      hipLaunchKernelGGL(states_dF_kernel, dim3(kNCH, B), dim3(256), 0, st, ws.alpha, ws.dctx, ws.dmean, S, T, ws.len, d_features);
+      DIC_LAUNCH_CHECK();
+    }
     DIC_TRY(launch_dP_Wz(w->enc_att_w, ws.WzT, ws.dPimg, B * kL, d_features, st));
   }
   return DIC_OK;
 }
 
+}  // namespace
+}  // namespace dic
+
+using namespace dic;
+
+extern "C" {
+
+size_t dic_decoder_states_workspace_bytes(int B, int S, int T, int V) {
+  if (!states_sizes_ok(B, S, T, V)) return 0;
+  bool ov;
+  return states_carve(nullptr, 0, B, S, T, &ov).bytes;
+}
+
+int dic_decoder_states_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                           long long id_start, long long id_end, int T, const int64_t* captions, const float* drop_mult,
+                           float* out_hidden, int64_t* out_targets, int* out_lengths, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  return states_fwd_route(StatesRoute{"decoder_states", false, nullptr, nullptr, nullptr}, w, V, feat_rgb, feat_depth, B, S, id_start,
+                          id_end, T, captions, drop_mult, out_hidden, out_targets, out_lengths, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
+int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, long long id_start, long long id_end, int T,
+                           const int64_t* captions, const float* drop_mult, const float* d_hidden, const dic_decoder_grads* g,
+                           float* d_features, void* workspace, size_t workspace_bytes, void* stream) {
+  return states_bwd_route(StatesRoute{"decoder_states", false, nullptr, nullptr, nullptr}, w, V, B, S, id_start, id_end, T, captions,
+                          drop_mult, d_hidden, g, d_features, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- the hard route (semantics in include/dic.h, kernels of its own in decoder_states_hard.hip) ----
+int dic_decoder_states_hard_sizes(int B, int S, int T, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "decoder_states_hard: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_TRY(states_check("decoder_states_hard", V, B, S, 0, 0, T));
+  bool ov;
+  *workspace_bytes = states_carve(nullptr, 0, B, S, T, &ov, true).bytes;
+  return DIC_OK;
+}
+
+int dic_decoder_states_hard_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                                long long id_start, long long id_end, int T, const int64_t* captions, const int* cells,
+                                const float* drop_mult, float* out_hidden, int64_t* out_targets, float* out_cell_logprobs,
+                                int* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  return states_fwd_route(StatesRoute{"decoder_states_hard", true, cells, out_cell_logprobs, nullptr}, w, V, feat_rgb, feat_depth, B,
+                          S, id_start, id_end, T, captions, drop_mult, out_hidden, out_targets, out_lengths, workspace,
+                          workspace_bytes, (hipStream_t)stream);
+}
+
+int dic_decoder_states_hard_bwd(const dic_decoder_weights* w, int V, int B, int S, long long id_start, long long id_end, int T,
+                                const int64_t* captions, const int* cells, const float* drop_mult, const float* d_hidden,
+                                const float* d_cell_logprobs, const dic_decoder_grads* g, float* d_features, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return states_bwd_route(StatesRoute{"decoder_states_hard", true, cells, nullptr, d_cell_logprobs}, w, V, B, S, id_start, id_end, T,
+                          captions, drop_mult, d_hidden, g, d_features, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"
+

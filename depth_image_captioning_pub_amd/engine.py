@@ -151,34 +151,43 @@ SCST_MAX_CELLS = 491520      # B * S * T: the limit of dic_decoder_states_fwd / 
 
 
 def scst_arguments(hard: bool, B: int, n_samples: int, max_length: int, baseline, uniform_u=None, drop_mult=None,
-                   global_tokens=None, virtual_world=None, reward_fn=None) -> int:
+                   global_tokens=None, virtual_world=None, reward_fn=None, gumbel_u=None, what: str = "scst_step") -> int:
     """The argument checks of CaptionTrainer.scst_step, made before anything is launched (no device needed).  Returns the
-    baseline mode of dic_scst_loss: 0 none | 1 others | 2 per caption | 3 per image ("greedy", or a tensor [B])."""
-    if hard:
+    baseline mode of dic_scst_loss: 0 none | 1 others | 2 per caption | 3 per image ("greedy", or a tensor [B]).
+    what="reinforce_step": the checks of CaptionTrainer.reinforce_step, the step of the hard trainers - there `hard` must be True,
+    gumbel_u is looked at, and the "greedy" baseline is not on offer (a greedy Gumbel-max caption is a draw itself)."""
+    reinforce = what == "reinforce_step"
+    if reinforce and not hard:
+        raise DicError("reinforce_step: the step trains hard-attention decoders through their drawn attention cells; a "
+                       "soft-attention trainer has scst_step")
+    if hard and not reinforce:
         raise DicError("scst_step: sampling and scoring are built for the soft-attention decoders only (a Gumbel-max decode draws "
                        "its attention already, and its likelihood is an expectation over those draws); there is no "
                        "hard-attention counterpart")
     S, T = int(n_samples), int(max_length)
     if reward_fn is not None and not callable(reward_fn):
-        raise DicError("scst_step: reward_fn must be callable: reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S]")
+        raise DicError(f"{what}: reward_fn must be callable: reward_fn(ids int64 [B,S,T], lengths int32 [B,S]) -> float [B,S]")
     if not 1 <= S <= 8:
-        raise DicError(f"scst_step: n_samples={S} is outside 1 .. 8 (the S-row routes share one feature read among at most 8 rows)")
+        raise DicError(f"{what}: n_samples={S} is outside 1 .. 8 (the S-row routes share one feature read among at most 8 rows)")
     if not 1 <= T <= 64:
-        raise DicError(f"scst_step: max_length={T} is outside 1 .. 64")
+        raise DicError(f"{what}: max_length={T} is outside 1 .. 64")
     if B < 1 or B * S * T > SCST_MAX_CELLS:
-        raise DicError(f"scst_step: B*n_samples*max_length = {B * S * T} is outside 1 .. {SCST_MAX_CELLS} (the states route's limit)")
-    mode = baseline_mode(baseline, B, S, ("others", "greedy"), "n_samples >= 2")
+        raise DicError(f"{what}: B*n_samples*max_length = {B * S * T} is outside 1 .. {SCST_MAX_CELLS} (the states route's limit)")
+    mode = baseline_mode(baseline, B, S, ("others",) if reinforce else ("others", "greedy"), "n_samples >= 2")
+    if gumbel_u is not None and tuple(gumbel_u.shape) != (T, B * S, native.L_CELLS):
+        raise DicError(f"{what}: gumbel_u must be [max_length, B*n_samples, {native.L_CELLS}] = [{T}, {B * S}, {native.L_CELLS}] "
+                       f"(per-row noise: a row is then a joint sample of tokens and cells), got {tuple(gumbel_u.shape)}")
     if uniform_u is not None and tuple(uniform_u.shape) != (T, B * S):
-        raise DicError(f"scst_step: uniform_u must be [max_length, B*n_samples] = [{T}, {B * S}], got {tuple(uniform_u.shape)}")
+        raise DicError(f"{what}: uniform_u must be [max_length, B*n_samples] = [{T}, {B * S}], got {tuple(uniform_u.shape)}")
     if drop_mult is not None and tuple(drop_mult.shape) != (B * S, T, native.D_HID):
-        raise DicError(f"scst_step: drop_mult must be [B*n_samples, max_length, {native.D_HID}] = [{B * S}, {T}, {native.D_HID}], got "
+        raise DicError(f"{what}: drop_mult must be [B*n_samples, max_length, {native.D_HID}] = [{B * S}, {T}, {native.D_HID}], got "
                        f"{tuple(drop_mult.shape)}")
     if global_tokens is not None and not (torch.is_tensor(global_tokens) and global_tokens.dtype == torch.int64
                                           and global_tokens.numel() == 1 and global_tokens.is_cuda):
-        raise DicError("scst_step: global_tokens must be an int64 device tensor of one element (the token count never visits the "
+        raise DicError(f"{what}: global_tokens must be an int64 device tensor of one element (the token count never visits the "
                        "host; train_step's host integer has no place here)")
     if virtual_world is not None and int(virtual_world) < 1:
-        raise DicError(f"scst_step: virtual_world={virtual_world} must be >= 1")
+        raise DicError(f"{what}: virtual_world={virtual_world} must be >= 1")
     return mode
 
 
@@ -676,8 +685,46 @@ class CaptionTrainer(BackboneTrainer):
         B = imgs.shape[0] if imgs is not None else (precomputed_features.shape[0] if precomputed_features is not None else 0)
         mode = scst_arguments(self.hard, B, n_samples, max_length, baseline, uniform_u, drop_mult, global_tokens, virtual_world,
                               reward_fn)
+        return self._policy_step("scst_step", None, mode, B, imgs, depth_map, reward_fn, id_start, id_end, n_samples, max_length,
+                                 temperature, top_k, top_p, baseline, uniform_u, drop_mult, precomputed_features, next_imgs,
+                                 global_tokens, apply_update, virtual_world)
+
+    def reinforce_step(self, imgs: Optional[torch.Tensor], depth_map: Optional[torch.Tensor], reward_fn, *, id_start: int,
+                       id_end: int, n_samples: int = 5, max_length: int = 30, temperature: float = 1.0, top_k: int = 0,
+                       top_p: float = 1.0, baseline="others", uniform_u: Optional[torch.Tensor] = None,
+                       drop_mult: Optional[torch.Tensor] = None, precomputed_features: Optional[torch.Tensor] = None,
+                       next_imgs=None, global_tokens: Optional[torch.Tensor] = None, apply_update: bool = True,
+                       virtual_world: Optional[int] = None, cell_weight: float = 1.0, gumbel_u: Optional[torch.Tensor] = None):
+        """scst_step for hard=True trainers: REINFORCE through the drawn attention cells (Show, Attend and Tell 4.2; DESIGN.md
+        5.26).  The rows are drawn with per-row attention noise (dic_decoder_sample_hard), so each is a joint sample (tokens, cells)
+        of the hard model; its joint log-probability token_lp + cell_weight * cell_lp (dic_decoder_states_hard_fwd +
+        dic_token_logprobs) enters dic_scst_loss, which is linear in it: the loss head's d_logprob goes back to the tokens as it is
+        and to the cells times cell_weight (dic_token_logprobs_bwd, dic_decoder_states_hard_bwd).  Everything else - rewards,
+        normaliser, global token count, exchange, guarded AdamW - is scst_step's; so are the keywords, except
+        baseline: "others" | a tensor [B,S] or [B] | None (no "greedy": a greedy Gumbel-max caption is itself a draw).
+        gumbel_u: float32 [max_length, B*n_samples, 196] in (0,1), the attention noise of every (step, row); default: the device
+          generator of the token draws, keyed by (seed, call number, rank).
+        cell_weight: the weight of the cells' log-probabilities in the loss (0: the attention is trained through the tokens only).
+        `last` also holds "cells" int32 [B,S,T] (-1 from each length on) and "cell_logprobs" [B,S,T]; a reward that looks at the
+        attention reads trainer.last_cells, set before reward_fn is called."""
+        B = imgs.shape[0] if imgs is not None else (precomputed_features.shape[0] if precomputed_features is not None else 0)
+        mode = scst_arguments(self.hard, B, n_samples, max_length, baseline, uniform_u, drop_mult, global_tokens, virtual_world,
+                              reward_fn, gumbel_u, what="reinforce_step")
+        return self._policy_step("reinforce_step", (float(cell_weight), gumbel_u), mode, B, imgs, depth_map, reward_fn, id_start,
+                                 id_end, n_samples, max_length, temperature, top_k, top_p, baseline, uniform_u, drop_mult,
+                                 precomputed_features, next_imgs, global_tokens, apply_update, virtual_world)
+
+    def _step_generator(self, salt: int) -> torch.Generator:
+        gen = torch.Generator(self.device)
+        gen.manual_seed((((self.seed * 1000003 + self.sample_count) * 64 + self.rank) ^ salt) & 0x7FFFFFFFFFFFFFFF)
+        return gen
+
+    def _policy_step(self, what, hard_opts, mode, B, imgs, depth_map, reward_fn, id_start, id_end, n_samples, max_length,
+                     temperature, top_k, top_p, baseline, uniform_u, drop_mult, precomputed_features, next_imgs, global_tokens,
+                     apply_update, virtual_world):
+        """The body of scst_step (hard_opts None) and reinforce_step (hard_opts = (cell_weight, gumbel_u)), after their checks."""
         if self.use_depth and depth_map is None:
-            raise DicError("scst_step: this trainer has a depth encoder: depth_map is required")
+            raise DicError(f"{what}: this trainer has a depth encoder: depth_map is required")
         S, T = int(n_samples), int(max_length)
         R = B * S
         feats = (self._open_step(imgs, next_imgs, lambda x: False) if precomputed_features is None
@@ -685,13 +732,23 @@ class CaptionTrainer(BackboneTrainer):
         if feats.shape[1] == native.L_COMPACT:
             feats = self._expand_cells(feats)
         fdep, dtape = self._depth_forward(depth_map, compact=False)
+        cells = None
+        drew = uniform_u is None or (hard_opts is not None and hard_opts[1] is None)
         if uniform_u is None:
-            gen = torch.Generator(self.device)
-            gen.manual_seed((((self.seed * 1000003 + self.sample_count) * 64 + self.rank) ^ 0x5C57) & 0x7FFFFFFFFFFFFFFF)
-            self.sample_count += 1
-            uniform_u = torch.rand((T, R), generator=gen, device=self.device)
-        ids, _, lengths = native.decoder_sample(self.dec_w, feats, fdep, id_start, id_end, S, uniform_u, T, float(temperature),
-                                                int(top_k), float(top_p))
+            uniform_u = torch.rand((T, R), generator=self._step_generator(0x5C57), device=self.device)
+        if hard_opts is None:
+            ids, _, lengths = native.decoder_sample(self.dec_w, feats, fdep, id_start, id_end, S, uniform_u, T, float(temperature),
+                                                    int(top_k), float(top_p))
+        else:
+            gumbel_u = hard_opts[1]
+            if gumbel_u is None:       # (clamped as _HardDecodeRoutes.attention_noise: -log(-log u) stays finite)
+                gumbel_u = torch.rand((T, R, native.L_CELLS), generator=self._step_generator(0x6A7D),
+                                      device=self.device).clamp_(1e-6, 1.0 - 1e-6)
+            ids, _, lengths, cells = native.decoder_sample_hard(self.dec_w, feats, fdep, id_start, id_end, S, uniform_u, gumbel_u, T,
+                                                                float(temperature), int(top_k), float(top_p), False,
+                                                                return_cells=True)
+            self.last_cells = cells
+        self.sample_count += int(drew)
         nworld = virtual_world if virtual_world is not None else self.world
         tokens, pending = global_tokens, None
         if tokens is None and (self.world > 1 and virtual_world is None):
@@ -706,7 +763,7 @@ class CaptionTrainer(BackboneTrainer):
             g_ids, _ = native.decoder_greedy(self.dec_w, feats, fdep, id_start, T)
             base = reward_fn(g_ids.unsqueeze(1), native.caption_lengths(g_ids, id_end).unsqueeze(1))
             if tuple(base.shape) != (B, 1):
-                raise DicError(f"scst_step: reward_fn must return [B,S] = [{B}, 1] for the greedy captions, got {tuple(base.shape)}")
+                raise DicError(f"{what}: reward_fn must return [B,S] = [{B}, 1] for the greedy captions, got {tuple(base.shape)}")
             base = base.detach().float().reshape(B).contiguous()
         elif torch.is_tensor(baseline):
             base = baseline.detach().to(self.device, torch.float32).contiguous()
@@ -714,22 +771,34 @@ class CaptionTrainer(BackboneTrainer):
         self._mark("reward")
         if drop_mult is None:
             drop_mult = self._draw_dropout(R, T)
-        hidden, targets, lens, tape = native.decoder_states_forward(self.dec_w, feats, fdep, id_start, id_end, ids, drop_mult)
+        if cells is None:
+            hidden, targets, lens, tape = native.decoder_states_forward(self.dec_w, feats, fdep, id_start, id_end, ids, drop_mult)
+        else:
+            hidden, targets, cell_lp, lens, tape = native.decoder_states_hard_forward(self.dec_w, feats, fdep, id_start, id_end, ids,
+                                                                                      cells, drop_mult)
         logprobs, lse = native.token_logprobs(hidden.view(T * R, native.D_HID), self.dec_w["linear.weight"],
                                               self.dec_w["linear.bias"], targets.view(-1))
         self._mark("states_fwd")
         if pending is not None:
             pending.wait()
-        loss, d_logprob, _ = native.scst_loss(logprobs.view(T, R), lens, rewards, base, mode, tokens)
+        # (dic_scst_loss is linear in the log-probabilities: the joint one enters as the elementwise sum)
+        joint = logprobs.view(T, R) if cells is None else logprobs.view(T, R) + hard_opts[0] * cell_lp
+        loss, d_logprob, _ = native.scst_loss(joint, lens, rewards, base, mode, tokens)
         self._mark("loss")
         d_hidden = native.token_logprobs_bwd_into(self.dec_g, hidden.view(T * R, native.D_HID), self.dec_w["linear.weight"],
                                                   self.dec_w["linear.bias"], targets.view(-1), lse, d_logprob.view(-1))
-        dfeat = native.decoder_states_backward_into(self.dec_g, tape, d_hidden.view(T, R, native.D_HID),
-                                                    need_features=self.use_depth)
+        if cells is None:
+            dfeat = native.decoder_states_backward_into(self.dec_g, tape, d_hidden.view(T, R, native.D_HID),
+                                                        need_features=self.use_depth)
+        else:
+            dfeat = native.decoder_states_hard_backward_into(self.dec_g, tape, d_hidden.view(T, R, native.D_HID),
+                                                             hard_opts[0] * d_logprob.view(T, R), need_features=self.use_depth)
         self._mark("states_bwd")
         self._finish_step(dtape, dfeat, apply_update)
         self.last = {"ids": ids, "lengths": lengths, "rewards": rewards, "logprobs": logprobs.view(T, B, S).permute(1, 2, 0),
                      "features": feats, "depth_features": fdep}
+        if cells is not None:
+            self.last.update(cells=cells, cell_logprobs=cell_lp.view(T, B, S).permute(1, 2, 0))
         return loss, rewards.mean().view(1)
 
     @torch.no_grad()

@@ -9,9 +9,10 @@ from .._lib import check, ptr, stream_ptr
 from ._core import D_ATT, D_EMB, D_ENC, D_HID, DEFAULT_CONV_MODE, L_CELLS, L_COMPACT, batch_sizes_of
 from .decode import (decoder_beam, decoder_beam_hard, decoder_greedy, decoder_sample, decoder_sample_hard, decoder_score,
                      decoder_score_hard, nic_beam, nic_greedy, nic_sample, nic_score)
-from .decoder import (DECODER_FIELDS, STATES_GRAD_KEYS, DecoderPtrs, DecoderTape, StatesTape, attention_backward, attention_forward,
-                      decoder_attention_relu_mask, decoder_backward, decoder_forward, decoder_ptrs, decoder_states_backward,
-                      decoder_states_backward_into, decoder_states_forward)
+from .decoder import (DECODER_FIELDS, STATES_GRAD_KEYS, DecoderPtrs, DecoderTape, HardStatesTape, StatesTape, attention_backward,
+                      attention_forward, decoder_attention_relu_mask, decoder_backward, decoder_forward, decoder_ptrs, decoder_states_backward,
+                      decoder_states_backward_into, decoder_states_forward, decoder_states_hard_backward,
+                      decoder_states_hard_backward_into, decoder_states_hard_forward)
 from .encoders import (CONV_MODES, DEPTH_FIELDS, ConvBnLayer, DepthBnState, DepthPtrs, DepthTape, ResNetRunner, depth_encoder_backward,
                        depth_encoder_decisions, depth_encoder_forward, depth_ptrs, depth_status_word, f16x2_weight_scale)
 from .nic import (NIC_EMB, NIC_FIELDS, NIC_STATES_GRAD_KEYS, NicPtrs, NicStatesTape, NicTape, nic_backward, nic_forward,

@@ -178,36 +178,70 @@ class StatesTape:
     drop_mult: Optional[torch.Tensor]
 
 
+@dataclass
+class HardStatesTape(StatesTape):
+    """Everything dic_decoder_states_hard_bwd needs from the matching forward call: StatesTape and the cells, int32 [B,S,T]."""
+    cells: Optional[torch.Tensor] = None
+
+
 def decoder_states_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, depth_features: Optional[torch.Tensor],
                            id_start: int, id_end: int, captions: torch.Tensor, drop_mult: Optional[torch.Tensor] = None):
     """dic_decoder_states_fwd: the hidden states of given captions, with a tape for decoder_states_backward (semantics:
     include/dic.h).  captions int64 [B,S,T] without '<start>', S <= 8 per image; drop_mult float32 [B*S,T,128] or None (eval).
     Returns (hidden float32 [T,R,128] - 0 from each row's length on -, targets int64 [T,R] - -1 there -, lengths int32 [B,S],
     tape), R = B*S, rows b*S + s."""
+    return _decoder_states_forward("decoder_states", weights, features, depth_features, id_start, id_end, captions, None, drop_mult)
+
+
+def decoder_states_hard_forward(weights: Dict[str, torch.Tensor], features: torch.Tensor, depth_features: Optional[torch.Tensor],
+                                id_start: int, id_end: int, captions: torch.Tensor, cells: torch.Tensor,
+                                drop_mult: Optional[torch.Tensor] = None):
+    """dic_decoder_states_hard_fwd: decoder_states_forward along GIVEN attention cells - int32 [B,S,T], the `cells` that
+    decoder_sample_hard / decoder_beam_hard return (anything from a row's length on, their -1 included).  Returns (hidden, targets,
+    cell_logprobs float32 [T,R] - log softmax(e)[cell], 0 from each row's length on; the layout of token_logprobs' result -,
+    lengths, tape for decoder_states_hard_backward)."""
+    return _decoder_states_forward("decoder_states_hard", weights, features, depth_features, id_start, id_end, captions, cells,
+                                   drop_mult)
+
+
+def _decoder_states_forward(route, weights, features, depth_features, id_start, id_end, captions, cells, drop_mult):
+    hard = route == "decoder_states_hard"
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, features, depth_features)
     cap = _dev(captions, "captions", torch.int64)
     if cap.dim() != 3 or cap.shape[0] != B:
-        raise _lib.DicError(f"decoder_states: captions must be [B,S,T] with B = {B}, got {tuple(captions.shape)}")
+        raise _lib.DicError(f"{route}: captions must be [B,S,T] with B = {B}, got {tuple(captions.shape)}")
     if tuple(f_rgb.shape[1:]) != (L_CELLS, D_ENC) or (f_dep is not None and tuple(f_dep.shape) != tuple(f_rgb.shape)):
-        raise _lib.DicError(f"decoder_states: features (and depth features) must be [B,{L_CELLS},{D_ENC}], got {tuple(f_rgb.shape)}")
+        raise _lib.DicError(f"{route}: features (and depth features) must be [B,{L_CELLS},{D_ENC}], got {tuple(f_rgb.shape)}")
     S, T = int(cap.shape[1]), int(cap.shape[2])
     R = B * S
+    if hard:
+        if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or tuple(cells.shape) != (B, S, T):
+            got = f"{cells.dtype} {tuple(cells.shape)}" if isinstance(cells, torch.Tensor) else type(cells).__name__
+            raise _lib.DicError(f"{route}: cells must be int32 [B,S,T] = [{B},{S},{T}], got {got}")
+        cells = _dev(cells, "cells", torch.int32)
     dm = None
     if drop_mult is not None:
         dm = _dev(drop_mult, "drop_mult")
         if tuple(dm.shape) != (R, T, D_HID):
-            raise _lib.DicError(f"decoder_states: drop_mult must be [B*S,T,{D_HID}] = [{R},{T},{D_HID}], got {tuple(dm.shape)}")
+            raise _lib.DicError(f"{route}: drop_mult must be [B*S,T,{D_HID}] = [{R},{T},{D_HID}], got {tuple(dm.shape)}")
     dev = f_rgb.device
-    ws = _workspace(lib.dic_decoder_states_workspace_bytes, dev, B, S, T, vocab)
+    query = lib.dic_decoder_states_hard_sizes if hard else lib.dic_decoder_states_workspace_bytes
+    ws = _workspace(query, dev, B, S, T, vocab)
     rr, tt = max(R, 1), max(T, 1)
     hidden = torch.empty((tt, rr, D_HID), dtype=torch.float32, device=dev)
     targets = torch.empty((tt, rr), dtype=torch.int64, device=dev)
     lengths = torch.empty((B, max(S, 1)), dtype=torch.int32, device=dev)
-    rc = lib.dic_decoder_states_fwd(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), T, ptr(cap),
-                                    ptr(dm), ptr(hidden), ptr(targets), ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
-    check(rc, "dic_decoder_states_fwd")
-    tape = StatesTape(ws, {k: t for (k, _), t in zip(DECODER_FIELDS, keep)}, vocab, B, S, T, int(id_start), int(id_end), cap, dm)
-    return hidden, targets, lengths, tape
+    tape = (HardStatesTape if hard else StatesTape)(ws, {k: t for (k, _), t in zip(DECODER_FIELDS, keep)}, vocab, B, S, T, int(id_start),
+                                                    int(id_end), cap, dm, *((cells,) if hard else ()))
+    head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), T, ptr(cap))
+    tail = (ptr(lengths), ptr(ws), ws.numel(), stream_ptr())
+    if not hard:
+        check(lib.dic_decoder_states_fwd(*head, ptr(dm), ptr(hidden), ptr(targets), *tail), "dic_decoder_states_fwd")
+        return hidden, targets, lengths, tape
+    cell_lp = torch.empty((tt, rr), dtype=torch.float32, device=dev)
+    check(lib.dic_decoder_states_hard_fwd(*head, ptr(cells), ptr(dm), ptr(hidden), ptr(targets), ptr(cell_lp), *tail),
+          "dic_decoder_states_hard_fwd")
+    return hidden, targets, cell_lp, lengths, tape
 
 
 def decoder_states_backward(tape: StatesTape, d_hidden: torch.Tensor, need_features: bool = True):
@@ -224,26 +258,53 @@ def decoder_states_backward_into(grads: Dict[str, torch.Tensor], tape: StatesTap
     return _decoder_states_backward(tape, d_hidden, need_features, grads)[1]
 
 
-def _decoder_states_backward(tape, d_hidden, need_features, grads):
+def decoder_states_hard_backward(tape: HardStatesTape, d_hidden: torch.Tensor, d_cell_logprobs: Optional[torch.Tensor] = None,
+                                 need_features: bool = True):
+    """dic_decoder_states_hard_bwd: backward through time of decoder_states_hard_forward.  d_hidden float32 [T,R,128],
+    d_cell_logprobs float32 [T,R] or None (= zeros); entries behind a caption's length are ignored.  Returns (grads: dict over the
+    15 keys STATES_GRAD_KEYS, d_features [B,196,2048] or None)."""
+    return _decoder_states_backward(tape, d_hidden, need_features, None, d_cell_logprobs)
+
+
+def decoder_states_hard_backward_into(grads: Dict[str, torch.Tensor], tape: HardStatesTape, d_hidden: torch.Tensor,
+                                      d_cell_logprobs: Optional[torch.Tensor] = None, need_features: bool = True):
+    """decoder_states_hard_backward with the 15 gradients written (not accumulated) into the caller's tensors, as
+    decoder_states_backward_into.  Returns d_features [B,196,2048] or None."""
+    return _decoder_states_backward(tape, d_hidden, need_features, grads, d_cell_logprobs)[1]
+
+
+def _decoder_states_backward(tape, d_hidden, need_features, grads, d_cell_logprobs=None):
     lib = _load()
+    hard = isinstance(tape, HardStatesTape)
+    route = "decoder_states_hard" if hard else "decoder_states"
     dh = _dev(d_hidden, "d_hidden")
     R = tape.B * tape.S
     if tuple(dh.shape) != (tape.T, R, D_HID):
-        raise _lib.DicError(f"decoder_states: d_hidden must be [T,R,{D_HID}] = [{tape.T},{R},{D_HID}], got {tuple(dh.shape)}")
+        raise _lib.DicError(f"{route}: d_hidden must be [T,R,{D_HID}] = [{tape.T},{R},{D_HID}], got {tuple(dh.shape)}")
+    dcl = None
+    if d_cell_logprobs is not None:
+        if not hard:
+            raise _lib.DicError("decoder_states: d_cell_logprobs belongs to a tape of decoder_states_hard_forward")
+        dcl = _dev(d_cell_logprobs, "d_cell_logprobs")
+        if tuple(dcl.shape) != (tape.T, R):
+            raise _lib.DicError(f"{route}: d_cell_logprobs must be [T,R] = [{tape.T},{R}], got {tuple(dcl.shape)}")
     wp, keep = decoder_ptrs(tape.weights)
     dev = dh.device
     if grads is None:
         grads = {k: torch.empty_like(tape.weights[k]) for k in STATES_GRAD_KEYS}
     else:
-        grads = {k: _grad_out(grads, k, tape.weights[k].shape, "decoder_states") for k in STATES_GRAD_KEYS}
+        grads = {k: _grad_out(grads, k, tape.weights[k].shape, route) for k in STATES_GRAD_KEYS}
     gp = DecoderPtrs()
     for key, field in DECODER_FIELDS:
         setattr(gp, field, grads[key].data_ptr() if key in grads else None)
     d_features = torch.empty((tape.B, L_CELLS, D_ENC), dtype=torch.float32, device=dev) if need_features else None
-    rc = lib.dic_decoder_states_bwd(C.byref(wp), tape.vocab, tape.B, tape.S, tape.id_start, tape.id_end, tape.T, ptr(tape.captions),
-                                    ptr(tape.drop_mult), ptr(dh), C.byref(gp), ptr(d_features), ptr(tape.workspace),
-                                    tape.workspace.numel(), stream_ptr())
-    check(rc, "dic_decoder_states_bwd")
+    head = (C.byref(wp), tape.vocab, tape.B, tape.S, tape.id_start, tape.id_end, tape.T, ptr(tape.captions))
+    tail = (C.byref(gp), ptr(d_features), ptr(tape.workspace), tape.workspace.numel(), stream_ptr())
+    if hard:
+        check(lib.dic_decoder_states_hard_bwd(*head, ptr(tape.cells), ptr(tape.drop_mult), ptr(dh), ptr(dcl), *tail),
+              "dic_decoder_states_hard_bwd")
+    else:
+        check(lib.dic_decoder_states_bwd(*head, ptr(tape.drop_mult), ptr(dh), *tail), "dic_decoder_states_bwd")
     return grads, d_features
 
 

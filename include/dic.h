@@ -364,6 +364,50 @@ int dic_decoder_states_bwd(const dic_decoder_weights* w, int V, int B, int S, lo
                            const int64_t* captions, const float* drop_mult, const float* d_hidden, const dic_decoder_grads* g,
                            float* d_features, void* workspace, size_t workspace_bytes, void* stream);
 
+/* hidden states of GIVEN captions along GIVEN attention cells, with a tape, and the backward through time: the joint likelihood
+ *   of a sample (tokens, cells) of the hard-attention decoder made differentiable.  argmax_l(e_l + g_l) with Gumbel noise g is an
+ *   exact draw from softmax(e), so a row of dic_decoder_sample_hard with per-row noise is a joint sample, and its joint
+ *   log-probability is sum_t [ log p(y_t | y_<t, s_<=t) + log softmax(e_t)[s_t] ] - every term differentiable in the 17 decoder
+ *   weights and the features, given tokens and cells (Show, Attend and Tell 4.2).  There is no reference implementation; this
+ *   comment is the specification.
+ *   Everything is that of dic_decoder_states_fwd / _bwd above, word for word: rows r = b*S + s, captions int64 [B,S,T] without
+ *     <start>, clamping, lengths derived on the device, drop_mult, out_hidden float [T,R,128] time-major and exactly 0 from the
+ *     length on, out_targets, out_lengths, the limits (1 <= S <= 8, 1 <= T <= 64, B*S*T <= 491 520), the order of the argument
+ *     checks, refusals before anything is launched - with a text that starts with "decoder_states_hard:".  The step differs:
+ *   Forward.  cells int [B,S,T], the layout of out_cells of dic_decoder_sample_hard / dic_decoder_beam_hard.  Step t of row r:
+ *     q = W_h h + b_h, e[l] = w . relu(P[b,l] + q) + b, alpha = softmax_l(e) (the kernel, roles and summation orders of the soft
+ *     route's step); ctx = F[b, cells[r,t], :], a gather; gate, LSTM cell and dropout as in the soft route.  No noise enters: the
+ *     cells are inputs.
+ *     out_cell_logprobs float [T,R], time-major - the layout dic_token_logprobs gives its log-probabilities, so the two add
+ *       elementwise: e[cell] - logsumexp_l(e) for t < length[r], exactly 0 from the length on.
+ *     A cell outside 0..195 at t < length[r] gives ctx = 0, cell log-probability 0 and no attention gradient from that (row, step)
+ *       (dic_decoder_sample_hard's rule for a row without a winner): never an out-of-range read.  Cells at or behind the length
+ *       are not read (the -1 of out_cells is accepted there, as is anything else).
+ *     The workspace keeps alpha [R,T,196], gates, gate activations, cell states, Q and the LSTM input rows - no context tape: the
+ *       backward gathers again.
+ *   Backward.  Same captions, cells and drop_mult.  d_hidden as above.  d_cell_logprobs (nullable = zeros, bytewise) float [T,R]:
+ *     the gradient of out_cell_logprobs; its entries with t >= length[r] are ignored (selected to 0, never multiplied).
+ *     d_e = d_cell_logprob * (onehot(cell) - alpha); from d_e, dq and dP as in the soft backward.  There is no
+ *     d alpha = d ctx . F pass.  d_ctx (through the gate) reaches F only at row cells[r,t].
+ *     d_features (nullable; when NULL that work is not done) float [B,196,2048] = the mean / initial-state path, plus the gathered
+ *       rows - several rows and steps of an image may hit one cell: they are added in ascending (s, t) -, plus dP W_z, in that order.
+ *     Writes (does not accumulate) the 15 gradients other than out_w / out_b, as above.
+ *   Properties: those of the soft pair, with "every summation order is a function of (B, S, T) and the cells alone": no float
+ *     atomics, two calls return identical bytes; forward row (b,s) depends only on image b, caption (b,s) and cells (b,s); F, P and
+ *     the mean once per image; the workspace size does not depend on V.
+ *   dic_decoder_states_hard_sizes hands the workspace size back through *workspace_bytes (0 with the refusal's code and text for
+ *   sizes the calls refuse).  No null pointer other than feat_depth, drop_mult, d_cell_logprobs, d_features, g->out_w, g->out_b.
+ *   DESIGN.md 5.26. */
+int dic_decoder_states_hard_sizes(int B, int S, int T, int V, size_t* workspace_bytes);
+int dic_decoder_states_hard_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                                long long id_start, long long id_end, int T, const int64_t* captions, const int* cells,
+                                const float* drop_mult, float* out_hidden, int64_t* out_targets, float* out_cell_logprobs,
+                                int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+int dic_decoder_states_hard_bwd(const dic_decoder_weights* w, int V, int B, int S, long long id_start, long long id_end, int T,
+                                const int64_t* captions, const int* cells, const float* drop_mult, const float* d_hidden,
+                                const float* d_cell_logprobs, const dic_decoder_grads* g, float* d_features, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* CIDEr-D (Vedantam et al. 2015) of S hypotheses per image against the image's references, over token ids, on the device: the reward
  *   of self-critical training and the metric `Cider()` of Captioning_models/evaluate_metrix.py:31 reports.  This comment is the
  *   specification: it restates pycocoevalcap's cider_scorer.py (whose `Cider` is CIDEr-D: clipping and a Gaussian length penalty),
