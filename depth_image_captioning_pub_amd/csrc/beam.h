@@ -29,8 +29,10 @@ int launch_argmax(const float* logits, int B, int V, int t, int T, long long* id
 
 // Rows [0, BK) of logits [BK][V]: lsm = logits - max - log sum exp(logits - max) (fp32), then the K best of score + lsm[v] (ties:
 // lower v), best first, into cand_val / cand_tok [row][K].  A finished beam has the single candidate (score, id_end).
+// ban (nullable): mask words of constrain.h, row r at ban + r * ban_stride (stride 0: one set of words for all rows); a live beam
+// does not offer a banned token, lsm is unchanged.
 int launch_beam_topk(int K, int BK, const float* logits, int V, const float* score, const int* fin, long long id_end,
-                     float* cand_val, int* cand_tok, hipStream_t st);
+                     float* cand_val, int* cand_tok, hipStream_t st, const unsigned* ban = nullptr, int ban_stride = 0);
 
 // End of a search over T steps: ranks the K hypotheses of each of the B images by score / length^length_penalty and follows the
 // back-pointers.  alphas_out (with alpha_hist) null: ids, scores and lengths only.  path: int [B*K*T] scratch.

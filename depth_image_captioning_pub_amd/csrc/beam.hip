@@ -1,5 +1,6 @@
 // The selection kernels both decoders launch (beam.h): the greedy arg-max, per-row top-K of the candidates and the final backtrack.
 #include "beam.h"
+#include "constrain.h"
 
 namespace dic {
 
@@ -44,12 +45,16 @@ int launch_argmax(const float* logits, int B, int V, int t, int T, long long* id
 // first, into cand_val / cand_tok [row][KB].  A finished beam has the single candidate (score, id_end); unused slots get
 // token -1.  grid (B*KB), 256 threads; the first 256*kTopkNPT logits of the row stay in registers over the three passes
 // (max, sum, selection), any beyond that are read again (V > 10240).
+// BANNED: ban [row * ban_stride + v / 32] bit v % 32 set = token v is not offered by a live beam (constrain.h).  The maximum and the
+// sum still run over all V logits - lsm stays the model's log-softmax - and a finished beam offers (score, id_end) whatever the
+// words say.  A row with fewer than KB unbanned tokens leaves token -1 in the unused slots.
 constexpr int kTopkNPT = 40;
-template <int KB>
+template <int KB, bool BANNED>
 __global__ void __launch_bounds__(256) beam_topk_kernel(const float* __restrict__ logits, int V,
                                                          const float* __restrict__ score, const int* __restrict__ fin,
                                                          long long id_end, float* __restrict__ cand_val,
-                                                         int* __restrict__ cand_tok) {
+                                                         int* __restrict__ cand_tok, const unsigned* __restrict__ ban,
+                                                         int ban_stride) {
   __shared__ float sv[2][4];
   __shared__ int si[2][4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -100,12 +105,22 @@ __global__ void __launch_bounds__(256) beam_topk_kernel(const float* __restrict_
       }
     }
   };
+  const unsigned* bw = BANNED ? ban + (long long)row * ban_stride : nullptr;
 #pragma unroll
   for (int i = 0; i < kTopkNPT; ++i) {
     const int v = tid + 256 * i;
-    if (v < V) offer(sc + ((xr[i] - m) - ls), v);
+    if constexpr (BANNED) {
+      if (v < V && !ban_bit(bw, v)) offer(sc + ((xr[i] - m) - ls), v);
+    } else {
+      if (v < V) offer(sc + ((xr[i] - m) - ls), v);
+    }
   }
-  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) offer(sc + ((x[v] - m) - ls), v);
+  for (int v = tid + 256 * kTopkNPT; v < V; v += 256) {
+    if constexpr (BANNED) {
+      if (ban_bit(bw, v)) continue;
+    }
+    offer(sc + ((x[v] - m) - ls), v);
+  }
   // KB rounds: the best head of the 256 lists wins and its thread moves on to its next element
 #pragma unroll
   for (int r = 0; r < KB; ++r) {
@@ -182,9 +197,14 @@ __global__ void __launch_bounds__(256) beam_backtrack_kernel(int KB, int T, int 
 }
 
 int launch_beam_topk(int K, int BK, const float* logits, int V, const float* score, const int* fin, long long id_end,
-                     float* cand_val, int* cand_tok, hipStream_t st) {
-  DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_topk_kernel<KB_>, dim3(BK), dim3(256), 0, st, logits, V, score, fin, id_end, cand_val,
-                                        cand_tok);)
+                     float* cand_val, int* cand_tok, hipStream_t st, const unsigned* ban, int ban_stride) {
+  if (ban != nullptr) {
+    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL((beam_topk_kernel<KB_, true>), dim3(BK), dim3(256), 0, st, logits, V, score, fin, id_end,
+                                          cand_val, cand_tok, ban, ban_stride);)
+  } else {
+    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL((beam_topk_kernel<KB_, false>), dim3(BK), dim3(256), 0, st, logits, V, score, fin, id_end,
+                                          cand_val, cand_tok, nullptr, 0);)
+  }
   DIC_LAUNCH_CHECK();
   return DIC_OK;
 }

@@ -1,0 +1,46 @@
+// Constrained decoding: the per-row, per-step set of banned tokens as a bit mask (constrain.hip; the rule is the header comment of
+// dic_token_ban_mask in include/dic.h).  Model-agnostic: token histories in, mask words out.  The masked forms of
+// beam_topk_kernel (beam.hip) and sample_token_kernel (sample.hip) read the words; dic_decoder_beam_constrained and
+// dic_decoder_sample_constrained (decoder_decode.hip) are the callers.
+//   launch_token_ban   token_ban_kernel: histories [R][T] int64 as they stand (a sampled row; the public entry point)
+//   launch_beam_ban    beam_ban_kernel: slot histories of a beam search, moved along the back-pointers of the last selection
+#pragma once
+#include "common.h"
+#include <cstdint>
+
+namespace dic {
+
+// what a caller asked for; a route takes a nullable pointer to one (null: the unconstrained entry points)
+struct DecodeConstraints {
+  const long long* suppress_ids;
+  int n_suppress, min_length, ngram;
+  bool active() const { return n_suppress > 0 || min_length > 0 || ngram > 0; }
+};
+
+static inline int ban_words(int V) { return (V + 31) / 32; }
+
+// The rule of a step.  static_words (nullable) [words]: the suppress list as mask words, built once per call; when null the list
+// itself (suppress_ids, n_suppress) is read.
+struct BanRule {
+  const unsigned* static_words;
+  const long long* suppress_ids; int n_suppress;
+  int V; long long id_end; int min_length, ngram;
+};
+
+// Rows [0, R) at step t: out[row][ceil(V/32)] = banned(row, t) from positions 0..t-1 of hist [R][T].  fin (nullable): rows with
+// fin[row] != 0 are skipped (their words keep what they held).
+int launch_token_ban(const BanRule& rule, const long long* hist, const int* fin, int R, int T, int t, unsigned* out, hipStream_t st);
+
+// Beam search, step t, rows b*K + k: the history of slot k is that of the hypothesis the selection of step t-1 put there - the
+// history of its parent bp_hist[t-1][row] (hist_old, positions 0..t-2) and the token tok_hist[t-1][row].  Writes it to hist_new
+// [BK][T] (the next step's hist_old: two buffers used in turn) and the mask words of the row.  Finished rows are skipped: their
+// descendants are finished too and nobody reads their history.  Without an n-gram rule no history is read or moved.
+int launch_beam_ban(const BanRule& rule, int K, int BK, int T, int t, const int* fin, const int* tok_hist, const int* bp_hist,
+                    const int* hist_old, int* hist_new, unsigned* out, hipStream_t st);
+
+#ifdef __HIPCC__
+// bit v of the words of a row (words: the row's first word)
+__device__ __forceinline__ bool ban_bit(const unsigned* __restrict__ words, int v) { return (words[v >> 5] >> (v & 31)) & 1u; }
+#endif
+
+}  // namespace dic

@@ -1,12 +1,15 @@
 // Decoding on the device: greedy (dic_decoder_greedy), beam search (dic_decoder_beam), sampling (dic_decoder_sample) and the
 // scoring of given captions (dic_decoder_score), and the hard-attention counterparts of the last three (dic_decoder_*_hard: the
-// same route bodies with the attention noise as an argument and hard_row_attn_kernel, decoder_hard.hip, as the attention step).
+// same route bodies with the attention noise as an argument and hard_row_attn_kernel, decoder_hard.hip, as the attention step),
+// and the constrained forms of beam search and sampling (dic_decoder_*_constrained: the same two bodies with a constraints record;
+// the banned-token masks are constrain.hip's, the masked selection kernels beam.hip's and sample.hip's).
 // The three routes keep S rows per image that share the image's F, P and mean:
 // their workspaces begin with one RowWs (row_carve), their start kernels call broadcast_state (and parse_caption) of decoder.h,
 // and every step begins with launch_row_step; what follows the LSTM cell - vocabulary GEMM, selection, hand-over - is the route's.
 #include "beam.h"
 #include "sample.h"
 #include "score.h"
+#include "constrain.h"
 #include <cmath>
 #include <algorithm>
 
@@ -470,6 +473,48 @@ int launch_row_step(const RowWs& ws, const dic_decoder_weights* w, int V, int B,
 }
 }  // namespace
 
+// ---- constrained decoding (dic_decoder_beam_constrained / dic_decoder_sample_constrained; the rule: dic_token_ban_mask) --------
+namespace {
+// what the constrained calls keep behind the workspace of the unconstrained route: the suppress list as mask words, the mask
+// words of every row and, for the beam search, the slot histories (two buffers used in turn)
+struct BanWs {
+  unsigned *static_words, *row_words;
+  int* hist[2];
+};
+
+void ban_carve(Carver& c, BanWs& w, size_t R, int T, int V, bool beam) {
+  w.static_words = c.take<unsigned>((size_t)ban_words(V));
+  w.row_words = c.take<unsigned>(R * ban_words(V));
+  w.hist[0] = w.hist[1] = nullptr;
+  if (beam) {
+    w.hist[0] = c.take<int>(R * T);
+    w.hist[1] = c.take<int>(R * T);
+  }
+}
+
+// the refusals the constraints add, behind the route's scalar checks; rows: K of the beam search, 1 for sampling
+int check_constraints(const char* route, const DecodeConstraints& c, int V, int max_length, int rows) {
+  DIC_REQUIRE(c.min_length >= 0, "%s: min_length=%d must be >= 0", route, c.min_length);
+  DIC_REQUIRE(c.ngram >= 0, "%s: no_repeat_ngram=%d must be >= 0 (0: off)", route, c.ngram);
+  DIC_REQUIRE(c.n_suppress >= 0, "%s: n_suppress=%d must be >= 0", route, c.n_suppress);
+  DIC_REQUIRE(c.n_suppress == 0 || c.suppress_ids != nullptr, "%s: null pointer (suppress_ids with n_suppress=%d)", route,
+              c.n_suppress);
+  const long long left = (long long)V - c.n_suppress - 1 - (c.ngram ? max_length : 0);
+  DIC_REQUIRE(left >= rows, "%s: V - n_suppress - 1%s = %lld tokens can be guaranteed unbanned at every step, fewer than the %d a "
+              "step needs (V=%d, n_suppress=%d, no_repeat_ngram=%d, max_length=%d)", route, c.ngram ? " - max_length" : "", left,
+              rows, V, c.n_suppress, c.ngram, max_length);
+  return DIC_OK;
+}
+
+// the suppress list as mask words, once per call: the mask kernel on one row without history, <end> ban or n-grams
+int build_static_words(const DecodeConstraints& c, int V, long long id_end, unsigned* words, hipStream_t st) {
+  return launch_token_ban(BanRule{nullptr, c.suppress_ids, c.n_suppress, V, id_end, 0, 0}, nullptr, nullptr, 1, 0, 0, words, st);
+}
+
+// does step t need words of its own per row?  Otherwise the static words serve every row (stride 0), or nothing is banned.
+bool step_has_row_words(const DecodeConstraints& c, int t) { return c.ngram > 0 || t < c.min_length; }
+}  // namespace
+
 // ---- beam search ------------------------------------------------------------------------------------------------------------
 namespace {
 struct BeamWs : RowWs {
@@ -481,7 +526,7 @@ struct BeamWs : RowWs {
   size_t bytes;
 };
 
-BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overflow) {
+BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overflow, BanWs* ban = nullptr) {
   Carver c(p, bytes);
   BeamWs w{};
   const size_t BK = (size_t)B * K;
@@ -499,6 +544,7 @@ BeamWs beam_carve(void* p, size_t bytes, int B, int K, int T, int V, bool* overf
   w.path = c.take<int>(BK * T);
   w.alpha_hist = c.take<float>(BK * T * kL);
   w.cell_hist = reinterpret_cast<int*>(w.alpha_hist);
+  if (ban) ban_carve(c, *ban, BK, T, V, true);
   w.bytes = c.off;
   if (overflow) *overflow = c.overflow;
   return w;
@@ -520,19 +566,23 @@ namespace {
 int beam_route(const char* route, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
                long long id_start, long long id_end, int max_length, float length_penalty, bool hard, const float* gumbel_u,
                int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths, float* alphas_out, int* out_cells,
-               void* workspace, size_t workspace_bytes, hipStream_t st) {
+               void* workspace, size_t workspace_bytes, hipStream_t st, const DecodeConstraints* con = nullptr) {
   // every argument check comes before the first HIP call
   DIC_REQUIRE(K >= 1 && K <= kBeamMax, "%s: beam width K=%d is outside 1..%d", route, K, kBeamMax);
   DIC_TRY(check_row_sizes(route, B, V, max_length));
   DIC_REQUIRE(V >= K, "%s: vocabulary V=%d is smaller than the beam width K=%d", route, V, K);
   DIC_TRY(check_token_ids(route, V, id_start, id_end));
   DIC_REQUIRE(length_penalty >= 0.f, "%s: length_penalty=%g must be >= 0 (NaN is refused too)", route, (double)length_penalty);
+  if (con) DIC_TRY(check_constraints(route, *con, V, max_length, K));
   DIC_TRY(check_hard_noise(route, hard, noise_shared, gumbel_u));
   DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace, "%s: null pointer", route);
   const int T = max_length, BK = B * K;
   bool ov = false;
-  BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov);
+  BanWs bws{};
+  BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov, con ? &bws : nullptr);
   if (ov) return workspace_too_small(route, workspace_bytes, ws.bytes);
+  const bool banned = con && con->active();      // every constraint off: nothing of it is launched, the mask is null
+  if (banned && con->n_suppress > 0) DIC_TRY(build_static_words(*con, V, id_end, bws.static_words, st));
   // per image, never per beam.  [h0 | c0] -> slot 1 of beam 0, then copied to the KB beams
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)K * 2 * kH, false}, st));
   hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
@@ -547,7 +597,20 @@ int beam_route(const char* route, const dic_decoder_weights* w, int V, const flo
       DIC_TRY(launch_row_step(ws, w, V, B, K, ws.prev, alpha_t, ws.Hdrop, 0, st));
     }
     DIC_TRY(gemm(BK, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
-    DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st));
+    const unsigned* ban = nullptr;
+    int ban_stride = 0;
+    if (banned) {
+      const BanRule rule{con->n_suppress > 0 ? bws.static_words : nullptr, nullptr, 0, V, id_end, con->min_length, con->ngram};
+      if (step_has_row_words(*con, t)) {
+        DIC_TRY(launch_beam_ban(rule, K, BK, T, t, ws.fin, ws.tok_hist, ws.bp_hist, bws.hist[(t + 1) & 1], bws.hist[t & 1],
+                                bws.row_words, st));
+        ban = bws.row_words;
+        ban_stride = ban_words(V);
+      } else {
+        ban = rule.static_words;
+      }
+    }
+    DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st, ban, ban_stride));
     DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
                                           BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
     DIC_LAUNCH_CHECK();
@@ -577,6 +640,31 @@ int dic_decoder_beam_hard(const dic_decoder_weights* w, int V, const float* feat
                     (hipStream_t)stream);
 }
 
+int dic_decoder_beam_constrained_sizes(int B, int K, int max_length, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "dic_decoder_beam_constrained_sizes: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_REQUIRE(beam_sizes_ok(B, K, max_length, V), "dic_decoder_beam_constrained_sizes: sizes B=%d K=%d max_length=%d V=%d are ones "
+              "the call refuses", B, K, max_length, V);
+  bool ov;
+  BanWs bws{};
+  *workspace_bytes = beam_carve(nullptr, 0, B, K, max_length, V, &ov, &bws).bytes;
+  return DIC_OK;
+}
+
+int dic_decoder_beam_constrained(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                                 long long id_start, long long id_end, int max_length, float length_penalty,
+                                 const int64_t* suppress_ids, int n_suppress, int min_length, int no_repeat_ngram, int mode,
+                                 const float* gumbel_u, int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths,
+                                 float* alphas_out, int* out_cells, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* route = "decoder_beam_constrained";
+  DIC_REQUIRE(mode == 0 || mode == 2, "%s: mode=%d must be 0 (soft) or 2 (hard attention)", route, mode);
+  const DecodeConstraints con{(const long long*)suppress_ids, n_suppress, min_length, no_repeat_ngram};
+  const bool hard = mode == 2;
+  return beam_route(route, w, V, feat_rgb, feat_depth, B, K, id_start, id_end, max_length, length_penalty, hard,
+                    hard ? gumbel_u : nullptr, hard ? noise_shared : 1, out_ids, out_scores, out_lengths, hard ? nullptr : alphas_out,
+                    hard ? out_cells : nullptr, workspace, workspace_bytes, (hipStream_t)stream, &con);
+}
+
 // ---- sampling ---------------------------------------------------------------------------------------------------------------
 namespace {
 struct SampleWs : RowWs {      // (BeamWs without the candidate, back-pointer and path arrays)
@@ -587,7 +675,7 @@ struct SampleWs : RowWs {      // (BeamWs without the candidate, back-pointer an
   size_t bytes;
 };
 
-SampleWs sample_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* overflow) {
+SampleWs sample_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* overflow, BanWs* ban = nullptr) {
   Carver c(p, bytes);
   SampleWs w{};
   const size_t R = (size_t)B * S;
@@ -598,6 +686,7 @@ SampleWs sample_carve(void* p, size_t bytes, int B, int S, int T, int V, bool* o
   w.prev = c.take<long long>(R);
   w.alpha_hist = c.take<float>(R * T * kL);
   w.cell_hist = reinterpret_cast<int*>(w.alpha_hist);
+  if (ban) ban_carve(c, *ban, R, T, V, false);
   w.bytes = c.off;
   if (overflow) *overflow = c.overflow;
   return w;
@@ -619,7 +708,8 @@ namespace {
 int sample_route(const char* route, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
                  long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
                  const float* uniform_u, bool hard, const float* gumbel_u, int noise_shared, int64_t* out_ids, float* out_logprobs,
-                 int* out_lengths, float* alphas_out, int* out_cells, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                 int* out_lengths, float* alphas_out, int* out_cells, void* workspace, size_t workspace_bytes, hipStream_t st,
+                 const DecodeConstraints* con = nullptr) {
   // every argument check comes before the first HIP call
   DIC_REQUIRE(S >= 1 && S <= kBeamMax, "%s: samples per image S=%d is outside 1..%d", route, S, kBeamMax);
   DIC_TRY(check_row_sizes(route, B, V, max_length));
@@ -628,12 +718,16 @@ int sample_route(const char* route, const dic_decoder_weights* w, int V, const f
               (double)temperature);
   DIC_REQUIRE(top_k >= 0 && top_k <= V, "%s: top_k=%d is outside 0..V=%d (0: no limit)", route, top_k, V);
   DIC_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p=%g is outside (0, 1] (1: off; NaN is refused too)", route, (double)top_p);
+  if (con) DIC_TRY(check_constraints(route, *con, V, max_length, 1));
   DIC_TRY(check_hard_noise(route, hard, noise_shared, gumbel_u));
   DIC_REQUIRE(w && feat_rgb && uniform_u && out_ids && out_logprobs && out_lengths && workspace, "%s: null pointer", route);
   const int T = max_length, R = B * S;
   bool ov = false;
-  SampleWs ws = sample_carve(workspace, workspace_bytes, B, S, T, V, &ov);
+  BanWs bws{};
+  SampleWs ws = sample_carve(workspace, workspace_bytes, B, S, T, V, &ov, con ? &bws : nullptr);
   if (ov) return workspace_too_small(route, workspace_bytes, ws.bytes);
+  const bool banned = con && con->active();      // every constraint off: nothing of it is launched, the mask is null
+  if (banned && con->n_suppress > 0) DIC_TRY(build_static_words(*con, V, id_end, bws.static_words, st));
   // per image, never per sample.  [h0 | c0] -> slot 1 of sample 0, then copied to the S rows
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)S * 2 * kH, false}, st));
   hipLaunchKernelGGL(sample_init_kernel, dim3(B), dim3(kH), 0, st, S, id_start, ws.fin, out_lengths, ws.prev, ws.Hst, ws.Cst);
@@ -647,9 +741,19 @@ int sample_route(const char* route, const dic_decoder_weights* w, int V, const f
       DIC_TRY(launch_row_step(ws, w, V, B, S, ws.prev, alpha_t, ws.Hdrop, 0, st));
     }
     DIC_TRY(gemm(R, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(ws.logits, V, w->out_b), st, 1, nullptr, 64));
-    DIC_TRY(launch_sample_token(SampleStep{ws.logits, R, V, temperature, top_k, top_p, uniform_u + (size_t)t * R, id_end, t, T,
-                                           ws.fin, out_lengths, ws.prev, (long long*)out_ids, out_logprobs, ws.Hst, ws.Cst, kH},
-                                st));
+    SampleStep step{ws.logits, R, V, temperature, top_k, top_p, uniform_u + (size_t)t * R, id_end, t, T,
+                    ws.fin, out_lengths, ws.prev, (long long*)out_ids, out_logprobs, ws.Hst, ws.Cst, kH};
+    if (banned) {
+      const BanRule rule{con->n_suppress > 0 ? bws.static_words : nullptr, nullptr, 0, V, id_end, con->min_length, con->ngram};
+      if (step_has_row_words(*con, t)) {      // a row's history is what it has drawn: positions 0..t-1 of its out_ids
+        DIC_TRY(launch_token_ban(rule, (const long long*)out_ids, ws.fin, R, T, t, bws.row_words, st));
+        step.ban = bws.row_words;
+        step.ban_stride = ban_words(V);
+      } else {
+        step.ban = rule.static_words;
+      }
+    }
+    DIC_TRY(launch_sample_token(step, st));
   }
   if (alphas_out) {
     hipLaunchKernelGGL(sample_alpha_gather_kernel, dim3(ceil_div((long long)R * T * kL, 256)), dim3(256), 0, st, ws.alpha_hist, R,
@@ -677,6 +781,32 @@ int dic_decoder_sample_hard(const dic_decoder_weights* w, int V, const float* fe
   return sample_route("decoder_sample_hard", w, V, feat_rgb, feat_depth, B, S, id_start, id_end, max_length, temperature, top_k,
                       top_p, uniform_u, true, gumbel_u, noise_shared, out_ids, out_logprobs, out_lengths, nullptr, out_cells,
                       workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int dic_decoder_sample_constrained_sizes(int B, int S, int max_length, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "dic_decoder_sample_constrained_sizes: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_REQUIRE(sample_sizes_ok(B, S, max_length, V), "dic_decoder_sample_constrained_sizes: sizes B=%d S=%d max_length=%d V=%d are "
+              "ones the call refuses", B, S, max_length, V);
+  bool ov;
+  BanWs bws{};
+  *workspace_bytes = sample_carve(nullptr, 0, B, S, max_length, V, &ov, &bws).bytes;
+  return DIC_OK;
+}
+
+int dic_decoder_sample_constrained(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                                   long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                                   const float* uniform_u, const int64_t* suppress_ids, int n_suppress, int min_length,
+                                   int no_repeat_ngram, int mode, const float* gumbel_u, int noise_shared, int64_t* out_ids,
+                                   float* out_logprobs, int* out_lengths, float* alphas_out, int* out_cells, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  const char* route = "decoder_sample_constrained";
+  DIC_REQUIRE(mode == 0 || mode == 2, "%s: mode=%d must be 0 (soft) or 2 (hard attention)", route, mode);
+  const DecodeConstraints con{(const long long*)suppress_ids, n_suppress, min_length, no_repeat_ngram};
+  const bool hard = mode == 2;
+  return sample_route(route, w, V, feat_rgb, feat_depth, B, S, id_start, id_end, max_length, temperature, top_k, top_p, uniform_u,
+                      hard, hard ? gumbel_u : nullptr, hard ? noise_shared : 1, out_ids, out_logprobs, out_lengths,
+                      hard ? nullptr : alphas_out, hard ? out_cells : nullptr, workspace, workspace_bytes, (hipStream_t)stream, &con);
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------------

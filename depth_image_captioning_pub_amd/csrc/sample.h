@@ -10,6 +10,8 @@ namespace dic {
 // A live row draws with u[row], writes out_ids / out_logprobs [row][T] at step t, sets fin when it drew id_end and length = t + 1.
 // A finished row writes (id_end, 0) and reads no logits.  Hst / Cst (nullable): recurrent state [R][2][state_n]; a live row
 // hands slot 1 (what the cell wrote) over to slot 0 (what the next step reads) - a sampled row is its own parent.
+// ban (nullable): mask words of constrain.h, row r at ban + r * ban_stride (stride 0: one set of words for all rows); a banned
+// token is outside the vocabulary of the step: never kept, never counted, never drawn.
 struct SampleStep {
   const float* logits; int R, V;
   float temperature; int top_k; float top_p;
@@ -18,6 +20,7 @@ struct SampleStep {
   int *fin, *length; long long* prev;
   long long* out_ids; float* out_logprobs;
   float *Hst, *Cst; int state_n;
+  const unsigned* ban = nullptr; int ban_stride = 0;
 };
 int launch_sample_token(const SampleStep& s, hipStream_t st);
 

@@ -1,5 +1,6 @@
 // sample_token_kernel: draws one token per row of logits (sample.h; the rule is the header comment of dic_decoder_sample).
 #include "sample.h"
+#include "constrain.h"
 
 namespace dic {
 
@@ -47,6 +48,10 @@ struct SampleOpAddF {
 // Draw: kept e (others -1) go to LDS in index order; thread i owns the contiguous span [40 i, 40 i + 40) of each 10 240-chunk,
 // one workgroup scan covers the span totals, then every thread walks its own span from its prefix and offers the first index
 // whose running sum exceeds u Z; the lowest offer wins.  No float atomics, no loop whose trip count depends on the data.
+// BANNED: a token whose bit is set in the row's mask words (a.ban, constrain.h) gets key 0, the value of a slot past V, wherever a
+// key is formed - the register-resident part and every re-read beyond 10 240 - so it is outside the maximum, every count, every
+// mass and the draw, u >= 1 included: it is not a member of the vocabulary at this step.
+template <bool BANNED>
 __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
   __shared__ float span_s[256 * kSampleLdsRow];
   __shared__ SampleRed red;
@@ -69,6 +74,13 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
   const float temp = a.temperature;
   int phase = 0;
   auto zof = [&](int v) { return x[v] / temp + 0.f; };      // (+0: -0 and +0 are one value, so they get one key)
+  const unsigned* bw = BANNED ? a.ban + (long long)row * a.ban_stride : nullptr;
+  auto keyof = [&](int v, float z) -> unsigned {            // the key of token v < V with value z
+    if constexpr (BANNED) {
+      if (ban_bit(bw, v)) return 0u;
+    }
+    return sample_key(z);
+  };
   // ---- pass 1: keys and their maximum
   unsigned kr[kSampleNPT];
   unsigned kmax = 0;
@@ -78,12 +90,12 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
     for (int i = 0; i < kSampleNPT; ++i) xr[i] = x[min(tid + 256 * i, V - 1)];
 #pragma unroll
     for (int i = 0; i < kSampleNPT; ++i) {
-      kr[i] = tid + 256 * i < V ? sample_key(xr[i] / temp + 0.f) : 0u;
+      kr[i] = tid + 256 * i < V ? keyof(tid + 256 * i, xr[i] / temp + 0.f) : 0u;
       kmax = kr[i] > kmax ? kr[i] : kmax;
     }
   }
   for (int v = tid + kSampleSpan; v < V; v += 256) {
-    const unsigned k = sample_key(zof(v));
+    const unsigned k = keyof(v, zof(v));
     kmax = k > kmax ? k : kmax;
   }
   kmax = sample_reduce(red, phase, kmax, SampleOpMaxU());
@@ -98,7 +110,7 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
     for (int i = 0; i < kSampleNPT; ++i) s += kr[i] >= th ? ev[i] : 0.f;
     for (int v = tid + kSampleSpan; v < V; v += 256) {
       const float z = zof(v);
-      s += sample_key(z) >= th ? expf(z - m) : 0.f;
+      s += keyof(v, z) >= th ? expf(z - m) : 0.f;
     }
     return __uint_as_float(sample_reduce(red, phase, __float_as_uint(s), SampleOpAddF()));
   };
@@ -112,7 +124,7 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
       unsigned c = 0;
 #pragma unroll
       for (int i = 0; i < kSampleNPT; ++i) c += kr[i] >= cand ? 1u : 0u;
-      for (int v = tid + kSampleSpan; v < V; v += 256) c += sample_key(zof(v)) >= cand ? 1u : 0u;
+      for (int v = tid + kSampleSpan; v < V; v += 256) c += keyof(v, zof(v)) >= cand ? 1u : 0u;
       c = sample_reduce(red, phase, c, SampleOpAddU());
       if (c >= (unsigned)a.top_k) th = cand;
     }
@@ -149,7 +161,7 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
       const int v = v0 + j;
       if (v >= V) return -1.f;
       const float z = zof(v);
-      return sample_key(z) >= tau ? expf(z - m) : -1.f;
+      return keyof(v, z) >= tau ? expf(z - m) : -1.f;
     };
     float tot = 0.f;
 #pragma unroll
@@ -198,7 +210,11 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const SampleStep a) {
 }
 
 int launch_sample_token(const SampleStep& s, hipStream_t st) {
-  hipLaunchKernelGGL(sample_token_kernel, dim3(s.R), dim3(256), 0, st, s);
+  if (s.ban != nullptr) {
+    hipLaunchKernelGGL(sample_token_kernel<true>, dim3(s.R), dim3(256), 0, st, s);
+  } else {
+    hipLaunchKernelGGL(sample_token_kernel<false>, dim3(s.R), dim3(256), 0, st, s);
+  }
   DIC_LAUNCH_CHECK();
   return DIC_OK;
 }

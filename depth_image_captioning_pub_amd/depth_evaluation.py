@@ -23,7 +23,7 @@ from . import metrics as metrics_mod
 from . import synthetic as syn
 from ._lib import DicError
 from .cider import CiderD
-from .Captioning_models import util
+from .Captioning_models import constrained, util
 from .Captioning_models.Base_caption_model.base_caption_models import CNNEncoder_Atten
 from .Captioning_models.config import ConfigTrain
 from .Captioning_models.Depth_caption_model.depth_models import (CD_RNNDecoderWithHardAttention,
@@ -56,8 +56,8 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
                       length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False,
-                      attention_seed: Optional[int] = None):
+                      top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False, suppress=None,
+                      min_length: int = 0, no_repeat_ngram: int = 0, attention_seed: Optional[int] = None):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
@@ -74,7 +74,13 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     synthetic.reference_captions(batch_size, vocab_size, seed=5000 + b) of batch b, five per image, scored on the device as decoded
     strings are (count_end=False); the idf table is that of all the evaluated images' references.  Nothing else depends on it.
     metrics=True ADDS the reference's report without METEOR - "Bleu_1" .. "Bleu_4" (corpus BLEU), "ROUGE_L" (mean over the images)
-    and "CIDEr" (as cider=True) - over the same references, by metrics.evaluation_scores.  Nothing else depends on it."""
+    and "CIDEr" (as cider=True) - over the same references, by metrics.evaluation_scores.  Nothing else depends on it.
+    suppress (a sequence of words or token ids, e.g. ("<start>", "<unk>", "<null>")), min_length, no_repeat_ngram: constrained
+    decoding (Captioning_models/constrained.py).  With the defaults (None, 0, 0) the loop, its results and the
+    written file are what they were without these keywords.  With any of them set the hypotheses come from the constrained beam
+    search - no suppressed token, no '<end>' before `min_length` words, no n-gram of `no_repeat_ngram` tokens twice; beam_size=1 is
+    then constrained greedy decoding - and, when n_samples > 0, the samples from the constrained sampler.  A hard model needs
+    attention_seed for either."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
@@ -91,6 +97,11 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     if int(n_samples) > 0 and atten != "soft" and attention_seed is None:
         raise DicError("n_samples > 0 needs atten='soft': sampling is built for the soft-attention decoder only (a hard model "
                        "samples conditional on its attention noise when attention_seed is given)")
+    constrained.check_constraints("Cdepth_evaluation", min_length, no_repeat_ngram)
+    constrain = bool(suppress is not None and len(suppress) > 0) or int(min_length) > 0 or int(no_repeat_ngram) > 0
+    if constrain and atten == "hard" and attention_seed is None:
+        raise DicError("suppress / min_length / no_repeat_ngram need attention_seed with atten='hard': the constrained routes of a "
+                       "hard model decode conditional on its attention noise")
     config = config or ConfigTrain()
     dev = config.device
     tag = f"depth_{atten}"
@@ -99,6 +110,9 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
         param_files = {"run0": [f"{tag}_encoder_best_synthetic0.pth", f"{tag}_decoder_best_synthetic0.pth",
                                 f"{tag}_D_encoder_best_synthetic0.pth"]}
     word_to_id, id_to_word = synthetic_vocabulary(config.vocab_size)
+    if constrain:
+        suppress = constrained.suppress_ids("Cdepth_evaluation", suppress, word_to_id)      # (an unknown word is refused before any work)
+        limits = dict(suppress=suppress, min_length=int(min_length), no_repeat_ngram=int(no_repeat_ngram))
     encoder = CNNEncoder_Atten(config.enc_img_size)                                          # depth_evaluation.py:108-129
     if atten == "soft":
         decoder = CD_RNNDecoderWithSoftAttention(config.dim_attention, config.dim_embedding, config.dim_encoder,
@@ -126,7 +140,12 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             feature = encoder(imgs)                                                         # :164
             if cider or metrics:
                 references += syn.reference_captions(config.batch_size, config.vocab_size, seed=5000 + b)
-            if int(beam_size) > 1 and atten == "hard":
+            if constrain:
+                seeds = dict(attention_seed=int(attention_seed) + b) if atten == "hard" else {}
+                hypos_id.append(constrained.constrained_beam_sample(decoder, feature, depth_features, word_to_id,
+                                                                    beam_size=int(beam_size), length_penalty=length_penalty,
+                                                                    **limits, **seeds))
+            elif int(beam_size) > 1 and atten == "hard":
                 hypos_id.append(decoder.hard_beam_sample(feature, depth_features, word_to_id, beam_size=int(beam_size),
                                                          length_penalty=length_penalty, attention_seed=int(attention_seed) + b))
             elif int(beam_size) > 1:
@@ -134,7 +153,12 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
                                                     length_penalty=length_penalty))
             else:
                 hypos_id.append(decoder.batch_sample(feature, depth_features, word_to_id))     # :165
-            if int(n_samples) > 0 and atten == "hard":
+            if int(n_samples) > 0 and constrain:
+                drawn = constrained.constrained_stochastic_sample(decoder, feature, depth_features, word_to_id,
+                                                                  n_samples=int(n_samples), temperature=temperature, top_k=top_k,
+                                                                  top_p=top_p, seed=int(seed) + b, **limits, **seeds)
+                sample_ids.append(drawn.reshape(drawn.shape[0], int(n_samples), -1))
+            elif int(n_samples) > 0 and atten == "hard":
                 drawn = decoder.hard_stochastic_sample(feature, depth_features, word_to_id, n_samples=int(n_samples),
                                                        temperature=temperature, top_k=top_k, top_p=top_p, seed=int(seed) + b,
                                                        attention_seed=int(attention_seed) + b)

@@ -7,8 +7,9 @@ import ctypes as C          # (native.C: tests set restypes through it)
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
 from ._core import D_ATT, D_EMB, D_ENC, D_HID, DEFAULT_CONV_MODE, L_CELLS, L_COMPACT, batch_sizes_of
-from .decode import (decoder_beam, decoder_beam_hard, decoder_greedy, decoder_sample, decoder_sample_hard, decoder_score,
-                     decoder_score_hard, nic_beam, nic_greedy, nic_sample, nic_score)
+from .decode import (decoder_beam, decoder_beam_constrained, decoder_beam_hard, decoder_greedy, decoder_sample,
+                     decoder_sample_constrained, decoder_sample_hard, decoder_score, decoder_score_hard, nic_beam, nic_greedy,
+                     nic_sample, nic_score, token_ban_mask)
 from .decoder import (DECODER_FIELDS, STATES_GRAD_KEYS, DecoderPtrs, DecoderTape, HardStatesTape, StatesTape, attention_backward,
                       attention_forward, decoder_attention_relu_mask, decoder_backward, decoder_forward, decoder_ptrs, decoder_states_backward,
                       decoder_states_backward_into, decoder_states_forward, decoder_states_hard_backward,

@@ -5,13 +5,13 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Union
 
 import torch
 
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
-from ._core import L_CELLS, _dev, _workspace
+from ._core import L_CELLS, _dev, _load, _workspace
 from .decoder import _decoder_prologue
 from .nic import _nic_prologue
 
@@ -71,6 +71,46 @@ def _hard_noise(what: str, gumbel_u: torch.Tensor, max_length: int, B: int, S: i
     return u
 
 
+def _suppress_ids(what: str, suppress, device) -> Optional[torch.Tensor]:
+    """The suppress list of a constrained call as int64 [n] on the device, None for an empty one: an int sequence or a 1-d integer
+    tensor (ids outside the vocabulary are ignored by the library, not here)."""
+    if suppress is None:
+        return None
+    if isinstance(suppress, torch.Tensor):
+        if suppress.dim() != 1 or suppress.dtype.is_floating_point or suppress.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise _lib.DicError(f"{what}: suppress must be a 1-d integer tensor, got {suppress.dtype} {tuple(suppress.shape)}")
+        t = suppress.to(device=device, dtype=torch.int64).contiguous()
+    else:
+        values = list(suppress)
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in values):
+            raise _lib.DicError(f"{what}: suppress must hold token ids (int), got {values!r}")
+        t = torch.tensor(values, dtype=torch.int64, device=device)
+    return t if t.numel() else None
+
+
+def _constraint_args(what: str, suppress, min_length, no_repeat_ngram, device):
+    """(the suppress tensor - to be kept alive across the call -, the four constraint arguments of a dic_decoder_*_constrained call)."""
+    sup = _suppress_ids(what, suppress, device)
+    return sup, (ptr(sup), int(sup.numel()) if sup is not None else 0, int(min_length), int(no_repeat_ngram))
+
+
+def token_ban_mask(hist: torch.Tensor, t: int, vocab: int, id_end: int, suppress=None, min_length: int = 0,
+                   no_repeat_ngram: int = 0) -> torch.Tensor:
+    """dic_token_ban_mask: the banned-token sets of constrained decoding as bit masks (semantics: include/dic.h).  hist: int64 [R,T]
+    on the device, the rows' token histories (positions 0..t-1 are read).  Returns int32 [R, ceil(vocab/32)] on the device: bit
+    v & 31 of word v >> 5 is set when token v is banned for the row at step t (the words are the library's uint32, bit for bit)."""
+    lib = _load()
+    if not isinstance(hist, torch.Tensor) or hist.dim() != 2:
+        raise _lib.DicError(f"token_ban_mask: hist must be int64 [R,T], got {tuple(getattr(hist, 'shape', ()))}")
+    h = _dev(hist, "hist", torch.int64)
+    R, T = int(h.shape[0]), int(h.shape[1])
+    sup, con = _constraint_args("token_ban_mask", suppress, min_length, no_repeat_ngram, h.device)
+    out = torch.empty((max(R, 1), (max(int(vocab), 1) + 31) // 32), dtype=torch.int32, device=h.device)
+    rc = lib.dic_token_ban_mask(ptr(h), R, T, int(t), int(vocab), con[0], con[1], int(id_end), con[2], con[3], ptr(out), stream_ptr())
+    check(rc, "dic_token_ban_mask")
+    return out
+
+
 def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
                    id_start: int, max_length: int = 30, mode: int = 0, gumbel_u: Optional[torch.Tensor] = None):
     """dic_decoder_greedy. Returns (ids int64 [B,max_length] on device, alphas [B,max_length,196])."""
@@ -86,35 +126,53 @@ def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
 
 
 # ---- attention decoder: beam / sample / score.  noise: None (soft) or (gumbel_u, noise_shared) (hard, conditional on that noise) -------
-def _decoder_beam(what, weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length, length_penalty, record, noise):
+def _decoder_beam(what, weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length, length_penalty, record, noise,
+                  constraints=None):
+    """constraints: None, or (suppress, min_length, no_repeat_ngram) - then the call is dic_decoder_beam_constrained, whose mode
+    argument says what `noise` says here."""
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
     K, dev = int(beam_size), f_rgb.device
     u = _hard_noise(what, noise[0], max_length, B, max(K, 1), noise[1]) if noise else None
-    ws = _workspace(lib.dic_decoder_beam_workspace_bytes, dev, B, K, max_length, vocab)
+    query = lib.dic_decoder_beam_workspace_bytes if constraints is None else lib.dic_decoder_beam_constrained_sizes
+    ws = _workspace(query, dev, B, K, max_length, vocab)
     ids, scores, lengths = _beam_outputs(B, K, max_length, dev)
     rec = _step_record(record, noise is not None, B, K, max_length, dev)
     head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, int(id_start), int(id_end), max_length, length_penalty)
     tail = (ptr(ids), ptr(scores), ptr(lengths), ptr(rec), ptr(ws), ws.numel(), stream_ptr())
-    rc = (lib.dic_decoder_beam(*head, *tail) if noise is None else
-          lib.dic_decoder_beam_hard(*head, ptr(u), int(bool(noise[1])), *tail))
+    if constraints is not None:
+        sup, con = _constraint_args(what, *constraints, dev)
+        alphas, cells = (None, rec) if noise else (rec, None)
+        rc = lib.dic_decoder_beam_constrained(*head, *con, 2 if noise else 0, ptr(u), int(bool(noise[1])) if noise else 1, *tail[:3],
+                                              ptr(alphas), ptr(cells), *tail[4:])
+    else:
+        rc = (lib.dic_decoder_beam(*head, *tail) if noise is None else
+              lib.dic_decoder_beam_hard(*head, ptr(u), int(bool(noise[1])), *tail))
     check(rc, "dic_" + what)
     return (ids, scores, lengths, rec) if record else (ids, scores, lengths)
 
 
 def _decoder_sample(what, weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u, max_length, temperature, top_k,
-                    top_p, record, noise):
+                    top_p, record, noise, constraints=None):
+    """constraints: as _decoder_beam's - then the call is dic_decoder_sample_constrained."""
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
     S, dev = int(n_samples), f_rgb.device
     u = _uniforms(what, uniform_u, max_length, B * max(S, 1))
     gu = _hard_noise(what, noise[0], max_length, B, max(S, 1), noise[1]) if noise else None
-    ws = _workspace(lib.dic_decoder_sample_workspace_bytes, dev, B, S, max_length, vocab)
+    query = lib.dic_decoder_sample_workspace_bytes if constraints is None else lib.dic_decoder_sample_constrained_sizes
+    ws = _workspace(query, dev, B, S, max_length, vocab)
     ids, logprobs, lengths = _sample_outputs(B, S, max_length, dev)
     rec = _step_record(record, noise is not None, B, S, max_length, dev)
     head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, S, int(id_start), int(id_end), max_length, temperature, int(top_k),
             top_p, ptr(u))
     tail = (ptr(ids), ptr(logprobs), ptr(lengths), ptr(rec), ptr(ws), ws.numel(), stream_ptr())
-    rc = (lib.dic_decoder_sample(*head, *tail) if noise is None else
-          lib.dic_decoder_sample_hard(*head, ptr(gu), int(bool(noise[1])), *tail))
+    if constraints is not None:
+        sup, con = _constraint_args(what, *constraints, dev)
+        alphas, cells = (None, rec) if noise else (rec, None)
+        rc = lib.dic_decoder_sample_constrained(*head, *con, 2 if noise else 0, ptr(gu), int(bool(noise[1])) if noise else 1,
+                                                *tail[:3], ptr(alphas), ptr(cells), *tail[4:])
+    else:
+        rc = (lib.dic_decoder_sample(*head, *tail) if noise is None else
+              lib.dic_decoder_sample_hard(*head, ptr(gu), int(bool(noise[1])), *tail))
     check(rc, "dic_" + what)
     return (ids, logprobs, lengths, rec) if record else (ids, logprobs, lengths)
 
@@ -173,6 +231,37 @@ def decoder_sample_hard(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor
     Returns (ids int64 [B,S,max_length], logprobs float32 [B,S,max_length], lengths int32 [B,S][, cells int32 [B,S,max_length]])."""
     return _decoder_sample("decoder_sample_hard", weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u, max_length,
                            temperature, top_k, top_p, return_cells, (gumbel_u, noise_shared))
+
+
+def decoder_beam_constrained(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
+                             id_start: int, id_end: int, beam_size: int, max_length: int = 30, length_penalty: float = 0.0,
+                             suppress: Union[Sequence[int], torch.Tensor, None] = None, min_length: int = 0,
+                             no_repeat_ngram: int = 0, gumbel_u: Optional[torch.Tensor] = None, noise_shared: bool = True,
+                             return_record: bool = False):
+    """dic_decoder_beam_constrained: the beam search of decoder_beam (gumbel_u None) or decoder_beam_hard (gumbel_u given) in which a
+    live beam never offers a banned token - `suppress` (token ids, an int sequence or integer tensor), '<end>' before step
+    `min_length`, and any token that would repeat an n-gram of `no_repeat_ngram` tokens (semantics: include/dic.h).  The scores stay
+    sums of the model's log-probabilities.  Returns (ids int64 [B,K,max_length], scores float32 [B,K], lengths int32 [B,K][,
+    alphas [B,K,max_length,196] (soft) or cells int32 [B,K,max_length] (hard) with return_record]), best first."""
+    return _decoder_beam("decoder_beam_constrained", weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length,
+                         length_penalty, return_record, None if gumbel_u is None else (gumbel_u, noise_shared),
+                         (suppress, min_length, no_repeat_ngram))
+
+
+def decoder_sample_constrained(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
+                               id_start: int, id_end: int, n_samples: int, uniform_u: torch.Tensor, max_length: int = 30,
+                               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                               suppress: Union[Sequence[int], torch.Tensor, None] = None, min_length: int = 0,
+                               no_repeat_ngram: int = 0, gumbel_u: Optional[torch.Tensor] = None, noise_shared: bool = False,
+                               return_record: bool = False):
+    """dic_decoder_sample_constrained: the draws of decoder_sample (gumbel_u None) or decoder_sample_hard (gumbel_u given) from a
+    vocabulary without the row's banned tokens (as decoder_beam_constrained's; semantics: include/dic.h): they are outside the
+    maximum, the top-k count, the nucleus and the normaliser, and are never returned.  Returns (ids int64 [B,S,max_length], logprobs
+    float32 [B,S,max_length] under the filtered, banned-free distribution, lengths int32 [B,S][, alphas or cells with
+    return_record])."""
+    return _decoder_sample("decoder_sample_constrained", weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u,
+                           max_length, temperature, top_k, top_p, return_record,
+                           None if gumbel_u is None else (gumbel_u, noise_shared), (suppress, min_length, no_repeat_ngram))
 
 
 def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,

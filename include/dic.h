@@ -325,6 +325,70 @@ int dic_decoder_score_hard(const dic_decoder_weights* w, int V, const float* fea
                            int noise_shared, float* out_logprobs, float* out_scores, int* out_lengths, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* Constrained decoding: banned tokens, a minimum length and no-repeat n-gram blocking for the beam search and the sampler of both
+ *   attention decoders, entirely on the device.  There is no reference implementation; these comments are the specification.
+ *   All three constraints are pure MASKS: the banned set of a row at a step is a function of the row's own token history, the step
+ *   and the parameters.  Logits are never rescaled (no repetition penalty).
+ *   Parameters: suppress_ids int64 [n_suppress] on the device (nullable when n_suppress = 0), min_length >= 0,
+ *     no_repeat_ngram >= 0 (0: off).
+ *   Banned set of a live row at step t with history y_0..y_{t-1} (the row's tokens so far, without <start>): the union of
+ *     - every suppress_ids[i] inside 0..V-1 (ids outside that range are ignored - the host cannot read them, so they are not
+ *       validated; duplicates are allowed);
+ *     - id_end, if t < min_length (a hypothesis that ends therefore has length >= min_length + 1: length counts <end>);
+ *     - for n = no_repeat_ngram >= 1 and t >= n-1: every y_{i+n-1} with 0 <= i <= t-n and y_i..y_{i+n-2} == y_{t-n+1}..y_{t-1}
+ *       (n = 1 bans every token already in the history).  History tokens outside 0..V-1 (possible only in dic_token_ban_mask,
+ *       whose caller supplies them) match like any value but are never banned themselves.
+ *
+ * dic_token_ban_mask ("dic_token_ban_mask:"): the banned sets as bit masks, model-agnostic.  hist int64 [R,T] on the device,
+ *   positions 0..t-1 of each row are read (nullable when t = 0), 0 <= t <= T.  out_mask uint32 [R][ceil(V/32)]: bit v & 31 of word
+ *   v >> 5 is set when v is banned for the row; bits at or beyond V are 0.  One workgroup per row; every mask word has one owner
+ *   thread that ORs the bans into it: no atomics of any kind, the words are a pure function of the inputs.  R, V > 0, T >= 0,
+ *   0 <= id_end < V, the parameter ranges above, no null pointer other than suppress_ids at n_suppress = 0 and hist at t = 0: a
+ *   violation returns a negative code with a dic_last_error() text before anything is launched.
+ *
+ * dic_decoder_beam_constrained ("decoder_beam_constrained:"): dic_decoder_beam (mode 0: gumbel_u, noise_shared and out_cells are
+ *   ignored) or dic_decoder_beam_hard (mode 2: alphas_out is ignored), word for word - start state, lsm = the log-softmax of the
+ *   UNMASKED logits, tie order, finished hypotheses, lengths, ranking, alphas_out / out_cells - with one change to the candidate
+ *   rule: a live beam offers score + lsm[v] only for v outside its banned set.  A finished beam still offers its single
+ *   (score, id_end) candidate, whatever the bans say.  out_scores therefore stay sums of the model's log-probabilities:
+ *   dic_decoder_score (dic_decoder_score_hard with the same shared noise) of the returned ids reproduces them.  The history of
+ *   slot k of an image at step t is the hypothesis that the selection of step t-1 put there (its parent's history along the
+ *   back-pointers, then its token).
+ *
+ * dic_decoder_sample_constrained ("decoder_sample_constrained:"): dic_decoder_sample (mode 0) or dic_decoder_sample_hard (mode 2),
+ *   word for word, over a vocabulary without the row's banned tokens: they are excluded from the maximum, from the top-k count
+ *   (top_k larger than the number of unbanned tokens keeps them all), from the nucleus mass, from Z and from "the last kept token".
+ *   out_logprobs is the log-probability under the filtered, banned-free distribution.  A banned token is never returned, for any
+ *   u, u >= 1 included.  A row's history is what it has drawn.
+ *
+ *   Refusals of the two calls, all before anything is launched, with a dic_last_error() text of the prefix above: mode outside
+ *   {0, 2}; everything the unconstrained call of the mode refuses, in its order; behind its scalar checks min_length < 0,
+ *   no_repeat_ngram < 0, n_suppress < 0, n_suppress > 0 with a null list, and
+ *       V - n_suppress - 1 - (no_repeat_ngram ? max_length : 0) < K        (1 in place of K for sampling):
+ *   a conservative bound that the host can check and that guarantees every live row K unbanned tokens at every step.
+ *   Workspace: more than the unconstrained calls need (mask words [B*K][ceil(V/32)], the suppress list as words, the slot
+ *   histories of the beam search); dic_decoder_*_constrained_sizes hand the size back through *workspace_bytes and return a
+ *   negative code (size 0) for sizes the calls refuse.
+ *   Properties: with n_suppress = 0, min_length = 0, no_repeat_ngram = 0 nothing of the mask machinery is launched and the results
+ *   are byte for byte those of the unconstrained entry point; row (b,s) depends only on image b, its own draws / noise and the
+ *   parameters; two calls return identical bytes; no float atomics (no atomics at all).  The suppress list is turned into mask
+ *   words once per call; a step without a per-row ban (no n-grams, t >= min_length) reads those words for every row. */
+int dic_token_ban_mask(const int64_t* hist, int R, int T, int t, int V, const int64_t* suppress_ids, int n_suppress,
+                       long long id_end, int min_length, int no_repeat_ngram, uint32_t* out_mask, void* stream);
+int dic_decoder_beam_constrained_sizes(int B, int K, int max_length, int V, size_t* workspace_bytes);
+int dic_decoder_beam_constrained(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                                 long long id_start, long long id_end, int max_length, float length_penalty,
+                                 const int64_t* suppress_ids, int n_suppress, int min_length, int no_repeat_ngram, int mode,
+                                 const float* gumbel_u, int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths,
+                                 float* alphas_out, int* out_cells, void* workspace, size_t workspace_bytes, void* stream);
+int dic_decoder_sample_constrained_sizes(int B, int S, int max_length, int V, size_t* workspace_bytes);
+int dic_decoder_sample_constrained(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int S,
+                                   long long id_start, long long id_end, int max_length, float temperature, int top_k, float top_p,
+                                   const float* uniform_u, const int64_t* suppress_ids, int n_suppress, int min_length,
+                                   int no_repeat_ngram, int mode, const float* gumbel_u, int noise_shared, int64_t* out_ids,
+                                   float* out_logprobs, int* out_lengths, float* alphas_out, int* out_cells, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* hidden states of GIVEN captions with a tape, and the backward through time: the differentiable form of dic_decoder_score's
  *   recurrence (soft attention, 196 cells), S captions per image that SHARE the image's F, P = W_z F + b_z and mean.  Composed with
  *   dic_token_logprobs / dic_token_logprobs_bwd it makes the log-probabilities of dic_decoder_score trainable (self-critical
