@@ -2,11 +2,13 @@
 // scoring of given captions (dic_decoder_score), and the hard-attention counterparts of the last three (dic_decoder_*_hard: the
 // same route bodies with the attention noise as an argument and hard_row_attn_kernel, decoder_hard.hip, as the attention step),
 // and the constrained forms of beam search and sampling (dic_decoder_*_constrained: the same two bodies with a constraints record;
-// the banned-token masks are constrain.hip's, the masked selection kernels beam.hip's and sample.hip's).
+// the banned-token masks are constrain.hip's, the masked selection kernels beam.hip's and sample.hip's), and the beam search of an
+// ensemble of soft-attention decoders (dic_decoder_beam_ensemble: M row workspaces, one beam; selection in beam_ensemble.hip).
 // The three routes keep S rows per image that share the image's F, P and mean:
 // their workspaces begin with one RowWs (row_carve), their start kernels call broadcast_state (and parse_caption) of decoder.h,
 // and every step begins with launch_row_step; what follows the LSTM cell - vocabulary GEMM, selection, hand-over - is the route's.
 #include "beam.h"
+#include "beam_ensemble.h"
 #include "sample.h"
 #include "score.h"
 #include "constrain.h"
@@ -663,6 +665,136 @@ int dic_decoder_beam_constrained(const dic_decoder_weights* w, int V, const floa
   return beam_route(route, w, V, feat_rgb, feat_depth, B, K, id_start, id_end, max_length, length_penalty, hard,
                     hard ? gumbel_u : nullptr, hard ? noise_shared : 1, out_ids, out_scores, out_lengths, hard ? nullptr : alphas_out,
                     hard ? out_cells : nullptr, workspace, workspace_bytes, (hipStream_t)stream, &con);
+}
+
+// ---- ensemble beam search (dic_decoder_beam_ensemble; semantics in include/dic.h, layout in DESIGN.md 5.28) ---------------------
+// M decoders, one beam: every member keeps its own RowWs, Hdrop and logits (equal blocks, member m at m * stride), the candidates,
+// scores, histories and the ban words exist once.  Per step: M x (launch_row_step -> vocabulary GEMM) -> ban kernel when the step
+// has row words -> beam_topk_ensemble_kernel -> beam_select_ensemble_kernel (beam_ensemble.hip), all on the one stream.
+namespace {
+struct EnsembleMemberWs : RowWs {
+  float *Hdrop, *logits;
+};
+
+struct EnsembleWs {
+  EnsembleMemberWs mem[kEnsembleMax];
+  size_t stride_floats;       // from a member's block to the next one's: the same carve, so the same distance for every array
+  float *cand_val, *score;
+  int *cand_tok, *fin, *length, *tok_hist, *bp_hist, *path;
+  long long* prev;
+  BanWs ban;
+  size_t bytes;
+};
+
+EnsembleWs ensemble_carve(void* p, size_t bytes, int M, int B, int K, int T, int V, bool* overflow) {
+  Carver c(p, bytes);
+  EnsembleWs w{};
+  const size_t BK = (size_t)B * K;
+  for (int m = 0; m < M; ++m) {
+    const size_t begin = c.off;
+    row_carve(c, w.mem[m], B, BK);
+    w.mem[m].Hdrop = c.take<float>(BK * kH);
+    w.mem[m].logits = c.take<float>(BK * V);
+    w.stride_floats = (c.off - begin) / sizeof(float);      // (every slice is a multiple of 256 bytes)
+  }
+  w.cand_val = c.take<float>(BK * K);
+  w.cand_tok = c.take<int>(BK * K);
+  w.score = c.take<float>(BK);
+  w.fin = c.take<int>(BK);
+  w.length = c.take<int>(BK);
+  w.prev = c.take<long long>(BK);
+  w.tok_hist = c.take<int>(BK * T);
+  w.bp_hist = c.take<int>(BK * T);
+  w.path = c.take<int>(BK * T);
+  ban_carve(c, w.ban, BK, T, V, true);
+  w.bytes = c.off;
+  if (overflow) *overflow = c.overflow;
+  return w;
+}
+}  // namespace
+
+int dic_decoder_beam_ensemble_sizes(int M, int B, int K, int max_length, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "dic_decoder_beam_ensemble_sizes: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_REQUIRE(M >= 1 && M <= kEnsembleMax && beam_sizes_ok(B, K, max_length, V), "dic_decoder_beam_ensemble_sizes: sizes M=%d B=%d "
+              "K=%d max_length=%d V=%d are ones the call refuses", M, B, K, max_length, V);
+  bool ov;
+  *workspace_bytes = ensemble_carve(nullptr, 0, M, B, K, max_length, V, &ov).bytes;
+  return DIC_OK;
+}
+
+int dic_decoder_beam_ensemble(const dic_decoder_weights* const w[], int M, int V, const float* const feat_rgb[],
+                              const float* const feat_depth[], int B, int K, long long id_start, long long id_end, int max_length,
+                              float length_penalty, const float* member_weights, int combine, const int64_t* suppress_ids,
+                              int n_suppress, int min_length, int no_repeat_ngram, int64_t* out_ids, float* out_scores,
+                              int* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* route = "decoder_beam_ensemble";
+  hipStream_t st = (hipStream_t)stream;
+  // every argument check comes before the first HIP call
+  DIC_REQUIRE(M >= 1 && M <= kEnsembleMax, "%s: member count M=%d is outside 1..%d", route, M, kEnsembleMax);
+  DIC_REQUIRE(K >= 1 && K <= kBeamMax, "%s: beam width K=%d is outside 1..%d", route, K, kBeamMax);
+  DIC_TRY(check_row_sizes(route, B, V, max_length));
+  DIC_REQUIRE(V >= K, "%s: vocabulary V=%d is smaller than the beam width K=%d", route, V, K);
+  DIC_TRY(check_token_ids(route, V, id_start, id_end));
+  DIC_REQUIRE(length_penalty >= 0.f, "%s: length_penalty=%g must be >= 0 (NaN is refused too)", route, (double)length_penalty);
+  DIC_REQUIRE(combine == 0 || combine == 1, "%s: combine=%d must be 0 (probabilities) or 1 (log-probabilities)", route, combine);
+  EnsembleMix mix{};
+  mix.M = M;
+  mix.combine = combine;
+  double total = 0.0;
+  for (int m = 0; m < M && member_weights; ++m) {
+    DIC_REQUIRE(std::isfinite(member_weights[m]) && member_weights[m] > 0.f, "%s: member_weights[%d]=%g must be finite and > 0", route,
+                m, (double)member_weights[m]);
+    total += (double)member_weights[m];
+  }
+  for (int m = 0; m < M; ++m) {
+    mix.w[m] = member_weights ? (float)((double)member_weights[m] / total) : 1.0f / (float)M;
+    mix.lw[m] = logf(mix.w[m]);
+  }
+  const DecodeConstraints con{(const long long*)suppress_ids, n_suppress, min_length, no_repeat_ngram};
+  DIC_TRY(check_constraints(route, con, V, max_length, K));
+  bool members = w != nullptr && feat_rgb != nullptr;
+  for (int m = 0; m < M && members; ++m) members = w[m] != nullptr && feat_rgb[m] != nullptr;
+  DIC_REQUIRE(members && out_ids && out_scores && out_lengths && workspace, "%s: null pointer", route);
+  const int T = max_length, BK = B * K;
+  bool ov = false;
+  EnsembleWs ws = ensemble_carve(workspace, workspace_bytes, M, B, K, T, V, &ov);
+  if (ov) return workspace_too_small(route, workspace_bytes, ws.bytes);
+  const bool banned = con.active();      // every constraint off: nothing of it is launched, the mask is null
+  if (banned && con.n_suppress > 0) DIC_TRY(build_static_words(con, V, id_end, ws.ban.static_words, st));
+  for (int m = 0; m < M; ++m) {          // per image and member.  [h0 | c0] -> slot 1 of beam 0; beam_init_kernel copies it to the KB beams
+    const EnsembleMemberWs& mw = ws.mem[m];
+    DIC_TRY(decoder_setup(w[m], feat_rgb[m], feat_depth ? feat_depth[m] : nullptr, B, kL, mw,
+                          InitState{mw.Hst + kH, mw.Cst + kH, (long long)K * 2 * kH, false}, st));
+    hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, mw.Hst, mw.Cst);
+    DIC_LAUNCH_CHECK();
+  }
+  for (int t = 0; t < T; ++t) {
+    for (int m = 0; m < M; ++m) {
+      const EnsembleMemberWs& mw = ws.mem[m];
+      DIC_TRY(launch_row_step(mw, w[m], V, B, K, ws.prev, nullptr, mw.Hdrop, 0, st));
+      DIC_TRY(gemm(BK, V, kH, op_rowk(mw.Hdrop, kH), op_rowk(w[m]->out_w, kH), ep_store(mw.logits, V, w[m]->out_b), st, 1, nullptr, 64));
+    }
+    const unsigned* ban = nullptr;
+    int ban_stride = 0;
+    if (banned) {
+      const BanRule rule{con.n_suppress > 0 ? ws.ban.static_words : nullptr, nullptr, 0, V, id_end, con.min_length, con.ngram};
+      if (step_has_row_words(con, t)) {
+        DIC_TRY(launch_beam_ban(rule, K, BK, T, t, ws.fin, ws.tok_hist, ws.bp_hist, ws.ban.hist[(t + 1) & 1], ws.ban.hist[t & 1],
+                                ws.ban.row_words, st));
+        ban = ws.ban.row_words;
+        ban_stride = ban_words(V);
+      } else {
+        ban = rule.static_words;
+      }
+    }
+    DIC_TRY(launch_beam_topk_ensemble(K, BK, ws.mem[0].logits, (long long)ws.stride_floats, mix, V, ws.score, ws.fin, id_end,
+                                      ws.cand_val, ws.cand_tok, st, ban, ban_stride));
+    DIC_TRY(launch_beam_select_ensemble(K, B, M, ws.cand_val, ws.cand_tok, V, id_end, t, ws.score, ws.fin, ws.length, ws.prev,
+                                        ws.tok_hist, ws.bp_hist, ws.mem[0].Hst, ws.mem[0].Cst, (long long)ws.stride_floats, st));
+  }
+  return launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, nullptr, ws.path,
+                               (long long*)out_ids, out_scores, out_lengths, nullptr, st);
 }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@ from . import synthetic as syn
 from ._lib import DicError
 from .cider import CiderD
 from .Captioning_models import constrained, util
+from .Captioning_models import ensemble as ensemble_mod
 from .Captioning_models.Base_caption_model.base_caption_models import CNNEncoder_Atten
 from .Captioning_models.config import ConfigTrain
 from .Captioning_models.Depth_caption_model.depth_models import (CD_RNNDecoderWithHardAttention,
@@ -52,12 +53,46 @@ def ids_to_captions(hypos_id: np.ndarray, id_to_word: Dict[int, str]) -> List[st
     return out
 
 
+def _ensemble_entry(config, save_directory, param_files, dpt, n_batches, word_to_id, id_to_word, beam_size, length_penalty,
+                    combine, limits, want_references, scores):
+    """The "ensemble" entry of Cdepth_evaluation: every triple of param_files loaded into modules of its own, each batch decoded
+    once by one beam over all of them (the batches, their seeds and references are the per-run loop's)."""
+    dev = config.device
+    members = []
+    for f_enc, f_dec, f_denc in param_files.values():
+        encoder = CNNEncoder_Atten(config.enc_img_size)
+        decoder = CD_RNNDecoderWithSoftAttention(config.dim_attention, config.dim_embedding, config.dim_encoder, config.dim_hidden,
+                                                 config.vocab_size)
+        depth_encoder = Depth_CNN_endoder(config.enc_img_size)
+        for m, f in ((encoder, f_enc), (decoder, f_dec), (depth_encoder, f_denc)):
+            m.load_state_dict(torch.load(f"{save_directory}/{f}", weights_only=True))
+            m.to(dev)
+            m.eval()
+        members.append((encoder, decoder, depth_encoder))
+    hypos_id, references = [], []
+    for b in range(n_batches):
+        raw = syn.raw_images(config.batch_size, seed=5000 + b).to(dev)
+        imgs, imgs_for_dep = util.device_transforms(raw)
+        depth_maps = dpt.depth_maps_for_training(imgs_for_dep)
+        if want_references:
+            references += syn.reference_captions(config.batch_size, config.vocab_size, seed=5000 + b)
+        hypos_id.append(ensemble_mod.ensemble_beam_sample([d for _, d, _ in members], [e(imgs) for e, _, _ in members],
+                                                          [de(depth_maps) for _, _, de in members], word_to_id,
+                                                          beam_size=beam_size, length_penalty=length_penalty, combine=combine,
+                                                          **limits))
+    hypos_id = np.concatenate(hypos_id)
+    entry = {"hypotheses": ids_to_captions(hypos_id, id_to_word), "ids": hypos_id}
+    entry.update(scores(hypos_id, references))
+    return entry
+
+
 @torch.no_grad()
 def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Optional[Dict[str, List[str]]] = None,
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
                       length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False, suppress=None,
-                      min_length: int = 0, no_repeat_ngram: int = 0, attention_seed: Optional[int] = None):
+                      min_length: int = 0, no_repeat_ngram: int = 0, ensemble: bool = False, ensemble_combine: str = "prob",
+                      attention_seed: Optional[int] = None):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
@@ -80,7 +115,13 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     written file are what they were without these keywords.  With any of them set the hypotheses come from the constrained beam
     search - no suppressed token, no '<end>' before `min_length` words, no n-gram of `no_repeat_ngram` tokens twice; beam_size=1 is
     then constrained greedy decoding - and, when n_samples > 0, the samples from the constrained sampler.  A hard model needs
-    attention_seed for either."""
+    attention_seed for either.
+    ensemble=True (atten="soft" only) ADDS the key "ensemble" to the result and to the written file: all triples of `param_files`
+    are loaded side by side and every batch is decoded ONCE by ensemble.ensemble_beam_sample over all of them - one beam over the
+    members' combined word distribution (ensemble_combine "prob": averaged probabilities, "logprob": averaged log-probabilities;
+    uniform weights) - with the loop's beam_size (1: ensemble greedy), length_penalty and constraints.  Its entry
+    holds "hypotheses", "ids" and the metrics / CIDEr figures when requested.  The per-run entries do not depend on it; a run key
+    named "ensemble" is refused."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
@@ -102,6 +143,12 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     if constrain and atten == "hard" and attention_seed is None:
         raise DicError("suppress / min_length / no_repeat_ngram need attention_seed with atten='hard': the constrained routes of a "
                        "hard model decode conditional on its attention noise")
+    if ensemble and atten != "soft":
+        raise DicError("ensemble=True needs atten='soft': the ensemble beam search is built for the soft-attention decoders only")
+    if ensemble and ensemble_combine not in ("prob", "logprob"):
+        raise DicError(f"ensemble_combine must be 'prob' or 'logprob', got {ensemble_combine!r}")
+    if ensemble and param_files is not None and "ensemble" in param_files:
+        raise DicError("param_files has a run named 'ensemble': with ensemble=True that key holds the ensemble's result")
     config = config or ConfigTrain()
     dev = config.device
     tag = f"depth_{atten}"
@@ -125,6 +172,16 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     for m in (encoder, decoder, depth_encoder, dpt):
         m.to(dev)
         m.eval()                                                                            # :131-134
+
+    def _scores(ids, refs):
+        if metrics:
+            return metrics_mod.evaluation_scores(torch.from_numpy(ids), refs, config.vocab_size, word_to_id["<end>"], dev)
+        if cider:
+            scorer = CiderD.from_references(refs, config.vocab_size, word_to_id["<end>"], count_end=False, device=dev)
+            ref_ids, ref_counts = scorer.pack_references(refs)
+            return {"CIDEr": float(scorer.corpus_score(torch.from_numpy(ids).long().to(dev), ref_ids, ref_counts))}
+        return {}
+
     results = {}
     for key, (f_enc, f_dec, f_denc) in param_files.items():
         encoder.load_state_dict(torch.load(f"{save_directory}/{f_enc}", weights_only=True))       # :139-144
@@ -176,13 +233,11 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             results[key]["sample_ids"] = sample_ids
         # depth_evaluation.py:178-184 scores the hypotheses with pycocoevalcap: BLEU, ROUGE-L and CIDEr are computed here on request,
         # over token ids on the device; METEOR (a Java jar and WordNet) is out of scope.
-        if metrics:
-            results[key].update(metrics_mod.evaluation_scores(torch.from_numpy(hypos_id), references, config.vocab_size,
-                                                              word_to_id["<end>"], dev))
-        elif cider:
-            scorer = CiderD.from_references(references, config.vocab_size, word_to_id["<end>"], count_end=False, device=dev)
-            ref_ids, ref_counts = scorer.pack_references(references)
-            results[key]["CIDEr"] = float(scorer.corpus_score(torch.from_numpy(hypos_id).long().to(dev), ref_ids, ref_counts))
+        results[key].update(_scores(hypos_id, references))
+    if ensemble:
+        results["ensemble"] = _ensemble_entry(config, save_directory, param_files, dpt, n_batches, word_to_id, id_to_word,
+                                              int(beam_size), length_penalty, ensemble_combine, limits if constrain else {},
+                                              cider or metrics, _scores)
     with open(os.path.join(save_directory, f"{useData}_hypotheses.json"), "w") as f:
         json.dump({k: v["hypotheses"] for k, v in results.items()}, f)
     return results

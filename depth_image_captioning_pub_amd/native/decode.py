@@ -12,7 +12,7 @@ import torch
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
 from ._core import L_CELLS, _dev, _load, _workspace
-from .decoder import _decoder_prologue
+from .decoder import _decoder_prologue, decoder_ptrs
 from .nic import _nic_prologue
 
 
@@ -262,6 +262,68 @@ def decoder_sample_constrained(weights: Dict[str, torch.Tensor], feat_rgb: torch
     return _decoder_sample("decoder_sample_constrained", weights, feat_rgb, feat_depth, id_start, id_end, n_samples, uniform_u,
                            max_length, temperature, top_k, top_p, return_record,
                            None if gumbel_u is None else (gumbel_u, noise_shared), (suppress, min_length, no_repeat_ngram))
+
+
+COMBINE_MODES = {"prob": 0, "logprob": 1}      # the `combine` argument of dic_decoder_beam_ensemble
+
+
+def _per_member(what: str, name: str, value, M: int) -> list:
+    """A feature argument of an ensemble call as a list of M entries: one tensor (or None) shared by all members, or a sequence of M."""
+    if value is None or isinstance(value, torch.Tensor):
+        return [value] * M
+    values = list(value)
+    if len(values) != M:
+        raise _lib.DicError(f"{what}: {name} must be one tensor or a sequence of {M} (one per member), got {len(values)}")
+    return values
+
+
+def decoder_beam_ensemble(weights_list: Sequence[Dict[str, torch.Tensor]], feat_rgb, feat_depth, id_start: int, id_end: int,
+                          beam_size: int, max_length: int = 30, length_penalty: float = 0.0,
+                          member_weights: Optional[Sequence[float]] = None, combine: str = "prob",
+                          suppress: Union[Sequence[int], torch.Tensor, None] = None, min_length: int = 0, no_repeat_ngram: int = 0):
+    """dic_decoder_beam_ensemble: ONE beam search over the combined word distribution of M soft-attention decoders, on the device
+    (semantics: include/dic.h).  weights_list: M state_dicts; feat_rgb / feat_depth: each a tensor shared by all members or a
+    sequence of M (feat_depth None, or an entry None: a base-soft member); member_weights: M positive floats (None: uniform),
+    normalised by the library; combine: "prob" averages the members' probabilities, "logprob" their log-probabilities; suppress /
+    min_length / no_repeat_ngram: the constraints of decoder_beam_constrained.
+    Returns (ids int64 [B,K,max_length], scores float32 [B,K] - sums of the combined log-probabilities -, lengths int32 [B,K]),
+    best first."""
+    what = "decoder_beam_ensemble"
+    lib = _load()
+    weights_list = list(weights_list)
+    M = len(weights_list)
+    if combine not in COMBINE_MODES:
+        raise _lib.DicError(f"{what}: combine must be one of {sorted(COMBINE_MODES)}, got {combine!r}")
+    if M < 1:
+        raise _lib.DicError(f"{what}: weights_list is empty")
+    rgb = [_dev(f, "features") for f in _per_member(what, "feat_rgb", feat_rgb, M)]
+    dep = [_dev(f, "depth_features") if f is not None else None for f in _per_member(what, "feat_depth", feat_depth, M)]
+    B, dev = int(rgb[0].shape[0]), rgb[0].device
+    vocab = int(weights_list[0]["linear.weight"].shape[0])
+    for m, (wd, fr, fd) in enumerate(zip(weights_list, rgb, dep)):
+        if int(wd["linear.weight"].shape[0]) != vocab:
+            raise _lib.DicError(f"{what}: member {m} has a vocabulary of {int(wd['linear.weight'].shape[0])}, member 0 one of {vocab}")
+        if tuple(fr.shape) != tuple(rgb[0].shape) or (fd is not None and tuple(fd.shape) != tuple(fr.shape)):
+            raise _lib.DicError(f"{what}: the features of member {m} must have the shape of member 0's, {tuple(rgb[0].shape)}")
+    packed = [decoder_ptrs(wd) for wd in weights_list]          # (struct, the tensors it points to): alive until the call returns
+    w_arr = (C.c_void_p * M)(*[C.addressof(p) for p, _ in packed])
+    rgb_arr = (C.c_void_p * M)(*[f.data_ptr() for f in rgb])
+    dep_arr = (C.c_void_p * M)(*[f.data_ptr() if f is not None else None for f in dep])
+    mw = None
+    if member_weights is not None:
+        given = [float(v) for v in member_weights]
+        if len(given) != M:
+            raise _lib.DicError(f"{what}: member_weights must hold {M} values (one per member), got {len(given)}")
+        mw = (C.c_float * M)(*given)
+    K, T = int(beam_size), int(max_length)
+    sup, con = _constraint_args(what, suppress, min_length, no_repeat_ngram, dev)
+    ws = _workspace(lib.dic_decoder_beam_ensemble_sizes, dev, M, B, K, T, vocab)
+    ids, scores, lengths = _beam_outputs(B, K, T, dev)
+    rc = lib.dic_decoder_beam_ensemble(w_arr, M, vocab, rgb_arr, dep_arr, B, K, int(id_start), int(id_end), T, float(length_penalty),
+                                       mw, COMBINE_MODES[combine], *con, ptr(ids), ptr(scores), ptr(lengths), ptr(ws), ws.numel(),
+                                       stream_ptr())
+    check(rc, "dic_" + what)
+    return ids, scores, lengths
 
 
 def decoder_score(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,

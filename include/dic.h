@@ -389,6 +389,40 @@ int dic_decoder_sample_constrained(const dic_decoder_weights* w, int V, const fl
                                    float* out_logprobs, int* out_lengths, float* alphas_out, int* out_cells, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ensemble beam search: M soft-attention decoders (depth-soft or base-soft, mixed freely) extend ONE set of beams, entirely on the
+ *   device: every launch is enqueued on `stream`, nothing is copied to the host, nothing synchronises.  There is no reference
+ *   implementation (the reference evaluates each run alone); this comment is the specification.
+ *   dic_decoder_beam_ensemble ("decoder_beam_ensemble:"): dic_decoder_beam, word for word - start state, finished beams, lengths,
+ *   tie order, ranking, layout of out_ids / out_scores / out_lengths - and, with a constraint set, dic_decoder_beam_constrained's
+ *   candidate rule (suppress_ids int64 [n_suppress] on the device, min_length, no_repeat_ngram; all off: nothing of it is
+ *   launched), with one change:
+ *   What a beam carries: one (h, c) per member.  Every member m runs the step body on the beam's previous token with its own
+ *     weights w[m] and features feat_rgb[m] (+ feat_depth[m]; feat_depth NULL, or an entry NULL: a base-soft member) and yields
+ *     lsm_m = logits_m - max - log sum exp(logits_m - max) in fp32, as specified for dic_decoder_beam.  w, feat_rgb, feat_depth
+ *     are HOST arrays of M pointers (to a host struct, to device features); entries may repeat.
+ *   Weights: member_weights (HOST, M floats, nullable).  Null: w_m = 1/M.  Otherwise w_m = (float)(given_m / sum given), the sum
+ *     and the quotient in double on the host.  lw_m = logf(w_m), on the host.
+ *   Combination, per token v:
+ *     combine 0 (probabilities are averaged):      c[v] = a + logf(sum_m expf((lsm_m[v] + lw_m) - a)),  a = max_m (lsm_m[v] + lw_m),
+ *                                                  the sum in ascending m (a = -inf: c[v] = -inf);
+ *     combine 1 (log-probabilities are averaged):  c[v] = sum_m w_m * lsm_m[v] in ascending m.  It is not renormalised.
+ *   A live beam offers score + c[v] for every v (with constraints on: every unbanned v); out_scores are sums of c.
+ *   Limits: 1 <= M <= 8; soft attention only; no alphas_out.
+ *   Property: at M = 1, either combine, the three outputs are byte for byte those of dic_decoder_beam, or of
+ *     dic_decoder_beam_constrained (mode 0) when a constraint is set.  Two calls return identical bytes; no atomics.
+ *   Refusals, all before anything is launched, in this order: M outside 1..8; the scalar checks of dic_decoder_beam in its order
+ *     (K, sizes, V >= K, id_start / id_end, length_penalty); combine outside {0, 1}; a member weight that is not finite and > 0; the
+ *     constraint checks of dic_decoder_beam_constrained; a null pointer - w, feat_rgb, any w[m] or feat_rgb[m], an output, the
+ *     workspace; a workspace smaller than dic_decoder_beam_ensemble_sizes hands back through *workspace_bytes (negative code and
+ *     size 0 for sizes the call refuses).  The workspace holds M times the per-decoder part of the beam search's (set-up buffers,
+ *     state, logits [B*K][V]) and one set of candidates, scores, histories and ban words. */
+int dic_decoder_beam_ensemble_sizes(int M, int B, int K, int max_length, int V, size_t* workspace_bytes);
+int dic_decoder_beam_ensemble(const dic_decoder_weights* const w[], int M, int V, const float* const feat_rgb[],
+                              const float* const feat_depth[], int B, int K, long long id_start, long long id_end, int max_length,
+                              float length_penalty, const float* member_weights, int combine, const int64_t* suppress_ids,
+                              int n_suppress, int min_length, int no_repeat_ngram, int64_t* out_ids, float* out_scores,
+                              int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+
 /* hidden states of GIVEN captions with a tape, and the backward through time: the differentiable form of dic_decoder_score's
  *   recurrence (soft attention, 196 cells), S captions per image that SHARE the image's F, P = W_z F + b_z and mean.  Composed with
  *   dic_token_logprobs / dic_token_logprobs_bwd it makes the log-probabilities of dic_decoder_score trainable (self-critical
