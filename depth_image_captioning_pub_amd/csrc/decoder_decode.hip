@@ -3,11 +3,13 @@
 // same route bodies with the attention noise as an argument and hard_row_attn_kernel, decoder_hard.hip, as the attention step),
 // and the constrained forms of beam search and sampling (dic_decoder_*_constrained: the same two bodies with a constraints record;
 // the banned-token masks are constrain.hip's, the masked selection kernels beam.hip's and sample.hip's), and the beam search of an
-// ensemble of soft-attention decoders (dic_decoder_beam_ensemble: M row workspaces, one beam; selection in beam_ensemble.hip).
+// ensemble of soft-attention decoders (dic_decoder_beam_ensemble: M row workspaces, one beam; selection in beam_ensemble.hip), and
+// the diverse beam search (dic_decoder_beam_diverse: the beam body with the start, selection and ranking of beam_diverse.hip).
 // The three routes keep S rows per image that share the image's F, P and mean:
 // their workspaces begin with one RowWs (row_carve), their start kernels call broadcast_state (and parse_caption) of decoder.h,
 // and every step begins with launch_row_step; what follows the LSTM cell - vocabulary GEMM, selection, hand-over - is the route's.
 #include "beam.h"
+#include "beam_diverse.h"
 #include "beam_ensemble.h"
 #include "sample.h"
 #include "score.h"
@@ -564,21 +566,29 @@ size_t dic_decoder_beam_workspace_bytes(int B, int K, int max_length, int V) {
 }
 
 // dic_decoder_beam (noise null) and dic_decoder_beam_hard: one body.  `route` is the prefix of the refusals.
+// div (nullable): the diverse beam search.  With more than one group the start, the selection and the final ranking are
+// beam_diverse.hip's; everything else - and with one group everything - is launched as for the plain search.
 namespace {
 int beam_route(const char* route, const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
                long long id_start, long long id_end, int max_length, float length_penalty, bool hard, const float* gumbel_u,
                int noise_shared, int64_t* out_ids, float* out_scores, int* out_lengths, float* alphas_out, int* out_cells,
-               void* workspace, size_t workspace_bytes, hipStream_t st, const DecodeConstraints* con = nullptr) {
+               void* workspace, size_t workspace_bytes, hipStream_t st, const DecodeConstraints* con = nullptr,
+               const DiverseBeam* div = nullptr) {
   // every argument check comes before the first HIP call
   DIC_REQUIRE(K >= 1 && K <= kBeamMax, "%s: beam width K=%d is outside 1..%d", route, K, kBeamMax);
+  if (div) DIC_REQUIRE(div->groups >= 1 && div->groups <= K && K % div->groups == 0, "%s: groups=%d must be in 1..K and divide the "
+                       "beam width K=%d", route, div->groups, K);
   DIC_TRY(check_row_sizes(route, B, V, max_length));
   DIC_REQUIRE(V >= K, "%s: vocabulary V=%d is smaller than the beam width K=%d", route, V, K);
   DIC_TRY(check_token_ids(route, V, id_start, id_end));
   DIC_REQUIRE(length_penalty >= 0.f, "%s: length_penalty=%g must be >= 0 (NaN is refused too)", route, (double)length_penalty);
-  if (con) DIC_TRY(check_constraints(route, *con, V, max_length, K));
+  if (div) DIC_REQUIRE(std::isfinite(div->diversity) && div->diversity >= 0.f, "%s: diversity=%g must be finite and >= 0", route,
+                       (double)div->diversity);
+  if (con) DIC_TRY(check_constraints(route, *con, V, max_length, K));      // (K, not K / groups: every live row offers K candidates)
   DIC_TRY(check_hard_noise(route, hard, noise_shared, gumbel_u));
   DIC_REQUIRE(w && feat_rgb && out_ids && out_scores && out_lengths && workspace, "%s: null pointer", route);
   const int T = max_length, BK = B * K;
+  const int Kp = div ? K / div->groups : K;      // group width; Kp == K: the plain search, launched as ever
   bool ov = false;
   BanWs bws{};
   BeamWs ws = beam_carve(workspace, workspace_bytes, B, K, T, V, &ov, con ? &bws : nullptr);
@@ -587,9 +597,13 @@ int beam_route(const char* route, const dic_decoder_weights* w, int V, const flo
   if (banned && con->n_suppress > 0) DIC_TRY(build_static_words(*con, V, id_end, bws.static_words, st));
   // per image, never per beam.  [h0 | c0] -> slot 1 of beam 0, then copied to the KB beams
   DIC_TRY(decoder_setup(w, feat_rgb, feat_depth, B, kL, ws, InitState{ws.Hst + kH, ws.Cst + kH, (long long)K * 2 * kH, false}, st));
-  hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
-                     ws.Cst);
-  DIC_LAUNCH_CHECK();
+  if (Kp < K) {
+    DIC_TRY(launch_beam_diverse_init(B, K, Kp, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst, ws.Cst, st));
+  } else {
+    hipLaunchKernelGGL(beam_init_kernel, dim3(B), dim3(kH), 0, st, K, id_start, ws.score, ws.fin, ws.length, ws.prev, ws.Hst,
+                       ws.Cst);
+    DIC_LAUNCH_CHECK();
+  }
   for (int t = 0; t < T; ++t) {
     if (hard) {     // slot k of image b consumes u[t, b*K + k] (or u[t, b]) whichever hypothesis the selection of step t-1 put there
       const HardStep hs = hard_step(gumbel_u, t, noise_shared, B, BK, out_cells ? ws.cell_hist + (size_t)t * BK : nullptr);
@@ -613,12 +627,23 @@ int beam_route(const char* route, const dic_decoder_weights* w, int V, const flo
       }
     }
     DIC_TRY(launch_beam_topk(K, BK, ws.logits, V, ws.score, ws.fin, id_end, ws.cand_val, ws.cand_tok, st, ban, ban_stride));
-    DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
-                                          BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
-    DIC_LAUNCH_CHECK();
+    if (Kp < K) {
+      DIC_TRY(launch_beam_diverse_select(K, Kp, B, div->diversity, ws.cand_val, ws.cand_tok, V, id_end, t, ws.score, ws.fin, ws.length,
+                                         ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst, st));
+    } else {
+      DIC_BEAM_SWITCH(K, hipLaunchKernelGGL(beam_select_kernel<KB_>, dim3(B), dim3(kH), 0, st, ws.cand_val, ws.cand_tok, V, id_end, t,
+                                            BK, ws.score, ws.fin, ws.length, ws.prev, ws.tok_hist, ws.bp_hist, ws.Hst, ws.Cst);)
+      DIC_LAUNCH_CHECK();
+    }
   }
-  DIC_TRY(launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, hard ? nullptr : ws.alpha_hist, ws.path,
-                                (long long*)out_ids, out_scores, out_lengths, alphas_out, st));
+  if (Kp < K) {
+    DIC_TRY(launch_beam_diverse_backtrack(B, K, Kp, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist,
+                                          hard ? nullptr : ws.alpha_hist, ws.path, (long long*)out_ids, out_scores, out_lengths,
+                                          alphas_out, st));
+  } else {
+    DIC_TRY(launch_beam_backtrack(B, K, T, length_penalty, ws.score, ws.length, ws.tok_hist, ws.bp_hist, hard ? nullptr : ws.alpha_hist,
+                                  ws.path, (long long*)out_ids, out_scores, out_lengths, alphas_out, st));
+  }
   // the cell of step t along returned hypothesis r: that of the slot the back-pointer path passes at step t
   if (hard && out_cells) DIC_TRY(launch_hard_cells(ws.cell_hist, ws.path, out_lengths, K, BK, T, out_cells, st));
   return DIC_OK;
@@ -665,6 +690,35 @@ int dic_decoder_beam_constrained(const dic_decoder_weights* w, int V, const floa
   return beam_route(route, w, V, feat_rgb, feat_depth, B, K, id_start, id_end, max_length, length_penalty, hard,
                     hard ? gumbel_u : nullptr, hard ? noise_shared : 1, out_ids, out_scores, out_lengths, hard ? nullptr : alphas_out,
                     hard ? out_cells : nullptr, workspace, workspace_bytes, (hipStream_t)stream, &con);
+}
+
+// ---- diverse beam search (dic_decoder_beam_diverse; semantics in include/dic.h, layout in DESIGN.md 5.29) -----------------------
+// The workspace is the constrained beam search's: the groups live in the K slots of an image and the selection works in LDS.
+int dic_decoder_beam_diverse_sizes(int B, int K, int groups, int max_length, int V, size_t* workspace_bytes) {
+  DIC_REQUIRE(workspace_bytes != nullptr, "dic_decoder_beam_diverse_sizes: null pointer (workspace_bytes)");
+  *workspace_bytes = 0;
+  DIC_REQUIRE(beam_sizes_ok(B, K, max_length, V) && groups >= 1 && groups <= K && K % groups == 0, "dic_decoder_beam_diverse_sizes: "
+              "sizes B=%d K=%d groups=%d max_length=%d V=%d are ones the call refuses", B, K, groups, max_length, V);
+  bool ov;
+  BanWs bws{};
+  *workspace_bytes = beam_carve(nullptr, 0, B, K, max_length, V, &ov, &bws).bytes;
+  return DIC_OK;
+}
+
+int dic_decoder_beam_diverse(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                             int groups, float diversity, long long id_start, long long id_end, int max_length,
+                             float length_penalty, const int64_t* suppress_ids, int n_suppress, int min_length,
+                             int no_repeat_ngram, int mode, const float* gumbel_u, int noise_shared, int64_t* out_ids,
+                             float* out_scores, int* out_lengths, float* alphas_out, int* out_cells, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  const char* route = "decoder_beam_diverse";
+  DIC_REQUIRE(mode == 0 || mode == 2, "%s: mode=%d must be 0 (soft) or 2 (hard attention)", route, mode);
+  const DecodeConstraints con{(const long long*)suppress_ids, n_suppress, min_length, no_repeat_ngram};
+  const DiverseBeam div{groups, diversity};
+  const bool hard = mode == 2;
+  return beam_route(route, w, V, feat_rgb, feat_depth, B, K, id_start, id_end, max_length, length_penalty, hard,
+                    hard ? gumbel_u : nullptr, hard ? noise_shared : 1, out_ids, out_scores, out_lengths, hard ? nullptr : alphas_out,
+                    hard ? out_cells : nullptr, workspace, workspace_bytes, (hipStream_t)stream, &con, &div);
 }
 
 // ---- ensemble beam search (dic_decoder_beam_ensemble; semantics in include/dic.h, layout in DESIGN.md 5.28) ---------------------

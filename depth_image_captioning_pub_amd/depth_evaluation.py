@@ -24,6 +24,7 @@ from . import synthetic as syn
 from ._lib import DicError
 from .cider import CiderD
 from .Captioning_models import constrained, util
+from .Captioning_models import diverse as diverse_mod
 from .Captioning_models import ensemble as ensemble_mod
 from .Captioning_models.Base_caption_model.base_caption_models import CNNEncoder_Atten
 from .Captioning_models.config import ConfigTrain
@@ -91,8 +92,8 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
                       n_batches: int = 2, dpt: Optional[DPT_Depthestimator] = None, beam_size: int = 1,
                       length_penalty: float = 0.0, n_samples: int = 0, temperature: float = 1.0, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, cider: bool = False, metrics: bool = False, suppress=None,
-                      min_length: int = 0, no_repeat_ngram: int = 0, ensemble: bool = False, ensemble_combine: str = "prob",
-                      attention_seed: Optional[int] = None):
+                      min_length: int = 0, no_repeat_ngram: int = 0, beam_groups: int = 1, diversity: float = 0.0,
+                      ensemble: bool = False, ensemble_combine: str = "prob", attention_seed: Optional[int] = None):
     """Returns {key: {"hypotheses": [...], "ids": np.int64 [N,30]}} per parameter triple.  `param_files` maps a key to
     [encoder, decoder, depth-encoder] checkpoint file names inside the run's save directory (config.depth_*_parameter_files
     in the reference, config.py:131-136); default = the best-validation files train_Cdepth_* wrote for run 0.
@@ -121,7 +122,13 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     members' combined word distribution (ensemble_combine "prob": averaged probabilities, "logprob": averaged log-probabilities;
     uniform weights) - with the loop's beam_size (1: ensemble greedy), length_penalty and constraints.  Its entry
     holds "hypotheses", "ids" and the metrics / CIDEr figures when requested.  The per-run entries do not depend on it; a run key
-    named "ensemble" is refused."""
+    named "ensemble" is refused.
+    beam_groups > 1: diverse beam search (Captioning_models/diverse.py) - the beam_size beams are beam_groups groups
+    (beam_groups must divide beam_size) that pay `diversity` for repeating an earlier group's token of the step.  The run's
+    hypothesis is the group winner with the highest ranking value score / length^length_penalty, ties to the lower group; the entry
+    gains "group_hypotheses", the beam_groups winners of every image in group order, and "group_ids" np.int64 [N,beam_groups,30],
+    and the group winners are also written to `<useData>_group_hypotheses.json`.  The constraints apply as above.  Refused with
+    beam_size == 1, with n_samples > 0 and with ensemble=True.  With the defaults (1, 0.0) nothing changes."""
     if useData != "synthetic":
         raise DicError(f"useData={useData!r}: MSCOCO and the original dataset are not available offline; use 'synthetic'")
     if atten not in ("soft", "hard"):
@@ -138,6 +145,16 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
     if int(n_samples) > 0 and atten != "soft" and attention_seed is None:
         raise DicError("n_samples > 0 needs atten='soft': sampling is built for the soft-attention decoder only (a hard model "
                        "samples conditional on its attention noise when attention_seed is given)")
+    if int(beam_groups) < 1:
+        raise DicError(f"beam_groups={beam_groups!r} must be at least 1")
+    if int(beam_groups) > 1:
+        if int(beam_size) == 1:
+            raise DicError("beam_groups > 1 needs beam_size > 1: the groups divide the beams of a beam search")
+        if int(n_samples) > 0:
+            raise DicError("beam_groups > 1 cannot be combined with n_samples > 0: take the variety from one of the two")
+        if ensemble:
+            raise DicError("beam_groups > 1 cannot be combined with ensemble=True: the ensemble route has no diverse form")
+        diverse_mod.check_groups("Cdepth_evaluation", beam_size, beam_groups, diversity)
     constrained.check_constraints("Cdepth_evaluation", min_length, no_repeat_ngram)
     constrain = bool(suppress is not None and len(suppress) > 0) or int(min_length) > 0 or int(no_repeat_ngram) > 0
     if constrain and atten == "hard" and attention_seed is None:
@@ -187,7 +204,7 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
         encoder.load_state_dict(torch.load(f"{save_directory}/{f_enc}", weights_only=True))       # :139-144
         decoder.load_state_dict(torch.load(f"{save_directory}/{f_dec}", weights_only=True))
         depth_encoder.load_state_dict(torch.load(f"{save_directory}/{f_denc}", weights_only=True))
-        hypos_id, sample_ids = [], []
+        hypos_id, sample_ids, group_ids = [], [], []
         references = []
         for b in range(n_batches):
             raw = syn.raw_images(config.batch_size, seed=5000 + b).to(dev)
@@ -197,7 +214,19 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             feature = encoder(imgs)                                                         # :164
             if cider or metrics:
                 references += syn.reference_captions(config.batch_size, config.vocab_size, seed=5000 + b)
-            if constrain:
+            if int(beam_groups) > 1:
+                seeds = dict(attention_seed=int(attention_seed) + b) if atten == "hard" else {}
+                kp = int(beam_size) // int(beam_groups)
+                ids, scores, lengths = diverse_mod.diverse_beam_sample(
+                    decoder, feature, depth_features, word_to_id, beam_size=int(beam_size), groups=int(beam_groups),
+                    diversity=float(diversity), length_penalty=length_penalty, return_all=True,
+                    **(limits if constrain else {}), **seeds)
+                ids, scores, lengths = ids[:, ::kp], scores[:, ::kp].astype(np.float64), lengths[:, ::kp].astype(np.float64)
+                value = scores / lengths ** float(length_penalty) if length_penalty else scores
+                best = value.argmax(axis=1)                      # (the first maximum: ties go to the lower group)
+                group_ids.append(ids)
+                hypos_id.append(ids[np.arange(ids.shape[0]), best])
+            elif constrain:
                 seeds = dict(attention_seed=int(attention_seed) + b) if atten == "hard" else {}
                 hypos_id.append(constrained.constrained_beam_sample(decoder, feature, depth_features, word_to_id,
                                                                     beam_size=int(beam_size), length_penalty=length_penalty,
@@ -231,6 +260,10 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
             sample_ids = np.concatenate(sample_ids)
             results[key]["samples"] = [ids_to_captions(rows, id_to_word) for rows in sample_ids]
             results[key]["sample_ids"] = sample_ids
+        if int(beam_groups) > 1:
+            group_ids = np.concatenate(group_ids)
+            results[key]["group_hypotheses"] = [ids_to_captions(rows, id_to_word) for rows in group_ids]
+            results[key]["group_ids"] = group_ids
         # depth_evaluation.py:178-184 scores the hypotheses with pycocoevalcap: BLEU, ROUGE-L and CIDEr are computed here on request,
         # over token ids on the device; METEOR (a Java jar and WordNet) is out of scope.
         results[key].update(_scores(hypos_id, references))
@@ -240,4 +273,7 @@ def Cdepth_evaluation(atten: str, useData: str, config=None, param_files: Option
                                               cider or metrics, _scores)
     with open(os.path.join(save_directory, f"{useData}_hypotheses.json"), "w") as f:
         json.dump({k: v["hypotheses"] for k, v in results.items()}, f)
+    if int(beam_groups) > 1:
+        with open(os.path.join(save_directory, f"{useData}_group_hypotheses.json"), "w") as f:
+            json.dump({k: v["group_hypotheses"] for k, v in results.items()}, f)
     return results

@@ -7,7 +7,7 @@ import ctypes as C          # (native.C: tests set restypes through it)
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
 from ._core import D_ATT, D_EMB, D_ENC, D_HID, DEFAULT_CONV_MODE, L_CELLS, L_COMPACT, batch_sizes_of
-from .decode import (COMBINE_MODES, decoder_beam, decoder_beam_constrained, decoder_beam_ensemble, decoder_beam_hard, decoder_greedy,
+from .decode import (COMBINE_MODES, decoder_beam, decoder_beam_constrained, decoder_beam_diverse, decoder_beam_ensemble, decoder_beam_hard, decoder_greedy,
                      decoder_sample,
                      decoder_sample_constrained, decoder_sample_hard, decoder_score, decoder_score_hard, nic_beam, nic_greedy,
                      nic_sample, nic_score, token_ban_mask)

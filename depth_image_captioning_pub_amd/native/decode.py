@@ -127,14 +127,18 @@ def decoder_greedy(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fea
 
 # ---- attention decoder: beam / sample / score.  noise: None (soft) or (gumbel_u, noise_shared) (hard, conditional on that noise) -------
 def _decoder_beam(what, weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length, length_penalty, record, noise,
-                  constraints=None):
+                  constraints=None, diverse=None):
     """constraints: None, or (suppress, min_length, no_repeat_ngram) - then the call is dic_decoder_beam_constrained, whose mode
-    argument says what `noise` says here."""
+    argument says what `noise` says here.  diverse: None, or (groups, diversity) - then, with constraints given, the call is
+    dic_decoder_beam_diverse, the constrained call with those two arguments behind the beam width."""
     lib, f_rgb, f_dep, B, vocab, wp, keep = _decoder_prologue(weights, feat_rgb, feat_depth)
     K, dev = int(beam_size), f_rgb.device
     u = _hard_noise(what, noise[0], max_length, B, max(K, 1), noise[1]) if noise else None
-    query = lib.dic_decoder_beam_workspace_bytes if constraints is None else lib.dic_decoder_beam_constrained_sizes
-    ws = _workspace(query, dev, B, K, max_length, vocab)
+    if diverse is not None:
+        ws = _workspace(lib.dic_decoder_beam_diverse_sizes, dev, B, K, int(diverse[0]), max_length, vocab)
+    else:
+        query = lib.dic_decoder_beam_workspace_bytes if constraints is None else lib.dic_decoder_beam_constrained_sizes
+        ws = _workspace(query, dev, B, K, max_length, vocab)
     ids, scores, lengths = _beam_outputs(B, K, max_length, dev)
     rec = _step_record(record, noise is not None, B, K, max_length, dev)
     head = (C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), B, K, int(id_start), int(id_end), max_length, length_penalty)
@@ -142,8 +146,11 @@ def _decoder_beam(what, weights, feat_rgb, feat_depth, id_start, id_end, beam_si
     if constraints is not None:
         sup, con = _constraint_args(what, *constraints, dev)
         alphas, cells = (None, rec) if noise else (rec, None)
-        rc = lib.dic_decoder_beam_constrained(*head, *con, 2 if noise else 0, ptr(u), int(bool(noise[1])) if noise else 1, *tail[:3],
-                                              ptr(alphas), ptr(cells), *tail[4:])
+        rest = (*con, 2 if noise else 0, ptr(u), int(bool(noise[1])) if noise else 1, *tail[:3], ptr(alphas), ptr(cells), *tail[4:])
+        if diverse is not None:
+            rc = lib.dic_decoder_beam_diverse(*head[:6], int(diverse[0]), float(diverse[1]), *head[6:], *rest)
+        else:
+            rc = lib.dic_decoder_beam_constrained(*head, *rest)
     else:
         rc = (lib.dic_decoder_beam(*head, *tail) if noise is None else
               lib.dic_decoder_beam_hard(*head, ptr(u), int(bool(noise[1])), *tail))
@@ -246,6 +253,22 @@ def decoder_beam_constrained(weights: Dict[str, torch.Tensor], feat_rgb: torch.T
     return _decoder_beam("decoder_beam_constrained", weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length,
                          length_penalty, return_record, None if gumbel_u is None else (gumbel_u, noise_shared),
                          (suppress, min_length, no_repeat_ngram))
+
+
+def decoder_beam_diverse(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor], id_start: int,
+                         id_end: int, beam_size: int, groups: int, diversity: float = 0.5, max_length: int = 30,
+                         length_penalty: float = 0.0, suppress: Union[Sequence[int], torch.Tensor, None] = None, min_length: int = 0,
+                         no_repeat_ngram: int = 0, gumbel_u: Optional[torch.Tensor] = None, noise_shared: bool = True,
+                         return_record: bool = False):
+    """dic_decoder_beam_diverse: diverse beam search (semantics: include/dic.h) - the `beam_size` beams of an image are `groups`
+    groups of beam_size / groups, each a beam search of its own whose selection at a step charges `diversity` for every earlier
+    group's survivor of that step with the same token.  Everything else is decoder_beam_constrained's (gumbel_u None: soft, given:
+    hard; the constraints; the scores stay sums of the model's log-probabilities).  Returns (ids int64 [B,K,max_length], scores
+    float32 [B,K], lengths int32 [B,K][, alphas [B,K,max_length,196] (soft) or cells int32 [B,K,max_length] (hard) with
+    return_record]), group-major: slots g*K/groups .. hold group g's hypotheses, best first inside the group."""
+    return _decoder_beam("decoder_beam_diverse", weights, feat_rgb, feat_depth, id_start, id_end, beam_size, max_length,
+                         length_penalty, return_record, None if gumbel_u is None else (gumbel_u, noise_shared),
+                         (suppress, min_length, no_repeat_ngram), (groups, diversity))
 
 
 def decoder_sample_constrained(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],

@@ -423,6 +423,51 @@ int dic_decoder_beam_ensemble(const dic_decoder_weights* const w[], int M, int V
                               int n_suppress, int min_length, int no_repeat_ngram, int64_t* out_ids, float* out_scores,
                               int* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* diverse beam search (Vijayakumar et al. 2016, Hamming diversity): the K beams of an image are G groups of K' = K / G, each a beam
+ *   search of its own that is charged for choosing, at a step, a token an earlier group has just chosen.  Entirely on the device:
+ *   every launch is enqueued on `stream`, nothing is copied to the host, nothing synchronises.  There is no reference
+ *   implementation; this comment is the specification.
+ *   dic_decoder_beam_diverse ("decoder_beam_diverse:"): dic_decoder_beam_constrained, word for word - mode 0 soft and mode 2 hard,
+ *   the attention noise, the constraint rule, lsm = the log-softmax of the UNMASKED logits, finished beams, lengths, alphas_out /
+ *   out_cells, "all constraints off launches nothing of the mask machinery" - with these changes:
+ *   Groups: G = groups, 1 <= G <= K, K % G == 0.  Slot k of an image belongs to group g = k / K'.  Hard noise is consumed by slot,
+ *     as in dic_decoder_beam_hard: u[t, b*K + k] or u[t, b].
+ *   Start: the first slot of every group starts at score 0, the other slots of the group at -inf.
+ *   Step t: the step body and the per-row candidate lists are the beam search's - a live row offers its K best unbanned
+ *     score + lsm[v] (ties: lower v), a finished row (score, id_end) only.  The groups are then decided in ascending g.
+ *     Count: n_g(v) = the number of survivors chosen at this step by groups g' < g whose parent was live and whose token is v.  A
+ *       finished hypothesis that is carried does not count: it emitted nothing at this step.
+ *     Selection value of a candidate (value c, token v) of a live row of group g: c if n_g(v) == 0, else
+ *       c - diversity * (float)n_g(v), in fp32 with the product rounded, then the difference rounded (no fused multiply-add).  A
+ *       finished row's single candidate is never penalised.
+ *     Selection: of the candidates of the group's own K' rows the K' best survive, ordered by (selection value descending, flat
+ *       index k*V + v ascending), k the slot index inside the image.
+ *     Scores: a survivor carries the UNPENALISED c; the penalty steers one selection and is then forgotten.  out_scores therefore
+ *       stay sums of the model's log-probabilities: dic_decoder_score (dic_decoder_score_hard with the same shared noise) of the
+ *       returned ids reproduces them.
+ *   Result: [B,K,...] group-major: slots g*K' .. g*K'+K'-1 hold group g's hypotheses, ranked inside the group by
+ *     score / length^length_penalty, descending, stable in the slot index.  Groups are never merged or de-duplicated: two groups may
+ *     return the same caption when diversity is small.
+ *   Why no extra pass over the logits: at most K - K' distinct tokens carry a penalty at a step and a penalty only lowers values,
+ *     so the K' best penalised candidates of a row lie among its K best unpenalised ones.
+ *   Properties: G = 1 with any diversity gives byte for byte the outputs of dic_decoder_beam_constrained (with the constraints off:
+ *     of dic_decoder_beam / dic_decoder_beam_hard) - the same kernels are launched; group 0 is never penalised; two calls return
+ *     identical bytes; no atomics; image b depends only on image b.
+ *   Refusals, all before anything is launched, in this order: mode outside {0, 2}; K outside 1..8; groups outside 1..K or not
+ *     dividing K; the remaining scalar checks of dic_decoder_beam in its order (sizes, V >= K, id_start / id_end, length_penalty);
+ *     diversity not finite or < 0; the constraint checks of dic_decoder_beam_constrained - their bound keeps K, not K', which
+ *     guarantees every live row the K unbanned candidates the argument above needs -; noise_shared outside {0, 1} and a null
+ *     gumbel_u (mode 2); a null pointer; a workspace smaller than dic_decoder_beam_diverse_sizes hands back through *workspace_bytes
+ *     (negative code and size 0 for sizes the call refuses).  The workspace is dic_decoder_beam_constrained's: the groups live in
+ *     the K slots of an image. */
+int dic_decoder_beam_diverse_sizes(int B, int K, int groups, int max_length, int V, size_t* workspace_bytes);
+int dic_decoder_beam_diverse(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int B, int K,
+                             int groups, float diversity, long long id_start, long long id_end, int max_length,
+                             float length_penalty, const int64_t* suppress_ids, int n_suppress, int min_length,
+                             int no_repeat_ngram, int mode, const float* gumbel_u, int noise_shared, int64_t* out_ids,
+                             float* out_scores, int* out_lengths, float* alphas_out, int* out_cells, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* hidden states of GIVEN captions with a tape, and the backward through time: the differentiable form of dic_decoder_score's
  *   recurrence (soft attention, 196 cells), S captions per image that SHARE the image's F, P = W_z F + b_z and mean.  Composed with
  *   dic_token_logprobs / dic_token_logprobs_bwd it makes the log-probabilities of dic_decoder_score trainable (self-critical
