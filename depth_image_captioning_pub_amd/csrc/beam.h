@@ -1,4 +1,4 @@
-// Token selection shared by the decode routes of both decoders (decoder_decode.hip, nic_decode.hip): the greedy arg-max, and the
+// Token selection shared by the decode routes of both decoders (decoder_decode.hip and decoder_beam.hip, nic_decode.hip): the greedy arg-max, and the
 // beam search of the routes that keep K hypotheses per image.  One candidate rule (include/dic.h), one copy of each piece:
 //   launch_argmax          argmax_kernel: the first maximum of a row of logits, the greedy token     (beam.hip)
 //   launch_beam_topk       beam_topk_kernel<K>: log-softmax of a row + its K best candidates          (beam.hip)

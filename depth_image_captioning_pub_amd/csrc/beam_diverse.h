@@ -1,4 +1,4 @@
-// Selection of the diverse beam search (dic_decoder_beam_diverse, decoder_decode.hip; the rule: include/dic.h): the K
+// Selection of the diverse beam search (dic_decoder_beam_diverse, decoder_beam.hip; the rule: include/dic.h): the K
 // beams of an image are G groups of K' = K / G, each a beam search of its own that pays `diversity` for every earlier group's survivor
 // of this step that emitted the same token.  The step body and the per-row candidates are the beam search's (beam.h): a penalty only
 // lowers values and at most K - K' tokens carry one, so the K' best penalised candidates of a row lie among the K best unpenalised
@@ -13,7 +13,7 @@
 
 namespace dic {
 
-// what a caller asked for; beam_route takes a nullable pointer to one (null: the plain entry points)
+// what a caller asked for; a BeamCall (decoder_beam.hip) holds a nullable pointer to one (null: the plain entry points)
 struct DiverseBeam {
   int groups;
   float diversity;

@@ -1,4 +1,4 @@
-// Token selection of the ensemble beam search (dic_decoder_beam_ensemble, decoder_decode.hip): M decoders extend ONE set of beams.
+// Token selection of the ensemble beam search (dic_decoder_beam_ensemble, decoder_beam.hip): M decoders extend ONE set of beams.
 // Every member writes its own [B*K][V] logits; the word distribution a beam offers is the weighted mixture of the members'
 // log-softmaxes (include/dic.h).  What follows the per-row candidates - beam_select_rank, the backtrack, the ban masks - is beam.h's
 // and constrain.h's, unchanged.

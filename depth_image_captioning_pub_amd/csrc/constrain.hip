@@ -95,6 +95,35 @@ int launch_beam_ban(const BanRule& rule, int K, int BK, int T, int t, const int*
   return DIC_OK;
 }
 
+void ban_carve(Carver& c, BanWs& w, size_t R, int T, int V, bool beam) {
+  w.static_words = c.take<unsigned>((size_t)ban_words(V));
+  w.row_words = c.take<unsigned>(R * ban_words(V));
+  w.hist[0] = w.hist[1] = nullptr;
+  if (beam) {
+    w.hist[0] = c.take<int>(R * T);
+    w.hist[1] = c.take<int>(R * T);
+  }
+}
+
+int check_constraints(const char* route, const DecodeConstraints& c, int V, int max_length, int rows) {
+  DIC_REQUIRE(c.min_length >= 0, "%s: min_length=%d must be >= 0", route, c.min_length);
+  DIC_REQUIRE(c.ngram >= 0, "%s: no_repeat_ngram=%d must be >= 0 (0: off)", route, c.ngram);
+  DIC_REQUIRE(c.n_suppress >= 0, "%s: n_suppress=%d must be >= 0", route, c.n_suppress);
+  DIC_REQUIRE(c.n_suppress == 0 || c.suppress_ids != nullptr, "%s: null pointer (suppress_ids with n_suppress=%d)", route,
+              c.n_suppress);
+  const long long left = (long long)V - c.n_suppress - 1 - (c.ngram ? max_length : 0);
+  DIC_REQUIRE(left >= rows, "%s: V - n_suppress - 1%s = %lld tokens can be guaranteed unbanned at every step, fewer than the %d a "
+              "step needs (V=%d, n_suppress=%d, no_repeat_ngram=%d, max_length=%d)", route, c.ngram ? " - max_length" : "", left,
+              rows, V, c.n_suppress, c.ngram, max_length);
+  return DIC_OK;
+}
+
+int build_static_words(const DecodeConstraints* con, int V, long long id_end, const BanWs& w, hipStream_t st) {
+  if (!con || !con->active() || con->n_suppress <= 0) return DIC_OK;
+  return launch_token_ban(BanRule{nullptr, con->suppress_ids, con->n_suppress, V, id_end, 0, 0}, nullptr, nullptr, 1, 0, 0,
+                          w.static_words, st);
+}
+
 }  // namespace dic
 
 using namespace dic;

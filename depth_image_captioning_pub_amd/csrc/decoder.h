@@ -6,10 +6,14 @@
 //                       the refusals the S-rows-per-image routes word alike
 //   decoder_fwd.hip     teacher-forced forward, stand-alone attention forward
 //   decoder_bwd.hip     BPTT backward and its tail (bias / weight gradients, dP W_z), stand-alone attention backward
-//   decoder_decode.hip  greedy decode; beam search, sampling and the scoring of given captions over one row workspace (RowWs) and
-//                       one step head (launch_row_step).  The selection kernels shared with the NIC beam search: beam.h / beam.hip;
-//                       the kernel that draws a token from a row of logits: sample.h / sample.hip; the fused projection +
-//                       log-sum-exp of the scoring route: score.h / score.hip
+//   decoder_decode.hip  greedy decode (the arg-max: beam.h / beam.hip)
+//   decoder_rows.hip    what beam search, sampling and the scoring of given captions share (decoder_rows.h): one row workspace
+//                       (RowWs), the call records and one step head (launch_row_step) with the attention step of all rows of an image
+//   decoder_beam.hip    beam search: plain, hard, constrained, diverse and ensemble entry points over one body.  The selection
+//                       kernels shared with the NIC beam search: beam.h / beam.hip; the diverse and ensemble selections:
+//                       beam_diverse.h, beam_ensemble.h; the banned-token masks and the ban step: constrain.h
+//   decoder_sample.hip  sampling; the kernel that draws a token from a row of logits: sample.h / sample.hip
+//   decoder_score.hip   scoring of given captions; the fused projection + log-sum-exp: score.h / score.hip
 //   decoder_hard.hip    the hard (Gumbel-max) attention step of those three routes' hard counterparts (hard_row_attn_kernel) and
 //                       the kernel that lays out the selected cells
 //   decoder_states.hip  hidden states of given captions with a tape and their backward through time, S captions per image that

@@ -11,7 +11,7 @@
 // HBM-bound attention/context kernels and one skinny fused LSTM GEMM run.
 //
 // This file: what every route shares - workspace carving, set-up, the attention step and LSTM cell kernels and their
-// launchers.  The routes themselves are in decoder_fwd.hip, decoder_bwd.hip and decoder_decode.hip (see decoder.h).
+// launchers.  The routes themselves are in decoder_fwd.hip, decoder_bwd.hip, decoder_decode.hip and the units behind decoder_rows.h (see decoder.h).
 #include "decoder.h"
 #include <algorithm>
 

@@ -1,5 +1,5 @@
 // Hard (Gumbel-max) attention step of the routes that keep S rows per image: dic_decoder_beam_hard, dic_decoder_sample_hard and
-// dic_decoder_score_hard (decoder_decode.hip; semantics in include/dic.h, layout and measurements in DESIGN.md 5.24).
+// dic_decoder_score_hard (decoder_beam.hip, decoder_sample.hip, decoder_score.hip; semantics in include/dic.h, layout and measurements in DESIGN.md 5.24).
 // The counterpart of beam_attn_kernel<KB> with one-hot attention weights: the context vector of a row is ONE row of the image's
 // F, so the pass over F that is the largest part of a soft step becomes a gather of 1 KB per row and chunk.
 #include "beam.h"

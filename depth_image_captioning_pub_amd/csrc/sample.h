@@ -1,5 +1,5 @@
 // Stochastic decoding: one drawn token per row of logits (temperature, top-k, nucleus), sample.hip.  Model-agnostic: rows of
-// [R][V] logits in, one token per row out; dic_decoder_sample (decoder_decode.hip) is its caller.  The rule of a step is the
+// [R][V] logits in, one token per row out; dic_decoder_sample (decoder_sample.hip) is its caller.  The rule of a step is the
 // header comment of dic_decoder_sample in include/dic.h.
 #pragma once
 #include "common.h"

@@ -1,6 +1,6 @@
 // Scoring given tokens: the vocabulary projection fused with a log-sum-exp and a target pick, score.hip.  Model-agnostic: rows of
 // [M][128] hidden states and one target per row in, one log-probability per row out; the [M][V] logits exist only as accumulator
-// tiles.  dic_token_logprobs (the C entry point, same file) and dic_decoder_score (decoder_decode.hip) are its callers.  The rule
+// tiles.  dic_token_logprobs (the C entry point, same file) and dic_decoder_score (decoder_score.hip) are its callers.  The rule
 // is the header comment of dic_token_logprobs in include/dic.h.
 #pragma once
 #include "common.h"

@@ -120,8 +120,9 @@ def test_prototype_vocabulary_is_closed(tmp_path, monkeypatch):
         _lib.load()
 
 
-# Workspace sizes are part of what a caller sees (it allocates them): pinned exactly, as commit 2ccc799 returned them, so that a
-# change to a carve - its order, a count, a new slice - shows here before it shows as a "workspace too small" elsewhere.
+# Workspace sizes are part of what a caller sees (it allocates them): pinned exactly, as commit 2ccc799 returned them (the *_sizes
+# queries: as commit f4c540a did), so that a change to a carve - its order, a count, a new slice - shows here before it shows as a
+# "workspace too small" elsewhere.
 _WORKSPACE_BYTES = [
     ("dic_decoder_beam_workspace_bytes", (1, 1, 1, 8), 7619584),                 # (B, K, max_length, V)
     ("dic_decoder_beam_workspace_bytes", (3, 3, 5, 300), 11531264),
@@ -145,12 +146,42 @@ _WORKSPACE_BYTES = [
     ("dic_decoder_workspace_bytes", (1, 1, 8, 1), 23315200),                     # (B, Tmax, V, n_packed)
     ("dic_decoder_workspace_bytes", (3, 5, 300, 12), 27843584),
     ("dic_decoder_workspace_bytes", (64, 30, 10000, 1500), 243776256),
+    ("dic_decoder_beam_constrained_sizes", (1, 1, 1, 8), 7620608),                # (B, K, max_length, V), through the out-pointer
+    ("dic_decoder_beam_constrained_sizes", (3, 3, 5, 300), 11532544),
+    ("dic_decoder_beam_constrained_sizes", (2, 8, 7, 1000), 10265600),
+    ("dic_decoder_beam_constrained_sizes", (64, 5, 30, 10000), 153750272),
+    ("dic_decoder_sample_constrained_sizes", (1, 1, 1, 8), 7618304),              # (B, S, max_length, V)
+    ("dic_decoder_sample_constrained_sizes", (3, 3, 5, 300), 11530240),
+    ("dic_decoder_sample_constrained_sizes", (2, 8, 7, 1000), 10261504),
+    ("dic_decoder_sample_constrained_sizes", (64, 5, 30, 10000), 153542912),
+    ("dic_decoder_beam_diverse_sizes", (1, 1, 1, 1, 8), 7620608),                 # (B, K, groups, max_length, V): 1 group, K's largest proper divisor
+    ("dic_decoder_beam_diverse_sizes", (3, 3, 1, 5, 300), 11532544),
+    ("dic_decoder_beam_diverse_sizes", (2, 8, 1, 7, 1000), 10265600),
+    ("dic_decoder_beam_diverse_sizes", (2, 8, 4, 7, 1000), 10265600),
+    ("dic_decoder_beam_diverse_sizes", (64, 5, 1, 30, 10000), 153750272),
+    ("dic_decoder_beam_ensemble_sizes", (1, 1, 1, 1, 8), 7619584),                # (M, B, K, max_length, V)
+    ("dic_decoder_beam_ensemble_sizes", (3, 1, 1, 1, 8), 22852096),
+    ("dic_decoder_beam_ensemble_sizes", (8, 1, 1, 1, 8), 60933376),
+    ("dic_decoder_beam_ensemble_sizes", (1, 3, 3, 5, 300), 11497216),
+    ("dic_decoder_beam_ensemble_sizes", (3, 3, 3, 5, 300), 34484480),
+    ("dic_decoder_beam_ensemble_sizes", (8, 3, 3, 5, 300), 91952640),
+    ("dic_decoder_beam_ensemble_sizes", (1, 2, 8, 7, 1000), 10177792),
+    ("dic_decoder_beam_ensemble_sizes", (3, 2, 8, 7, 1000), 30519552),
+    ("dic_decoder_beam_ensemble_sizes", (8, 2, 8, 7, 1000), 81373952),
+    ("dic_decoder_beam_ensemble_sizes", (1, 64, 5, 30, 10000), 146223872),
+    ("dic_decoder_beam_ensemble_sizes", (3, 64, 5, 30, 10000), 437445376),
+    ("dic_decoder_beam_ensemble_sizes", (8, 64, 5, 30, 10000), 1165499136),
 ]
 
 
-@pytest.mark.parametrize("query,sizes,want", _WORKSPACE_BYTES, ids=[f"{q[4:-16]}-{'x'.join(map(str, a))}" for q, a, _ in _WORKSPACE_BYTES])
+@pytest.mark.parametrize("query,sizes,want", _WORKSPACE_BYTES,
+                         ids=[f"{q[4:-16] if q.endswith('_workspace_bytes') else q[4:]}-{'x'.join(map(str, a))}" for q, a, _ in _WORKSPACE_BYTES])
 def test_decoder_workspace_sizes_are_pinned(query, sizes, want):
     fn = getattr(ctypes.CDLL(build.build()), query)
+    if query.endswith("_sizes"):       # int status, the size through the last argument
+        got = ctypes.c_size_t(0)
+        assert fn(*sizes, ctypes.byref(got)) == 0 and got.value == want
+        return
     fn.restype = ctypes.c_size_t
     assert fn(*sizes) == want
 
