@@ -10,54 +10,20 @@ two is the one orc.rows_undecidable_by_oracle uses.  At most 10 % of a case's im
 import functools
 
 import torch
-import torch.nn.functional as F
 
 from depth_image_captioning_pub_amd import synthetic as syn
-from oracle import captioning_oracle as orc
+from tests import decode_steps as ds
 from tests.helpers import GOLDEN_THREADS, torch_threads
 
-MAX_UNDECIDABLE_SHARE = 0.10
+MAX_UNDECIDABLE_SHARE = ds.MAX_UNDECIDABLE_SHARE
+_double = ds.double
 
 
 def beam_search(w, fr, fd, K, id_start, id_end, T):
-    """The step loop.  Returns the K survivors of every image in beam order, unranked: ids [B,K,T], score [B,K], length [B,K],
-    alphas [B,K,T,196] (the attention weights along each hypothesis) and the smallest step margin [B] (float64)."""
-    fused = fr + fd if fd is not None else fr
-    B, V, dt = fused.shape[0], w["linear.weight"].shape[0], fused.dtype
-    h, c = orc.init_state(w, fused)
-    h, c, ff = h.repeat_interleave(K, 0), c.repeat_interleave(K, 0), fused.repeat_interleave(K, 0)
-    score = torch.full((B, K), float("-inf"), dtype=dt)
-    score[:, 0] = 0
-    fin = torch.zeros((B, K), dtype=torch.bool)
-    length = torch.zeros((B, K), dtype=torch.int64)
-    ids = torch.zeros((B, K, T), dtype=torch.int64)
-    alphas = torch.zeros((B, K, T, fused.shape[1]), dtype=dt)
-    prev = torch.full((B * K,), id_start, dtype=torch.int64)
-    mingap = torch.full((B,), float("inf"), dtype=torch.float64)
-    for t in range(T):
-        e = F.embedding(prev, w["embed.weight"])
-        ctx, alpha = orc.soft_attention(w, ff, h)
-        gate = torch.sigmoid(F.linear(h, w["f_beta.weight"], w["f_beta.bias"]))
-        h2, c2 = orc.lstm_cell(w, torch.cat((e, gate * ctx), 1), h, c)
-        lsm = F.linear(h2, w["linear.weight"], w["linear.bias"]).log_softmax(1).view(B, K, V)
-        cand = score.unsqueeze(2) + lsm
-        only = torch.full_like(cand, float("-inf"))
-        only[:, :, id_end] = score
-        cand = torch.where(fin.unsqueeze(2).expand(B, K, V), only, cand)
-        top = cand.view(B, K * V).topk(K + 1, dim=1)          # value K+1 is only used for the margin
-        mingap = torch.minimum(mingap, (top.values[:, K - 1] - top.values[:, K]).double())
-        sel, score = top.indices[:, :K], top.values[:, :K]
-        src, tok = sel // V, sel % V
-        gi = (src + torch.arange(B).unsqueeze(1) * K).view(-1)
-        was_fin = fin.gather(1, src)
-        ids = ids.gather(1, src.unsqueeze(2).expand(B, K, T)).clone()
-        ids[:, :, t] = tok
-        alphas = alphas.gather(1, src.view(B, K, 1, 1).expand_as(alphas)).clone()
-        alphas[:, :, t] = alpha.view(B, K, -1).gather(1, src.unsqueeze(2).expand(B, K, alpha.shape[1]))
-        length = torch.where(was_fin, length.gather(1, src), torch.full_like(length, t + 1))
-        fin = was_fin | (tok == id_end)
-        h, c, prev = h2[gi], c2[gi], tok.reshape(-1)
-    return {"ids": ids, "score": score, "length": length, "alphas": alphas, "mingap": mingap}
+    """decode_steps.beam_search over the soft step.  Returns the K survivors of every image in beam order, unranked: ids [B,K,T],
+    score [B,K], length [B,K], alphas [B,K,T,196] (the attention weights along each hypothesis) and the smallest step margin [B]
+    (float64)."""
+    return ds.beam_search(ds.SoftRows(w, fr, fd, id_start), K, id_end, T)
 
 
 def rank(raw, lp=0.0):
@@ -80,18 +46,14 @@ def beam(w, fr, fd, K, id_start, id_end, T, lp=0.0):
     return rank(beam_search(w, fr, fd, K, id_start, id_end, T), lp)
 
 
-def _double(d):
-    return {k: v.double() for k, v in d.items()}
-
-
 # ---- the input sets of the GPU comparison (tests/test_beam_gpu.py); the CPU suite pins their decidable share ----------------------
-def _peaked(vocab, seed):
+def _peaked(vocab, seed, end_offset=8.0):
     """Plain synthetic weights give near-uniform word distributions in which <end> never enters a beam: sharpen the vocabulary
-    projection and favour <end>."""
+    projection and favour <end> by `end_offset`."""
     w = syn.decoder_weights(vocab, seed=seed)
     w["linear.weight"] = w["linear.weight"] * 30
     w["linear.bias"] = w["linear.bias"].clone()
-    w["linear.bias"][syn.special_token_ids(vocab)["<end>"]] += 8.0
+    w["linear.bias"][syn.special_token_ids(vocab)["<end>"]] += end_offset
     return w
 
 
@@ -121,7 +83,7 @@ def case_search(name, double):
     c = CASES[name]
     w, fr, fd, s, e = case_inputs(name)
     if double:
-        w, fr, fd = _double(w), fr.double(), (fd.double() if fd is not None else None)
+        w, fr, fd = ds.double((w, fr, fd))
     with torch.no_grad(), torch_threads(GOLDEN_THREADS):
         return beam_search(w, fr, fd, c["K"], s, e, c["T"])
 
@@ -140,7 +102,5 @@ def case_reference(name, lp=0.0):
     images are undecidable (a test error, not a skip)."""
     r32, r64 = rank(case_search(name, False), lp), rank(case_search(name, True), lp)
     ok, dist = decide(r32, r64)
-    share = 1.0 - float(ok.double().mean())
-    if share > MAX_UNDECIDABLE_SHARE:
-        raise AssertionError(f"case {name} (length_penalty {lp}): {int((~ok).sum())} of {ok.numel()} images are undecidable")
+    ds.capped(ok, f"case {name} (length_penalty {lp})")
     return r64, ok, dist

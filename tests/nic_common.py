@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from depth_image_captioning_pub_amd import synthetic as syn
+from tests.decode_steps import double          # (the fp64 cast, under the name the NIC tests use)
 from tests.helpers import GOLDEN_THREADS, torch_threads
 
 GAP_FACTOR = 16.0
@@ -88,10 +89,6 @@ def nic_greedy(w, features, max_length=30):
         logits.append(lg)
         x = F.embedding(tok, w["embed.weight"])
     return torch.stack(ids, 1), gap, torch.stack(logits, 1)
-
-
-def double(d):
-    return {k: v.double() for k, v in d.items()}
 
 
 # ---- the input sets of the GPU comparison (tests/test_nic_gpu.py); the CPU suite pins their decidable share -----------------------

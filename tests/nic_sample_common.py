@@ -22,9 +22,9 @@ torch.rand((T, B*S)) of manual_seed(useed)."""
 import functools
 
 import torch
-import torch.nn.functional as F
 
 from depth_image_captioning_pub_amd import synthetic as syn
+from tests import decode_steps as ds
 from tests import nic_beam_common as nb
 from tests import nic_common as nc
 from tests import sample_common as sc
@@ -59,39 +59,14 @@ def threshold_gap(z, top_k, top_p, with_tau):
 
 
 def sample_decode(w, features, S, id_end, T, u, temperature=1.0, top_k=0, top_p=1.0):
-    """The step loop over rows r = b*S + s with the draws u [T, B*S]; features [B,300].  Returns ids [B,S,T] (id_end behind the
-    first id_end), logprobs [B,S,T] (0 there), lengths [B,S], and per row the quantities of every step [B,S,T,4] (NaN at frozen
-    steps), the smallest margin over its live steps [B,S] and the threshold gap of every step [B,S,T] (threshold_gap; NaN at frozen
-    steps, inf where no threshold is in force)."""
-    B, dt = features.shape[0], features.dtype
-    R = B * S
-    z = features.new_zeros((R, w["lstm.weight_hh_l0"].shape[1]))
-    st, x = (z, z, z, z), features.repeat_interleave(S, 0)          # no start token: the image is the step-0 input of every row
-    V = w["linear.weight"].shape[0]
-    u = u.to(dt)
-    ids = torch.full((R, T), id_end, dtype=torch.int64)
-    logprobs = torch.zeros((R, T), dtype=dt)
-    lengths = torch.full((R,), T, dtype=torch.int64)
-    quant = torch.full((R, T, 4), float("nan"), dtype=dt)
-    margin = torch.full((R,), float("inf"), dtype=dt)
-    tgap = torch.full((R, T), float("nan"), dtype=dt)
-    fin = torch.zeros((R,), dtype=torch.bool)
-    for t in range(T):
-        h1, st = nc._step(w, x, st)
-        logits = F.linear(h1, w["linear.weight"], w["linear.bias"])
-        tok, lp, q, mg = sc.draw_step(logits, u[t], temperature, top_k, top_p)
-        live = ~fin
-        tgap[live, t] = threshold_gap(logits / temperature, top_k, top_p, q[:, 2])[live]
-        ids[live, t] = tok[live]
-        logprobs[live, t] = lp[live]
-        quant[live, t] = q[live]
-        margin = torch.where(live, torch.minimum(margin, mg), margin)
-        ended = live & (tok == id_end)
-        lengths[ended] = t + 1
-        fin = fin | ended
-        x = F.embedding(tok.clamp(0, V - 1), w["embed.weight"])     # (a frozen row runs on; nothing of it is recorded)
-    return {"ids": ids.view(B, S, T), "logprobs": logprobs.view(B, S, T), "lengths": lengths.view(B, S),
-            "quant": quant.view(B, S, T, 4), "margin": margin.view(B, S), "tgap": tgap.view(B, S, T)}
+    """decode_steps.sample_decode over the NIC step, rows r = b*S + s with the draws u [T, B*S]; features [B,300].  Returns ids
+    [B,S,T] (id_end behind the first id_end), logprobs [B,S,T] (0 there), lengths [B,S], and per row the quantities of every step
+    [B,S,T,4] (NaN at frozen steps), the smallest margin over its live steps [B,S] and the threshold gap of every step [B,S,T]
+    (threshold_gap; NaN at frozen steps, inf where no threshold is in force)."""
+    def tgap(logits, q):
+        return threshold_gap(logits / temperature, top_k, top_p, q[:, 2])
+    return ds.sample_decode(ds.NicRows(w, features), S, id_end, T, u, temperature=temperature, top_k=top_k, top_p=top_p,
+                            step_extra=("tgap", tgap))
 
 
 # ---- the input sets of the GPU comparison; the CPU suite pins their decidable share ---------------------------------------------
@@ -155,9 +130,7 @@ def case_reference(name, pi):
     """fp64 restatement, decidable mask [B,S] and the fp32-to-fp64 log-probability distance of a case (over its decidable rows);
     raises when more than 10 % of its rows are undecidable (a test error, not a skip)."""
     r64, ok = case_decision(name, pi)
-    share = 1.0 - float(ok.double().mean())
-    if share > sc.MAX_UNDECIDABLE_SHARE:
-        raise AssertionError(f"case {name} {PARAMS[pi]}: {int((~ok).sum())} of {ok.numel()} rows are undecidable")
+    ds.capped(ok, f"case {name} {PARAMS[pi]}", "rows")
     lp_dist = float((case_decode(name, pi, False)["logprobs"].double() - r64["logprobs"])[ok].abs().max())
     return r64, ok, lp_dist
 

@@ -14,9 +14,9 @@ t1 takes the distance of b5_s3_v333 - the same weights and inputs, and 15 values
 import functools
 
 import torch
-import torch.nn.functional as F
 
 from depth_image_captioning_pub_amd import synthetic as syn
+from tests import decode_steps as ds
 from tests import nic_beam_common as nb
 from tests import nic_common as nc
 from tests import score_common as sco
@@ -25,22 +25,9 @@ from tests.helpers import GOLDEN_THREADS, torch_threads
 
 def score(w, features, captions, id_end):
     """dic_nic_score as its header comment states it, in the precision of `w` / `features`.  captions int64 [B,S,T].  Returns
-    logprobs [B,S,T] (0 from the row's length on), scores [B,S] (the sum in ascending t) and lengths [B,S]."""
-    B, S, T = captions.shape
-    V, dt = w["linear.weight"].shape[0], features.dtype
-    R = B * S
-    caps = captions.reshape(R, T)
-    length = sco.lengths_of(caps, id_end)
-    tok = caps.clamp(0, V - 1)
-    z = features.new_zeros((R, w["lstm.weight_hh_l0"].shape[1]))
-    st, x = (z, z, z, z), features.repeat_interleave(S, 0)          # no start token: the image is the step-0 input of every row
-    logprobs = torch.zeros((R, T), dtype=dt)
-    for t in range(T):
-        h1, st = nc._step(w, x, st)
-        target = torch.where(t < length, tok[:, t], torch.full_like(length, -1))
-        logprobs[:, t] = sco.token_logprobs(h1, w["linear.weight"], w["linear.bias"], target)[0]
-        x = F.embedding(tok[:, t], w["embed.weight"])
-    return {"logprobs": logprobs.view(B, S, T), "scores": sco.ascending_sum(logprobs).view(B, S), "lengths": length.view(B, S)}
+    logprobs [B,S,T] (0 from the row's length on), scores [B,S] (the sum in ascending t) and lengths [B,S]: decode_steps.score
+    over the NIC step."""
+    return ds.score(ds.NicRows(w, features), captions, id_end)
 
 
 # ---- the input sets ---------------------------------------------------------------------------------------------------------------

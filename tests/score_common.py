@@ -15,8 +15,8 @@ import functools
 import torch
 import torch.nn.functional as F
 
-from oracle import captioning_oracle as orc
 from tests import beam_common as bc
+from tests import decode_steps as ds
 from tests import sample_common as sc
 from tests.helpers import GOLDEN_THREADS, torch_threads
 
@@ -49,30 +49,8 @@ def lengths_of(captions, id_end):
 
 def score_decode(w, fr, fd, id_start, id_end, captions):
     """dic_decoder_score as its header comment states it.  captions int64 [B,S,T] without <start>.  Returns logprobs [B,S,T] (0 from
-    the row's length on), scores [B,S] (the sum in ascending t) and lengths [B,S]."""
-    fused = fr + fd if fd is not None else fr
-    B, S, T = captions.shape
-    V, dt = w["linear.weight"].shape[0], fused.dtype
-    R = B * S
-    caps = captions.reshape(R, T)
-    length = lengths_of(caps, id_end)
-    tok = caps.clamp(0, V - 1)
-    h, c = orc.init_state(w, fused)
-    h, c, ff = h.repeat_interleave(S, 0), c.repeat_interleave(S, 0), fused.repeat_interleave(S, 0)
-    prev = torch.full((R,), min(max(id_start, 0), V - 1), dtype=torch.int64)
-    logprobs = torch.zeros((R, T), dtype=dt)
-    for t in range(T):
-        e = F.embedding(prev, w["embed.weight"])
-        ctx, _ = orc.soft_attention(w, ff, h)
-        gate = torch.sigmoid(F.linear(h, w["f_beta.weight"], w["f_beta.bias"]))
-        h, c = orc.lstm_cell(w, torch.cat((e, gate * ctx), 1), h, c)
-        target = torch.where(t < length, tok[:, t], torch.full_like(length, -1))
-        logprobs[:, t] = token_logprobs(h, w["linear.weight"], w["linear.bias"], target)[0]
-        prev = tok[:, t]
-    scores = torch.zeros((R,), dtype=dt)
-    for t in range(T):
-        scores = scores + logprobs[:, t]
-    return {"logprobs": logprobs.view(B, S, T), "scores": scores.view(B, S), "lengths": length.view(B, S)}
+    the row's length on), scores [B,S] (the sum in ascending t) and lengths [B,S]: decode_steps.score over the soft step."""
+    return ds.score(ds.SoftRows(w, fr, fd, id_start), captions, id_end)
 
 
 def ascending_sum(logprobs):
@@ -92,7 +70,7 @@ def case_captions(name):
 def case_score(name, double):
     w, fr, fd, s, e, _ = sc.case_inputs(name)
     if double:
-        w, fr, fd = bc._double(w), fr.double(), (fd.double() if fd is not None else None)
+        w, fr, fd = ds.double((w, fr, fd))
     with torch.no_grad(), torch_threads(GOLDEN_THREADS):
         return score_decode(w, fr, fd, s, e, case_captions(name))
 
@@ -110,7 +88,7 @@ def beam_case_score(name, double):
     w, fr, fd, s, e = bc.case_inputs(name)
     ids = bc.rank(bc.case_search(name, True))["ids"]
     if double:
-        w, fr, fd = bc._double(w), fr.double(), (fd.double() if fd is not None else None)
+        w, fr, fd = ds.double((w, fr, fd))
     with torch.no_grad(), torch_threads(GOLDEN_THREADS):
         return score_decode(w, fr, fd, s, e, ids)
 
