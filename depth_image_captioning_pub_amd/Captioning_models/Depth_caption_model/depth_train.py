@@ -21,6 +21,7 @@ from ...cider import CiderD
 from ..._lib import DicError
 from ...engine import CaptionTrainer, look_ahead
 from ..config import ConfigTrain
+from ..scheduled import scheduled_sampling_prob
 
 lam = 0.7             # depth_train.py:25
 tqdm_disable = True   # depth_train.py:24
@@ -110,13 +111,18 @@ def _scst_epochs(trainer, config, rank: int, first_epoch: int, n_epochs: int, re
 
 
 def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None, depth_branch: bool = True,
-           tag: str = None, save_directory: str = None, scst_epochs: int = None):
+           tag: str = None, save_directory: str = None, scst_epochs: int = None, scheduled_sampling: dict = None):
     """Shared loop of train_Cdepth_{soft,hard} and (depth_branch=False: no depth encoder, decoder-only optimiser, two
     checkpoints) of train_base_{soft,hard} (Base_caption_model/base_train.py:24-234, 248-460).
     scst_epochs (default: config.scst_epochs, 0): further epochs of self-critical training behind the cross-entropy epochs, soft
-    attention only; their mean reward per epoch goes to <tag>_scst_reward_<useData><ext>.csv."""
+    attention only; their mean reward per epoch goes to <tag>_scst_reward_<useData><ext>.csv.
+    scheduled_sampling (default: config.scheduled_sampling, None = off): dict(start=, increase_every=, increase_prob=, max_prob=), the keyword arguments of
+    scheduled.scheduled_sampling_prob - the cross-entropy steps of an epoch feed the decoder its own tokens with that epoch's
+    probability (CaptionTrainer.train_step sampling_prob; no counterpart in the reference).  Validation stays teacher-forced."""
     config = config or ConfigTrain()
     scst_epochs = int(getattr(config, "scst_epochs", 0) if scst_epochs is None else scst_epochs)
+    if scheduled_sampling is None:
+        scheduled_sampling = getattr(config, "scheduled_sampling", None)
     if scst_epochs < 0:
         raise DicError(f"scst_epochs={scst_epochs} must be >= 0")
     if scst_epochs > 0 and hard:
@@ -155,6 +161,9 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
     for epoch in range(config.num_epochs):
         if hard and epoch % config.temp_sch == 0:                       # depth_train.py:481-483
             temp = temp_anneal(epoch)
+        ss_prob = scheduled_sampling_prob(epoch, **scheduled_sampling) if scheduled_sampling else 0.0
+        if stats is not None and scheduled_sampling:
+            stats.setdefault("sampling_probs", []).append(ss_prob)
         window, losses = deque(), []
         # with the DPT front-end the "dataset" is the same every epoch (that is what makes the depth cache meaningful)
         def on_device():
@@ -170,7 +179,7 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
             # the T draws of one iteration come as one [T,B,196] tensor from a stream keyed by (epoch, iteration, rank)
             u = _gumbel_draws(max(lens) - 1, len(lens), epoch, it, rank, int(ext)).to(dev) if hard else None
             loss = trainer.train_step(imgs, depth, caps, lens, gumbel_u=u, temp=float(temp),
-                                      next_imgs=[f[1] for f in following])
+                                      next_imgs=[f[1] for f in following], sampling_prob=ss_prob)
             losses.append(loss)                                         # device tensors: no per-iteration host sync
             window.append(loss)
             if len(window) > config.moving_avg:

@@ -40,3 +40,6 @@ class ConfigTrain(object):
         self.scst_epochs = 0            # further epochs of CaptionTrainer.scst_step; 0 = none, nothing differs
         self.scst_samples = 5           # captions sampled per image
         self.scst_reward_weights = {"CIDEr": 1.0}       # metrics.reward_fn weights: CIDEr, Bleu_1..4, ROUGE_L
+        # scheduled sampling in the cross-entropy epochs (not in the reference): None = off, nothing differs; else
+        # dict(start=, increase_every=, increase_prob=, max_prob=), the keyword arguments of scheduled.scheduled_sampling_prob
+        self.scheduled_sampling = None

@@ -5,6 +5,8 @@
 //   decoder.hip         what the routes share: workspace carving, set-up, the attention step and LSTM cell kernels + launchers,
 //                       the refusals the S-rows-per-image routes word alike
 //   decoder_fwd.hip     teacher-forced forward, stand-alone attention forward
+//   decoder_scheduled.hip  the teacher-forced forward with scheduled sampling: per-step projection and the kernel that picks the
+//                       token a step is fed (dic_decoder_fwd_scheduled)
 //   decoder_bwd.hip     BPTT backward and its tail (bias / weight gradients, dP W_z), stand-alone attention backward
 //   decoder_decode.hip  greedy decode (the arg-max: beam.h / beam.hip)
 //   decoder_rows.hip    what beam search, sampling and the scoring of given captions share (decoder_rows.h): one row workspace
@@ -122,6 +124,9 @@ struct AttnStepArgs {
   int do_gate; FusedLstm fl; int nrows;
 };
 int launch_attn_step(const AttnStepArgs& a, int cells, hipStream_t st);
+
+// Compact layout: group softmax ac [B*T][49] -> the returned attention weights a [B*T][196], alpha_cell = beta_group / 4; n = B*T*196
+int launch_expand_alphas(const float* ac, float* a, long long n, hipStream_t st);
 
 // Hard (Gumbel-max) attention step over the S rows of each of B images (hard_row_attn_kernel<S>, decoder_hard.hip): the
 // arguments of beam_attn_kernel with the step's noise u_t ([B][196] when noise_shared, else [B*S][196]) in place of the attention

@@ -32,6 +32,12 @@ __global__ void __launch_bounds__(256) expand_alphas_kernel(const float* __restr
   a[i] = 0.25f * ac[bt * kLc + g];
 }
 
+int launch_expand_alphas(const float* ac, float* a, long long n, hipStream_t st) {
+  hipLaunchKernelGGL(expand_alphas_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ac, a, n);
+  DIC_LAUNCH_CHECK();
+  return DIC_OK;
+}
+
 // The persistent forward loop (csrc/experiments/decoder_persist.hip, switch 141) is a parked experiment: correct, but at
 // batch 64 it takes 20 us per step against 21.7 us for the two launches it replaces.  It exists only in the
 // experiments build; the product library always runs the per-step launches.
@@ -107,11 +113,8 @@ static int decoder_fwd_impl(const dic_decoder_weights* w, int V, const float* fe
     DIC_TRY(launch_lstm_fwd(LstmCell{ws.slab_g, ws.bcat, drop_mult, ws.Hall, ws.Call, ws.Gact, ws.Hdrop, kS_LSTM, pl.bs[tl], pl.off[tl]},
                             tl, T, st));
   }
-  if (cells != kL) {      // returned attention weights in the reference's 196-cell layout: alpha_cell = beta_group / 4
-    const long long n = (long long)B * T * kL;
-    hipLaunchKernelGGL(expand_alphas_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws.alpha_c, alphas_out, n);
-    DIC_LAUNCH_CHECK();
-  }
+  // returned attention weights in the reference's 196-cell layout: alpha_cell = beta_group / 4
+  if (cells != kL) DIC_TRY(launch_expand_alphas(ws.alpha_c, alphas_out, (long long)B * T * kL, st));
   // logits (time-major packed rows) = dropout(h) W_o^T + b_o    (depth_models.py:197,204)
   DIC_TRY(gemm(N, V, kH, op_rowk(ws.Hdrop, kH), op_rowk(w->out_w, kH), ep_store(logits_packed, V, w->out_b), st));
   return DIC_OK;

@@ -1,9 +1,13 @@
 """CLI with the reference's argument convention (depth_main.py:14-35):
     python -m depth_image_captioning_pub_amd.depth_main {soft,hard} cnn {coco,original,synthetic} [--scst-epochs N]
+                                                         [--ss-start N --ss-every K --ss-inc P --ss-max P]
 (the reference script itself does not run as shipped - quirk Q5 - so this keeps its intent: 3 repetitions of
 train_Cdepth_{soft,hard}(i, useData)).  `mlp` is a no-op in the reference (depth_main.py:27-28,34-35) and here.
 --scst-epochs N (not in the reference): N further epochs of self-critical training behind the cross-entropy epochs
-(CaptionTrainer.scst_step, soft attention only; default: config.scst_epochs = 0)."""
+(CaptionTrainer.scst_step, soft attention only; default: config.scst_epochs = 0).
+--ss-start N --ss-every K --ss-inc P --ss-max P (not in the reference): scheduled sampling in the cross-entropy epochs - from
+epoch N on the decoder is fed its own tokens with a probability that rises by P every K epochs up to the maximum
+(Captioning_models/scheduled.py; defaults 5, 0.05, 0.25).  The default --ss-start -1 means off."""
 from __future__ import annotations
 
 import sys
@@ -11,6 +15,7 @@ import sys
 import numpy as np
 import torch
 
+from .Captioning_models.Depth_caption_model import depth_train
 from .Captioning_models.Depth_caption_model.depth_train import train_Cdepth_hard, train_Cdepth_soft
 
 
@@ -49,12 +54,60 @@ def take_scst_epochs(args):
     return rest, n
 
 
+SS_OPTIONS = {"--ss-start": ("start", int, -1), "--ss-every": ("increase_every", int, 5), "--ss-inc": ("increase_prob", float, 0.05),
+              "--ss-max": ("max_prob", float, 0.25)}
+
+
+def take_scheduled_sampling(args):
+    """(args without the --ss-* options, the scheduled_sampling dict of the training loops or None when --ss-start is absent or
+    negative); ValueError on a bad value.  Both `--ss-start N` and `--ss-start=N` are read."""
+    rest, got, i = [], {}, 0
+    while i < len(args):
+        a = str(args[i])
+        name = a.split("=", 1)[0]
+        if name in SS_OPTIONS:
+            key, kind, _ = SS_OPTIONS[name]
+            if "=" in a:
+                value = a.split("=", 1)[1]
+            else:
+                i += 1
+                if i >= len(args):
+                    raise ValueError(f"{name} needs a value")
+                value = str(args[i])
+            try:
+                got[key] = kind(value)
+            except ValueError:
+                raise ValueError(f"{name} needs {'an integer' if kind is int else 'a number'}, got {value!r}") from None
+        else:
+            rest.append(args[i])
+        i += 1
+    ss = {key: got.get(key, default) for key, _, default in SS_OPTIONS.values()}
+    if ss["start"] < 0:
+        return rest, None
+    if ss["increase_every"] < 1:
+        raise ValueError(f"--ss-every needs a positive integer, got {ss['increase_every']!r}")
+    if not (0.0 <= ss["increase_prob"] <= 1.0 and 0.0 <= ss["max_prob"] <= 1.0):
+        raise ValueError("--ss-inc and --ss-max need probabilities in [0, 1]")
+    return rest, ss
+
+
+def scheduled_config(train_module, scheduled):
+    """The config argument of a run: None (the training loop builds its own) without a schedule, else the loop's ConfigTrain with
+    the schedule set (the training entry points keep their signatures; the schedule travels in the config, as scst_epochs can)."""
+    if scheduled is None:
+        return None
+    config = train_module.ConfigTrain()
+    config.scheduled_sampling = scheduled
+    return config
+
+
 def main(argv=None):
     torch_seed()
     exp_time = EXP_TIME
     datas = ["coco", "original", "synthetic"]
     try:
         args, scst_epochs = take_scst_epochs(list(sys.argv if argv is None else argv))
+        args, scheduled = take_scheduled_sampling(args)
     except ValueError as e:
         print(e)
         return 1
@@ -72,7 +125,7 @@ def main(argv=None):
         print("input {soft/hard} {cnn/mlp} {coco/original/synthetic}")
         return 1
     for i in range(exp_time):
-        fn(i, use_data, scst_epochs=scst_epochs)
+        fn(i, use_data, config=scheduled_config(depth_train, scheduled), scst_epochs=scst_epochs)
     return 0
 
 

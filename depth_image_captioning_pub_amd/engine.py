@@ -607,8 +607,15 @@ class CaptionTrainer(BackboneTrainer):
                    drop_mult: Optional[torch.Tensor] = None, gumbel_u: Optional[torch.Tensor] = None,
                    temp: float = 1.0, precomputed_features: Optional[torch.Tensor] = None,
                    next_imgs=None, global_tokens: Optional[int] = None,
-                   apply_update: bool = True, virtual_world: Optional[int] = None) -> torch.Tensor:
+                   apply_update: bool = True, virtual_world: Optional[int] = None, sampling_prob: float = 0.0,
+                   sampling_pick: str = "sample", sampling_temperature: float = 1.0, coin_u: Optional[torch.Tensor] = None,
+                   draw_u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One iteration of depth_train.py:168-221. Returns the loss as a 1-element device tensor (no host sync).
+        sampling_prob > 0: scheduled sampling (dic_decoder_fwd_scheduled; no counterpart in the reference) - step t >= 1 of a row is
+          fed, with that probability, a token picked from the row's own logits of step t-1 (sampling_pick "sample": drawn from
+          softmax(logits / sampling_temperature); "argmax") in place of the caption's; the loss targets stay the caption's tokens and
+          self.last["fed_ids"] holds what was fed.  coin_u / draw_u: float32 [max(lengths)-1, B] draws in [0,1); default: a device
+          generator keyed by (seed, call number, rank).  0 is the teacher-forced step, call for call.
         next_imgs: images of the following batch, or the list [batch i+1, batch i+2, ...] of the next batches in order; their
           (frozen) ResNet forwards run ahead on side streams, up to `prefetch_depth` (3) at a time.  A prefetched forward is
           matched to a later train_step by OBJECT IDENTITY of the images tensor: pass the very tensor objects announced here
@@ -627,8 +634,21 @@ class CaptionTrainer(BackboneTrainer):
         if drop_mult is None:
             drop_mult = self._draw_dropout(B, tmax)
         mode = 1 if self.hard else 0
-        logits, alphas, tape = native.decoder_forward(self.dec_w, feats, fdep, captions, lengths, drop_mult, mode=mode,
-                                                      gumbel_u=gumbel_u, temp=temp, workspace=self.dec_ws)
+        fed_ids = None
+        if not float(sampling_prob) > 0.0:
+            if float(sampling_prob) != 0.0:
+                raise DicError(f"train_step: sampling_prob={sampling_prob!r} must be in [0, 1]")
+            logits, alphas, tape = native.decoder_forward(self.dec_w, feats, fdep, captions, lengths, drop_mult, mode=mode,
+                                                          gumbel_u=gumbel_u, temp=temp, workspace=self.dec_ws)
+        else:
+            gen = None
+            if coin_u is None or (draw_u is None and sampling_pick == "sample"):
+                gen = self._step_generator(0x55A3)
+                self.sample_count += 1
+            logits, alphas, fed_ids, tape = native.decoder_forward_scheduled(
+                self.dec_w, feats, fdep, captions, lengths, float(sampling_prob), sampling_pick, float(sampling_temperature),
+                coin_u=coin_u, draw_u=draw_u, generator=gen, drop_mult=drop_mult, mode=mode, gumbel_u=gumbel_u, temp=temp,
+                workspace=self.dec_ws)
         self.dec_ws = tape.workspace
         self._mark("decoder_fwd")
         targets = native.pack_targets(captions, lengths)                                     # :210-213
@@ -642,6 +662,8 @@ class CaptionTrainer(BackboneTrainer):
         self._mark("decoder_bwd")
         self._finish_step(dtape, dfeat, apply_update)
         self.last = {"logits": logits, "alphas": alphas, "features": feats, "depth_features": fdep}
+        if fed_ids is not None:
+            self.last["fed_ids"] = fed_ids
         if self.keep_outputs:
             self.last["decoder_tape"] = tape           # parity tests: native.decoder_attention_relu_mask(tape)
         return loss

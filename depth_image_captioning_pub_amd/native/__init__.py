@@ -11,8 +11,9 @@ from .decode import (COMBINE_MODES, decoder_beam, decoder_beam_constrained, deco
                      decoder_sample,
                      decoder_sample_constrained, decoder_sample_hard, decoder_score, decoder_score_hard, nic_beam, nic_greedy,
                      nic_sample, nic_score, token_ban_mask)
-from .decoder import (DECODER_FIELDS, STATES_GRAD_KEYS, DecoderPtrs, DecoderTape, HardStatesTape, StatesTape, attention_backward,
-                      attention_forward, decoder_attention_relu_mask, decoder_backward, decoder_forward, decoder_ptrs, decoder_states_backward,
+from .decoder import (DECODER_FIELDS, SCHEDULED_PICKS, STATES_GRAD_KEYS, DecoderPtrs, DecoderTape, HardStatesTape, StatesTape, attention_backward,
+                      attention_forward, decoder_attention_relu_mask, decoder_backward, decoder_forward, decoder_forward_scheduled,
+                      decoder_ptrs, decoder_states_backward,
                       decoder_states_backward_into, decoder_states_forward, decoder_states_hard_backward,
                       decoder_states_hard_backward_into, decoder_states_hard_forward)
 from .encoders import (CONV_MODES, DEPTH_FIELDS, ConvBnLayer, DepthBnState, DepthPtrs, DepthTape, ResNetRunner, depth_encoder_backward,

@@ -120,6 +120,70 @@ def decoder_forward(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, fe
     return logits, alphas, tape
 
 
+SCHEDULED_PICKS = ("argmax", "sample")      # `pick` of dic_decoder_fwd_scheduled: 0, 1
+
+
+def decoder_forward_scheduled(weights: Dict[str, torch.Tensor], feat_rgb: torch.Tensor, feat_depth: Optional[torch.Tensor],
+                              captions: torch.Tensor, lengths: Sequence[int], sampling_prob: float, pick: str = "sample",
+                              pick_temperature: float = 1.0, coin_u: Optional[torch.Tensor] = None,
+                              draw_u: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+                              drop_mult: Optional[torch.Tensor] = None, mode: int = 0, gumbel_u: Optional[torch.Tensor] = None,
+                              temp: float = 1.0, workspace: Optional[torch.Tensor] = None):
+    """dic_decoder_fwd_scheduled: decoder_forward with scheduled sampling (the rule: include/dic.h).  Position t >= 1 of a row is
+    fed, where coin_u[t,b] < sampling_prob, the token picked from the row's own logits of step t-1 - pick "argmax": their first
+    maximum; "sample": a draw from softmax(logits / pick_temperature) with draw_u[t,b] - and the caption's token elsewhere.
+    coin_u / draw_u: float32 [Tmax,B] in [0,1) on the device; a missing one that the call needs is torch.rand of `generator`
+    (a generator of the features' device; None: the device's default one).  Returns (logits_packed [N,V], alphas [B,Tmax,196],
+    fed_ids int64 [B,Tmax], tape): the tape's captions are fed_ids, so decoder_backward(tape, ...) is the backward.  The layout is
+    selected by the feature shape, as in decoder_forward."""
+    lib = _load()
+    B = feat_rgb.shape[0]
+    cells = int(feat_rgb.shape[1])
+    if cells not in (L_CELLS, L_COMPACT) or feat_rgb.shape[2] != D_ENC:
+        raise _lib.DicError(f"features must be [B,{L_CELLS},{D_ENC}] or [B,{L_COMPACT},{D_ENC}], got {tuple(feat_rgb.shape)}")
+    if feat_depth is not None and tuple(feat_depth.shape) != tuple(feat_rgb.shape):
+        raise _lib.DicError("depth features must have the shape of the RGB features")
+    if pick not in SCHEDULED_PICKS:
+        raise _lib.DicError(f"decoder_forward_scheduled: pick must be one of {SCHEDULED_PICKS}, got {pick!r}")
+    prob = float(sampling_prob)
+    dec_len = [int(l) - 1 for l in lengths]
+    tmax = max(dec_len)
+    bsz = batch_sizes_of(dec_len)
+    n_packed = sum(bsz)
+    vocab = weights["linear.weight"].shape[0]
+    dev = feat_rgb.device
+    wp, keep = decoder_ptrs(weights)
+    f_rgb = _dev(feat_rgb, "features")
+    f_dep = _dev(feat_depth, "depth_features") if feat_depth is not None else None
+    caps = captions if captions.is_contiguous() else captions.contiguous()
+    if caps.dtype != torch.int64 or not caps.is_cuda:
+        raise _lib.DicError("captions must be an int64 GPU tensor")
+    uniforms = []
+    for name, u, needed in (("coin_u", coin_u, prob > 0.0), ("draw_u", draw_u, prob > 0.0 and pick == "sample")):
+        if u is None and needed:
+            u = torch.rand((tmax, B), generator=generator, device=dev)
+        if u is not None:
+            u = _dev(u, name)
+            if tuple(u.shape) != (tmax, B):
+                raise _lib.DicError(f"decoder_forward_scheduled: {name} must be [Tmax,B] = [{tmax},{B}], got {tuple(u.shape)}")
+        uniforms.append(u)
+    coin, draw = uniforms
+    workspace = _workspace(lib.dic_decoder_workspace_bytes, dev, B, tmax, vocab, n_packed, reuse=workspace)
+    logits = torch.empty((n_packed, vocab), dtype=torch.float32, device=dev)
+    alphas = torch.empty((B, tmax, L_CELLS), dtype=torch.float32, device=dev)
+    fed = torch.empty((B, tmax), dtype=torch.int64, device=dev)
+    dm = _dev(drop_mult, "drop_mult") if drop_mult is not None else None
+    gu = _dev(gumbel_u, "gumbel_u") if gumbel_u is not None else None
+    rc = lib.dic_decoder_fwd_scheduled(C.byref(wp), vocab, ptr(f_rgb), ptr(f_dep), cells, ptr(caps), caps.stride(0),
+                                       _i32_host(dec_len), B, ptr(dm), mode, ptr(gu), temp, prob, SCHEDULED_PICKS.index(pick),
+                                       float(pick_temperature), ptr(coin), ptr(draw), ptr(fed), ptr(logits), ptr(alphas),
+                                       ptr(workspace), workspace.numel(), stream_ptr())
+    check(rc, "dic_decoder_fwd_scheduled")
+    tape = DecoderTape(workspace, dec_len, bsz, n_packed, tmax, vocab, fed, dm, mode, float(temp), alphas,
+                       {k: t for (k, _), t in zip(DECODER_FIELDS, keep)}, cells)
+    return logits, alphas, fed, tape
+
+
 def decoder_backward(tape: DecoderTape, dlogits: torch.Tensor, dalphas: Optional[torch.Tensor],
                      grads: Optional[Dict[str, torch.Tensor]] = None, want_dfeatures: bool = True):
     """dic_decoder_bwd. Returns (grads dict keyed like state_dict, d_features [B,196,2048] or None)."""

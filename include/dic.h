@@ -119,6 +119,45 @@ int dic_decoder_bwd_cells(const dic_decoder_weights* w, int V, int cells, const 
                           const float* dalphas, const float* alphas, const dic_decoder_grads* g, float* d_features,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scheduled sampling (Bengio et al. 2015) on the teacher-forced forward: at each step the decoder is fed, with probability
+ *   sampling_prob, a token picked from its own previous-step distribution in place of the caption's.  There is no reference
+ *   implementation; this comment is the specification.
+ *   The arguments up to temp, and logits_packed, alphas, workspace (dic_decoder_workspace_bytes, unchanged), workspace_bytes mean
+ *   what they mean for dic_decoder_fwd / dic_decoder_fwd_cells.  cells is 196 or 49; 49 requires mode 0; modes 1 and 2 take the
+ *   attention step unchanged.  captions needs cap_stride >= Tmax = dec_lengths[0].
+ *   coin_u: float [Tmax,B] on the device, values in [0,1); may be NULL when sampling_prob == 0.
+ *   draw_u: float [Tmax,B] on the device, values in [0,1); may be NULL when pick == 0.
+ *   fed_ids: int64 [B,Tmax], output: the token every step was fed.
+ *   Randomness is an input, as gumbel_u (quirk Q6): the library draws nothing, the call is a pure function of its arguments.
+ *   Row b with n = dec_lengths[b] (clamp: into [0,V)):
+ *     fed[b,0] = clamp(captions[b,0]).
+ *     1 <= t < n: the position FIRES iff coin_u[t,b] < sampling_prob, compared in fp32 (0 never fires, 1 always does).
+ *       fired:  fed[b,t] = pick(x), x the row of THE RETURNED logits_packed of (b, t-1) (packed row off[t-1] + b): the pick reads
+ *               exactly the values the caller gets back;
+ *       else:   fed[b,t] = clamp(captions[b,t]).
+ *     t >= n: fed[b,t] = captions[b,t].
+ *   pick 0: the first maximum of x; a row without one (all NaN or all -inf) gives 0 (the rule of dic_decoder_greedy).
+ *   pick 1: the draw of dic_decoder_sample with top-k and top-p off and no ban: z_v = x_v / pick_temperature in fp32,
+ *     e_v = exp(z_v - max z), Z = sum e; the token is the first v, in index order, whose inclusive running sum exceeds
+ *     draw_u[t,b] * Z; if rounding leaves none (or draw_u >= 1) it is V - 1.  The association order of the sums is free.
+ *   Step t embeds fed[b,t]; everything else in the step is dic_decoder_fwd's, in particular logits = dropout(h) W_o^T + b_o.
+ *   The fed tokens are constants of the graph: dic_decoder_bwd / dic_decoder_bwd_cells called with captions = fed_ids,
+ *   cap_stride = Tmax and this call's workspace IS the backward.
+ *   Properties: row b depends only on image b, row b of captions and drop_mult, and column b of coin_u / draw_u (and of gumbel_u).
+ *   sampling_prob == 0 computes what dic_decoder_fwd[_cells] computes.  Nothing is copied to the host and nothing synchronises
+ *   (the dec_lengths upload is dic_decoder_fwd's).  At most two launches per step more than dic_decoder_fwd: the step's vocabulary
+ *   projection (in place of the one batched projection after the loop; the same work in total) and the kernel that picks the token.
+ *   Refused (negative code, dic_last_error() starts with "decoder_fwd_scheduled:"), on the host before the first HIP call:
+ *   sampling_prob outside [0,1] or NaN; pick not 0 or 1; with pick 1 a pick_temperature that is not finite and > 0; a null
+ *   fed_ids; a null coin_u with sampling_prob > 0; a null draw_u with pick 1 and sampling_prob > 0; cells 49 with mode != 0; and
+ *   what dic_decoder_fwd refuses. */
+int dic_decoder_fwd_scheduled(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth, int cells,
+                              const int64_t* captions, int cap_stride, const int* dec_lengths, int B, const float* drop_mult,
+                              int mode, const float* gumbel_u, float temp,
+                              float sampling_prob, int pick, float pick_temperature, const float* coin_u, const float* draw_u,
+                              int64_t* fed_ids, float* logits_packed, float* alphas, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* greedy decoding: batch_sample / sample (depth_models.py:216-305 soft, 698-789 hard with Gumbel-max).
  *   Starts from id_start (<start>), max_length steps, dropout off, token = argmax(linear(h)); the previous
  *   token stays on the device (the reference copies it to the host every step, :298-299).  argmax is the first maximum; a row
