@@ -322,6 +322,7 @@ class NicTrainer(BackboneTrainer):
         self.head_w, self.head_b = (self.flat.view(self.flat.data, "encoder.linear." + k) for k in ("weight", "bias"))
         self.head_gw, self.head_gb = (self.flat.view(self.flat.grad, "encoder.linear." + k) for k in ("weight", "bias"))
         self.dec_span = (0, self.flat.total)
+        self._clip_spans = [("nic", self.flat.total)]      # last_span_norms of a clipped update (max_grad_norm): the whole buffer
         self.dec_ws: Optional[torch.Tensor] = None
         self.states_ws: Optional[torch.Tensor] = None
         self.sample_count = 0          # scst steps that drew their own uniforms: part of the sampling generator's key
@@ -484,6 +485,7 @@ def train_nic(ext, useData: str = "synthetic", config=None, stats=None):
     val_loss_file = f"{save_directory}/nic_val_loss{ext}.csv"
     trainer = NicTrainer(config.vocab_size, device=config.device, seed=123 + int(ext), lr=config.lr, dropout=config.dropout,
                          resnet_layers=resnet_layers, conv_mode=getattr(config, "conv_mode", None))
+    trainer.max_grad_norm = getattr(config, "clip_grad_norm", None)      # None: unclipped updates (base_main nic --clip-grad-norm X)
     print(f"[nic] frozen ResNet-152 convolutions in {trainer.conv_mode} arithmetic (config.conv_mode)", flush=True)
     if stats is not None:
         stats.update(conv_mode=trainer.conv_mode)

@@ -145,6 +145,7 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
     trainer = CaptionTrainer(config.vocab_size, device=config.device, seed=123 + int(ext), lr=config.lr, hard=hard,
                              dropout=config.dropout, lam=lam, process_group=process_group, use_depth=depth_branch,
                              conv_mode=getattr(config, "conv_mode", None))
+    trainer.max_grad_norm = getattr(config, "clip_grad_norm", None)      # None: unclipped updates (--clip-grad-norm X of the mains)
     if rank == 0:
         print(f"[{tag}] frozen ResNet-152 convolutions in {trainer.conv_mode} arithmetic (config.conv_mode; bench.py --conv-mode "
               f"default: {native.DEFAULT_CONV_MODE})", flush=True)

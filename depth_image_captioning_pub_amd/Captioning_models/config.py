@@ -43,3 +43,6 @@ class ConfigTrain(object):
         # scheduled sampling in the cross-entropy epochs (not in the reference): None = off, nothing differs; else
         # dict(start=, increase_every=, increase_prob=, max_prob=), the keyword arguments of scheduled.scheduled_sampling_prob
         self.scheduled_sampling = None
+        # global-norm gradient clipping of every optimiser update (not in the reference): None = off, nothing differs;
+        # else the maximum L2 norm of the whole gradient, a finite float > 0 (the trainers' max_grad_norm)
+        self.clip_grad_norm = None

@@ -18,6 +18,9 @@ nic_scst_sample_step is the same step on captions drawn with dic_nic_sample (DES
 The hard-attention decoders train through their drawn attention cells instead: hard_sample_tensors draws joint
 samples (tokens, cells), hard_caption_logprobs gives their joint log-probability with a tape (dic_decoder_states_hard_fwd / _bwd),
 hard_reinforce_step is the step; its engine form is CaptionTrainer.reinforce_step.
+Gradient clipping: every step here runs backward() and optimizer.step() inside one function, so pass
+ClippedOptimizer(optimizer, max_grad_norm) as its optimiser (clip_grad_norm_ in front of step(); the trainers clip their flat
+buffer on the device, trainer.max_grad_norm).
 Out of scope: a METEOR reward (a Java jar and WordNet, not a rule over token ids) -
 reward_fn is the seam for any other reward."""
 from __future__ import annotations
@@ -27,6 +30,31 @@ import torch
 from .. import losses, native
 from .Depth_caption_model.depth_models import _CaptionDecoderBase, _HardCaptionStatesFn, _contig, _param
 from .util import given_captions, token_uniforms
+
+
+class ClippedOptimizer:
+    """A torch optimiser whose step() first clips the gradients of its parameters to the global L2 norm max_grad_norm
+    (torch.nn.utils.clip_grad_norm_).  The steps of this module run loss.backward() and optimizer.step() inside one function, so
+    a caller cannot clip in between: hand them ClippedOptimizer(optimizer, max_grad_norm) as their `optimizer` instead (their
+    parameter lists stay as they are).  These parameters are separate torch tensors; the engine's trainers clip their flat buffer
+    on the device with dic_grad_norm / dic_adamw_step_clipped (trainer.max_grad_norm)."""
+
+    def __init__(self, optimizer, max_grad_norm):
+        max_grad_norm = float(max_grad_norm)
+        if not 0.0 < max_grad_norm < float("inf"):
+            raise native._lib.DicError(f"ClippedOptimizer: max_grad_norm={max_grad_norm!r} must be a finite number above 0")
+        self.optimizer, self.max_grad_norm = optimizer, max_grad_norm
+
+    @property
+    def param_groups(self):
+        return self.optimizer.param_groups
+
+    def zero_grad(self, set_to_none=True):
+        self.optimizer.zero_grad(set_to_none=set_to_none)
+
+    def step(self):
+        torch.nn.utils.clip_grad_norm_([p for group in self.optimizer.param_groups for p in group["params"]], self.max_grad_norm)
+        return self.optimizer.step()
 
 
 def scst_step(decoder, optimizer, features, depth_features, word_to_id, reward_fn, n_samples=5, max_length=30, temperature=1.0,

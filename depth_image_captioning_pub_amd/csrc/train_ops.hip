@@ -107,14 +107,29 @@ __global__ void __launch_bounds__(256) pack_targets_kernel(const long long* __re
 }
 
 // ---- AdamW (torch.optim.AdamW single-tensor math, fp32) -----------------------------------------
+// CLIP (dic_adamw_step_clipped): the gradient is g * *grad_scale, rounded to fp32 before anything uses it.  The empty asm hides
+// the product from the optimiser: left visible it is fused into the subtraction behind it (v_fma_f32 scale, g, -m - also through
+// __fmul_rn), and the step differs in the last bit from one on gradients scaled in a pass of their own.  A scale that is not
+// finite - dic_grad_norm's verdict on a non-finite norm - drops the step like a raised guard word.
+template <bool CLIP>
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ v, long long n,
                                                      float decay, float beta1, float beta2, float step_size,
-                                                     float inv_bc2_sqrt, float eps, const unsigned* __restrict__ skip_if_raised) {
+                                                     float inv_bc2_sqrt, float eps, const unsigned* __restrict__ skip_if_raised,
+                                                     const float* __restrict__ grad_scale) {
   if (skip_if_raised && *skip_if_raised != 0u) return;       // f16x2 overflow guard (dic.h): parameters and moments stay as they are
+  float scale = 1.f;
+  if constexpr (CLIP) {
+    scale = *grad_scale;
+    if (!isfinite(scale)) return;
+  }
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const float gi = g[i];
+    float gi = g[i];
+    if constexpr (CLIP) {
+      gi *= scale;
+      asm volatile("" : "+v"(gi));
+    }
     float pi = p[i] * decay;                                    // p *= 1 - lr*wd
     const float mi = m[i] + (gi - m[i]) * (1.f - beta1);        // exp_avg.lerp_(grad, 1-beta1)
     const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;    // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
@@ -212,17 +227,33 @@ int dic_adamw_step(float* params, const float* grads, float* exp_avg, float* exp
   return dic_adamw_step_guarded(params, grads, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, stream);
 }
 
-int dic_adamw_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step,
-                           float lr, float beta1, float beta2, float eps, float weight_decay, const uint32_t* skip_if_raised,
-                           void* stream) {
+// One launch for the three AdamW entry points: grad_scale NULL = the plain kernel, else the clipped one.
+static int adamw_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, const uint32_t* skip_if_raised,
+                        const float* grad_scale, void* stream) {
   DIC_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0 && step >= 1, "adamw: bad arguments");
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   const int blocks = (int)std::min<long long>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
-                     n, 1.0f - lr * weight_decay, beta1, beta2, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), eps,
-                     (const unsigned*)skip_if_raised);
+  hipLaunchKernelGGL(grad_scale ? adamw_kernel<true> : adamw_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                     params, grads, exp_avg, exp_avg_sq, n, 1.0f - lr * weight_decay, beta1, beta2, (float)((double)lr / bc1),
+                     (float)(1.0 / sqrt(bc2)), eps, (const unsigned*)skip_if_raised, grad_scale);
   DIC_LAUNCH_CHECK();
   return DIC_OK;
+}
+
+int dic_adamw_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, const uint32_t* skip_if_raised,
+                           void* stream) {
+  return adamw_launch(params, grads, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, weight_decay, skip_if_raised, nullptr,
+                      stream);
+}
+
+int dic_adamw_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, const uint32_t* skip_if_raised,
+                           const float* grad_scale, void* stream) {
+  DIC_REQUIRE(grad_scale != nullptr, "adamw_step_clipped: grad_scale is null (hand it dic_grad_norm's out + 1)");
+  return adamw_launch(params, grads, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, weight_decay, skip_if_raised, grad_scale,
+                      stream);
 }
 
 int dic_dropout_mask(float* out, long long n, float p, uint64_t seed, uint64_t offset, void* stream) {

@@ -1,15 +1,19 @@
 """CLI with the reference's argument convention (depth_main.py:14-35):
     python -m depth_image_captioning_pub_amd.depth_main {soft,hard} cnn {coco,original,synthetic} [--scst-epochs N]
                                                          [--ss-start N --ss-every K --ss-inc P --ss-max P]
+                                                         [--clip-grad-norm X]
 (the reference script itself does not run as shipped - quirk Q5 - so this keeps its intent: 3 repetitions of
 train_Cdepth_{soft,hard}(i, useData)).  `mlp` is a no-op in the reference (depth_main.py:27-28,34-35) and here.
 --scst-epochs N (not in the reference): N further epochs of self-critical training behind the cross-entropy epochs
 (CaptionTrainer.scst_step, soft attention only; default: config.scst_epochs = 0).
 --ss-start N --ss-every K --ss-inc P --ss-max P (not in the reference): scheduled sampling in the cross-entropy epochs - from
 epoch N on the decoder is fed its own tokens with a probability that rises by P every K epochs up to the maximum
-(Captioning_models/scheduled.py; defaults 5, 0.05, 0.25).  The default --ss-start -1 means off."""
+(Captioning_models/scheduled.py; defaults 5, 0.05, 0.25).  The default --ss-start -1 means off.
+--clip-grad-norm X (not in the reference): every optimiser update clips the gradient to the global L2 norm X, a finite number
+above 0, on the device (the trainers' max_grad_norm; default: config.clip_grad_norm = None, no clipping)."""
 from __future__ import annotations
 
+import math
 import sys
 
 import numpy as np
@@ -91,13 +95,41 @@ def take_scheduled_sampling(args):
     return rest, ss
 
 
-def scheduled_config(train_module, scheduled):
-    """The config argument of a run: None (the training loop builds its own) without a schedule, else the loop's ConfigTrain with
-    the schedule set (the training entry points keep their signatures; the schedule travels in the config, as scst_epochs can)."""
-    if scheduled is None:
+def take_clip_grad_norm(args):
+    """(args without `--clip-grad-norm X` / `--clip-grad-norm=X`, X as a float or None when the option is absent); ValueError on a
+    value that is missing, not a number, not above 0 or not finite."""
+    rest, x, i = [], None, 0
+    while i < len(args):
+        a = str(args[i])
+        if a == "--clip-grad-norm" or a.startswith("--clip-grad-norm="):
+            if "=" in a:
+                value = a.split("=", 1)[1]
+            else:
+                i += 1
+                if i >= len(args):
+                    raise ValueError("--clip-grad-norm needs a value")
+                value = str(args[i])
+            try:
+                x = float(value)
+            except ValueError:
+                raise ValueError(f"--clip-grad-norm needs a number, got {value!r}") from None
+            if not (x > 0.0 and math.isfinite(x)):
+                raise ValueError(f"--clip-grad-norm needs a finite number above 0, got {value!r}")
+        else:
+            rest.append(args[i])
+        i += 1
+    return rest, x
+
+
+def run_config(train_module, scheduled, clip_grad_norm=None):
+    """The config argument of a run: None (the training loop builds its own) without a schedule and without clipping, else the
+    loop's ConfigTrain with them set (the training entry points keep their signatures; both travel in the config, as scst_epochs
+    can)."""
+    if scheduled is None and clip_grad_norm is None:
         return None
     config = train_module.ConfigTrain()
     config.scheduled_sampling = scheduled
+    config.clip_grad_norm = clip_grad_norm
     return config
 
 
@@ -108,6 +140,7 @@ def main(argv=None):
     try:
         args, scst_epochs = take_scst_epochs(list(sys.argv if argv is None else argv))
         args, scheduled = take_scheduled_sampling(args)
+        args, clip = take_clip_grad_norm(args)
     except ValueError as e:
         print(e)
         return 1
@@ -125,7 +158,7 @@ def main(argv=None):
         print("input {soft/hard} {cnn/mlp} {coco/original/synthetic}")
         return 1
     for i in range(exp_time):
-        fn(i, use_data, config=scheduled_config(depth_train, scheduled), scst_epochs=scst_epochs)
+        fn(i, use_data, config=run_config(depth_train, scheduled, clip), scst_epochs=scst_epochs)
     return 0
 
 

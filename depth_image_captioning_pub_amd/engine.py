@@ -295,6 +295,20 @@ class BackboneTrainer:
         self._guard_host = torch.zeros(16, dtype=torch.int32).pin_memory()
         self._guard_pending: List[tuple] = []      # (ring slot, event, step number) of copies in flight
         self._guard_slot = 0
+        # Global-norm gradient clipping (include/dic.h, dic_grad_norm / dic_adamw_step_clipped).  A plain attribute
+        # switches it: None = apply_update() is the unclipped update, a finite float > 0 = the L2 norm of the whole flat gradient
+        # buffer - behind the data-parallel exchange, so every rank clips the same sum - is held to it.  What the last clipped
+        # update found stays on the device (reading it is the caller's synchronisation): the norm, the coefficient the gradient
+        # was scaled by, the norm of each named span of the buffer, and how many updates were dropped because their norm was
+        # not finite (those leave parameters and moments untouched, like a raised guard word).
+        self.max_grad_norm: Optional[float] = None
+        self._clip_out = torch.zeros(2 + native.GRAD_NORM_MAX_SPANS, dtype=torch.float32, device=self.device)
+        self._clip_scratch = torch.empty(native.GRAD_NORM_SCRATCH_BYTES // 8, dtype=torch.float64, device=self.device)
+        self._clip_spans: Optional[List[tuple]] = None       # [(name, exclusive end in self.flat)], set by the subclass; None: one span "all"
+        self.last_grad_norm = self._clip_out[0:1]
+        self.last_clip_coef = self._clip_out[1:2]
+        self.last_span_norms: Dict[str, torch.Tensor] = {}
+        self.nonfinite_grad_steps = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.step_count = 0
         self.rng_offset = 0
         self.seed = seed
@@ -493,11 +507,35 @@ class BackboneTrainer:
                                                     self.device)
         return mask
 
+    def _measure_gradient(self) -> None:
+        """dic_grad_norm over self.flat.grad with self.max_grad_norm: fills last_grad_norm / last_clip_coef / last_span_norms (and
+        nonfinite_grad_steps) on the device."""
+        max_norm = self.max_grad_norm
+        if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not (0.0 < max_norm < float("inf")):
+            raise DicError(f"max_grad_norm={max_norm!r} must be None (no clipping) or a finite number above 0")
+        spans = self._clip_spans or [("all", self.flat.total)]
+        # The norm runs over the WHOLE flat buffer, the alignment padding between the tensors included.  That is the norm of the
+        # gradient only while the padding of flat.grad is zero: FlatParams allocates it zeroed, every backward writes through
+        # the tensors' views, and the exchange sums zeros (tests/test_clip_gpu.py holds the norm to the one over the views).
+        native.grad_norm(self.flat.grad, float(max_norm), [end for _, end in spans], out=self._clip_out,
+                         nonfinite_steps=self.nonfinite_grad_steps, scratch=self._clip_scratch)
+        if not self.last_span_norms:
+            self.last_span_norms = {name: self._clip_out[2 + s:3 + s] for s, (name, _) in enumerate(spans)}
+
     def apply_update(self) -> None:
-        """AdamW on the flat buffer with whatever self.flat.grad holds (depth_train.py:221)."""
+        """AdamW on the flat buffer with whatever self.flat.grad holds (depth_train.py:221).  With self.max_grad_norm set, on that
+        gradient clipped to the global L2 norm max_grad_norm (torch.nn.utils.clip_grad_norm_'s rule; self.flat.grad itself stays
+        as it is): two more launches, no host synchronisation.  An update whose norm is not finite is dropped on the device and
+        counted in nonfinite_grad_steps; the host cannot know, so step_count (Adam's bias correction) still counts it."""
+        if self.max_grad_norm is not None:
+            self._measure_gradient()
         self.step_count += 1
-        native.adamw_step(self.flat.data, self.flat.grad, self.flat.exp_avg, self.flat.exp_avg_sq, self.step_count,
-                          lr=self.lr, skip_if_raised=self.guard)
+        if self.max_grad_norm is None:
+            native.adamw_step(self.flat.data, self.flat.grad, self.flat.exp_avg, self.flat.exp_avg_sq, self.step_count,
+                              lr=self.lr, skip_if_raised=self.guard)
+        else:
+            native.adamw_step_clipped(self.flat.data, self.flat.grad, self.flat.exp_avg, self.flat.exp_avg_sq, self.step_count,
+                                      self.last_clip_coef, lr=self.lr, skip_if_raised=self.guard)
         self._guard_publish()
 
     def state_dicts(self):
@@ -541,6 +579,7 @@ class CaptionTrainer(BackboneTrainer):
         self.enc_g = {k: self.flat.view(self.flat.grad, "depth_encoder." + k) for k in self.enc_names}
         self.dec_span = self.flat.span(["decoder." + k for k in self.dec_names])
         self.enc_span = self.flat.span(["depth_encoder." + k for k in self.enc_names]) if use_depth else None
+        self._clip_spans = [("decoder", self.dec_span[1])] + ([("depth_encoder", self.enc_span[1])] if use_depth else [])
         self.enc_state = {k: v.to(self.device).contiguous() for k, v in depth_state.items()} if use_depth else {}
         self.depth_fwd_count = 0       # train-mode depth-encoder forwards (= BatchNorm num_batches_tracked)
         self.sample_count = 0          # scst_step calls that drew their own uniforms: part of the sampling generator's key

@@ -21,8 +21,9 @@ from .encoders import (CONV_MODES, DEPTH_FIELDS, ConvBnLayer, DepthBnState, Dept
 from .nic import (NIC_EMB, NIC_FIELDS, NIC_STATES_GRAD_KEYS, NicPtrs, NicStatesTape, NicTape, nic_backward, nic_forward,
                   nic_head_backward, nic_head_forward, nic_pack_targets, nic_ptrs, nic_shapes, nic_states_backward,
                   nic_states_forward)
-from .train_ops import (adamw_step, bleu, bn_ema_update, caption_lengths, caption_loss, cider_d, dropout_advance, dropout_draw,
-                        dropout_mask, gather_rows, pack_targets, rouge_l, scst_loss, token_logprobs, token_logprobs_bwd,
+from .train_ops import (GRAD_NORM_MAX_SPANS, GRAD_NORM_PASS, GRAD_NORM_SCRATCH_BYTES, adamw_step, adamw_step_clipped, bleu,
+                        bn_ema_update, caption_lengths, caption_loss, cider_d, dropout_advance, dropout_draw, dropout_mask,
+                        gather_rows, grad_norm, pack_targets, rouge_l, scst_loss, token_logprobs, token_logprobs_bwd,
                         token_logprobs_bwd_into)
 
 # which of dic_struct_bytes -> the ctypes mirror of that struct of include/dic.h (_core._load checks them all, once, and reads both names from here)

@@ -2,6 +2,7 @@
 the self-critical loss, row gathers and the caption metrics."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Dict, Optional, Sequence
 
@@ -56,6 +57,54 @@ def adamw_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor,
                                     lr, beta1, beta2, eps, weight_decay,
                                     _guard_ptr(skip_if_raised), stream_ptr())
     check(rc, "dic_adamw_step_guarded")
+
+
+GRAD_NORM_SCRATCH_BYTES = 65536     # DIC_GRAD_NORM_SCRATCH_BYTES of include/dic.h
+GRAD_NORM_MAX_SPANS = 8             # DIC_GRAD_NORM_MAX_SPANS
+GRAD_NORM_PASS = 1024 * 256 * 4     # elements one pass of dic_grad_norm's fixed grid covers (DIC_GRAD_NORM_BLOCKS * 1024)
+
+
+def grad_norm(grads: torch.Tensor, max_norm: float = 0.0, span_ends: Optional[Sequence[int]] = None,
+              out: Optional[torch.Tensor] = None, nonfinite_steps: Optional[torch.Tensor] = None,
+              scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dic_grad_norm: out float32 [2 + n_spans] on the device = (L2 norm of the flat fp32 buffer `grads`, clip coefficient
+    fminf(1, max_norm / (norm + 1e-6)) - 1 for max_norm <= 0, NaN when the norm is not finite -, the norm of every span).
+    span_ends: ascending exclusive ends, the last one grads.numel() (None: one span).  nonfinite_steps: int32 device word raised by
+    one when the norm is not finite.  out / scratch (GRAD_NORM_SCRATCH_BYTES bytes): the caller's buffers, allocated when None.
+    fp64 accumulation, bit-identical from run to run; no host synchronisation (semantics: include/dic.h)."""
+    lib = _load()
+    g = _inplace_f32(grads, "grad_norm needs a contiguous fp32 GPU buffer")
+    ends = [int(e) for e in span_ends] if span_ends is not None else None
+    n_spans = len(ends) if ends is not None else 1
+    if out is None:
+        out = torch.empty(2 + max(n_spans, 1), dtype=torch.float32, device=g.device)
+    elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= 2 + n_spans):
+        raise _lib.DicError(f"grad_norm: out must be a contiguous fp32 GPU tensor of at least {2 + n_spans} elements")
+    if scratch is None:
+        scratch = torch.empty(GRAD_NORM_SCRATCH_BYTES // 8, dtype=torch.float64, device=g.device)
+    elif not (scratch.is_cuda and scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= GRAD_NORM_SCRATCH_BYTES):
+        raise _lib.DicError(f"grad_norm: scratch must be a contiguous GPU tensor of at least {GRAD_NORM_SCRATCH_BYTES} bytes")
+    host_ends = (C.c_longlong * n_spans)(*ends) if ends else None
+    rc = lib.dic_grad_norm(ptr(g), g.numel(), host_ends, n_spans, float(max_norm), ptr(out), _guard_ptr(nonfinite_steps),
+                           ptr(scratch), stream_ptr())
+    check(rc, "dic_grad_norm")
+    return out
+
+
+def adamw_step_clipped(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int,
+                       grad_scale: torch.Tensor, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                       weight_decay: float = 0.01, skip_if_raised: Optional[torch.Tensor] = None) -> None:
+    """dic_adamw_step_clipped: adamw_step on grads * grad_scale[0] (grad_scale: a float32 device tensor, grad_norm(...)[1:2]) without
+    writing the scaled gradients; bit-identical to grads.mul_(grad_scale) followed by adamw_step.  `grads` stays as it is.  The step is
+    dropped on the device when grad_scale[0] is not finite or the guard word is raised."""
+    lib = _load()
+    for t in (params, grads, exp_avg, exp_avg_sq):
+        _inplace_f32(t, "adamw_step_clipped needs contiguous fp32 GPU buffers")
+    if not (grad_scale.is_cuda and grad_scale.dtype == torch.float32 and grad_scale.numel() >= 1 and grad_scale.is_contiguous()):
+        raise _lib.DicError("adamw_step_clipped: grad_scale must be a contiguous float32 GPU tensor (grad_norm(...)[1:2])")
+    rc = lib.dic_adamw_step_clipped(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), step,
+                                    lr, beta1, beta2, eps, weight_decay, _guard_ptr(skip_if_raised), ptr(grad_scale), stream_ptr())
+    check(rc, "dic_adamw_step_clipped")
 
 
 def bn_ema_update(running: torch.Tensor, delta: torch.Tensor, momentum: float = 0.1,

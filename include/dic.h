@@ -929,6 +929,49 @@ int dic_adamw_step_guarded(float* params, const float* grads, float* exp_avg, fl
                            float lr, float beta1, float beta2, float eps, float weight_decay, const uint32_t* skip_if_raised,
                            void* stream);
 
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ before optimizer.step(); no counterpart in the reference,
+ *      which never clips): dic_grad_norm measures a flat fp32 gradient buffer, dic_adamw_step_clipped applies the update with the
+ *      gradient scaled by what it found.  Both are enqueued on `stream`; the host never sees the norm unless it reads `out`.
+ *
+ * dic_grad_norm writes (all device, fp32)
+ *   out[0]      the L2 norm of grads[0..n)
+ *   out[1]      the clip coefficient fminf(1, max_norm / (out[0] + 1e-6f)), evaluated in fp32 - clip_grad_norm_'s rule.
+ *               max_norm <= 0: no clipping is wanted, out[1] = 1.
+ *   out[2 + s]  the norm of span s, s < n_spans: `out` holds 2 + n_spans floats.
+ * span_ends: HOST array of n_spans ascending exclusive ends, the last one n (span s = [span_ends[s-1], span_ends[s]), span 0
+ *   starts at 0; boundaries need no alignment); NULL with n_spans = 1: one span.  Read during the call only.
+ *   n_spans <= DIC_GRAD_NORM_MAX_SPANS.
+ * A norm that is NOT FINITE (an inf or NaN element, or a sum beyond the fp32 range) makes out[1] NaN whatever max_norm is and,
+ *   when nonfinite_steps (device word, nullable) is given, raises *nonfinite_steps by one; dic_adamw_step_clipped then drops the
+ *   step.  This differs ON PURPOSE from clip_grad_norm_(error_if_nonfinite=False), which multiplies every gradient by NaN and
+ *   lets the optimiser write NaN into the parameters and both moments for good.
+ * Arithmetic: every square and every partial sum in fp64 ((double)g * g is exact), one fp64 square root, one rounding to fp32:
+ *   |out[0] - true| <= 2^-23 * true, and buffers of 1e30 or of 1e-30 elements get their true norm (an fp32 accumulation returns
+ *   inf resp. 0).  out[0] is computed as the root of the sum of the span sums in span order.
+ * Order: a fixed grid of DIC_GRAD_NORM_BLOCKS workgroups of 256 threads; element i belongs to group i / 4 and group q to thread
+ *   q mod (DIC_GRAD_NORM_BLOCKS * 256), so one pass of the grid covers DIC_GRAD_NORM_BLOCKS * 1024 elements and the assignment
+ *   depends on n alone; partial sums are combined in fixed trees by a second one-workgroup launch.  The same values give the same
+ *   bits on every run and at every alignment of `grads`.
+ * grads: any 4-byte aligned device address, any n > 0.  A 16-byte aligned buffer is read with 16-byte loads, any other with the
+ *   same groups as four 4-byte loads; the n mod 4 last elements are read singly.  Nothing outside [0, n) is read.
+ * scratch: DIC_GRAD_NORM_SCRATCH_BYTES of device memory, 8-byte aligned, contents irrelevant before and after the call.
+ * Refused on the host before any HIP call (the offending value is in dic_last_error()): n <= 0, NaN max_norm, n_spans outside
+ *   1..DIC_GRAD_NORM_MAX_SPANS, ends that do not ascend or do not finish at n, null grads / out / scratch. */
+#define DIC_GRAD_NORM_BLOCKS 1024
+#define DIC_GRAD_NORM_MAX_SPANS 8
+#define DIC_GRAD_NORM_SCRATCH_BYTES 65536   /* DIC_GRAD_NORM_BLOCKS * DIC_GRAD_NORM_MAX_SPANS fp64 partial sums */
+int dic_grad_norm(const float* grads, long long n, const long long* span_ends, int n_spans, float max_norm, float* out,
+                  uint32_t* nonfinite_steps, void* scratch, void* stream);
+/* dic_adamw_step_guarded on the gradient g' = g * *grad_scale (one fp32 multiply per element; grad_scale: device pointer, hand it
+ * dic_grad_norm's out + 1), everything after that multiply being dic_adamw_step's arithmetic operation for operation: parameters
+ * and moments are bit-identical to scaling the gradients in an fp32 pass of their own and calling dic_adamw_step_guarded - without
+ * that pass's read and write of the buffer.  `grads` is NOT modified.  Nothing is written when *skip_if_raised (nullable) is
+ * non-zero or when *grad_scale is not finite (dic_grad_norm's verdict on a non-finite norm): parameters and both moments stay as
+ * they were. */
+int dic_adamw_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, const uint32_t* skip_if_raised,
+                           const float* grad_scale, void* stream);
+
 /* ---- data parallel (the reference itself is single-GPU, config.py:68): the path has ONE exchange step, a
  *      sum all-reduce of the flat gradient buffer between dic_decoder_bwd / dic_depth_encoder_bwd and dic_adamw_step.  The
  *      Python engine issues it through torch.distributed (backend "nccl" = RCCL); these entry points are the same exchange
