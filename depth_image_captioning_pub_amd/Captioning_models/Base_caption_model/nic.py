@@ -337,6 +337,7 @@ class NicTrainer(BackboneTrainer):
                     drop_mult: Optional[torch.Tensor] = None, dropout: bool = True, keep_guard: bool = False) -> torch.Tensor:
         """Head + decoder forward, loss, backward and AdamW on a final feature map [B,cells,2048] (nic.py:278-290).  Unless
         keep_guard, the map is taken as given (no ResNet forward behind it: the overflow guard word is cleared)."""
+        eps = self._checked_label_smoothing()
         if not keep_guard:
             self._guard_take(None)
         B, tmax = fmap.shape[0], max(lengths)
@@ -346,8 +347,8 @@ class NicTrainer(BackboneTrainer):
         logits, tape = native.nic_forward(self.dec_w, feats, captions, lengths, drop_mult, workspace=self.dec_ws)
         self.dec_ws = tape.workspace
         self._mark("nic_fwd")
-        loss, dlogits, _ = native.caption_loss(logits, native.nic_pack_targets(captions, lengths), None,
-                                               in_place=not self.keep_outputs)
+        # (no alphas: lam is not read; self.label_smoothing > 0: the smoothed objective, the plain NLL goes to self.last["nll"])
+        loss, nll, dlogits, _ = self._loss_head(eps, logits, native.nic_pack_targets(captions, lengths), None, 0.7, 1.0, 1.0)
         self._mark("loss")
         _, dfeat = native.nic_backward(tape, dlogits, grads=self.dec_g)
         self._head_backward(pooled, dfeat)
@@ -355,6 +356,8 @@ class NicTrainer(BackboneTrainer):
         self.apply_update()                    # AdamW on the flat buffer, skipped on the device when the guard word is raised
         self._mark("adamw")
         self.last = {"logits": logits, "features": feats, "map": fmap}
+        if nll is not None:
+            self.last["nll"] = nll
         return loss
 
     def train_step(self, imgs: torch.Tensor, captions: torch.Tensor, lengths: Sequence[int], next_imgs=None) -> torch.Tensor:
@@ -486,6 +489,7 @@ def train_nic(ext, useData: str = "synthetic", config=None, stats=None):
     trainer = NicTrainer(config.vocab_size, device=config.device, seed=123 + int(ext), lr=config.lr, dropout=config.dropout,
                          resnet_layers=resnet_layers, conv_mode=getattr(config, "conv_mode", None))
     trainer.max_grad_norm = getattr(config, "clip_grad_norm", None)      # None: unclipped updates (base_main nic --clip-grad-norm X)
+    trainer.label_smoothing = getattr(config, "label_smoothing", 0.0)    # 0: the plain cross-entropy (base_main nic --label-smoothing E)
     print(f"[nic] frozen ResNet-152 convolutions in {trainer.conv_mode} arithmetic (config.conv_mode)", flush=True)
     if stats is not None:
         stats.update(conv_mode=trainer.conv_mode)
@@ -494,14 +498,22 @@ def train_nic(ext, useData: str = "synthetic", config=None, stats=None):
     val_loss_best = float("inf")
     history = []
     for epoch in range(config.num_epochs):
-        losses = []
+        losses, nlls = [], []
         # the frozen ResNet runs ahead of the step on side streams (as in depth_train._train)
         stream_it = ((imgs.to(dev), caps.to(dev), lens) for imgs, caps, lens in
                      _synthetic_batches(config, config.iters_per_epoch, 1000 * epoch))
         for (imgs, caps, lens), following in look_ahead(stream_it):
             losses.append(trainer.train_step(imgs, caps, lens, next_imgs=[f[0] for f in following]))      # no per-iteration host sync
+            if "nll" in trainer.last:
+                nlls.append(trainer.last["nll"])
         trainer.check_status()          # f16x2 overflow guard: raises DicError if a step of this epoch tripped it
         train_loss = float(torch.stack(losses).mean().item())
+        if nlls:                        # label smoothing: the plain NLL beside the smoothed objective the CSV records
+            train_nll = float(torch.stack(nlls).mean().item())
+            print(f"[nic] epoch {epoch}: objective {train_loss:.4f} (label_smoothing={trainer.label_smoothing:g}), nll {train_nll:.4f}",
+                  flush=True)
+            if stats is not None:
+                stats.setdefault("train_nll", []).append(train_nll)
         with open(train_loss_file, "a") as f:
             print(f"{epoch}, {train_loss}", file=f)
         val_losses = [trainer.eval_loss(imgs.to(dev), caps.to(dev), lens) for imgs, caps, lens in _synthetic_batches(config, n_val, 777)]

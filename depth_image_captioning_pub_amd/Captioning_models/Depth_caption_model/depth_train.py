@@ -146,6 +146,7 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
                              dropout=config.dropout, lam=lam, process_group=process_group, use_depth=depth_branch,
                              conv_mode=getattr(config, "conv_mode", None))
     trainer.max_grad_norm = getattr(config, "clip_grad_norm", None)      # None: unclipped updates (--clip-grad-norm X of the mains)
+    trainer.label_smoothing = getattr(config, "label_smoothing", 0.0)    # 0: the plain cross-entropy (--label-smoothing E of the mains)
     if rank == 0:
         print(f"[{tag}] frozen ResNet-152 convolutions in {trainer.conv_mode} arithmetic (config.conv_mode; bench.py --conv-mode "
               f"default: {native.DEFAULT_CONV_MODE})", flush=True)
@@ -165,7 +166,7 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
         ss_prob = scheduled_sampling_prob(epoch, **scheduled_sampling) if scheduled_sampling else 0.0
         if stats is not None and scheduled_sampling:
             stats.setdefault("sampling_probs", []).append(ss_prob)
-        window, losses = deque(), []
+        window, losses, nlls = deque(), [], []
         # with the DPT front-end the "dataset" is the same every epoch (that is what makes the depth cache meaningful)
         def on_device():
             """Batches of the epoch on the device (with the DPT front-end: normalised + depth maps from prediction / cache)."""
@@ -182,11 +183,20 @@ def _train(ext, useData, hard: bool, config=None, process_group=None, stats=None
             loss = trainer.train_step(imgs, depth, caps, lens, gumbel_u=u, temp=float(temp),
                                       next_imgs=[f[1] for f in following], sampling_prob=ss_prob)
             losses.append(loss)                                         # device tensors: no per-iteration host sync
+            if "nll" in trainer.last:                                   # label smoothing: the plain NLL beside the objective
+                nlls.append(trainer.last["nll"])
             window.append(loss)
             if len(window) > config.moving_avg:
                 window.popleft()
         trainer.check_status()          # f16x2 overflow guard: raises DicError if a step of this epoch tripped it (engine.py)
         train_loss = float(torch.stack(losses).mean().item())
+        if nlls:                        # the CSV keeps the objective that was optimised; the plain NLL is what compares across epsilons
+            train_nll = float(torch.stack(nlls).mean().item())
+            if stats is not None:
+                stats.setdefault("train_nll", []).append(train_nll)
+            if rank == 0:
+                print(f"[{tag}] epoch {epoch}: objective {train_loss:.4f} (label_smoothing={trainer.label_smoothing:g}), "
+                      f"nll {train_nll:.4f}", flush=True)
         if rank == 0:
             with open(train_loss_file, "a") as f:
                 print(f"{epoch}, {train_loss}", file=f)

@@ -46,3 +46,6 @@ class ConfigTrain(object):
         # global-norm gradient clipping of every optimiser update (not in the reference): None = off, nothing differs;
         # else the maximum L2 norm of the whole gradient, a finite float > 0 (the trainers' max_grad_norm)
         self.clip_grad_norm = None
+        # label smoothing of the cross-entropy epochs (not in the reference): F.cross_entropy's label_smoothing in
+        # [0, 1]; 0 = off, nothing differs.  Validation loss and the self-critical epochs stay unsmoothed (the trainers' label_smoothing)
+        self.label_smoothing = 0.0

@@ -1,7 +1,8 @@
 """CLI with the reference's argument convention (base_main.py:14-43):
     python -m depth_image_captioning_pub_amd.base_main {soft,hard} {coco,original,synthetic} [--scst-epochs N]
                                                      [--ss-start N --ss-every K --ss-inc P --ss-max P] [--clip-grad-norm X]
-    python -m depth_image_captioning_pub_amd.base_main nic [synthetic] [--clip-grad-norm X]
+                                                     [--label-smoothing E]
+    python -m depth_image_captioning_pub_amd.base_main nic [synthetic] [--clip-grad-norm X] [--label-smoothing E]
 = 3 repetitions of train_base_{soft,hard}(i, useData) (base_main.py:23-27, 31-35) resp. of train_nic(i) (Show-and-Tell,
 base_main.py:40-42; the reference's nic branch takes no data argument, here it defaults to `synthetic`, and any other value
 raises the DicError the other trainers raise for `coco` / `original`).  The reference's hard branch compares instead of assigning
@@ -13,7 +14,7 @@ import sys
 from .Captioning_models.Base_caption_model import base_train, nic
 from .Captioning_models.Base_caption_model.base_train import train_base_hard, train_base_soft
 from .Captioning_models.Base_caption_model.nic import train_nic
-from .depth_main import EXP_TIME, run_config, take_clip_grad_norm, take_scheduled_sampling, take_scst_epochs, torch_seed
+from .depth_main import EXP_TIME, run_config, take_clip_grad_norm, take_label_smoothing, take_scheduled_sampling, take_scst_epochs, torch_seed
 
 
 def main(argv=None):
@@ -23,6 +24,7 @@ def main(argv=None):
         args, scst_epochs = take_scst_epochs(list(sys.argv if argv is None else argv))      # (depth_main's option: soft only)
         args, scheduled = take_scheduled_sampling(args)      # (depth_main's options; the NIC baseline has no such route)
         args, clip = take_clip_grad_norm(args)               # (depth_main's option; every trainer, the NIC one too)
+        args, smoothing = take_label_smoothing(args)         # (depth_main's option; every trainer, the NIC one too)
     except ValueError as e:
         print(e)
         return 1
@@ -31,14 +33,14 @@ def main(argv=None):
         return 1
     if args[1] == "nic":
         for i in range(EXP_TIME):
-            train_nic(i, args[2] if len(args) > 2 else "synthetic", config=run_config(nic, None, clip))
+            train_nic(i, args[2] if len(args) > 2 else "synthetic", config=run_config(nic, None, clip, label_smoothing=smoothing))
         return 0
     fn = {"soft": train_base_soft, "hard": train_base_hard}.get(args[1])
     if fn is None or len(args) < 3 or args[2] not in datas:
         print("input coco or original")
         return 1
     for i in range(EXP_TIME):
-        fn(i, args[2], config=run_config(base_train, scheduled, clip), scst_epochs=scst_epochs)
+        fn(i, args[2], config=run_config(base_train, scheduled, clip, label_smoothing=smoothing), scst_epochs=scst_epochs)
     return 0
 
 

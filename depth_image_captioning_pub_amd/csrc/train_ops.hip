@@ -12,10 +12,17 @@ namespace dic {
 // `dlogits` MAY ALIAS `logits` (in-place gradient): neither pointer is __restrict__.  (They were in round 1: the compiler
 // was then free to sink thread 0's read of x[target] below the barrier, where another thread may already have stored
 // that element's gradient - the row's loss, and only the loss, came out wrong whenever the timing allowed it.)
+// SMOOTH (dic_caption_loss_smoothed): loss_row = lse - (1 - eps) x[target] - eps mean(x), nll_rows gets the plain row, and
+// dlogits = (softmax(x) - (1 - eps) onehot - eps / V) * gscale.  The row's sum rides, in fp64, in the pass that sums exp(x - m): it
+// is complete - like x[target] - before the barrier that precedes the first store, so the aliasing argument above holds unchanged.
+// The plain instance keeps the statements it had: dic_caption_loss returns the bytes it returned before the template.
+template <bool SMOOTH>
 __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(const float* logits,
                                                           const long long* __restrict__ targets, int V, float gscale,
-                                                          float* __restrict__ loss_rows, float* dlogits) {
+                                                          float eps, float* __restrict__ loss_rows,
+                                                          float* __restrict__ nll_rows, float* dlogits) {
   __shared__ float red[8];
+  __shared__ double redx[4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* x = logits + (long long)row * V;
   float m = -INFINITY;
@@ -25,7 +32,19 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(const float* logits,
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float s = 0.f;
-  for (int v = tid; v < V; v += 256) s += expf(x[v] - m);
+  double sx = 0.0;
+  if constexpr (SMOOTH) {
+    for (int v = tid; v < V; v += 256) {
+      const float xv = x[v];
+      s += expf(xv - m);
+      sx += (double)xv;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+    if (lane == 0) redx[w] = sx;
+  } else {
+    for (int v = tid; v < V; v += 256) s += expf(x[v] - m);
+  }
   s = wave_sum(s);
   if (lane == 0) red[4 + w] = s;
   __syncthreads();
@@ -36,13 +55,33 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(const float* logits,
   // loss becomes NaN - the step's loss is then NaN, which no caller can mistake for a result - and the address is clamped
   const bool bad_target = tg < 0 || tg >= V;
   tg = tg < 0 ? 0 : (tg >= V ? V - 1 : tg);
-  if (tid == 0) loss_rows[row] = bad_target ? __builtin_nanf("") : lse - x[tg];
+  if constexpr (SMOOTH) {
+    if (tid == 0) {
+      const float xt = x[tg];
+      const float nll_row = lse - xt;
+      const float mean = (float)((redx[0] + redx[1] + redx[2] + redx[3]) / (double)V);
+      // eps = 0 takes the plain row itself (not lse - 1 * xt - 0 * mean, which an infinite logit would turn into NaN)
+      const float smooth_row = eps == 0.f ? nll_row : (lse - (1.f - eps) * xt) - eps * mean;
+      loss_rows[row] = bad_target ? __builtin_nanf("") : smooth_row;
+      nll_rows[row] = bad_target ? __builtin_nanf("") : nll_row;
+    }
+  } else {
+    if (tid == 0) loss_rows[row] = bad_target ? __builtin_nanf("") : lse - x[tg];
+  }
   __threadfence_block();
   __syncthreads();                       // dlogits may alias logits: the read of x[tg] is done before any store below
   float* dx = dlogits + (long long)row * V;
-  for (int v = tid; v < V; v += 256) {
-    const float p = expf(x[v] - lse);
-    dx[v] = (p - (v == tg ? 1.f : 0.f)) * gscale;
+  if constexpr (SMOOTH) {
+    const float on = 1.f - eps, u = eps / (float)V;
+    for (int v = tid; v < V; v += 256) {
+      const float p = expf(x[v] - lse);
+      dx[v] = ((p - (v == tg ? on : 0.f)) - u) * gscale;
+    }
+  } else {
+    for (int v = tid; v < V; v += 256) {
+      const float p = expf(x[v] - lse);
+      dx[v] = (p - (v == tg ? 1.f : 0.f)) * gscale;
+    }
   }
 }
 
@@ -175,20 +214,20 @@ using namespace dic;
 
 extern "C" {
 
-int dic_caption_loss(const float* logits, const int64_t* targets, int n_packed, int V, const float* alphas, int B,
-                     int Tmax, float lam, float ce_grad_scale, float reg_grad_scale, float* loss, float* dlogits,
-                     float* dalphas, float* scratch, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DIC_REQUIRE(logits && targets && loss && dlogits && scratch, "caption_loss: null pointer");
-  DIC_REQUIRE(n_packed > 0 && V > 0, "caption_loss: empty input");
-  float* loss_rows = scratch;
-  float* reg_rows = scratch + n_packed;
-  hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(n_packed), dim3(256), 0, st, logits, (const long long*)targets, V,
-                     ce_grad_scale / (float)n_packed, loss_rows, dlogits);
+// dic_caption_loss (nll_rows == NULL: the plain kernel) and dic_caption_loss_smoothed behind their argument checks
+static int caption_loss_launch(const float* logits, const int64_t* targets, int n_packed, int V, const float* alphas, int B,
+                               int Tmax, float lam, float eps, float ce_grad_scale, float reg_grad_scale, float* loss, float* nll,
+                               float* dlogits, float* dalphas, float* loss_rows, float* nll_rows, float* reg_rows, hipStream_t st) {
+  const float gscale = ce_grad_scale / (float)n_packed;
+  if (nll_rows)
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<true>, dim3(n_packed), dim3(256), 0, st, logits, (const long long*)targets, V, gscale, eps,
+                       loss_rows, nll_rows, dlogits);
+  else
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<false>, dim3(n_packed), dim3(256), 0, st, logits, (const long long*)targets, V, gscale, 0.f,
+                       loss_rows, (float*)nullptr, dlogits);
   DIC_LAUNCH_CHECK();
   float reg_scale = 0.f;
   if (alphas) {
-    DIC_REQUIRE(dalphas != nullptr && B > 0 && Tmax > 0, "caption_loss: dalphas required with alphas");
     reg_scale = lam / ((float)B * (float)DIC_L);
     hipLaunchKernelGGL(alpha_reg_kernel, dim3(B), dim3(256), 0, st, alphas, Tmax, reg_scale * reg_grad_scale, reg_rows,
                        dalphas);
@@ -197,7 +236,37 @@ int dic_caption_loss(const float* logits, const int64_t* targets, int n_packed, 
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, loss_rows, n_packed,
                      alphas ? reg_rows : (const float*)nullptr, B, reg_scale, loss);
   DIC_LAUNCH_CHECK();
+  if (nll) {
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, nll_rows, n_packed, (const float*)nullptr, B, 0.f, nll);
+    DIC_LAUNCH_CHECK();
+  }
   return DIC_OK;
+}
+
+int dic_caption_loss(const float* logits, const int64_t* targets, int n_packed, int V, const float* alphas, int B,
+                     int Tmax, float lam, float ce_grad_scale, float reg_grad_scale, float* loss, float* dlogits,
+                     float* dalphas, float* scratch, void* stream) {
+  DIC_REQUIRE(logits && targets && loss && dlogits && scratch, "caption_loss: null pointer");
+  DIC_REQUIRE(n_packed > 0 && V > 0, "caption_loss: empty input");
+  if (alphas) DIC_REQUIRE(dalphas != nullptr && B > 0 && Tmax > 0, "caption_loss: dalphas required with alphas");
+  return caption_loss_launch(logits, targets, n_packed, V, alphas, B, Tmax, lam, 0.f, ce_grad_scale, reg_grad_scale, loss, nullptr,
+                             dlogits, dalphas, scratch, nullptr, scratch + n_packed, (hipStream_t)stream);
+}
+
+int dic_caption_loss_smoothed(const float* logits, const int64_t* targets, int n_packed, int V, const float* alphas, int B,
+                              int Tmax, float lam, float label_smoothing, float ce_grad_scale, float reg_grad_scale,
+                              float* loss, float* nll, float* dlogits, float* dalphas, float* scratch, void* stream) {
+  // every argument check comes before the first HIP call
+  DIC_REQUIRE(logits && targets && loss && dlogits && scratch, "dic_caption_loss_smoothed: null pointer");
+  DIC_REQUIRE(n_packed > 0 && V > 0, "dic_caption_loss_smoothed: empty input (n_packed=%d, V=%d)", n_packed, V);
+  DIC_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f,
+              "dic_caption_loss_smoothed: label_smoothing=%g is outside [0, 1]", (double)label_smoothing);
+  if (alphas)
+    DIC_REQUIRE(dalphas != nullptr && B > 0 && Tmax > 0, "dic_caption_loss_smoothed: dalphas required with alphas (B=%d, Tmax=%d)", B,
+                Tmax);
+  return caption_loss_launch(logits, targets, n_packed, V, alphas, B, Tmax, lam, label_smoothing, ce_grad_scale, reg_grad_scale, loss,
+                             nll, dlogits, dalphas, scratch, scratch + n_packed, scratch + 2 * (long long)n_packed,
+                             (hipStream_t)stream);
 }
 
 int dic_pack_targets(const int64_t* captions, int cap_stride, const int* dec_lengths, int B, int64_t* targets,

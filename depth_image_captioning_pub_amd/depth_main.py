@@ -1,7 +1,7 @@
 """CLI with the reference's argument convention (depth_main.py:14-35):
     python -m depth_image_captioning_pub_amd.depth_main {soft,hard} cnn {coco,original,synthetic} [--scst-epochs N]
                                                          [--ss-start N --ss-every K --ss-inc P --ss-max P]
-                                                         [--clip-grad-norm X]
+                                                         [--clip-grad-norm X] [--label-smoothing E]
 (the reference script itself does not run as shipped - quirk Q5 - so this keeps its intent: 3 repetitions of
 train_Cdepth_{soft,hard}(i, useData)).  `mlp` is a no-op in the reference (depth_main.py:27-28,34-35) and here.
 --scst-epochs N (not in the reference): N further epochs of self-critical training behind the cross-entropy epochs
@@ -10,7 +10,10 @@ train_Cdepth_{soft,hard}(i, useData)).  `mlp` is a no-op in the reference (depth
 epoch N on the decoder is fed its own tokens with a probability that rises by P every K epochs up to the maximum
 (Captioning_models/scheduled.py; defaults 5, 0.05, 0.25).  The default --ss-start -1 means off.
 --clip-grad-norm X (not in the reference): every optimiser update clips the gradient to the global L2 norm X, a finite number
-above 0, on the device (the trainers' max_grad_norm; default: config.clip_grad_norm = None, no clipping)."""
+above 0, on the device (the trainers' max_grad_norm; default: config.clip_grad_norm = None, no clipping).
+--label-smoothing E (not in the reference): the cross-entropy epochs minimise F.cross_entropy's label-smoothed loss with E in
+[0, 1] (the trainers' label_smoothing; default: config.label_smoothing = 0, the plain loss) and print the plain
+negative log-likelihood beside it; validation loss and the self-critical epochs stay unsmoothed."""
 from __future__ import annotations
 
 import math
@@ -121,15 +124,43 @@ def take_clip_grad_norm(args):
     return rest, x
 
 
-def run_config(train_module, scheduled, clip_grad_norm=None):
-    """The config argument of a run: None (the training loop builds its own) without a schedule and without clipping, else the
-    loop's ConfigTrain with them set (the training entry points keep their signatures; both travel in the config, as scst_epochs
-    can)."""
-    if scheduled is None and clip_grad_norm is None:
+def take_label_smoothing(args):
+    """(args without `--label-smoothing E` / `--label-smoothing=E`, E as a float or None when the option is absent); ValueError on a
+    value that is missing, not a number or outside [0, 1]."""
+    rest, x, i = [], None, 0
+    while i < len(args):
+        a = str(args[i])
+        if a == "--label-smoothing" or a.startswith("--label-smoothing="):
+            if "=" in a:
+                value = a.split("=", 1)[1]
+            else:
+                i += 1
+                if i >= len(args):
+                    raise ValueError("--label-smoothing needs a value")
+                value = str(args[i])
+            try:
+                x = float(value)
+            except ValueError:
+                raise ValueError(f"--label-smoothing needs a number, got {value!r}") from None
+            if not 0.0 <= x <= 1.0:
+                raise ValueError(f"--label-smoothing needs a number in [0, 1], got {value!r}")
+        else:
+            rest.append(args[i])
+        i += 1
+    return rest, x
+
+
+def run_config(train_module, scheduled, clip_grad_norm=None, *, label_smoothing=None):
+    """The config argument of a run: None (the training loop builds its own) without a schedule, without clipping and without
+    label smoothing, else the loop's ConfigTrain with them set (the training entry points keep their signatures; all three travel
+    in the config, as scst_epochs can)."""
+    if scheduled is None and clip_grad_norm is None and label_smoothing is None:
         return None
     config = train_module.ConfigTrain()
     config.scheduled_sampling = scheduled
     config.clip_grad_norm = clip_grad_norm
+    if label_smoothing is not None:
+        config.label_smoothing = label_smoothing
     return config
 
 
@@ -141,6 +172,7 @@ def main(argv=None):
         args, scst_epochs = take_scst_epochs(list(sys.argv if argv is None else argv))
         args, scheduled = take_scheduled_sampling(args)
         args, clip = take_clip_grad_norm(args)
+        args, smoothing = take_label_smoothing(args)
     except ValueError as e:
         print(e)
         return 1
@@ -158,7 +190,7 @@ def main(argv=None):
         print("input {soft/hard} {cnn/mlp} {coco/original/synthetic}")
         return 1
     for i in range(exp_time):
-        fn(i, use_data, config=run_config(depth_train, scheduled, clip), scst_epochs=scst_epochs)
+        fn(i, use_data, config=run_config(depth_train, scheduled, clip, label_smoothing=smoothing), scst_epochs=scst_epochs)
     return 0
 
 

@@ -309,6 +309,11 @@ class BackboneTrainer:
         self.last_clip_coef = self._clip_out[1:2]
         self.last_span_norms: Dict[str, torch.Tensor] = {}
         self.nonfinite_grad_steps = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # Label smoothing of the cross-entropy steps (include/dic.h, dic_caption_loss_smoothed).  A plain attribute
+        # like max_grad_norm: 0 = the steps call native.caption_loss as they always did; a float in (0, 1] = they call the smoothed
+        # head, return its objective and keep the plain negative log-likelihood in self.last["nll"].  eval_loss and the
+        # self-critical steps do not look at it.
+        self.label_smoothing: float = 0.0
         self.step_count = 0
         self.rng_offset = 0
         self.seed = seed
@@ -507,6 +512,20 @@ class BackboneTrainer:
                                                     self.device)
         return mask
 
+    def _checked_label_smoothing(self) -> float:
+        """self.label_smoothing as a float in [0, 1] (DicError otherwise): the cross-entropy steps ask before they enqueue anything."""
+        return native.check_label_smoothing(self.label_smoothing, type(self).__name__)
+
+    def _loss_head(self, eps: float, logits, targets, alphas, lam: float, ce_scale: float, reg_scale: float):
+        """(loss, nll or None, dlogits, dalphas) of a cross-entropy step: native.caption_loss at eps = 0, exactly as before the
+        attribute existed; native.caption_loss_smoothed above."""
+        if eps == 0.0:
+            loss, dlogits, dalphas = native.caption_loss(logits, targets, alphas, lam, grad_scale=ce_scale, reg_grad_scale=reg_scale,
+                                                         in_place=not self.keep_outputs)
+            return loss, None, dlogits, dalphas
+        return native.caption_loss_smoothed(logits, targets, alphas, lam, label_smoothing=eps, grad_scale=ce_scale,
+                                            reg_grad_scale=reg_scale, in_place=not self.keep_outputs)
+
     def _measure_gradient(self) -> None:
         """dic_grad_norm over self.flat.grad with self.max_grad_norm: fills last_grad_norm / last_clip_coef / last_span_norms (and
         nonfinite_grad_steps) on the device."""
@@ -665,6 +684,7 @@ class CaptionTrainer(BackboneTrainer):
         apply_update=False leaves the (scaled, all-reduced) gradients in self.flat.grad and skips AdamW;
         virtual_world=N scales the gradients as rank-of-N would without any collective - together they let one process
           reproduce an N-rank step shard by shard (tests)."""
+        eps = self._checked_label_smoothing()
         B = imgs.shape[0] if imgs is not None else precomputed_features.shape[0]
         tmax = max(lengths) - 1
         feats = (self._open_step(imgs, next_imgs, lambda x: self._compact(x, depth_map)) if precomputed_features is None
@@ -693,9 +713,8 @@ class CaptionTrainer(BackboneTrainer):
         targets = native.pack_targets(captions, lengths)                                     # :210-213
         nworld = virtual_world if virtual_world is not None else self.world
         ce_scale, reg_scale = gradient_scales(int(targets.shape[0]), nworld, global_tokens)
-        loss, dlogits, dalphas = native.caption_loss(logits, targets, None if self.hard else alphas, self.lam,
-                                                     grad_scale=ce_scale, reg_grad_scale=reg_scale,
-                                                     in_place=not self.keep_outputs)         # :214-216
+        loss, nll, dlogits, dalphas = self._loss_head(eps, logits, targets, None if self.hard else alphas, self.lam, ce_scale,
+                                                      reg_scale)                                # :214-216
         self._mark("loss")
         _, dfeat = native.decoder_backward(tape, dlogits, dalphas, grads=self.dec_g)         # :219
         self._mark("decoder_bwd")
@@ -703,6 +722,8 @@ class CaptionTrainer(BackboneTrainer):
         self.last = {"logits": logits, "alphas": alphas, "features": feats, "depth_features": fdep}
         if fed_ids is not None:
             self.last["fed_ids"] = fed_ids
+        if nll is not None:
+            self.last["nll"] = nll
         if self.keep_outputs:
             self.last["decoder_tape"] = tape           # parity tests: native.decoder_attention_relu_mask(tape)
         return loss

@@ -1,7 +1,8 @@
 """Differentiable token log-probabilities: torch autograd over dic_token_logprobs / dic_token_logprobs_bwd (include/dic.h).  The
 vocabulary projection, its log-sum-exp and both of their gradients run in the fused kernels of csrc/score.hip and
-csrc/score_bwd.hip; the [M,V] logits and their gradient are never stored.  Nothing here falls back to torch ops: tensors that
-do not live on the GPU raise DicError."""
+csrc/score_bwd.hip; the [M,V] logits and their gradient are never stored.  Label smoothing adds the rows' mean logit, which needs
+no logits either (dic_token_mean_logit / dic_token_mean_logit_bwd, csrc/score_mean.hip): smoothed_cross_entropy.  Nothing here
+falls back to torch ops: tensors that do not live on the GPU raise DicError."""
 from __future__ import annotations
 
 from typing import Optional
@@ -64,6 +65,48 @@ def reduce_logprobs(logprobs: torch.Tensor, targets: torch.Tensor, weights: Opti
     live = targets >= 0
     denom = live.sum().to(rows.dtype) if weights is None else (weights * live.to(weights.dtype)).sum()
     return rows.sum() / denom
+
+
+class _TokenMeanLogit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, weight, bias):
+        mean, state = native.token_mean_logit(hidden, weight, bias)
+        ctx.save_for_backward(hidden)
+        ctx.state, ctx.vocab = state, int(weight.shape[0])      # the call's workspace: the column means the backward reads
+        return mean
+
+    @staticmethod
+    def backward(ctx, d_mean):
+        (hidden,) = ctx.saved_tensors
+        need = tuple(ctx.needs_input_grad[:3])
+        if not any(need):
+            return None, None, None
+        return native.token_mean_logit_bwd(hidden, d_mean, ctx.vocab, ctx.state, need)
+
+
+def token_mean_logit(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """mean [M] of native.token_mean_logit, differentiable with respect to hidden [M,128], weight [V,128] and bias [V]:
+    mean[m] = (hidden[m] @ weight.T + bias).mean(), from the column means of weight - the [M,V] logits are never computed."""
+    return _TokenMeanLogit.apply(hidden, weight, bias)
+
+
+def smoothed_cross_entropy(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, targets: torch.Tensor,
+                           label_smoothing: float, weights: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
+    """linear_cross_entropy with F.cross_entropy's label_smoothing = e in [0, 1], still without the [M,V] logits: per live row
+        -(1 - e) logprob - e (mean - lse)        = lse - (1 - e) x[target] - e mean_v x_v
+    with (logprob, lse) of token_logprobs and mean of token_mean_logit, reduced as linear_cross_entropy reduces (reduce_logprobs:
+    weights, reduction and the divisor of "mean" mean what they mean there).  Rows with a negative target contribute 0 and get no
+    gradient.  e = 0 makes linear_cross_entropy's calls and no other: the value and the three gradients are its bytes."""
+    if reduction not in ("mean", "sum", "none"):
+        raise _lib.DicError(f"smoothed_cross_entropy: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    eps = native.check_label_smoothing(label_smoothing, "smoothed_cross_entropy")
+    logprobs, lse = token_logprobs(hidden, weight, bias, targets)
+    if eps == 0.0:
+        return reduce_logprobs(logprobs, targets, weights, reduction)
+    mean = token_mean_logit(hidden, weight, bias)
+    # reduce_logprobs negates (and weighs) what it is given: hand it the row's smoothed log-likelihood, 0 on ignored rows
+    smooth = (1.0 - eps) * logprobs + eps * torch.where(targets >= 0, mean - lse, torch.zeros_like(lse))
+    return reduce_logprobs(smooth, targets, weights, reduction)
 
 
 def self_critical_loss(logprobs: torch.Tensor, lengths: torch.Tensor, rewards: torch.Tensor, baseline="others") -> torch.Tensor:

@@ -22,9 +22,9 @@ from .nic import (NIC_EMB, NIC_FIELDS, NIC_STATES_GRAD_KEYS, NicPtrs, NicStatesT
                   nic_head_backward, nic_head_forward, nic_pack_targets, nic_ptrs, nic_shapes, nic_states_backward,
                   nic_states_forward)
 from .train_ops import (GRAD_NORM_MAX_SPANS, GRAD_NORM_PASS, GRAD_NORM_SCRATCH_BYTES, adamw_step, adamw_step_clipped, bleu,
-                        bn_ema_update, caption_lengths, caption_loss, cider_d, dropout_advance, dropout_draw, dropout_mask,
-                        gather_rows, grad_norm, pack_targets, rouge_l, scst_loss, token_logprobs, token_logprobs_bwd,
-                        token_logprobs_bwd_into)
+                        bn_ema_update, caption_lengths, caption_loss, caption_loss_smoothed, check_label_smoothing, cider_d,
+                        dropout_advance, dropout_draw, dropout_mask, gather_rows, grad_norm, pack_targets, rouge_l, scst_loss,
+                        token_logprobs, token_logprobs_bwd, token_logprobs_bwd_into, token_mean_logit, token_mean_logit_bwd)
 
 # which of dic_struct_bytes -> the ctypes mirror of that struct of include/dic.h (_core._load checks them all, once, and reads both names from here)
 STRUCT_MIRRORS = ((0, ConvBnLayer), (1, DecoderPtrs), (2, DecoderPtrs), (3, DepthPtrs), (4, DepthPtrs), (5, DepthBnState),

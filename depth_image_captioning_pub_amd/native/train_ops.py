@@ -45,6 +45,41 @@ def caption_loss(logits: torch.Tensor, targets: torch.Tensor, alphas: Optional[t
     return loss, dlogits, dalphas
 
 
+def check_label_smoothing(value, what: str) -> float:
+    """`value` as a float in [0, 1]; DicError naming it otherwise (NaN included).  `what`: the caller, for the message."""
+    try:
+        eps = float(value)
+    except (TypeError, ValueError):
+        raise _lib.DicError(f"{what}: label_smoothing={value!r} is not a number") from None
+    if not 0.0 <= eps <= 1.0:
+        raise _lib.DicError(f"{what}: label_smoothing={eps:g} is outside [0, 1]")
+    return eps
+
+
+def caption_loss_smoothed(logits: torch.Tensor, targets: torch.Tensor, alphas: Optional[torch.Tensor], lam: float = 0.7,
+                          label_smoothing: float = 0.0, grad_scale: float = 1.0, in_place: bool = False,
+                          reg_grad_scale: Optional[float] = None):
+    """dic_caption_loss_smoothed: caption_loss with F.cross_entropy's label_smoothing in [0, 1] (semantics: include/dic.h).
+    Returns (loss [1] - the smoothed objective plus the regulariser -, nll [1] - the plain mean negative log-likelihood, the number
+    to log -, dlogits, dalphas or None).  At label_smoothing = 0 loss, dlogits and dalphas are caption_loss's bytes."""
+    lib = _load()
+    eps = check_label_smoothing(label_smoothing, "caption_loss_smoothed")
+    n, v = logits.shape
+    dev = logits.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    nll = torch.empty(1, dtype=torch.float32, device=dev)
+    dlogits = logits if in_place else torch.empty_like(logits)
+    B = alphas.shape[0] if alphas is not None else 0
+    T = alphas.shape[1] if alphas is not None else 0
+    dalphas = torch.empty_like(alphas) if alphas is not None else None
+    scratch = torch.empty(2 * n + B + 8, dtype=torch.float32, device=dev)
+    rc = lib.dic_caption_loss_smoothed(ptr(logits), ptr(targets), n, v, ptr(alphas), B, T, lam, eps, grad_scale,
+                                       grad_scale if reg_grad_scale is None else reg_grad_scale,
+                                       ptr(loss), ptr(nll), ptr(dlogits), ptr(dalphas), ptr(scratch), stream_ptr())
+    check(rc, "dic_caption_loss_smoothed")
+    return loss, nll, dlogits, dalphas
+
+
 def adamw_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int,
                lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                weight_decay: float = 0.01, skip_if_raised: Optional[torch.Tensor] = None) -> None:
@@ -210,6 +245,46 @@ def _token_logprobs_bwd(hidden, weight, bias, targets, lse, d_logprob, d_lse, ne
                                     ptr(d_bias), ptr(ws), ws.numel(), stream_ptr())
     check(rc, "dic_token_logprobs_bwd")
     return d_hidden, d_weight, d_bias
+
+
+def token_mean_logit(hidden: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor):
+    """dic_token_mean_logit: mean_v (hidden[m] @ weight.T + bias)_v per row, from the column means of weight and the mean of bias,
+    the [M,V] logits never computed (semantics: include/dic.h).  hidden float32 [M,128], weight [V,128], bias [V].
+    Returns (mean float32 [M], state): `state` is the call's workspace, which holds the means token_mean_logit_bwd reads."""
+    lib = _load()
+    h, w, b = _dev(hidden, "hidden"), _dev(weight, "weight"), _dev(bias, "bias")
+    if h.dim() != 2 or h.shape[1] != D_HID or w.dim() != 2 or w.shape[1] != D_HID or tuple(b.shape) != (w.shape[0],):
+        raise _lib.DicError(f"token_mean_logit: hidden must be [M,{D_HID}], weight [V,{D_HID}] and bias [V], got {tuple(h.shape)}, "
+                            f"{tuple(w.shape)} and {tuple(b.shape)}")
+    M, V = h.shape[0], w.shape[0]
+    ws = _workspace(lib.dic_token_mean_logit_sizes, h.device, M, V)
+    mean = torch.empty((M,), dtype=torch.float32, device=h.device)
+    check(lib.dic_token_mean_logit(ptr(h), ptr(w), ptr(b), M, V, ptr(mean), ptr(ws), ws.numel(), stream_ptr()), "dic_token_mean_logit")
+    return mean, ws
+
+
+def token_mean_logit_bwd(hidden: torch.Tensor, d_mean: torch.Tensor, vocab: int, state: torch.Tensor, need=(True, True, True)):
+    """dic_token_mean_logit_bwd: the gradients of sum(d_mean * mean) of token_mean_logit with respect to hidden, weight and bias.
+    state: what token_mean_logit returned beside the mean, for the same weight, bias and M.  d_mean float32 [M]; vocab = V.
+    need: which of (d_hidden [M,128], d_weight [V,128], d_bias [V]) to compute; one that was not requested is None.  Every row
+    of d_weight is the same 128-vector and every element of d_bias the same value: the kernel writes them once, and d_weight /
+    d_bias are stride-0 views of them (call .contiguous() for tensors of their own)."""
+    lib = _load()
+    h, g = _dev(hidden, "hidden"), _dev(d_mean, "d_mean")
+    if h.dim() != 2 or h.shape[1] != D_HID or tuple(g.shape) != (h.shape[0],):
+        raise _lib.DicError(f"token_mean_logit_bwd: hidden must be [M,{D_HID}] and d_mean [M], got {tuple(h.shape)} and {tuple(g.shape)}")
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.uint8 and state.is_contiguous()):
+        raise _lib.DicError("token_mean_logit_bwd: state must be the uint8 GPU workspace token_mean_logit returned")
+    need = tuple(bool(n) for n in need)
+    if len(need) != 3:
+        raise _lib.DicError(f"token_mean_logit_bwd: need must name three outputs, got {len(need)}")
+    M, V = h.shape[0], int(vocab)
+    d_hidden = torch.empty((M, D_HID), dtype=torch.float32, device=h.device) if need[0] else None
+    row = torch.empty((D_HID,), dtype=torch.float32, device=h.device) if need[1] else None
+    val = torch.empty((1,), dtype=torch.float32, device=h.device) if need[2] else None
+    check(lib.dic_token_mean_logit_bwd(ptr(h), ptr(g), M, V, ptr(d_hidden), ptr(row), ptr(val), ptr(state), state.numel(),
+                                       stream_ptr()), "dic_token_mean_logit_bwd")
+    return (d_hidden, row.unsqueeze(0).expand(V, D_HID) if need[1] else None, val.expand(V) if need[2] else None)
 
 
 def cider_d(hyp_ids: torch.Tensor, ref_ids: torch.Tensor, ref_counts: torch.Tensor, id_end: int, vocab: int,

@@ -279,6 +279,34 @@ int dic_token_logprobs_bwd(const float* hidden, const float* out_w, const float*
                            const float* d_logprob, const float* d_lse, int M, int V, float* d_hidden, float* d_out_w,
                            float* d_out_b, void* workspace, size_t workspace_bytes, void* stream);
 
+/* mean logit per row of hidden states, the [M,V] logits never computed: the quantity label smoothing adds to the fused loss head
+ *   (losses.smoothed_cross_entropy).  Model-agnostic (K = DIC_H = 128); this comment is the specification.
+ *   hidden float [M,128], out_w float [V,128], out_b float [V] on the device.
+ *     mean_v x_mv = hidden_m . wbar + bbar,   wbar[k] = mean_v out_w[v,k],  bbar = mean_v out_b[v]
+ *     wbar, bbar: summed in fp64 (64 rows of out_w per workgroup, the partial sums added in ascending order), divided by V in fp64
+ *       and rounded to fp32 ONCE
+ *     out_mean[m] = (one fp32 fma chain over hidden[m,k] wbar[k] in ascending k, from 0) + bbar        float [M]
+ *   The workspace keeps (wbar [128], bbar) in its first 129 floats: it is what dic_token_mean_logit_bwd reads, so the backward
+ *   takes the workspace the forward filled, untouched in between.
+ *   dic_token_mean_logit_bwd, for d_mean float [M] (the gradient arriving at out_mean), writes - not accumulates -
+ *     d_hidden[m,k] = d_mean[m] wbar[k]                              float [M,128]
+ *     d_out_w_row[k] = (1/V) sum_m d_mean[m] hidden[m,k]             float [128]: the row EVERY d_out_w[v,:] equals
+ *     d_out_b_val[0] = (1/V) sum_m d_mean[m]                         float [1]:   the value EVERY d_out_b[v] equals
+ *   The sums over m run in fp64 over groups of 256 rows, the groups added in ascending order; the division by V is made in fp64
+ *   and the result rounded to fp32 once.  Each of the three outputs may be NULL, in which case its work is not done; at least
+ *   one must be given.  Everything is enqueued on `stream`; nothing is copied to the host, nothing synchronises.
+ *   Properties: no float atomics; every summation order is a function of V (forward) or M (backward) alone, so two calls return
+ *   identical bytes.  out_mean[m] and d_hidden row m depend only on row m's inputs, out_w, out_b and V - never on M or on the
+ *   other rows: a row evaluated alone returns the bytes it returns inside a batch.
+ *   M, V > 0, M <= 65535 * 128, no null pointer other than the backward's three outputs, at least one of those, a workspace of
+ *   dic_token_mean_logit_sizes(M, V) bytes (one size for both calls): a violation returns a negative code and a dic_last_error()
+ *   text that starts with the function's name, before any HIP call; the size query writes 0 for sizes the calls refuse. */
+int dic_token_mean_logit_sizes(int M, int V, size_t* workspace_bytes);
+int dic_token_mean_logit(const float* hidden, const float* out_w, const float* out_b, int M, int V, float* out_mean,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int dic_token_mean_logit_bwd(const float* hidden, const float* d_mean, int M, int V, float* d_hidden, float* d_out_w_row,
+                             float* d_out_b_val, void* workspace, size_t workspace_bytes, void* stream);
+
 /* scoring of GIVEN captions by the soft-attention decoder (depth-soft, or base-soft with feat_depth = NULL): the log-probability
  *   the model gives every token of S captions per image.  Entirely on the device: every launch is enqueued on `stream`, nothing
  *   is copied to the host, nothing synchronises.  There is no reference implementation; this comment is the specification.
@@ -912,6 +940,29 @@ int dic_attention_bwd(const float* enc_att_w, const float* enc_att_b, const floa
 int dic_caption_loss(const float* logits, const int64_t* targets, int n_packed, int V, const float* alphas, int B,
                      int Tmax, float lam, float ce_grad_scale, float reg_grad_scale, float* loss, float* dlogits,
                      float* dalphas, float* scratch, void* stream);
+/* ---- the same loss with LABEL SMOOTHING (F.cross_entropy(label_smoothing = e)): per packed row of logits x, target t,
+ *      e = label_smoothing in [0, 1]
+ *        lse      = logsumexp(x)
+ *        nll_row  = lse - x[t]
+ *        loss_row = lse - (1 - e) x[t] - e mean_v(x)                              (nll_row itself at e = 0)
+ *        dlogits[v] = (softmax(x)_v - (1 - e) [v == t] - e / V) * ce_grad_scale / n_packed
+ *      loss[0] = mean of loss_row + the regulariser of dic_caption_loss; nll (nullable): nll[0] = the plain mean of nll_row,
+ *      without smoothing and without the regulariser - the number to log and to compare across e.  Both means are finished in fp64
+ *      by the kernel that finishes dic_caption_loss.  Every other argument, the regulariser, dalphas and the two gradient scales
+ *      are dic_caption_loss's.  mean_v(x) is summed in fp64 in the pass that sums exp(x - max): the row is read as often as
+ *      dic_caption_loss reads it.
+ *      dlogits MAY ALIAS logits: x[t], the row's sum and its log-sum-exp are complete before the barrier that precedes the
+ *      first store of a gradient.
+ *      e = 0: loss, dlogits and dalphas hold the bytes dic_caption_loss writes for the same inputs.  Any e: nll[0] holds the bytes
+ *      dic_caption_loss writes to loss[0] with alphas = NULL.
+ *      A target outside [0, V) makes loss and nll NaN; every gradient stays finite, and the other rows' are what they would be.
+ *      Refused before any HIP call, with a dic_last_error() text that starts with "dic_caption_loss_smoothed:": a null pointer
+ *      among logits, targets, loss, dlogits, scratch; n_packed <= 0 or V <= 0; alphas without dalphas (or with B, Tmax <= 0);
+ *      label_smoothing negative, above 1 or NaN (the text names it: label_smoothing=-0.1).
+ *      scratch: >= (2 * n_packed + B + 8) floats. */
+int dic_caption_loss_smoothed(const float* logits, const int64_t* targets, int n_packed, int V, const float* alphas, int B,
+                              int Tmax, float lam, float label_smoothing, float ce_grad_scale, float reg_grad_scale,
+                              float* loss, float* nll, float* dlogits, float* dalphas, float* scratch, void* stream);
 /* packed targets = pack_padded_sequence(captions[:,1:], lengths-1).data (depth_train.py:210-213);
  * `targets` needs room for n_packed int64 + B int32 (the tail holds the device copy of dec_lengths). */
 int dic_pack_targets(const int64_t* captions, int cap_stride, const int* dec_lengths, int B, int64_t* targets,
