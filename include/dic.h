@@ -10,7 +10,13 @@
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*), no hidden synchronisation;
  *   - return 0 on success, a negative code on failure, never throw; dic_last_error() gives the text;
  *   - the library owns no device memory: scratch comes in as (workspace, workspace_bytes), sized by
- *     the matching *_workspace_bytes() query; one call at a time per workspace.
+ *     the matching *_workspace_bytes() / *_sizes() query; one call at a time per workspace.  A `workspace` must be aligned to
+ *     256 bytes: its slices are cut at multiples of 256 from its first byte (a `scratch` / `tail_ws` array of a stated element
+ *     count is one plain array and needs the alignment its own comment states, else that of its element type).  Workspace and
+ *     scratch may arrive with any contents: a call reads no byte of them that it, or the forward call whose tape it consumes,
+ *     has not written.  A call stores nothing outside the workspace_bytes it was given and the documented extent of its
+ *     outputs, and it writes every element of every output array it is handed unless that array's comment says otherwise
+ *     (tests/test_buffer_contract_gpu.py);
  *   - all floating point is IEEE fp32 (exact-fp32 MFMA), token ids are int64.
  */
 #ifndef DIC_H_
@@ -89,7 +95,8 @@ size_t dic_decoder_workspace_bytes(int B, int Tmax, int V, int n_packed);
  *   drop_mult: [B,Tmax,H] multiplier (0 or 1/(1-p)) or NULL for eval (quirk Q6: mask is an input);
  *   mode 0 soft | 1 Gumbel-softmax with temp (attention.py:12-25) | 2 Gumbel-max one-hot (:34-48);
  *   gumbel_u: [Tmax,B,196] uniform draws (modes 1,2);
- *   logits_packed: [n_packed,V] time-major rows (= PackedSequence.data, :204); alphas: [B,Tmax,196]. */
+ *   logits_packed: [n_packed,V] time-major rows (= PackedSequence.data, :204); alphas: [B,Tmax,196], rows (b,t) with
+ *   t >= dec_lengths[b] are written as 0 (the reference's new_zeros, :176: dic_caption_loss sums all Tmax steps). */
 int dic_decoder_fwd(const dic_decoder_weights* w, int V, const float* feat_rgb, const float* feat_depth,
                     const int64_t* captions, int cap_stride, const int* dec_lengths, int B, const float* drop_mult,
                     int mode, const float* gumbel_u, float temp, float* logits_packed, float* alphas, void* workspace,
@@ -127,7 +134,7 @@ int dic_decoder_bwd_cells(const dic_decoder_weights* w, int V, int cells, const 
  *   attention step unchanged.  captions needs cap_stride >= Tmax = dec_lengths[0].
  *   coin_u: float [Tmax,B] on the device, values in [0,1); may be NULL when sampling_prob == 0.
  *   draw_u: float [Tmax,B] on the device, values in [0,1); may be NULL when pick == 0.
- *   fed_ids: int64 [B,Tmax], output: the token every step was fed.
+ *   fed_ids: int64 [B,Tmax], output: the token every step was fed (all B*Tmax entries are written, see t >= n below).
  *   Randomness is an input, as gumbel_u (quirk Q6): the library draws nothing, the call is a pure function of its arguments.
  *   Row b with n = dec_lengths[b] (clamp: into [0,V)):
  *     fed[b,0] = clamp(captions[b,0]).
@@ -216,7 +223,7 @@ int dic_decoder_beam(const dic_decoder_weights* w, int V, const float* feat_rgb,
  *   Finished rows: after a row draws id_end at step t its length is t + 1 (otherwise T); later positions hold id_end with
  *     log-probability 0 and the row's logits are no longer read.
  *   out_ids int64 [B,S,T], out_logprobs float [B,S,T], out_lengths int [B,S], alphas_out (nullable) [B,S,T,196]: the attention
- *   weights of each row's own steps (steps at or behind `length`: unspecified).
+ *   weights of each row's own steps (steps at or behind `length`: unspecified values - written or left as they were).
  *   1 <= S <= 8, B, V > 0, max_length >= 1, 0 <= id_start, id_end < V, temperature finite and > 0, 0 <= top_k <= V,
  *   0 < top_p <= 1 (NaN refused), no null pointer other than feat_depth and alphas_out, a workspace of sufficient size: a violation
  *   returns a negative code and a dic_last_error() text that starts with "decoder_sample:", before anything is launched; the
