@@ -102,7 +102,7 @@ int dic_debug_conv_bf3(const uint16_t* const x_planes[3], int B, int H, int W, i
   return conv_fwd_bf3(x_planes, d, w_planes, y, bn_partial, mtiles_out, tail_ws, (hipStream_t)stream, nullptr, nullptr, nullptr);
 }
 /* development aid (not in dic.h): the launch plan of one split-operand convolution, without operands and without a GPU (plan_bf3,
- * gemm_bf3.hip; routes and flags at bf3_plan_route - flag 32 on route 0 plans without a tail workspace, as dic_linear_* launches).  name receives the kernel as the profiler names it (without "void dic::" and the
+ * bf3_plan.cpp; routes and flags at bf3_plan_route, gemm_bf3.hip - flag 32 on route 0 plans without a tail workspace, as dic_linear_* launches).  name receives the kernel as the profiler names it (without "void dic::" and the
  * parameter list), out the grid, the workgroup size, the fix-up (0 none, 1 remainder of the 128x128 kernels over out[3] quadrants,
  * 2 / 3 64x64 tail over out[3] tiles, 3: fused with the BatchNorm finalize when asked), the BatchNorm partial-sum rows and the profile
  * key.  Returns 1 when the route does not take the shape. */

@@ -37,7 +37,7 @@ ACT_SCALE = nk.ACT_SCALE                    # kF16ActScale: f16x2 activation pla
 FP32_THREADS = 16
 WGRAD, PLANES, NO_STATS = 3, 0, 16          # routes / flag of dic_debug_bf3_plan
 TAIL_SLABS = 1024                           # kResnetTailSlabs: the tail workspace the encoder hands the data gradient
-REMAINDER_GRID = 256                        # workgroups a K-sliced launch may use (gemm_bf3.hip)
+REMAINDER_GRID = 256                        # workgroups a K-sliced launch may use (Bf3Policy::remainder_grid, csrc/bf3_plan.h)
 GRAD_SCALES = nk.GRAD_SCALES                # 1e-6, 1, 1e4
 
 

@@ -1,7 +1,9 @@
-"""The launch plan of the split-operand contractions (plan_bf3, csrc/gemm_bf3.hip) on the CPU: kernel, grid, workgroup size, fix-up,
-BatchNorm partial-sum rows and profile key for every convolution of the product's hot path.  The plan makes no HIP call, so
-dic_debug_bf3_plan runs without a GPU.  tests/golden/bf3_plan.json was recorded from the launches of the library before the plan
-was separated from them (each launch reported instead of made), so this pins the policy as it was."""
+"""The launch plan of the split-operand contractions (plan_bf3, csrc/bf3_plan.cpp: a function of the launch's parameters and a
+Bf3Policy value, csrc/bf3_plan.h) on the CPU: kernel, grid, workgroup size, fix-up, BatchNorm partial-sum rows and profile key for every
+convolution of the product's hot path.  The plan makes no HIP call, so dic_debug_bf3_plan runs without a GPU; it answers for the
+process-wide policy, which the tests set through the switch codes and restore.  tests/golden/bf3_plan.json was recorded from the
+launches of the library before the plan was separated from them (each launch reported instead of made), and
+tests/golden/bf3_plan_switches.json from the library before the policy became a value, so both pin the policy as it was."""
 import ctypes
 import json
 import os
@@ -97,3 +99,44 @@ def test_plan_matches_the_recorded_launches():
     finally:
         assert lib.dic_conv_persistent_grid(224) == 0 and lib.dic_debug_force_staged_gemm(20) == 0
     assert seen == sum(len(v) for v in golden.values())
+
+
+# The product's other plan-visible switches, each one code away from the default: {code: the code that restores the default}.
+# tests/golden/bf3_plan_switches.json holds, per code, the cases of switch_cases() whose plan differs from the default setting's
+# ("224" of bf3_plan.json), recorded from the library as it stood before the policy became a value.
+SWITCHES = {70: 79, 73: 79, 75: 78, 90: 91, 81: 80, 94: 95, 96: 97, 112: 113, 115: 114, 118: 119, 120: 121, 24: 20}
+GOLDEN_SWITCHES = os.path.join(os.path.dirname(__file__), "golden", "bf3_plan_switches.json")
+
+
+def switch_cases():
+    return sorted(set(resnet_cases(1, 64)) | set(resnet_cases(0, 64)) | set(depth_encoder_cases(1)) | set(depth_encoder_cases(0)))
+
+
+def test_plan_under_each_switch():
+    """Every case either has the plan recorded for the switch, which differs from the default's, or keeps the default plan."""
+    lib = ctypes.CDLL(build.build())
+    lib.dic_last_error.restype = ctypes.c_char_p
+    with open(GOLDEN) as f:
+        default = json.load(f)["224"]
+    with open(GOLDEN_SWITCHES) as f:
+        golden = json.load(f)
+    cases = switch_cases()
+    keys = {" ".join(map(str, case)) for case in cases}
+    assert len(cases) == 126 and sorted(golden) == sorted(map(str, SWITCHES))
+    assert lib.dic_conv_persistent_grid(224) == 0 and lib.dic_debug_force_staged_gemm(20) == 0
+    for code, restore in SWITCHES.items():
+        want = golden[str(code)]
+        assert want, f"switch {code}: no recorded plan differs from the default's"
+        assert set(want) <= keys, f"switch {code}: recorded cases outside switch_cases()"
+        try:
+            assert lib.dic_debug_force_staged_gemm(code) == 0
+            for case in cases:
+                key = " ".join(map(str, case))
+                if key in want:
+                    assert want[key] != default[key], (code, key)
+                assert query(lib, case) == want.get(key, default[key]), (code, key)
+        finally:
+            assert lib.dic_debug_force_staged_gemm(restore) == 0
+        for case in cases[::9]:                     # the restoring code brings the default back
+            key = " ".join(map(str, case))
+            assert query(lib, case) == default[key], (code, restore, key)
